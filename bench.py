@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json headline metric on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]      (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up W steps, times exactly K steps, and prints the headline line.  --full adds everything else (below).
+--dump-outputs DIR writes what the last timed step delivered as DIR/<name>.npy (zoomed waterfall lines of its block, the tail of every
+VFO's output): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload by --cfg (default: 3 on one GPU, 5 on several):
   2  10 MS/s, 65536-pt Nuttall FFT + log-power + waterfall line only (dense framing: every sample transformed)   [HBM-bound]
@@ -19,7 +23,9 @@ page-locked host memory and handed on in batches (multi.StreamRunner; with N > 1
 blocks pushed AND all their results delivered.  `--mode ordinary` runs the same blocks as ordinary passes (one launch per stage).
 Inputs come from sdrplusplus_amd/workloads.synth — the numpy generator the CPU baseline and the parity tests use too.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
+Prints ONE JSON line on rank 0 with metric / value / unit / ms_per_step (one timed step) / dtype / higher_is_better; --full adds
+  self_check     the first blocks through the pipelined path and through ordinary passes, bit-identical (untimed)
+  steady_state   (one GPU, K < 100) the same loop over 200 blocks
   roofline       dominant kernel (pipelined: the tick launch = every stage of the path over one block), HIP events on its launch stream
                  inside the timed region (algorithmic flops or bytes / time)
   cpu_baseline   the reference's own RxVFO / demodulator / FFT code (oracle/_ref) timed on this host on a bounded sample
@@ -362,10 +368,38 @@ def self_check(torch, np, local, cfg, push, nvfo, bufs, ref_block, data_width=10
     return out
 
 
+def last_step_outputs(np, ctx, runner, info, push, sr, pipelined, steps):
+    """What the timed path handed its caller for the LAST timed step, as float32 arrays: the zoomed waterfall lines of that block (delivered
+    into page-locked host memory and on to the device tensor `lines` in pipelined mode; sdrpp_fft_read in an ordinary pass) and the tail of
+    every VFO's output stream (sdrpp_vfo_read: the most recent launch — with launch groups up to `group` blocks, so only the last
+    push * rate / sr - 8 samples, which belong to the last block whatever the grouping).  Read after the timed region, untimed."""
+    out = {}
+    if pipelined:
+        lines = runner.lines.cpu().numpy()
+        k = (steps - 1) % runner.gather_every  # every timed region starts a fresh batch: the last step's block sits in slot (steps - 1) % gather_every
+        n = int(lines[k, runner.max_lines, 0])
+        out["waterfall_zoomed_lines"] = np.ascontiguousarray(lines[k, :n], dtype=np.float32)
+    else:
+        _raw, zoomed, _ix = ctx.fft_read()
+        out["waterfall_zoomed_lines"] = np.ascontiguousarray(zoomed, dtype=np.float32)
+    if info["vids"]:
+        got = ctx.vfo_read_many(info["vids"])
+        cap = max(1, (48 << 20) // (8 * len(got)))  # (the whole dump stays under 64 MB)
+        tails = []
+        for a, (_m, rate, _b, _c, _x) in zip(got, info["plan"]):
+            keep = max(1, min(int(push * rate / sr) - 8, cap, len(a)))
+            tails.append(np.asarray(a[len(a) - keep:], dtype=np.float32))
+        out["vfo_out_tail"] = np.ascontiguousarray(np.concatenate(tails))
+        out["vfo_out_tail_lengths"] = np.array([len(t) for t in tails], dtype=np.float64)
+    return out
+
+
 def run_workload(torch, np, device, local, cfg, push, mode, steps, warmup, nvfo, world=1, rank=0, af=False, ref_block=None, inputs=None, data_width=1024, lag=8, gather_every=4, exact_ssb=False, check=False,
-                 group=1, adaptive=True, regions=1):
+                 group=1, adaptive=True, regions=1, detail=True, capture=False):
     """One measured run of a configuration.  mode 'pipelined': sdrpp_set_pipelined, one launch per block; 'ordinary': one launch per
-    stage.  Returns (result dict for rank 0, inputs) — the inputs can be handed to a second run of the same configuration."""
+    stage.  Returns (result dict for rank 0, inputs) — the inputs can be handed to a second run of the same configuration.
+    detail=False: set up, warm up, time the steps, nothing else (no per-kernel calibration pass, no HIP events in the timed region, no
+    steady-state region).  capture: the result dict carries `outputs`, what the last timed step delivered (last_step_outputs)."""
     from sdrplusplus_amd import capi, multi, workloads
 
     base = 4 if cfg == 5 else cfg
@@ -421,40 +455,44 @@ def run_workload(torch, np, device, local, cfg, push, mode, steps, warmup, nvfo,
         need = min(capi.RESULT_SLOTS - 2, int(ctx.pipeline_stats()["depth"]) + 1) * group
         if need > runner.lag:
             runner.lag = lag = need
-    # calibration (untimed): every kernel family bracketed by HIP events to find the dominant one and record the per-kernel split
-    ctx.timing_enable(True)
-    ncal = max(2, min(5, steps)) if not pipelined else max(8, min(24, steps))
-    for i in range(ncal):
-        runner.step(i)
-    runner.finish()
-    torch.cuda.synchronize()
-    fam_all = ctx.timing_read()
-    kernel_ms_all = {k: v[0] / ncal for k, v in fam_all.items() if v[0] > 0}
-    # dominant family = the longest one on the CRITICAL stream: in an ordinary pass with VFOs the FFT branch runs on a second stream as filler
-    # behind the VFO bank (its launches stretch while they wait for CUs, which says nothing about the kernels themselves), so only
-    # the VFO-bank families compete there; FFT-only runs (cfg 2) have just the FFT families.  Pipelined: the tick launch is everything.
-    filler = {"fft_pass1", "fft_pass2", "fft_single", "zoom_palette"} if nvfo else set()
-    cand = {k: v for k, v in kernel_ms_all.items() if k not in filler} or kernel_ms_all
-    dom = max(cand, key=cand.get) if cand else None
-    # timed region: only the dominant family keeps its event pair (two event records per launch on its launch stream)
-    ctx.timing_enable(True, families=[ctx.family_index(dom)] if dom else [])
+    kernel_ms_all, fam, dom = {}, {}, None
+    if detail:
+        # calibration (untimed): every kernel family bracketed by HIP events to find the dominant one and record the per-kernel split
+        ctx.timing_enable(True)
+        ncal = max(2, min(5, steps)) if not pipelined else max(8, min(24, steps))
+        for i in range(ncal):
+            runner.step(i)
+        runner.finish()
+        torch.cuda.synchronize()
+        fam_all = ctx.timing_read()
+        kernel_ms_all = {k: v[0] / ncal for k, v in fam_all.items() if v[0] > 0}
+        # dominant family = the longest one on the CRITICAL stream: in an ordinary pass with VFOs the FFT branch runs on a second stream as filler
+        # behind the VFO bank (its launches stretch while they wait for CUs, which says nothing about the kernels themselves), so only
+        # the VFO-bank families compete there; FFT-only runs (cfg 2) have just the FFT families.  Pipelined: the tick launch is everything.
+        filler = {"fft_pass1", "fft_pass2", "fft_single", "zoom_palette"} if nvfo else set()
+        cand = {k: v for k, v in kernel_ms_all.items() if k not in filler} or kernel_ms_all
+        dom = max(cand, key=cand.get) if cand else None
+        # timed region: only the dominant family keeps its event pair (two event records per launch on its launch stream)
+        ctx.timing_enable(True, families=[ctx.family_index(dom)] if dom else [])
     blocks0 = runner.collected
     gs0 = ctx.pipeline_group_stats() if pipelined else None
     ticks0 = ctx.pipeline_stats()["ticks"] if pipelined else 0
     # `regions` timed regions of EXACTLY `steps` steps each (median of 5); the first one carries the dominant family's event pairs
     elapsed = runner.timed(steps, first=warmup)
-    fam = ctx.timing_read()
-    ctx.timing_enable(False)
+    if detail:
+        fam = ctx.timing_read()
+        ctx.timing_enable(False)
     gs1 = ctx.pipeline_group_stats() if pipelined else None
     ticks1 = ctx.pipeline_stats()["ticks"] if pipelined else 0
     region_s = [elapsed]
     for q in range(1, max(1, int(regions))):
         region_s.append(runner.timed(steps, first=warmup + q * steps))
     elapsed = sorted(region_s)[len(region_s) // 2]
+    outputs = last_step_outputs(np, ctx, runner, info, push, sr, pipelined, steps) if (capture and rank == 0) else None
     # a short timed region (the driver's 20 steps) is a third pipeline fill and drain — depth - 1 launches at either end carry less than a block's
     # work: the same loop over 200 blocks next to it, so that both numbers come from the same process on the same box
     steady = None
-    if pipelined and world == 1 and steps < 100:
+    if detail and pipelined and world == 1 and steps < 100:
         st_steps = 200
         st_elapsed = runner.timed(st_steps, first=warmup + steps)
         steady = {"steps": st_steps, "value": round(push * st_steps / st_elapsed / 1e6, 3), "ms_per_step": round(st_elapsed / st_steps * 1e3, 5), "unit": "Msamples/s"}
@@ -525,12 +563,13 @@ def run_workload(torch, np, device, local, cfg, push, mode, steps, warmup, nvfo,
         out = {
             "value": round(value, 3), "ms_per_step": round(elapsed / steps * 1e3, 5), "steps": steps, "warmup": warmup,
             "timed_regions": {"n": len(region_s), "value": "median", "Msamples_per_s": [round(world * push * steps / t / 1e6, 1) for t in region_s],
-                              "note": "every region = exactly `steps` pushes AND the delivery of all their results, bracketed by device synchronisation; roofline.* comes from the first region (the one with HIP events on the launches)"},
+                              "note": "every region = exactly `steps` pushes AND the delivery of all their results, bracketed by device synchronisation" +
+                                      ("; roofline.* comes from the first region (the one with HIP events on the launches)" if detail else "")},
             "workload": workload_string(cfg, sr, N, nvfo, mode_names, pipelined),
             "samples_per_step_per_gpu": push, "mode": mode, "reference_block": ref_block if (ref_block and ref_block < push) else push,
             "input_blocks_rotated": len(bufs), "input_bytes_rotated": len(bufs) * push * 8, "af_chain": bool(af and nvfo), "device": ctx.device_info(),
             "roofline": roof, "roofline_fft": roof_fft, "roofline_path": roof_path,
-            "kernel_ms_per_step": {k: round(v, 5) for k, v in sorted(kernel_ms_all.items(), key=lambda kv: -kv[1])},
+            "kernel_ms_per_step": {k: round(v, 5) for k, v in sorted(kernel_ms_all.items(), key=lambda kv: -kv[1])} if detail else None,
             "realtime_factor": round(per_gpu / sr, 1), "sr": sr, "fft": N, "nvfo": nvfo,
             "nco": ("SSB / DSB / raw channels: the reference's float rotator recursion on the device (nco_mode 2: every channel inside the north-star tolerance against the "
                     "compiled reference at arbitrary offsets); FM / AM channels closed form") if exact_ssb else ("closed form: FM / AM inside the tolerance for any run length; SSB / DSB audio and the raw IF differ from the reference by ITS rotator's rounding drift — "
@@ -553,6 +592,8 @@ def run_workload(torch, np, device, local, cfg, push, mode, steps, warmup, nvfo,
             out["self_check"] = checked
         if steady is not None:
             out["steady_state"] = steady
+        if outputs is not None:
+            out["outputs"] = outputs
         out["rank_local_s"] = runner.local_elapsed
     else:
         out = {"rank_local_s": runner.local_elapsed}
@@ -917,7 +958,12 @@ def main():
     ap.add_argument("--mode", choices=("pipelined", "ordinary"), default="pipelined", help="pipelined: one launch per block (sdrpp_set_pipelined); ordinary: one launch per stage")
     ap.add_argument("--group", type=int, default=4, help="pipelined mode: blocks one launch may carry (sdrpp_set_pipeline_group; 1 = one launch per block, as in rounds 3-5)")
     ap.add_argument("--group-fixed", action="store_true", help="always wait for --group blocks (default: adaptive — a push goes out at once while the device has fewer than two launches in flight)")
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of --steps steps each; value = their median (SURVEY.md 8d)")
+    ap.add_argument("--regions", type=int, default=None, help="timed regions of --steps steps each; value = their median (SURVEY.md 8d) (default: 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure as well: the untimed self check, the per-kernel calibration pass and roofline "
+                                                        "(HIP events in the first timed region), 5 timed regions, the 200-step steady-state region, the ceiling and cfg 2 / cfg 4 "
+                                                        "runs, the CPU baseline and the by-push report (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step delivered (zoomed waterfall lines of its block, "
+                                                                        "the tail of every VFO's output) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--ref-block", type=int, default=-1, help="reference block inside a push (default sr/200, what the file source cuts; 0: the push is one block)")
     ap.add_argument("--nvfo", type=int, default=32)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -991,8 +1037,16 @@ def main():
     if mode == "ordinary":
         push = max(1, push // N) * N  # whole frames per step (the ordinary protocol copies a fixed number of lines)
     ref_block = None if args.ref_block < 0 else args.ref_block
+    # a plain run does what its headline figure needs and nothing else; --full adds the self check, the per-kernel figures and the other measurements
+    full = args.full
+    regions = args.regions if args.regions is not None else (5 if full else 1)
     head, inputs = run_workload(torch, np, device, local, cfg, push, mode, args.steps, args.warmup, nvfo, world=world, rank=rank, af=args.af, ref_block=ref_block, exact_ssb=args.nco == "ssb-exact",
-                                check=not args.no_self_check, group=args.group, adaptive=not args.group_fixed, regions=args.regions)
+                                check=full and not args.no_self_check, group=args.group, adaptive=not args.group_fixed, regions=regions, detail=full,
+                                capture=args.dump_outputs is not None)
+    if rank == 0 and args.dump_outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in head.pop("outputs").items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     per_rank = None
     if dist is not None:  # every rank's own rate (its K blocks over its own wall time, before it waits for the slowest rank)
         mine = {"rank": rank, "device": "cuda:%d" % local, "local_s": head["rank_local_s"]}
@@ -1012,12 +1066,13 @@ def main():
                    "reference_block": head["reference_block"], "streams": world, "parallelism": "one independent IQ stream per GPU" + ("; RCCL gather of zoomed waterfall lines to rank 0" if world > 1 else ""),
                    "input_blocks_rotated": head["input_blocks_rotated"], "input_bytes_rotated": head["input_bytes_rotated"], "af_chain": head["af_chain"], "device": head["device"],
                    "results_delivered": head.get("results_delivered"), "nco": head["nco"]},
-        "roofline": head["roofline"], "roofline_fft": head["roofline_fft"], "roofline_path": head["roofline_path"],
-        "kernel_ms_per_step": head["kernel_ms_per_step"],
-        "kernel_ms_note": "per-family HIP-event times from an untimed calibration pass; pipelined mode has ONE family (tick: the launch per block); ordinary passes: the FFT branch and the VFO bank run on two "
-                          "streams and overlap, so the entries sum to more than ms_per_step; roofline.avg_launch_ms is the dominant family re-measured inside the timed region",
+        "roofline_path": head["roofline_path"],
         "realtime_factor": head["realtime_factor"],
     }
+    if full:
+        out.update({"roofline": head["roofline"], "roofline_fft": head["roofline_fft"], "kernel_ms_per_step": head["kernel_ms_per_step"],
+                    "kernel_ms_note": "per-family HIP-event times from an untimed calibration pass; pipelined mode has ONE family (tick: the launch per block); ordinary passes: the FFT branch and the VFO bank run on two "
+                                      "streams and overlap, so the entries sum to more than ms_per_step; roofline.avg_launch_ms is the dominant family re-measured inside the timed region"})
     if rccl:
         out["rccl"] = rccl
     if per_rank:
@@ -1027,7 +1082,7 @@ def main():
             out[k] = head[k]
     del inputs
     torch.cuda.empty_cache()
-    if world == 1 and not args.no_others:
+    if full and world == 1 and not args.no_others:
         others = {}
         try:  # last round's headline geometry: ONE ordinary pass over 2^24 samples (1.7 s of the stream — more than a dsp::stream can hand over)
             r, inp = run_workload(torch, np, device, local, cfg, max(1, (1 << 24) // N) * N, "ordinary", 10, 2, nvfo, af=args.af, ref_block=0)
@@ -1076,7 +1131,7 @@ def main():
             except Exception as e:
                 others["cfg%d" % oc] = {"error": repr(e)[:300]}
         out["other_configs"] = others
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(base, nvfo, N)
             if out["cpu_baseline"]:
@@ -1085,7 +1140,7 @@ def main():
                     out["gpu_over_cpu_process_only"] = round(out["value"] / out["cpu_baseline"]["process_only"]["value"], 1)
         except Exception as e:  # the baseline is a reported number, never a reason to lose the GPU result
             out["cpu_baseline"] = {"error": repr(e)}
-    if world == 1 and base == 3 and not args.no_by_push:
+    if full and world == 1 and base == 3 and not args.no_by_push:
         try:
             out["by_push"] = by_push_report(torch, capi, workloads, sr, nvfo, N, group=args.group)
         except Exception as e:

@@ -14,20 +14,16 @@ CSRC = os.path.join(ROOT, "sdrplusplus_amd", "csrc")
 
 
 EMU = os.path.join(ROOT, "tests", "emu")
-REF = "/root/reference"
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "test_blocks_ref")
 
 
 def _build(tmp, lib="product", headers="standalone", source="test_blocks.cpp"):
-    """tests/host_cpp/test_blocks.cpp against the test double of dsp::block / dsp::stream or against the reference's REAL headers
-    (+ the radio module's demod::Demodulator interface, extracted by oracle/Makefile), linked with the product library or — for runs
-    on a machine without a GPU — with the CPU emulator build of the same sources (tests/emu)."""
+    """tests/host_cpp/test_blocks.cpp against the test double of dsp::block / dsp::stream (the build against the reference's REAL headers
+    is oracle/_ref/test_blocks_ref, made by oracle/Makefile), linked with the product library or — for runs on a machine without a GPU —
+    with the CPU emulator build of the same sources (tests/emu)."""
     exe = os.path.join(tmp, "%s_%s_%s" % (source.split(".")[0], lib, headers))
     cmd = ["g++", "-std=c++17", "-O2", "-w", "-o", exe, os.path.join(ROOT, "tests", "host_cpp", source)]
-    if headers == "reference":
-        cmd += ["-DSDRPP_GPU_TEST_DEMOD_IFACE", "-I" + os.path.join(ROOT, "oracle", "shim"), "-I" + REF + "/core/src", "-I" + os.path.join(ROOT, "oracle", "_ref")]
-    else:
-        cmd += ["-I" + os.path.join(ROOT, "tests", "host_cpp", "standalone")]
+    cmd += ["-I" + os.path.join(ROOT, "tests", "host_cpp", "standalone")]
     if lib == "emu":
         S.locked_make("-C", EMU, "-s")
         cmd += ["-L" + EMU, "-l:libsdrpp_gpu_emu.so", "-Wl,-rpath," + EMU]
@@ -37,7 +33,7 @@ def _build(tmp, lib="product", headers="standalone", source="test_blocks.cpp"):
     return exe
 
 
-def _run_graph_and_check(exe, mode, tmp, drain_ms=None):
+def _run_graph_and_check(exe, mode, tmp, drain_ms=None, env=None):
     """Source thread -> IQFrontEnd -> sink threads (the way SDR++ drives it), 12 blocks of cfg 1, outputs against the oracle."""
     from sdrplusplus_amd import capi, workloads
 
@@ -46,7 +42,7 @@ def _run_graph_and_check(exe, mode, tmp, drain_ms=None):
     x = workloads.synth(1, B * nblk, seed=5)
     x.view(np.float32).tofile(os.path.join(tmp, "iq.f32"))
     r = subprocess.run([exe, os.path.join(ROOT, "sdrplusplus_amd", "data", "decim_plans.bin"), os.path.join(tmp, "iq.f32"), str(sr), str(B), str(N), str(rate), tmp, mode] +
-                       ([str(drain_ms)] if drain_ms else []), capture_output=True, text=True, timeout=600)
+                       ([str(drain_ms)] if drain_ms else []), capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = np.fromfile(os.path.join(tmp, "lines.f32"), np.float32).reshape(-1, N)
     ifs = np.fromfile(os.path.join(tmp, "if.f32"), np.float32).view(np.complex64)
@@ -97,15 +93,20 @@ def test_host_mirror_threaded_graph_on_the_emulator(mode):
         _run_graph_and_check(_build(tmp, lib="emu"), mode, tmp, drain_ms=6000 if mode.startswith("pipelined") else 3000)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/core/src/dsp"), reason="needs the reference tree")
+@pytest.mark.skipif(not os.path.exists(REF_BIN), reason="oracle/_ref/test_blocks_ref not built (needs the reference tree at build time)")
 def test_host_mirror_links_and_runs_against_the_reference_headers():
     """The same source compiled against SDR++'s REAL core/src/dsp/block.h, stream.h, types.h, multirate/decim/plans.h and the radio
-    module's demod::Demodulator interface (decoder_modules/radio/src/demod.h, cut out at build time), LINKED and RUN (CPU emulator
-    library): IQFrontEnd derives from the real dsp::block, speaks the real dsp::stream<T>, FusedDemodulator overrides every pure
+    module's demod::Demodulator interface (decoder_modules/radio/src/demod.h, cut out at build time) — oracle/_ref/test_blocks_ref, built
+    by oracle/Makefile — LINKED and RUN here against the CPU emulator library (found first through LD_LIBRARY_PATH under the product
+    library's name): IQFrontEnd derives from the real dsp::block, speaks the real dsp::stream<T>, FusedDemodulator overrides every pure
     virtual of the real interface."""
-    S.locked_make("-C", os.path.join(ROOT, "oracle"), "-s", "_ref/demod_iface.h")
+    S.locked_make("-C", EMU, "-s")
     with tempfile.TemporaryDirectory() as tmp:
-        _run_graph_and_check(_build(tmp, lib="emu", headers="reference"), "bypass", tmp, drain_ms=3000)
+        libdir = os.path.join(tmp, "lib")
+        os.makedirs(libdir)
+        os.symlink(os.path.join(EMU, "libsdrpp_gpu_emu.so"), os.path.join(libdir, "libsdrpp_gpu.so"))
+        env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join([libdir] + [p for p in os.environ.get("LD_LIBRARY_PATH", "").split(os.pathsep) if p]))
+        _run_graph_and_check(REF_BIN, "bypass", tmp, drain_ms=3000, env=env)
 
 
 def _run_reconfig_and_check(exe, tmp, nextra, wait_ms):
@@ -464,7 +465,7 @@ def test_bench_protocol_over_rccl_with_one_rank():
     import sys
 
     env = dict(os.environ, SDRPP_BENCH_FORCE_RCCL="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29577", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "6", "--no-others", "--no-by-push", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "6", "--full", "--no-others", "--no-by-push", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -1,4 +1,4 @@
-run() { python bench.py --steps 200 --warmup 10 --no-others --no-by-push --no-cpu-baseline --no-self-check 2>/dev/null | tail -1 | python -c "
+run() { python bench.py --full --steps 200 --warmup 10 --no-others --no-by-push --no-cpu-baseline --no-self-check 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$1:', d['value'], 'MS/s', d['ms_per_step'], 'ms/step, tick', d['roofline']['avg_launch_ms'], 'ms, frac', d['roofline']['frac'], d['pipeline']['roles'][:4])"; }
 export SDRPP_GPU_TICK_FCM16W=1

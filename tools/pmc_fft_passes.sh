@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p $R/$O
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $R/bench.py --cfg 2 --mode ordinary --push 16777216 --ref-block 0 --steps 12 --warmup 3 --no-others --no-by-push --no-cpu-baseline --no-self-check"
+BENCH="python $R/bench.py --full --cfg 2 --mode ordinary --push 16777216 --ref-block 0 --steps 12 --warmup 3 --no-others --no-by-push --no-cpu-baseline --no-self-check"
 DBS=""; i=0
 for ctr in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS" "SQ_INSTS_VMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" "SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS" "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p $R/$O
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $R/bench.py --no-others --no-by-push --no-cpu-baseline --no-self-check --steps 60 --warmup 10 $*"
+BENCH="python $R/bench.py --full --no-others --no-by-push --no-cpu-baseline --no-self-check --steps 60 --warmup 10 $*"
 i=0
 DBS=""
 for ctr in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES" "SQC_ICACHE_MISSES_DUPLICATE SQC_TC_INST_REQ SQC_ICACHE_BUSY_CYCLES" "SQ_IFETCH SQ_IFETCH_LEVEL SQ_BUSY_CYCLES"; do

@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p $R/$O
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $R/bench.py --mode ordinary --push 1000000 --no-others --no-by-push --no-cpu-baseline --no-self-check --steps 40 --warmup 5"
+BENCH="python $R/bench.py --full --mode ordinary --push 1000000 --no-others --no-by-push --no-cpu-baseline --no-self-check --steps 40 --warmup 5"
 i=0
 DBS=""
 for ctr in "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU" "SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM" "SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES" "FETCH_SIZE" "WRITE_SIZE"; do
@@ -20,6 +20,6 @@ for ctr in "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU" "SQ_INSTS_LDS SQ_INSTS_VM
 done
 cd $R
 first=$(echo $DBS | cut -d' ' -f1)
-python tools/rocpd_summary.py $first --pmc $DBS --out $O/${TAG}_per_role_instruction_mix.md --title "per-role instruction mix: headline workload as ONE ORDINARY PASS per 10^6-sample block (python bench.py --mode ordinary --push 1000000)" 2>&1 | tail -2
+python tools/rocpd_summary.py $first --pmc $DBS --out $O/${TAG}_per_role_instruction_mix.md --title "per-role instruction mix: headline workload as ONE ORDINARY PASS per 10^6-sample block (python bench.py --full --mode ordinary --push 1000000)" 2>&1 | tail -2
 head -80 $O/${TAG}_per_role_instruction_mix.md
 find $O -name "*.db" -size +4M -delete

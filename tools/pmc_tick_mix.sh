@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p $R/$O
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $R/bench.py --no-others --no-by-push --no-cpu-baseline --no-self-check --steps 60 --warmup 10 $*"
+BENCH="python $R/bench.py --full --no-others --no-by-push --no-cpu-baseline --no-self-check --steps 60 --warmup 10 $*"
 i=0
 DBS=""
 for ctr in "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU" "SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM" "SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_INST_CYCLES_VALU" \

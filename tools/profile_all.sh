@@ -8,14 +8,14 @@ O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$PWD}
-( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | tail -4
+( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | tail -4
 tail -c 600 $O/bench_default.json; echo
 for c in 2 4; do
-    timeout 600 python bench.py --cfg $c --no-others > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err
+    timeout 600 python bench.py --full --cfg $c --no-others > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err
     tail -c 300 $O/bench_cfg$c.json; echo
 done
 echo "== rocprofv3 kernel trace"
-BENCH="python $R/bench.py --no-others --no-by-push --no-cpu-baseline"
+BENCH="python $R/bench.py --full --no-others --no-by-push --no-cpu-baseline"
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/trace -o t -- $BENCH --steps 200 > $R/$O/trace.log 2>&1
 for ctr in FETCH_SIZE WRITE_SIZE; do
@@ -25,7 +25,7 @@ timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --kernel-
 cd $R
 T=$(find $O/trace -name "*.db" | head -1); F=$(find $O/pmc_FETCH_SIZE -name "*.db" | head -1); W=$(find $O/pmc_WRITE_SIZE -name "*.db" | head -1); Q=$(find $O/pmc_SQ -name "*.db" | head -1)
 python tools/rocpd_summary.py $T --pmc $F $W $Q --out $O/${TAG}_cfg3_pipelined_1M.md --json $O/pmc_traffic_cfg3_push1000000.json \
-    --title "round 3, final state: headline workload (cfg 3, pipelined mode, 10^6-sample blocks, zoomed lines delivered), python bench.py --no-others --no-by-push --no-cpu-baseline" \
+    --title "round 3, final state: headline workload (cfg 3, pipelined mode, 10^6-sample blocks, zoomed lines delivered), python bench.py --full --no-others --no-by-push --no-cpu-baseline" \
     --meta push=1000000 cfg=3 nvfo=32 mode=pipelined 2>&1 | tail -3
 head -24 $O/${TAG}_cfg3_pipelined_1M.md
 grep -h "\"value\"" $O/trace.log | tail -c 400; echo
