@@ -35,8 +35,6 @@ struct Stream {
     int n_extra = 0, rot = 0;
     int clevel = 0;  // pipelined mode: level of the role that consumes this stream with memory (its history carry runs there)
     int wlevel = 0;  // pipelined mode: level of the role that WRITES this stream in the current block (0: not written by a role of this plan)
-    float* prev_data = nullptr;  // pipelined mode: the data buffer of the block before (stream_rotate) and its sample count — where a piped back end
-    int prev_n = 0;              // finds the tail of the previous block (do_vfos_plan: pipe_in)
 };
 
 // Tap tables of the matrix-core FIR kernel (vfo_toep_kernel): zero-padded taps + per-lane base indices (one set per carried
@@ -45,7 +43,6 @@ struct ToepTab {
     float* d_tl = nullptr;
     int* d_lb = nullptr;  // [nvar][64]
     int tl_len = 0, nsteps = 0, s_in = 0, rows = 0, nvar = 0;
-    int kind = 0;  // 1 decimator, 2 resampler, 4 channel filter, 8 audio low-pass
     bool ok = false;
 };
 
@@ -278,7 +275,6 @@ struct sdrpp_ctx {
     int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines
     int num_cus = 256;
     int tick_l0_at = getenv("SDRPP_GPU_TICK_L0_AT") ? atoi(getenv("SDRPP_GPU_TICK_L0_AT")) : 0;  // (read when the context is created)
-    bool tick_order = getenv("SDRPP_GPU_TICK_ORDER") ? atoi(getenv("SDRPP_GPU_TICK_ORDER")) != 0 : true;  // longest roles first inside a tick (diagnostic switch)
     // grid rules of the roles inside a tick (the stand-alone kernels size their grids for a GPU of their own; in a tick ~8 roles share it, and
     // fewer, longer workgroups amortise the per-workgroup prologues): environment overrides are for measurements
     // workgroups of a pass-1 / pass-2 launch (fft_walk_grid; 0: one tile per workgroup).  Measured on 65536-point frames, 2^24 samples per pass
@@ -287,30 +283,12 @@ struct sdrpp_ctx {
     int fft_p1_grid = getenv("SDRPP_GPU_FFT_P1_GRID") ? atoi(getenv("SDRPP_GPU_FFT_P1_GRID")) : 1024;
     int fft_p2_grid = getenv("SDRPP_GPU_FFT_P2_GRID") ? atoi(getenv("SDRPP_GPU_FFT_P2_GRID")) : 0;
     int fft_tick_grid = getenv("SDRPP_GPU_FFT_TICK_GRID") ? atoi(getenv("SDRPP_GPU_FFT_TICK_GRID")) : 0;  // ... of a pass-1 / pass-2 role inside a tick (a shared GPU: 18.4 / 16.2 / 18.8 / 18.5 GS/s at 0 / 64 / 128 / 256; cfg 2: 61.7 / - / 57.0)
-    bool fft_p1_c32 = getenv("SDRPP_GPU_FFT_P1_C32") != nullptr;  // measurement switch: 32 instead of 16 columns per pass-1 workgroup of a 65536-point transform
     int tick_zoom_groups = getenv("SDRPP_GPU_TICK_ZOOM_GROUPS") ? atoi(getenv("SDRPP_GPU_TICK_ZOOM_GROUPS")) : 8;
     int tick_fcm_waves = getenv("SDRPP_GPU_TICK_FCM_WAVES") ? atoi(getenv("SDRPP_GPU_TICK_FCM_WAVES")) : 768;
     int tick_toep_blocks = getenv("SDRPP_GPU_TICK_TOEP_BLOCKS") ? atoi(getenv("SDRPP_GPU_TICK_TOEP_BLOCKS")) : 256;
-    // FM back ends as ONE role of the tick (last decimator -> resampler -> channel filter -> discriminator + audio low-pass in a workgroup, the
-    // streams between them in LDS: pipe_kernels.h) instead of four roles on four ticks.  Bit-identical, two levels shallower, half the
-    // inter-stage traffic — and SLOWER wherever it was measured (profiles/r04j_pipe_role_sweep.log): a segment's four coupled stages are one
-    // long dependent walk (10^6-sample blocks: tick 82.6 us with 256 workgroups, 70.8 with 512, against 50.0 for the four roles; sr/200 blocks
-    // 32 us against 12), and blocks shorter than a filter history per VFO (cfg 4's NFM channels at sr/200) would fall back to ordinary passes.
-    // Off by default; SDRPP_GPU_TICK_PIPE=1 for measurements (tests/test_pipelined.py keeps it bit-identical).
-    // Large blocks in pipelined mode: the ratio-32 front end in its 16 x 16 x 4 shape walking its tiles (vfo_frontcm16w_body: 84 registers, 31 KB of
-    // LDS), so that the whole tick runs in the FOUR-wavefronts-per-SIMD build of the tick kernel (tick_kernel<2>) instead of the three the
-    // 32 x 32 x 2 front end's 168 registers / 41 KB allow.  Built to test the reading that the SIMDs idle behind latency with three wavefronts
-    // each — and measured (10^6-sample blocks, 200 steps, profiles/r04n_*, r04o_*): the SAME roles at three and at four wavefronts per SIMD take
-    // 55.8 / 55.9 us per tick (768 front-end workgroups; 57.5 / 55.6 with 1 024): occupancy is NOT what limits the tick, and the 16 x 16 x 4 front
-    // end itself costs 5.5 us more than the 32 x 32 x 2 one (49.9 us: twice the LDS reads and twice the vector instructions per matrix cycle).
-    // Bit-identical (tests/test_pipelined.py), off by default: a measurement switch.
-    bool tick_fcm16w = getenv("SDRPP_GPU_TICK_FCM16W") ? atoi(getenv("SDRPP_GPU_TICK_FCM16W")) != 0 : false;
-    int tick_fcm16w_blocks = getenv("SDRPP_GPU_TICK_FCM16W_BLOCKS") ? std::max(1, atoi(getenv("SDRPP_GPU_TICK_FCM16W_BLOCKS"))) : 512;
     int tick_land_blocks = getenv("SDRPP_GPU_TICK_LAND_BLOCKS") ? std::max(1, atoi(getenv("SDRPP_GPU_TICK_LAND_BLOCKS"))) : 64;  // workgroups of a tick's landing copy (host-fed blocks), at most
     int tick_lds_cap = 24 * 1024;       // LDS window of the many-phase resampler as a role of a tick (launch_polyc)
     int tick_lds_cap_fir = 40 * 1024;   // ... of the register-blocked FIR roles (launch_fir)
-    bool tick_pipe = getenv("SDRPP_GPU_TICK_PIPE") ? atoi(getenv("SDRPP_GPU_TICK_PIPE")) != 0 : false;
-    int tick_pipe_blocks = getenv("SDRPP_GPU_TICK_PIPE_BLOCKS") ? std::max(1, atoi(getenv("SDRPP_GPU_TICK_PIPE_BLOCKS"))) : 256;
     long arena_begins = 0;                // blocks planned so far (block_bounds: one per ordinary pass / per block of a pipelined run)
     int arena_allocs = 0;
     long test_fail_pass = 0;              // SDRPP_GPU_TEST_FAIL_ARENA (see arena_push)
@@ -319,24 +297,16 @@ struct sdrpp_ctx {
     float2 pre_dc_last = { 0.0f, 0.0f };  // the DC blocker's estimate when it was last looked at (sdrpp_preproc_reconfigure: the reference's block object lives on through every re-plan of the chain)
     std::vector<const volatile uint32_t*> stage_pend;  // sdrpp_push_staged_when: the block's first launch waits (on the host) for these words to reach 0
     bool rot_exact_single = getenv("SDRPP_GPU_ROT_EXACT_SINGLE") != nullptr;  // measurement switch: the one-wavefront form of the reference rotator
-    // VFOs per workgroup of vfo_rotate_exact4_kernel (1 .. 64).  The chain wavefront costs the same for 1 or 64 VFOs (a lane each); the three
-    // wavefronts that apply the phases take ~100 cycles per VFO and chunk: beyond ~16 VFOs they, not the chain, set the pace of the workgroup
-    // and the input is 8 bytes per sample however often it is read.
     // 32-output tiles per front-end job up to which the ratio-32 front end runs in its small-block shape (vfo_frontcm16_body); 0: never.
     // Unset: 256 for ordinary passes (sr/200 pushes 764 -> 814 MS/s) and for pipelined blocks that are read where they lie in device memory
     // (3.48 -> 3.96 GS/s), never for blocks the tick's landing copy fetches from host memory — workgroups that share a CU with a landing-copy
     // workgroup start 8 us late, which the longer front end hides and the short one does not (DESIGN_HISTORY.md 4b, profiles/r03zl-r03zn).
     int fcm16_max_tiles = getenv("SDRPP_GPU_FCM16_MAX_TILES") ? atoi(getenv("SDRPP_GPU_FCM16_MAX_TILES")) : -1;
     bool plan_block_from_host = false;    // the block being planned reaches the device through a landing copy
-    // phases handed over per full chunk: every 4th / 8th / 16th (cfg 4's 43 SSB channels, the family's time per 2^20 samples: 14.2 / 13.4 / 13.0 ms,
-    // profiles/r03x_*; the applying wavefronts take up to SKIP - 1 steps per sample themselves, so fewer VFOs per workgroup go with a larger stride)
-    int rot_exact_skip = getenv("SDRPP_GPU_ROTX_SKIP") ? atoi(getenv("SDRPP_GPU_ROTX_SKIP")) : 16;
+    // VFOs per workgroup of vfo_rotate_exact4_kernel (1 .. 64).  The chain wavefront costs the same for 1 or 64 VFOs (a lane each); the three
+    // wavefronts that apply the phases take ~100 cycles per VFO and chunk: beyond ~16 VFOs they, not the chain, set the pace of the workgroup
+    // and the input is 8 bytes per sample however often it is read.
     int rot_exact_vpw = [] { const char* e = getenv("SDRPP_GPU_ROTX_VPW"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : (v > 64 ? 64 : v); }();
-    // Grids of a block that is planned while the device has nothing (factor 4) or one launch (2) in flight: its roles will run in ticks that hold little
-    // else — the fill of the pipeline after a pause, a host slower than the device — where the grid rules above (sized for a tick that ~8 roles of
-    // as many blocks share) leave most of the device idle.  The results do not depend on the grids.  SDRPP_GPU_TICK_SPARSE=0: off (measurements).
-    int plan_sparse = 1;
-    bool tick_sparse_boost = getenv("SDRPP_GPU_TICK_SPARSE") ? atoi(getenv("SDRPP_GPU_TICK_SPARSE")) != 0 : false;  // (measured: no gain on the 20-step line, profiles/r06j_sparse_ab.log — off)
     bool tick_planning = false;           // a block is being planned for the tick queue: emit() queues, plain launches abort the plan
     bool tick_abort = false;              // ... and met a launch that has no role in the tick kernel: the block runs as an ordinary pass
     int plan_top = 0;                     // highest level + 1 the block being planned uses
@@ -401,15 +371,10 @@ struct sdrpp_ctx {
     hipEvent_t tick_ev_start[kTickEvents] = {}; // timing on: the start event of that tick's launch (the pair is read out when the entry comes round again, or at timing_flush)
     int tick_ev_next = 0;
     uint64_t tick_ev_last = 0;                 // the newest tick an event stands behind
-    // measurement switches: an event behind every n-th tick with results (a waiter takes the first event at or behind its tick, recording one on
-    // demand); the event as the tick launch's own completion signal (hipExtLaunchKernelGGL's stop event) instead of a packet of its own
-    int tick_ev_every = getenv("SDRPP_GPU_TICK_EVENT_EVERY") ? std::max(1, atoi(getenv("SDRPP_GPU_TICK_EVENT_EVERY"))) : 1;
-    bool tick_ev_ext = getenv("SDRPP_GPU_TICK_EVENT_EXT") ? atoi(getenv("SDRPP_GPU_TICK_EVENT_EXT")) != 0 : true;  // (15.8 against 15.2 GS/s with the event as a packet of its own: profiles/r04h_*)
-    int tick_ev_skipped = 0;
     void* bank_plan = nullptr;            // the context's BankPlan (plan_vfo.h), re-used block after block
     void (*bank_plan_free)(void*) = nullptr;
     // how the blocks of a pipelined run were executed (sdrpp_pipeline_stats: tests and bench.py assert the mode they mean to measure)
-    int64_t stat_tick_blocks = 0, stat_pass_blocks = 0, stat_crowded = 0, stat_last_depth = 0, stat_set2 = 0, stat_last_table_bytes = 0;
+    int64_t stat_tick_blocks = 0, stat_pass_blocks = 0, stat_crowded = 0, stat_last_depth = 0, stat_last_table_bytes = 0;
     int64_t stat_role_wgs[64] = {};
 
     // timing

@@ -198,8 +198,6 @@ int stream_ring_ensure(sdrpp_ctx* c, Stream& s) {
 }
 void stream_rotate(Stream& s) {
     if (s.n_extra == 0 || !s.base) { return; }
-    s.prev_data = s.data;
-    s.prev_n = s.n;
     std::swap(s.base, s.extra[s.rot]);
     s.data = s.base;
     s.rot = (s.rot + 1) % s.n_extra;
@@ -270,9 +268,7 @@ int upload_blocked(sdrpp_ctx* c, float** dst, const float* h, int K, int D, int*
 void toep_free(ToepTab& T) {
     dev_free(T.d_tl);
     dev_free(T.d_lb);
-    const int kind = T.kind;
     T = ToepTab{};
-    T.kind = kind;
 }
 int toep_upload(sdrpp_ctx* c, ToepTab& T, const std::vector<float>& tl, const std::vector<int>& lb) {
     dev_free(T.d_tl);
@@ -288,11 +284,6 @@ int toep_upload(sdrpp_ctx* c, ToepTab& T, const std::vector<float>& tl, const st
     // long filters stay on the register-blocked VALU kernels
     const int span = (2 * 16 - 1) * T.s_in + 4 * T.nsteps, pl = (span + 8) & ~3;
     T.ok = ((size_t)((T.tl_len + 3) & ~3) + (size_t)4 * 2 * pl) * sizeof(float) <= (size_t)(160 * 1024 / 3);
-    // A/B switch for benchmarking: SDRPP_GPU_VALU_FIR=<mask> keeps the register-blocked VALU kernels (1: decimators, 2: resampler,
-    // 4: channel filter, 8: audio low-pass; 15 = all)
-    if (const char* e = getenv("SDRPP_GPU_VALU_FIR")) {
-        if (atoi(e) & T.kind) { T.ok = false; }
-    }
     return SDRPP_OK;
 }
 // FIR decimating by D: tile = 15 outputs, window offset k' = D * m + k  ->  B[k'][m] = h[k' - D * m]
@@ -497,7 +488,6 @@ void launch_role(sdrpp_ctx* c, const sdrpp_ctx::RoleLaunch& r) {
     case TR_FCM_10: hipLaunchKernelGGL((vfo_frontcm_kernel<10, 0, 0>), grid, b256, r.lds, st, e.p.src, (const FrontCMJob*)e.jobs); break;
     case TR_FCM_16: hipLaunchKernelGGL((vfo_frontcm_kernel<16, 0, 0>), grid, b256, r.lds, st, e.p.src, (const FrontCMJob*)e.jobs); break;
     case TR_FCM16_132_4: hipLaunchKernelGGL((vfo_frontcm16_kernel<132, 4>), grid, b256, r.lds, st, e.p.src, (const FrontCMJob*)e.jobs); break;
-    case TR_FCM16W_132_4: hipLaunchKernelGGL((vfo_frontcm16w_kernel<132, 4>), grid, b256, r.lds, st, e.p.src, (const FrontCMJob*)e.jobs); break;
     case TR_FCL_0: hipLaunchKernelGGL((vfo_frontcl_kernel<0>), grid, dim3(128), r.lds, st, e.p.src, (const FrontCMJob*)e.jobs); break;
     case TR_FCL_PF: hipLaunchKernelGGL((vfo_frontcl_kernel<SDRPP_FCL_PF>), grid, dim3(128), r.lds, st, e.p.src, (const FrontCMJob*)e.jobs); break;
     case TR_TOEP_C: hipLaunchKernelGGL((vfo_toep_kernel<2, 2, false>), grid, b256, r.lds, st, (const ToepJob*)e.jobs); break;

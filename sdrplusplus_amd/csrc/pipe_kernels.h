@@ -461,7 +461,7 @@ __device__ __forceinline__ void pipe_role(float* smp, const PipeJob* __restrict_
     }
 }
 
-// (body of the launch and of the tick kernel's TR_PIPE role: bid.x = segment, gdim.x = segments per VFO, bid.y = job)
+// (body of vfo_pipe_kernel: bid.x = segment, gdim.x = segments per VFO, bid.y = job)
 template <int G>
 __device__ __forceinline__ void vfo_pipe_body(const KIdx bid, const KIdx gdim, float* smp, const PipeJob* __restrict__ jobs) {
     const PipeJob* __restrict__ Jp = jobs + bid.y;

@@ -135,13 +135,8 @@ int run_fft_chunk(sdrpp_ctx* c, const IqSrc& src, const FrameGeom& g, float* out
         case 5: launch_p1<5, 128>(c, src, g, lg2); break;
         case 6: launch_p1<6, 64>(c, src, g, lg2); break;
         case 7: launch_p1<7, 32>(c, src, g, lg2); break;
-        case 8:
-            // 16 columns (128-byte row segments, 256 work-items, 34 KB of LDS: four workgroups per CU) against 32 (256-byte segments, 512
-            // work-items, 66 KB: two): 0.064-0.069 ms against 0.098-0.106 per 2^24 samples (round 2 had measured the wider one 7 % ahead: before
-            // the window values left the load path)
-            if (c->fft_p1_c32) { launch_p1<8, 32>(c, src, g, lg2); }
-            else { launch_p1<8, 16>(c, src, g, lg2); }
-            break;
+        // (16 columns, 34 KB of LDS: four workgroups per CU; 32 columns, 66 KB, took 0.098-0.106 ms against 0.064-0.069 per 2^24 samples: DESIGN.md 6)
+        case 8: launch_p1<8, 16>(c, src, g, lg2); break;
         case 9: launch_p1<9, 8>(c, src, g, lg2); break;
         case 10: launch_p1<10, 4>(c, src, g, lg2); break;
         default: return fail(c, SDRPP_ERR_UNSUPPORTED, "fft pass-1 size 2^%d unsupported", lg1);

@@ -147,19 +147,12 @@ bool pipe_layout(PipeJob& J, size_t* lds_bytes) { return pipe_layout_try(J, 2, l
 // Segments per VFO, 0 = this push is better served by the separate launches.  A segment pays one warm-up macro tile per stage and the
 // pipeline's fill: with fewer than ~12 last-stage macro tiles per segment of a full grid the four launches win (measured: 1 M-sample
 // pushes of the 32-VFO bank, 2.6 tiles per segment, 14 % slower) — unless the push is so small that it is launch-bound anyway.
-int pipe_segments(const std::vector<PipeJob>& pipes, int forced, size_t lds, int tick_blocks = 0) {
+int pipe_segments(const std::vector<PipeJob>& pipes, int forced, size_t lds) {
     if (pipes.empty()) { return 0; }
     const int bpc = std::max(kPipeBpcMin, std::min(kPipeBpc, (int)((size_t)(160 * 1024) / std::max<size_t>(lds, 1))));
     int max_nmt = 1;
     for (auto& pj : pipes) { max_nmt = std::max(max_nmt, (pj.st[3].nout + kPipeG * 16 * pj.st[3].rows - 1) / (kPipeG * 16 * pj.st[3].rows)); }
     if (forced >= 2) { return std::min(forced, max_nmt); }
-    if (tick_blocks > 0) {
-        // a role of the tick kernel (pipelined mode): ALWAYS the pipeline — whether a VFO's back end runs as one role or as four is a property of
-        // its filters, never of the block, because the streams between the stages are handed from block to block differently in the two forms
-        // (do_vfos_plan) — with about `tick_blocks` workgroups for the whole role (a tick's roles share the GPU) and at least two last-stage
-        // macro tiles per segment (every segment pays one warm-up macro tile per stage)
-        return std::max(1, std::min((tick_blocks + (int)pipes.size() - 1) / (int)pipes.size(), (max_nmt + 1) / 2));
-    }
     const int s_full = (256 * bpc + (int)pipes.size() - 1) / (int)pipes.size();
     if (max_nmt >= 12 * s_full) { return s_full; }
     if (max_nmt <= 16) { return std::max(1, (max_nmt + 1) / 2); }  // two macro tiles per workgroup: the chain of hand-offs is what a small push waits for (B = 50 000: 53 us per push with one segment, 48.5 with three)
@@ -221,8 +214,11 @@ struct BankPlan {
     Lev<FirBJob> audio_fm;  // WFM/NFM: IF -> discriminator -> low-pass -> stereo, one kernel
     // the same work on the matrix cores (vfo_toep_kernel) whenever the VFO has a tap table for it
     Lev<ToepJob> t_dec, t_poly, t_chan, t_audio, t_audio_fm;
-    std::vector<PipeJob> pipes;  // FM back ends that run as one pipelined launch (all at the level of their decimator)
+    std::vector<PipeJob> pipes;  // FM back ends that run as one pipelined launch (ordinary passes only)
     size_t pipe_lds = 0;
+    PipeJob* d_pipes = nullptr;
+    int pipe_seg = 0;  // segments per VFO of that launch
+    int pipe_lvl = 0;  // its level: the latest at which any of its jobs starts (levels only order the launches of a pass)
     // radio AF chain (stereo frames have the layout of complex samples, so the same kernels serve)
     Lev<ToepJob> t_af_dec, t_af_poly, t_af_hpf;
     Lev<FirBJob> af_dec, af_hpf;
@@ -234,7 +230,7 @@ struct BankPlan {
     // front-end jobs (group_front)
     struct S1Launch { int vt; std::vector<Stage1Job> jobs; int max_nout = 0; int tile = 256; size_t lds = 0; };
     struct F2Launch { int vt; std::vector<Front2Job> jobs; int max_blocks = 0; size_t lds = 0; };
-    struct FCMLaunch { std::vector<FrontCMJob> jobs; int max_blocks = 0; size_t lds = 0; bool w16 = false; int w16_blocks = 0; };
+    struct FCMLaunch { std::vector<FrontCMJob> jobs; int max_blocks = 0; size_t lds = 0; };
     S1Launch s1l[4];
     F2Launch f2l[4];
     FCMLaunch fcm[3];  // PF 6 / 10 / 16
@@ -251,9 +247,6 @@ struct BankPlan {
     RetuneJob* d_retune = nullptr;
     RotJob* d_rot = nullptr;
     const int* d_fb = nullptr;
-    struct PipeGroup { int lvl = 0; std::vector<PipeJob> jobs; PipeJob* dev = nullptr; int seg = 0; };
-    std::vector<PipeGroup> pgroups;
-    int pipe_top = 0;
     struct ToepList { Lev<ToepJob>* L; int npl, width; bool quad; int fam; int role; };
     static constexpr int kToepLists = 8;
     ToepList tlists[kToepLists] = { { &t_dec, 2, 2, false, F_DECIM, TR_TOEP_C },      { &t_poly, 2, 2, false, F_POLY, TR_TOEP_C },       { &t_chan, 2, 2, false, F_FIR, TR_TOEP_C },
@@ -279,7 +272,7 @@ struct BankPlan {
         ticking = c->tick_planning;
         L0 = ticking ? c->plan_lvl0 : 0;
         blocks = fb.size() > 1;
-        s1.clear(); rot.clear(); rotx.clear(); retune.clear(); pipes.clear(); pgroups.clear();
+        s1.clear(); rot.clear(); rotx.clear(); retune.clear(); pipes.clear();
         lev_reset(f_dec); lev_reset(poly);
         for (auto& q : polyb) { lev_reset(q); }
         lev_reset(chan); lev_reset(seq); lev_reset(pre); lev_reset(audio); lev_reset(audio_fm);
@@ -287,8 +280,10 @@ struct BankPlan {
         lev_reset(t_af_dec); lev_reset(t_af_poly); lev_reset(t_af_hpf); lev_reset(af_dec); lev_reset(af_hpf); lev_reset(af_poly); lev_reset(af_deemp);
         lev_reset(ssbx_l); lev_reset(carry);
         pipe_lds = 0;
+        d_pipes = nullptr;
+        pipe_seg = 0;
+        pipe_lvl = 0;
         max_rot = 0;
-        pipe_top = 0;
         fcl_nw = 2;
         for (int i = 0; i < 4; i++) {
             s1l[i].jobs.clear(); s1l[i].max_nout = 0; s1l[i].tile = 256; s1l[i].lds = 0;
@@ -297,10 +292,10 @@ struct BankPlan {
             d_f2[i] = nullptr;
         }
         for (int i = 0; i < 3; i++) {
-            fcm[i].jobs.clear(); fcm[i].max_blocks = 0; fcm[i].lds = 0; fcm[i].w16 = false; fcm[i].w16_blocks = 0;
+            fcm[i].jobs.clear(); fcm[i].max_blocks = 0; fcm[i].lds = 0;
             d_fcm[i] = nullptr;
         }
-        fcl.jobs.clear(); fcl.max_blocks = 0; fcl.lds = 0; fcl.w16 = false; fcl.w16_blocks = 0;
+        fcl.jobs.clear(); fcl.max_blocks = 0; fcl.lds = 0;
         d_fcl = nullptr; d_rotx = nullptr; d_retune = nullptr; d_rot = nullptr; d_fb = nullptr;
         for (auto& row : tplan) {
             for (auto& q : row) { q = ToepPlan{}; }
@@ -459,26 +454,11 @@ struct BankPlan {
                 cur = nxt;
             }
         }
-        // the FM back end as one pipelined launch: last decimator, resampler, channel filter, discriminator + audio low-pass all in
-        // their matrix form, and the pipeline's LDS layout fits
+        // the FM back end as one pipelined launch (ordinary passes): last decimator, resampler, channel filter, discriminator + audio low-pass all
+        // in their matrix form, and the pipeline's LDS layout fits
         const int last_dec = v.d.n_stages - 1;
-        bool piped_be = c->pipe_on && (!ticking || c->tick_pipe) && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= first_sep && v.tp_stage[last_dec].ok &&
+        bool piped_be = c->pipe_on && !ticking && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= first_sep && v.tp_stage[last_dec].ok &&
                         v.i_poly >= 0 && v.tp_poly.ok && v.i_chan >= 0 && v.chan_ntaps > 0 && v.tp_chan.ok && v.tp_audio.ok;
-        // Pipelined mode: the four stages of a piped back end run in ONE tick (level L), so a stage cannot take the history of its input stream
-        // from the side buffer — the carry that fills it from the previous block's tail runs one level behind that block's pipeline role, i.e. in
-        // the very tick this block's role runs in.  It reads the tail where the previous block's role left it instead: the end of the previous
-        // block's data buffer (the buffers are a ring of kRing, that one is not written again for three more ticks).  Needs the previous block to
-        // have produced at least a history's worth of samples; a block after a shorter one runs as an ordinary pass (which waits for everything
-        // queued and finds the side buffers complete).  With nothing queued the side buffers ARE complete and are used as they stand.
-        auto pipe_in = [&](Stream& sx) -> StreamIn {
-            StreamIn in = stream_in(sx);
-            if (ticking && sx.hist_len > 0 && !c->tickq.empty()) {
-                if (sx.prev_data && sx.prev_n >= sx.hist_len) { in.hist = sx.prev_data + (size_t)(sx.prev_n - sx.hist_len) * (size_t)sx.width; }
-                else { c->tick_abort = true; }
-            }
-            return in;
-        };
-        const bool tick_piped = ticking;  // (all four stages at the level of the decimator)
         PipeJob pj{};
         size_t pj_lds = 0;
         if (piped_be) {
@@ -515,13 +495,10 @@ struct BankPlan {
             const int no = poly_nout(cur->n, v.poff, v.pphase, v.d.interp, v.d.decim);
             if (need_bnd) { bounds_poly(bnd, v.poff, v.pphase, v.d.interp, v.d.decim); }
             if (split) { bounds_poly(tk, v.poff, v.pphase, v.d.interp, v.d.decim); }
-            if (piped_be && tick_piped) { cur->clevel = lvl + 1; }  // (its tail is carried one level behind the role that writes it)
-            else {
-                lvl++;
-                cur->clevel = lvl;
-            }
+            lvl++;
+            cur->clevel = lvl;
             if (piped_be) {
-                pj.st[1] = toep_job(v.tp_poly, v.pphase, tick_piped ? pipe_in(*cur) : stream_in(*cur), nxt->data, v.poff - (v.tpp - 1), no, 0.0f);
+                pj.st[1] = toep_job(v.tp_poly, v.pphase, stream_in(*cur), nxt->data, v.poff - (v.tpp - 1), no, 0.0f);
                 pj.keep[1] = std::max(0, no - nxt->hist_len);
             }
             else if (v.tp_poly.ok) { t_poly.add(lvl, toep_job(v.tp_poly, v.pphase, stream_in(*cur), nxt->data, v.poff - (v.tpp - 1), no, 0.0f)); }
@@ -541,13 +518,10 @@ struct BankPlan {
         }
         if (v.i_chan >= 0 && v.chan_ntaps > 0) {
             Stream* nxt = &v.st[(size_t)v.i_chan];
-            if (piped_be && tick_piped) { cur->clevel = lvl + 1; }
-            else {
-                lvl++;
-                cur->clevel = lvl;
-            }
+            lvl++;
+            cur->clevel = lvl;
             if (piped_be) {
-                pj.st[2] = toep_job(v.tp_chan, 0, tick_piped ? pipe_in(*cur) : stream_in(*cur), nxt->data, -(v.chan_ntaps - 1), cur->n, 0.0f);
+                pj.st[2] = toep_job(v.tp_chan, 0, stream_in(*cur), nxt->data, -(v.chan_ntaps - 1), cur->n, 0.0f);
                 pj.keep[2] = 0;  // the IF stream is the RxVFO's output: all of it
             }
             else if (v.tp_chan.ok) { t_chan.add(lvl, toep_job(v.tp_chan, 0, stream_in(*cur), nxt->data, -(v.chan_ntaps - 1), cur->n, 0.0f)); }
@@ -570,13 +544,10 @@ struct BankPlan {
         const int nbnd = need_bnd ? (int)bnd.size() : 0;
         if (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) {
             Stream& out = v.st[(size_t)v.i_out];
-            if (piped_be && tick_piped) { cur->clevel = lvl + 1; }
-            else {
-                lvl++;
-                cur->clevel = lvl;
-            }
+            lvl++;
+            cur->clevel = lvl;
             if (piped_be) {
-                pj.st[3] = toep_job(v.tp_audio, 0, tick_piped ? pipe_in(*cur) : stream_in(*cur), out.data, -(v.audio_ntaps - 1), nif, v.d.inv_deviation);
+                pj.st[3] = toep_job(v.tp_audio, 0, stream_in(*cur), out.data, -(v.audio_ntaps - 1), nif, v.d.inv_deviation);
                 pipes.push_back(pj);
                 pipe_lds = std::max(pipe_lds, pj_lds);
             }
@@ -826,7 +797,7 @@ struct BankPlan {
                 const int long_blocks = m_long ? std::max(1, (int)((size_t)(160 * 1024) / ((size_t)frontcl_lds_floats(K, lgD, fcl_nw) * 4))) : 0;
                 // (a launch group brings one job per push: together they get the wavefronts one job of the whole block would)
                 const int nsub = std::max<int>(1, (int)c->grp_ends.size());
-                const int resident = std::max(64, (m_long ? 256 * long_blocks * fcl_nw : (c->tick_planning ? std::min(3072, c->tick_fcm_waves * c->plan_sparse) : 3072)) / nsub);
+                const int resident = std::max(64, (m_long ? 256 * long_blocks * fcl_nw : (c->tick_planning ? std::min(3072, c->tick_fcm_waves) : 3072)) / nsub);
                 job.tiles_per_wave = std::max(1, (ntiles + resident - 1) / resident);
                 job.atab = reinterpret_cast<const float*>(d_taps);
                 job.ptab = d_taps + (size_t)NP4 * 32;
@@ -843,12 +814,6 @@ struct BankPlan {
                 }
                 else {
                     FCMLaunch& L = fcm[m_pf == 6 ? 0 : (m_pf == 10 ? 1 : 2)];
-                    if (ticking && c->tick_fcm16w && K == 132 && lgD == 4 && (L.jobs.empty() || L.w16)) {
-                        // the 16 x 16 x 4 shape walking its tiles: the field counts tiles per WORKGROUP there (vfo_frontcm16w_body)
-                        job.tiles_per_wave = std::max(1, (ntiles + c->tick_fcm16w_blocks - 1) / c->tick_fcm16w_blocks);
-                        L.w16 = true;
-                        L.w16_blocks = std::max(L.w16_blocks, (ntiles + job.tiles_per_wave - 1) / job.tiles_per_wave);
-                    }
                     L.jobs.push_back(job);
                     L.max_blocks = std::max(L.max_blocks, (ntiles + 4 * job.tiles_per_wave - 1) / (4 * job.tiles_per_wave));
                     L.lds = std::max(L.lds, (size_t)frontcm_layout(K, lgD).total * 4);
@@ -970,9 +935,7 @@ struct BankPlan {
             // mostly start-up (window fetch, tile phasor, epilogue) around a matrix loop of 3 us (16 rows) .. 12 us (32 rows), and a wavefront that
             // walks several tiles fetches the next window under the current loop — but the walks must still fill the device: the best setting
             // put ~0.7 of the resident wavefront slots to work (cfg 4 at 10^6-sample blocks: 2 tiles per 32-row, 4 per 16-row wavefront, 8.29 ->
-            // 8.89 GS/s; at 307 200: 1 and 2, 5.11 -> 5.26; twice that was 15 % slower at either size).  SDRPP_GPU_FCL_TPW / _TPW16 override.
-            static const int tpw32_env = getenv("SDRPP_GPU_FCL_TPW") ? atoi(getenv("SDRPP_GPU_FCL_TPW")) : 0;
-            static const int tpw16_env = getenv("SDRPP_GPU_FCL_TPW16") ? atoi(getenv("SDRPP_GPU_FCL_TPW16")) : 0;
+            // 8.89 GS/s; at 307 200: 1 and 2, 5.11 -> 5.26; twice that was 15 % slower at either size).
             size_t lds_max = 0;
             for (auto& jb : fcl.jobs) { lds_max = std::max(lds_max, (size_t)frontcl_lds_floats(jb.ntaps, jb.log2_decim, fcl_nw) * 4); }
             const int long_blocks = std::max(1, (int)((size_t)(160 * 1024) / std::max<size_t>(lds_max, 1)));
@@ -982,9 +945,8 @@ struct BankPlan {
             // the SAME number of tiles took 1.5x as long in one job as in another: the tick ended on the 400-tap jobs' workgroups (last end 337 us against a
             // mean life of 220, profiles/r06q_tick_timeline_cfg4_B1000000_group4.txt).  Walk lengths now follow a cost model, tile ~ c0 + c1 * taps (16-row
             // tiles: 0.45 of the matrix part), so that every wavefront of the role is busy about equally long; the total number of wavefronts still follows
-            // the 0.7-of-the-resident-slots rule.  SDRPP_GPU_FCL_BALANCE=0: the old rule (measurements).
-            static const bool balance = getenv("SDRPP_GPU_FCL_BALANCE") ? atoi(getenv("SDRPP_GPU_FCL_BALANCE")) != 0 : true;
-            static const double c0 = getenv("SDRPP_GPU_FCL_C0") ? atof(getenv("SDRPP_GPU_FCL_C0")) : 1.5, c1 = getenv("SDRPP_GPU_FCL_C1") ? atof(getenv("SDRPP_GPU_FCL_C1")) : 0.031;
+            // the 0.7-of-the-resident-slots rule (profiles/r06s_fcl_balance.log).
+            constexpr double c0 = 1.5, c1 = 0.031;
             auto tile_cost = [&](const FrontCMJob& jb) { return c0 + c1 * (double)jb.ntaps * (jb.nv <= 16 ? 0.45 : 1.0); };
             double total_cost = 0.0;
             for (auto& jb : fcl.jobs) {
@@ -995,12 +957,11 @@ struct BankPlan {
             for (auto& jb : fcl.jobs) {
                 const int tile_n = jb.nv <= 16 ? 16 : SDRPP_FCM_TILE;
                 const int ntiles = (jb.nout + tile_n - 1) / tile_n;
-                const int env = tile_n == 16 ? tpw16_env : tpw32_env;
                 // (ticks: the rule above.  An ordinary pass has the device to itself and its pushes are long: one resident round per JOB as before —
                 // the 0.7 rule gave walks of 34 tiles at 2^24-sample pushes and lost 17 % there, profiles/r05z_bench_default.json vs r05d)
                 const int resident = 256 * long_blocks * fcl_nw;
-                int tpw = env > 0 ? env : (ticking ? std::max(1, (int)((double)ntiles * (double)fcl.jobs.size() / target + 0.75)) : std::max(1, (ntiles + resident - 1) / resident));
-                if (env <= 0 && ticking && balance && fcl.jobs.size() > 1) { tpw = std::max(1, (int)(per_wave / tile_cost(jb) + 0.5)); }
+                int tpw = ticking ? std::max(1, (int)((double)ntiles * (double)fcl.jobs.size() / target + 0.75)) : std::max(1, (ntiles + resident - 1) / resident);
+                if (ticking && fcl.jobs.size() > 1) { tpw = std::max(1, (int)(per_wave / tile_cost(jb) + 0.5)); }
                 jb.tiles_per_wave = tpw;
                 fcl.max_blocks = std::max(fcl.max_blocks, (ntiles + fcl_nw * tpw - 1) / (fcl_nw * tpw));
             }
@@ -1024,10 +985,9 @@ struct BankPlan {
             if (!d_rotx_head) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
         }
         if ((!rotx.empty() && (!d_rotx || !d_fb)) || (!retune.empty() && !d_retune) || (!rot.empty() && !d_rot)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
-        // Pipelined back ends.  An ordinary pass: ONE launch, at the latest level any of its jobs starts at (levels only order the launches of a
-        // pass) — or none, when this push is better served by the separate launches.  Pipelined mode: one role per LEVEL (a role that ran later
-        // than its VFO's level would find the history of its first stage's input overwritten by the next block's carry), always the pipeline.
-        if (!pipes.empty() && !ticking && pipe_segments(pipes, c->pipe_on, pipe_lds) == 0) {  // not this push: the same four jobs go to the separate launches
+        // Pipelined back ends: ONE launch — or none, when this push is better served by the separate launches
+        pipe_seg = pipe_segments(pipes, c->pipe_on, pipe_lds);
+        if (!pipes.empty() && pipe_seg == 0) {  // not this push: the same four jobs go to the separate launches
             for (auto& pj : pipes) {
                 t_dec.add(pj.lvl, pj.st[0]);
                 t_poly.add(pj.lvl + 1, pj.st[1]);
@@ -1036,30 +996,16 @@ struct BankPlan {
             }
             pipes.clear();
         }
-        for (auto& pj : pipes) {
-            PipeGroup* g = nullptr;
-            for (auto& q : pgroups) {
-                if (!ticking || q.lvl == pj.lvl) { g = &q; }
-            }
-            if (!g) {
-                pgroups.emplace_back();
-                g = &pgroups.back();
-                g->lvl = pj.lvl;
-            }
-            g->lvl = std::max(g->lvl, pj.lvl);
-            g->jobs.push_back(pj);
-        }
-        for (auto& g : pgroups) {
-            g.seg = pipe_segments(g.jobs, c->pipe_on, pipe_lds, ticking ? c->tick_pipe_blocks : 0);
-            g.dev = arena_push(c, g.jobs);
-            if (!g.dev) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
-            pipe_top = std::max(pipe_top, g.lvl + 1);
+        if (!pipes.empty()) {
+            for (auto& pj : pipes) { pipe_lvl = std::max(pipe_lvl, pj.lvl); }
+            d_pipes = arena_push(c, pipes);
+            if (!d_pipes) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
         }
         for (int i = 0; i < kToepLists; i++) {
             Lev<ToepJob>& L = *tlists[i].L;
             for (int l = 0; l < L.top; l++) {
                 if (L.at[l].empty()) { continue; }
-                tplan[i][l] = toep_plan(L.at[l], tlists[i].npl, c->tick_planning ? std::min(2048, c->tick_toep_blocks * c->plan_sparse) : 2048);
+                tplan[i][l] = toep_plan(L.at[l], tlists[i].npl, c->tick_planning ? std::min(2048, c->tick_toep_blocks) : 2048);
                 if (tplan[i][l].lds > (size_t)kMaxLds) { return fail(c, SDRPP_ERR_UNSUPPORTED, "matrix-core FIR window does not fit in LDS"); }
             }
             if (!arena_push_lev(c, L)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
@@ -1085,15 +1031,13 @@ struct BankPlan {
             FamilyTimer t(c, F_S1);
             if (!rotx.empty() && n_in > 0) {
                 if (c->rot_exact_single) { launch(c, vfo_rotate_exact_kernel, dim3(((unsigned)rotx.size() + 63) / 64), dim3(64), (size_t)64 * 65 * sizeof(float2), src, (const RotXJob*)d_rotx, (int)rotx.size(), d_fb, (int)fb.size()); }
-                else if (c->tick_planning && c->rot_exact_skip >= 16) {  // pipelined: the chain as a role of the tick (level 1: its VFOs' first stages follow at level 2)
+                else if (c->tick_planning) {  // pipelined: the chain as a role of the tick (level 1: its VFOs' first stages follow at level 2)
                     emit(c, L0 + 1, F_S1, TR_ROTX16, ((int)rotx.size() + c->rot_exact_vpw - 1) / c->rot_exact_vpw, 1, SDRPP_ROTX4_LDS_BYTES, d_rotx_head, &src);
                 }
                 else {
                     const int vpw = c->rot_exact_vpw;
                     const dim3 grid(((unsigned)rotx.size() + vpw - 1) / vpw);
-                    if (c->rot_exact_skip >= 16) { launch(c, vfo_rotate_exact4_kernel<16>, grid, dim3(256), SDRPP_ROTX4_LDS_BYTES, src, (const RotXJob*)d_rotx, (int)rotx.size(), d_fb, (int)fb.size(), vpw); }
-                    else if (c->rot_exact_skip >= 8) { launch(c, vfo_rotate_exact4_kernel<8>, grid, dim3(256), SDRPP_ROTX4_LDS_BYTES, src, (const RotXJob*)d_rotx, (int)rotx.size(), d_fb, (int)fb.size(), vpw); }
-                    else { launch(c, vfo_rotate_exact4_kernel<4>, grid, dim3(256), SDRPP_ROTX4_LDS_BYTES, src, (const RotXJob*)d_rotx, (int)rotx.size(), d_fb, (int)fb.size(), vpw); }
+                    launch(c, vfo_rotate_exact4_kernel<16>, grid, dim3(256), SDRPP_ROTX4_LDS_BYTES, src, (const RotXJob*)d_rotx, (int)rotx.size(), d_fb, (int)fb.size(), vpw);
                 }
             }
             for (int k = 0; k < 4; k++) {
@@ -1161,10 +1105,6 @@ struct BankPlan {
                 for (auto& jb : fcm[k].jobs) {
                     max_tiles = std::max(max_tiles, (jb.nout + SDRPP_FCM_TILE - 1) / SDRPP_FCM_TILE);
                     one_tile = one_tile && jb.tiles_per_wave == 1;
-                }
-                if (fcm[k].w16 && role == TR_FCM_132_4 && !(one_tile && max_tiles <= 256 && !c->plan_block_from_host)) {
-                    emit(c, L0 + 1, F_S1, TR_FCM16W_132_4, fcm[k].w16_blocks, (int)fcm[k].jobs.size(), (size_t)frontcm16w_layout(132, 4).total * 4, d_fcm[k], &src);
-                    continue;
                 }
                 const int small_limit = c->fcm16_max_tiles >= 0 ? c->fcm16_max_tiles : ((c->tick_planning && c->plan_block_from_host) ? 0 : 256);
                 if (role == TR_FCM_132_4 && one_tile && max_tiles > 0 && max_tiles <= small_limit) {
@@ -1338,7 +1278,7 @@ struct BankPlan {
         int rc = SDRPP_OK;
         int top = std::max({ t_dec.top, t_poly.top, t_chan.top, t_audio.top, t_audio_fm.top, t_af_dec.top, t_af_poly.top, t_af_hpf.top, f_dec.top, poly.top,
                              polyb[0].top, polyb[1].top, polyb[2].top, polyb[3].top, chan.top, seq.top, pre.top, audio.top, audio_fm.top, af_dec.top, af_hpf.top,
-                             af_poly.top, af_deemp.top, ssbx_l.top, carry.top, pipe_top });
+                             af_poly.top, af_deemp.top, ssbx_l.top, carry.top, d_pipes ? pipe_lvl + 1 : 0 });
         for (int l = 1; l < top; l++) {
             {
                 FamilyTimer t(c, F_DECIM);
@@ -1348,11 +1288,10 @@ struct BankPlan {
                     if (rc) { return rc; }
                 }
             }
-            for (auto& g : pgroups) {
-                if (g.lvl != l || g.seg <= 0) { continue; }
+            if (d_pipes && l == pipe_lvl) {
                 FamilyTimer t(c, F_PIPE);
                 c->pipe_launched = true;
-                emit(c, l, F_PIPE, TR_PIPE, g.seg, (int)g.jobs.size(), pipe_lds, g.dev);
+                emit(c, l, F_PIPE, TR_PIPE, pipe_seg, (int)pipes.size(), pipe_lds, d_pipes);
             }
             {
                 FamilyTimer t(c, F_POLY);

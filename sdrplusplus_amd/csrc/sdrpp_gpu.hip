@@ -671,7 +671,6 @@ int sdrpp_preproc_configure(sdrpp_ctx* c, int n_stages, const int* stage_decim, 
         P.staps[s].assign(stage_taps[s], stage_taps[s] + stage_ntaps[s]);
         rc = upload_blocked(c, &P.d_staps[s], P.staps[s].data(), (int)P.staps[s].size(), P.decim_s[s], &P.s_kp[s]);
         if (rc) { return rc; }
-        P.tp[s].kind = 1;
         rc = toep_build_fir(c, P.tp[s], P.staps[s].data(), (int)P.staps[s].size(), P.decim_s[s]);
         if (rc) { return rc; }
         cap = cap / (size_t)P.decim_s[s] + 2;
@@ -832,7 +831,6 @@ int sdrpp_vfo_add(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
         rc = upload(c, &v->d_staps_nat[s], v->staps[s].data(), v->staps[s].size());
         if (rc) { return rc; }
         if (s >= 1 || v->nco_exact) {  // stage 0 runs as a plain FIR only behind the reference rotator
-            v->tp_stage[s].kind = 1;
             rc = toep_build_fir(c, v->tp_stage[s], v->staps[s].data(), (int)v->staps[s].size(), d->stage_decim[s]);
             if (rc) { return rc; }
         }
@@ -887,7 +885,6 @@ int sdrpp_vfo_add(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
         for (int i = 0; i < tot; i++) { bank[(size_t)((d->interp - 1) - (i % d->interp)) * tpp + (size_t)(i / d->interp)] = (i < d->resamp_ntaps) ? v->rtaps[(size_t)i] : 0.0f; }  // polyphase_bank.h:31-34
         rc = upload(c, &v->d_bank, bank.data(), bank.size());
         if (rc) { return rc; }
-        v->tp_poly.kind = 2;
         rc = toep_build_poly(c, v->tp_poly, bank, d->interp, d->decim, tpp);
         if (rc) { return rc; }
         if (d->interp <= 8) {  // register-blocked kernel: per carried phase, taps of one full phase cycle
@@ -916,7 +913,6 @@ int sdrpp_vfo_add(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
         v->ctaps_chan.assign(d->chan_taps, d->chan_taps + d->chan_ntaps);
         rc = upload_blocked(c, &v->d_chan, v->ctaps_chan.data(), (int)v->ctaps_chan.size(), 1, &v->chan_kp);
         if (rc) { return rc; }
-        v->tp_chan.kind = 4;
         rc = toep_build_fir(c, v->tp_chan, v->ctaps_chan.data(), (int)v->ctaps_chan.size(), 1);
         if (rc) { return rc; }
         v->chan_ntaps = d->chan_ntaps;
@@ -932,7 +928,6 @@ int sdrpp_vfo_add(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
             v->audio_ntaps = an;
             rc = upload_blocked(c, &v->d_audio, v->ataps.data(), (int)v->ataps.size(), 1, &v->audio_kp);
             if (rc) { return rc; }
-            v->tp_audio.kind = 8;
             rc = toep_build_fir(c, v->tp_audio, v->ataps.data(), (int)v->ataps.size(), 1);
             if (rc) { return rc; }
             if (!fm) {  // AM: the sequential envelope/AGC kernel writes a real stream for the low-pass; FM demodulates inside the FIR kernel
@@ -1142,7 +1137,6 @@ int sdrpp_vfo_set_channel_taps(sdrpp_ctx* c, int id, const float* taps, int n) {
     if (n > 0) {
         int rc = upload_blocked(c, &v.d_chan, v.ctaps_chan.data(), n, 1, &v.chan_kp);
         if (rc) { return rc; }
-        v.tp_chan.kind = 4;
         rc = toep_build_fir(c, v.tp_chan, v.ctaps_chan.data(), n, 1);
         if (rc) { return rc; }
     }
@@ -1215,7 +1209,6 @@ int sdrpp_vfo_set_af(sdrpp_ctx* c, int id, const sdrpp_af_desc* af) {
         a.staps[s].assign(af->stage_taps[s], af->stage_taps[s] + af->stage_ntaps[s]);
         rc = upload_blocked(c, &a.d_staps[s], a.staps[s].data(), (int)a.staps[s].size(), a.decim_s[s], &a.s_kp[s]);
         if (rc) { return rc; }
-        a.tp_stage[s].kind = 1;
         rc = toep_build_fir(c, a.tp_stage[s], a.staps[s].data(), (int)a.staps[s].size(), a.decim_s[s]);
         if (rc) { return rc; }
         cap = cap / (size_t)a.decim_s[s] + 2;
@@ -1230,7 +1223,6 @@ int sdrpp_vfo_set_af(sdrpp_ctx* c, int id, const sdrpp_af_desc* af) {
         for (int i = 0; i < tot; i++) { bank[(size_t)((a.interp - 1) - (i % a.interp)) * a.tpp + (size_t)(i / a.interp)] = (i < af->resamp_ntaps) ? a.rtaps[(size_t)i] : 0.0f; }  // polyphase_bank.h:31-34
         rc = upload(c, &a.d_bank, bank.data(), bank.size());
         if (rc) { return rc; }
-        a.tp_poly.kind = 2;
         rc = toep_build_poly(c, a.tp_poly, bank, a.interp, a.decim, a.tpp);
         if (rc) { return rc; }
         cap = cap * (size_t)a.interp / (size_t)a.decim + 4;
@@ -1241,7 +1233,6 @@ int sdrpp_vfo_set_af(sdrpp_ctx* c, int id, const sdrpp_af_desc* af) {
         a.htaps.assign(af->hpf_taps, af->hpf_taps + af->hpf_ntaps);
         rc = upload_blocked(c, &a.d_hpf, a.htaps.data(), (int)a.htaps.size(), 1, &a.hpf_kp);
         if (rc) { return rc; }
-        a.tp_hpf.kind = 4;
         rc = toep_build_fir(c, a.tp_hpf, a.htaps.data(), (int)a.htaps.size(), 1);
         if (rc) { return rc; }
         a.i_hpf = add_stream(0, cap);
@@ -2023,7 +2014,7 @@ int sdrpp_result_take_lines(sdrpp_ctx* c, uint64_t ticket, float* zoomed_dst, in
 }
 int sdrpp_pipeline_stats(sdrpp_ctx* c, int64_t* out, int max) {
     if (!c || !out || max < 0) { return SDRPP_ERR_INVALID; }
-    const int64_t head[SDRPP_PIPELINE_STATS_HEAD] = { (int64_t)c->ticks, c->stat_tick_blocks, c->stat_pass_blocks, c->stat_crowded, c->stat_last_depth, (int64_t)TR_COUNT, c->stat_set2, c->stat_last_table_bytes };
+    const int64_t head[SDRPP_PIPELINE_STATS_HEAD] = { (int64_t)c->ticks, c->stat_tick_blocks, c->stat_pass_blocks, c->stat_crowded, c->stat_last_depth, (int64_t)TR_COUNT, 0, c->stat_last_table_bytes };  // [6]: reserved, always 0
     int n = 0;
     for (; n < SDRPP_PIPELINE_STATS_HEAD && n < max; n++) { out[n] = head[n]; }
     for (int r = 0; r < TR_COUNT && n < max; r++, n++) { out[n] = c->stat_role_wgs[r]; }
@@ -2032,7 +2023,7 @@ int sdrpp_pipeline_stats(sdrpp_ctx* c, int64_t* out, int max) {
 const char* sdrpp_pipeline_role_name(int role) {
     static const char* const names[] = { "none", "copy", "carry", "rot", "fcm_132_4", "fcm_6", "fcm_10", "fcm_16", "fcm16_132_4", "fcl_0", "fcl_pf", "toep_c", "toep_r", "toep_q",
                                          "firb_c", "firb_r", "firb_s", "firb_q", "pre", "seq", "fft_s10", "fft_s11", "fft_s12", "fft_p1_5", "fft_p1_6", "fft_p1_7", "fft_p1_8", "fft_p1_9",
-                                         "fft_p1_10", "fft_p2_7", "fft_p2_8", "fft_p2_9", "fft_p2_10", "fft_p2row", "fft_tr", "zoom_16", "zoom_4", "zoom_1", "fcm16w_132_4", "polyc", "deemp_p0", "deemp_p1",
+                                         "fft_p1_10", "fft_p2_7", "fft_p2_8", "fft_p2_9", "fft_p2_10", "fft_p2row", "fft_tr", "zoom_16", "zoom_4", "zoom_1", "polyc", "deemp_p0", "deemp_p1",
                                          "dc_p0", "dc_p1", "wf_ring", "wf_trace", "pipe", "rotx16", "fird", "ssbx", "s1_1", "s1d_1", "f2_1", "poly" };
     static_assert(sizeof(names) / sizeof(names[0]) == TR_COUNT, "role names out of step with TickRole");
     return (role >= 0 && role < TR_COUNT) ? names[role] : nullptr;

@@ -63,39 +63,31 @@ bool tick_is_done(const sdrpp_ctx* c, uint64_t nticks) { return !c->h_tick_flag 
 // travels with this tick's upload.
 // expected lifetime of a workgroup of a role relative to the others (tools/tick_trace.py timelines), for the order inside a tick
 inline int tick_role_weight(int role, bool crowded) {
-    // result copies write page-locked host memory over the bus: few workgroups whose life is mostly that round trip — started last they are the
-    // tail of the tick, started first they finish in its shadow (SDRPP_GPU_TICK_COPY_FIRST=0: the old order, for measurements)
-    static const bool copy_first = getenv("SDRPP_GPU_TICK_COPY_FIRST") ? atoi(getenv("SDRPP_GPU_TICK_COPY_FIRST")) != 0 : true;
     if (role == TR_ROTX16) { return 120; }  // the reference's rotator recursion over the whole block: milliseconds — it IS the tick, everything else runs in its shadow
-    if (role == TR_COPY && copy_first) { return 110; }
+    // result copies write page-locked host memory over the bus: few workgroups whose life is mostly that round trip — started last they are the
+    // tail of the tick, started first they finish in its shadow
+    if (role == TR_COPY) { return 110; }
     // FFT pass 1: since its workgroups walk their tiles and take the lean loader they live ~12 us at 10^6-sample blocks, shorter than the
     // Toeplitz roles' 17-33 us.  In a CROWDED tick (more workgroups than the GPU holds at once: they are handed out in index order) they go
     // behind the filters and pass 2, so that the tick ends on short workgroups: 18.6 -> 19.6 GS/s at 10^6-sample blocks; in a tick whose
     // workgroups are all resident from the start the order only decides who gets going first, and pass 1 early is worth 2 % at 200 000-sample
-    // blocks (profiles/r03z_tick_p1_weight.log; SDRPP_GPU_TICK_P1_WEIGHT: measurement switch)
-    static const int p1_weight = getenv("SDRPP_GPU_TICK_P1_WEIGHT") ? atoi(getenv("SDRPP_GPU_TICK_P1_WEIGHT")) : 0;
-    if (role >= TR_FFT_P1_5 && role <= TR_FFT_P1_10) { return p1_weight > 0 ? p1_weight : (crowded ? 45 : 70); }
+    // blocks (profiles/r03z_tick_p1_weight.log)
+    if (role >= TR_FFT_P1_5 && role <= TR_FFT_P1_10) { return crowded ? 45 : 70; }
     // the long first stages (cfg 4): far more workgroups than the GPU holds, 58 us each — behind the sequential recursions (few, long), in front
     // of everything else: with four tile engines per workgroup they are 60 % of the tick's workgroup time, and started late they ARE its tail
     // (weight 72 against 58: 10^6-sample blocks 6.02 -> 6.13 GS/s, 307 200: 3.19 -> 3.78; behind the filters, 40 / 15: 5.77 / 5.64 and 3.11 / 3.07;
-    // profiles/r04w_fcl_weight.log — with two engines per workgroup, round 3, the order hardly mattered: profiles/r03zj_*;
-    // SDRPP_GPU_TICK_FCL_WEIGHT: measurement switch)
-    static const int fcl_weight = getenv("SDRPP_GPU_TICK_FCL_WEIGHT") ? atoi(getenv("SDRPP_GPU_TICK_FCL_WEIGHT")) : 72;
+    // profiles/r04w_fcl_weight.log — with two engines per workgroup, round 3, the order hardly mattered: profiles/r03zj_*)
     switch (role) {
-    case TR_FCL_0: case TR_FCL_PF: return fcl_weight;
+    case TR_FCL_0: case TR_FCL_PF: return 72;
     case TR_FCM_132_4: case TR_FCM_6: case TR_FCM_10: case TR_FCM_16: case TR_FCM16_132_4: case TR_S1_1: case TR_S1D_1: case TR_F2_1: return 90;
     case TR_SEQ: case TR_SSBX: return 85;
-    case TR_FFT_P1_5: case TR_FFT_P1_6: case TR_FFT_P1_7: case TR_FFT_P1_8: case TR_FFT_P1_9: case TR_FFT_P1_10: case TR_FIRB_C: case TR_FIRB_R: case TR_FIRB_S: case TR_FIRB_Q: return 70;
+    case TR_FIRB_C: case TR_FIRB_R: case TR_FIRB_S: case TR_FIRB_Q: return 70;
     case TR_POLYC: return 55;
     case TR_DEEMP_P1: case TR_DC_P1: return 52;
     case TR_DEEMP_P0: case TR_DC_P0: return 48;
-    case TR_PIPE: return 80;  // the longest-lived workgroups behind the front end: a whole segment of four stages
     case TR_TOEP_Q: return 65;
     case TR_TOEP_C: case TR_TOEP_R: case TR_FFT_S10: case TR_FFT_S11: case TR_FFT_S12: return 60;
-    case TR_FFT_P2_7: case TR_FFT_P2_8: case TR_FFT_P2_9: case TR_FFT_P2_10: case TR_FFT_P2ROW: {
-        static const int p2_weight = getenv("SDRPP_GPU_TICK_P2_WEIGHT") ? atoi(getenv("SDRPP_GPU_TICK_P2_WEIGHT")) : 50;  // (measurement switch)
-        return p2_weight;
-    }
+    case TR_FFT_P2_7: case TR_FFT_P2_8: case TR_FFT_P2_9: case TR_FFT_P2_10: case TR_FFT_P2ROW: return 50;
     case TR_FFT_TR: return 25;
     case TR_ROT: case TR_PRE: return 30;
     case TR_ZOOM_16: case TR_ZOOM_4: case TR_ZOOM_1: return 20;
@@ -118,12 +110,10 @@ int tick_launch(sdrpp_ctx* c, const CopyJob* land) {
         // order: longest workgroups first (front ends, FFT pass 1, the filters; zoom / carry / copies last), so that the tick ends on
         // short ones instead of on a front end that only got its turn when everything else was through (10^6-sample blocks: the front
         // end started 46 us into an 81 us tick).  The table is final here: later blocks only add to later ticks.
-        if (c->tick_order) {
-            long long wgs = 0;
-            for (auto& r : nx) { wgs += (long long)r.e.gx * r.e.gy; }
-            const bool crowded = wgs > 3ll * c->num_cus;  // (three workgroups of the tick kernel per CU)
-            std::stable_sort(nx.begin(), nx.end(), [crowded](const sdrpp_ctx::RoleLaunch& a, const sdrpp_ctx::RoleLaunch& b) { return tick_role_weight(a.e.role, crowded) > tick_role_weight(b.e.role, crowded); });
-        }
+        long long wgs = 0;
+        for (auto& r : nx) { wgs += (long long)r.e.gx * r.e.gy; }
+        const bool crowded = wgs > 3ll * c->num_cus;  // (three workgroups of the tick kernel per CU)
+        std::stable_sort(nx.begin(), nx.end(), [crowded](const sdrpp_ctx::RoleLaunch& a, const sdrpp_ctx::RoleLaunch& b) { return tick_role_weight(a.e.role, crowded) > tick_role_weight(b.e.role, crowded); });
         if (nx.size() > SDRPP_TICK_MAX_ENTRIES) { return fail(c, SDRPP_ERR_UNSUPPORTED, "internal: %zu roles in one tick", nx.size()); }
         const size_t off = (c->arena_off + 63) & ~(size_t)63;
         if (off + sizeof(TickTable) > kArenaBytes) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
@@ -150,7 +140,7 @@ int tick_launch(sdrpp_ctx* c, const CopyJob* land) {
     }
     int blocks = l0.blocks[0] + l0.blocks[1];
     size_t lds = 0;
-    bool set1 = false, set2 = true;  // set2: every role of this tick exists in the four-wavefronts-per-SIMD build (tick_kernels.h)
+    bool set1 = false;
     long long role_wgs = 0;
     bool to_host = false;
     for (auto& r : now) {
@@ -159,7 +149,6 @@ int tick_launch(sdrpp_ctx* c, const CopyJob* land) {
         role_wgs += (long long)r.e.gx * r.e.gy;
         lds = std::max(lds, r.lds);
         set1 = set1 || r.e.role == TR_FCL_PF || r.e.role == TR_FCM_6 || r.e.role == TR_FCM_10 || r.e.role == TR_FCM_16;  // (roles that exist in the 247-register build only: tick_kernels.h)
-        set2 = set2 && !(r.e.role == TR_ROTX16 || r.e.role == TR_FCL_PF || r.e.role == TR_FCL_0 || r.e.role == TR_FCM_132_4 || r.e.role == TR_FCM_6 || r.e.role == TR_FCM_10 || r.e.role == TR_FCM_16 || r.e.role == TR_FFT_S12);
         if (r.e.role >= 0 && r.e.role < 64) { c->stat_role_wgs[r.e.role] += (int64_t)r.e.gx * r.e.gy; }
     }
     if (role_wgs > 3ll * c->num_cus) { c->stat_crowded++; }
@@ -190,13 +179,8 @@ int tick_launch(sdrpp_ctx* c, const CopyJob* land) {
         // of their own in the queue): the stop event orders the tick's result writes for the host (host_ctx.h), start + stop time the launch.
         const bool timed = c->timing && ((c->timing_mask >> F_TICK) & 1u);
         c->fam_launch[F_TICK]++;
-        bool want_ev = timed;
-        if (to_host && c->tick_ev_ext && ++c->tick_ev_skipped >= c->tick_ev_every) {
-            c->tick_ev_skipped = 0;
-            want_ev = true;
-        }
         hipEvent_t ea = nullptr;
-        if (want_ev) {
+        if (timed || to_host) {
             const int k = c->tick_ev_next;
             stop_ev = tick_event_take(c, c->ticks);
             if (!stop_ev) { return fail(c, SDRPP_ERR_HIP, "hipEventCreate failed"); }
@@ -206,25 +190,12 @@ int tick_launch(sdrpp_ctx* c, const CopyJob* land) {
             }
         }
         HostScope hs("launch");
-        static const bool allow2 = getenv("SDRPP_GPU_TICK_SET2") ? atoi(getenv("SDRPP_GPU_TICK_SET2")) != 0 : true;  // (measurement switch)
-        const bool use2 = allow2 && set2 && !set1 && c->tick_fcm16w && lds <= (size_t)40 * 1024;
-        if (use2) { c->stat_set2++; }
         if (stop_ev) {
             if (set1) { hipExtLaunchKernelGGL((tick_kernel<1>), dim3((unsigned)blocks), dim3(256), (unsigned)lds, c->stream, ea, stop_ev, 0, l0, tab, done); }
-            else if (use2) { hipExtLaunchKernelGGL((tick_kernel<2>), dim3((unsigned)blocks), dim3(256), (unsigned)lds, c->stream, ea, stop_ev, 0, l0, tab, done); }
             else { hipExtLaunchKernelGGL((tick_kernel<0>), dim3((unsigned)blocks), dim3(256), (unsigned)lds, c->stream, ea, stop_ev, 0, l0, tab, done); }
         }
         else if (set1) { hipLaunchKernelGGL((tick_kernel<1>), dim3((unsigned)blocks), dim3(256), lds, c->stream, l0, tab, done); }
-        else if (use2) { hipLaunchKernelGGL((tick_kernel<2>), dim3((unsigned)blocks), dim3(256), lds, c->stream, l0, tab, done); }
         else { hipLaunchKernelGGL((tick_kernel<0>), dim3((unsigned)blocks), dim3(256), lds, c->stream, l0, tab, done); }
-    }
-    if (to_host && !c->tick_ev_ext) {  // measurement switch: the event as a packet of its own behind the launch
-        if (++c->tick_ev_skipped >= c->tick_ev_every) {
-            c->tick_ev_skipped = 0;
-            hipEvent_t ev = tick_event_take(c, c->ticks);
-            if (!ev) { return fail(c, SDRPP_ERR_HIP, "hipEventCreate failed"); }
-            HIPCHK(c, hipEventRecord(ev, c->stream));
-        }
     }
     c->arena_tick[c->arena_slot] = c->ticks;
     c->next_tab = tab_dev_next;
@@ -250,8 +221,8 @@ bool tick_eligible(sdrpp_ctx* c) {
     if ((c->pre.on && c->pre.ref_order) || c->deferred) { return false; }  // (the reference-order arithmetic of the pre-processing chain has no roles)
     for (auto& kv : c->vfos) {
         const Vfo& v = *kv.second;
-        // (reference-rotator VFOs have their roles since round 5 — TR_ROTX16 / TR_FIRD / TR_SSBX; the measurement forms of that rotator have not)
-        if ((v.nco_exact && (c->rot_exact_single || c->rot_exact_skip < 16)) || !v.recs.empty() || v.st.size() > 24) { return false; }
+        // (reference-rotator VFOs have their roles since round 5 — TR_ROTX16 / TR_FIRD / TR_SSBX; its one-wavefront form has not)
+        if ((v.nco_exact && c->rot_exact_single) || !v.recs.empty() || v.st.size() > 24) { return false; }
     }
     return true;
 }
@@ -577,11 +548,6 @@ int tick_push(sdrpp_ctx* c, const float* d_iq, int64_t count, const CopyJob* lan
         if (c->pre.on) {
             for (auto& st : c->pre.st) { stream_rotate(st); }
             stream_rotate(c->pre.out);
-        }
-        c->plan_sparse = 1;
-        if (c->tick_sparse_boost && c->h_tick_flag) {
-            const int in_flight = (int)((unsigned)c->ticks - *(const volatile unsigned*)c->h_tick_flag);
-            c->plan_sparse = in_flight <= 0 ? 4 : (in_flight == 1 ? 2 : 1);
         }
         c->tick_planning = true;
         c->tick_abort = false;

@@ -105,12 +105,11 @@ enum TickRole : int {
     TR_FFT_P2_7, TR_FFT_P2_8, TR_FFT_P2_9, TR_FFT_P2_10,             // p.p2
     TR_FFT_P2ROW, TR_FFT_TR,                                         // p.p2 (long transforms: 4096-point rows in place; transpose into bin order, aux = doZoom group size)
     TR_ZOOM_16, TR_ZOOM_4, TR_ZOOM_1,                                // p.z
-    TR_FCM16W_132_4,  // vfo_frontcm16w_body<132, 4>: the ratio-32 front end in 16 x 16 x 4 shape walking `tiles_per_wave` tiles per workgroup (large blocks, SET = 2)
     TR_POLYC,      // PolyJob[gy], aux = LDS window in float2: vfo_polyc_body (many-phase resampler, cycle-major: the AF chain's 96/125)
     TR_DEEMP_P0, TR_DEEMP_P1,  // DeempJob[gy]: vfo_deemph_body<0, 0 / 1> (de-emphasis: segment maps, then the outputs one level later)
     TR_DC_P0, TR_DC_P1,        // DeempJob[gy]: vfo_deemph_body<1, 0 / 1> (the front end's DC blocker)
     TR_WF_RING, TR_WF_TRACE,   // p.wf: raw lines into the waterfall's ring; FFT trace smoothing / hold over the block's zoomed lines
-    TR_PIPE,       // PipeJob[gy], gx = segments per VFO: vfo_pipe_body<1> — an FM back end (last decimator, resampler, channel filter, discriminator + audio low-pass) as ONE role
+    TR_PIPE,       // PipeJob[gy], gx = segments per VFO: vfo_pipe_kernel<1> — an FM back end (last decimator, resampler, channel filter, discriminator + audio low-pass) in ONE launch (ordinary passes only: the planner never puts it into a tick)
     // reference-rotator VFOs (sdrpp_vfo_desc.nco_mode = 2) inside a pipelined bank (round 5): the chain bounds the tick, every VFO's results stay pipelined
     TR_ROTX16,     // RotXHead (jobs), p.src, gx = workgroups of `vpw` VFOs: vfo_rotate_exact4_body<16> — the reference's float rotator recursion at the full rate
     TR_FIRD,       // FirBJob[gy]: vfo_fir_direct_body<false> (plain decimators whose window fits no LDS tile: the first stages behind that rotator)
@@ -227,13 +226,12 @@ __device__ TickTraceRec g_tick_trace[SDRPP_TICK_TRACE_CAP];
 __device__ unsigned g_tick_trace_n;
 #endif
 
-// SET 0: every role but TR_FCL_PF (168 registers: three wavefronts per SIMD); SET 1: all roles (247 registers: two); SET 2: every role that
-// fits 128 registers and 40 KB of LDS — i.e. all but the 32 x 32 x 2 front ends, the long first stages and the one-pass 4096-point transform —
-// FOUR wavefronts per SIMD: the build a tick runs in when its front end has the 16 x 16 x 4 shape (tick_set_for, tick_host.h).
+// SET 0: every role but TR_FCL_PF and the run-time-geometry front ends (168 registers: three wavefronts per SIMD); SET 1: all roles (247
+// registers: two).
 // (SET 0 squeezed into 128 registers by the compiler — four wavefronts per SIMD, the matrix front end spilling 668 bytes per lane — was
 // measured slower at every block size: 12.9 against 13.3 GS/s at 10^6 samples, 2.5 against 3.1 at 50 000; profiles/r03e)
 template <int SET>
-__global__ __launch_bounds__(256, SET == 1 ? 2 : (SET == 2 ? 4 : 3)) void tick_kernel(TickL0 l0, const TickTable* __restrict__ tab, TickDone done) {
+__global__ __launch_bounds__(256, SET == 1 ? 2 : 3) void tick_kernel(TickL0 l0, const TickTable* __restrict__ tab, TickDone done) {
     HIP_DYNAMIC_SHARED(float, smem)
     int b = (int)blockIdx.x;
     const int nb0 = l0.blocks[0] + l0.blocks[1];
@@ -271,13 +269,11 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : (SET == 2 ? 4 : 3)) void tick_k
             switch (e_role) {
             case TR_COPY: copy_body(bid, gdim, reinterpret_cast<const CopyJob*>(e_jobs)); break;
             case TR_CARRY: carry_body(bid, gdim, reinterpret_cast<const CarryJob*>(e_jobs), e_aux); break;
-            case TR_ROTX16:
-                if constexpr (SET != 2) {  // (71 KB of LDS: not in the four-wavefronts-per-SIMD build)
-                    const IqSrc src = e.p.src;
-                    const RotXHead h = *reinterpret_cast<const RotXHead*>(e_jobs);
-                    vfo_rotate_exact4_body<16>(bid.x, reinterpret_cast<float2*>(smem), src, h.jobs, h.njobs, h.bounds, h.nb, h.vpw);
-                }
-                break;
+            case TR_ROTX16: {
+                const IqSrc src = e.p.src;
+                const RotXHead h = *reinterpret_cast<const RotXHead*>(e_jobs);
+                vfo_rotate_exact4_body<16>(bid.x, reinterpret_cast<float2*>(smem), src, h.jobs, h.njobs, h.bounds, h.nb, h.vpw);
+            } break;
             case TR_FIRD: vfo_fir_direct_body<false>(bid, gdim, reinterpret_cast<const FirBJob*>(e_jobs)); break;
             case TR_POLY: vfo_poly_body(bid, reinterpret_cast<float2*>(smem), reinterpret_cast<const PolyJob*>(e_jobs)); break;
             case TR_S1_1: { const IqSrc src = e.p.src; vfo_stage1_body<1>(bid, reinterpret_cast<float2*>(smem), e_aux, 256, src, reinterpret_cast<const Stage1Job*>(e_jobs)); } break;
@@ -288,9 +284,7 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : (SET == 2 ? 4 : 3)) void tick_k
                 if (j < e_aux) { vfo_ssb_rotate_exact_body(j, reinterpret_cast<const SsbRotXJob*>(e_jobs)); }
             } break;
             case TR_ROT: { const IqSrc src = e.p.src; vfo_rotate_body(bid, gdim, src, reinterpret_cast<const RotJob*>(e_jobs)); } break;
-            case TR_FCM_132_4:
-                if constexpr (SET != 2) { const IqSrc src = e.p.src; vfo_frontcm_body<10, 132, 4>(bid, smem, src, reinterpret_cast<const FrontCMJob*>(e_jobs)); }
-                break;
+            case TR_FCM_132_4: { const IqSrc src = e.p.src; vfo_frontcm_body<10, 132, 4>(bid, smem, src, reinterpret_cast<const FrontCMJob*>(e_jobs)); } break;
             // (the front ends with RUN-TIME geometry — any composite filter but the ratio-32 plan's <132 taps, / 16> — need more registers than the 168 of the
             // SET = 0 build: there they spilled 57 registers, 204 bytes of scratch per work-item for the whole kernel, VERDICT r5.  They live in the
             // 247-register build only; a tick that holds one runs as tick_kernel<1>)
@@ -304,9 +298,7 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : (SET == 2 ? 4 : 3)) void tick_k
                 if constexpr (SET == 1) { const IqSrc src = e.p.src; vfo_frontcm_body<16, 0, 0>(bid, smem, src, reinterpret_cast<const FrontCMJob*>(e_jobs)); }
                 break;
             case TR_FCM16_132_4: { const IqSrc src = e.p.src; vfo_frontcm16_body<132, 4>(bid, smem, src, reinterpret_cast<const FrontCMJob*>(e_jobs)); } break;
-            case TR_FCL_0:
-                if constexpr (SET != 2) { const IqSrc src = e.p.src; vfo_frontcl_body<0>(bid, smem, src, reinterpret_cast<const FrontCMJob*>(e_jobs), e_aux == 4 ? 4 : 2); }
-                break;
+            case TR_FCL_0: { const IqSrc src = e.p.src; vfo_frontcl_body<0>(bid, smem, src, reinterpret_cast<const FrontCMJob*>(e_jobs), e_aux == 4 ? 4 : 2); } break;
             case TR_FCL_PF:
                 if constexpr (SET == 1) { const IqSrc src = e.p.src; vfo_frontcl_body<SDRPP_FCL_PF>(bid, smem, src, reinterpret_cast<const FrontCMJob*>(e_jobs), e_aux == 4 ? 4 : 2); }
                 break;
@@ -331,9 +323,7 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : (SET == 2 ? 4 : 3)) void tick_k
                 break;
             case TR_FFT_S10: tick_fft_single<10, 4>(bid, smem, e.p.fs); break;
             case TR_FFT_S11: tick_fft_single<11, 2>(bid, smem, e.p.fs); break;
-            case TR_FFT_S12:
-                if constexpr (SET != 2) { tick_fft_single<12, 1>(bid, smem, e.p.fs); }
-                break;
+            case TR_FFT_S12: tick_fft_single<12, 1>(bid, smem, e.p.fs); break;
             case TR_FFT_P1_5: tick_fft_p1<5, 128>(bid, gdim, smem, e.p.p1); break;
             case TR_FFT_P1_6: tick_fft_p1<6, 64>(bid, gdim, smem, e.p.p1); break;
             case TR_FFT_P1_7: tick_fft_p1<7, 32>(bid, gdim, smem, e.p.p1); break;
@@ -352,7 +342,6 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : (SET == 2 ? 4 : 3)) void tick_k
             case TR_ZOOM_16: tick_zoom<16>(bid, smem, e.p.z, e_aux > 0 ? e_aux : 1); break;
             case TR_ZOOM_4: tick_zoom<4>(bid, smem, e.p.z, e_aux > 0 ? e_aux : 1); break;
             case TR_ZOOM_1: tick_zoom<1>(bid, smem, e.p.z, e_aux > 0 ? e_aux : 1); break;
-            case TR_FCM16W_132_4: { const IqSrc src = e.p.src; vfo_frontcm16w_body<132, 4>(bid, smem, src, reinterpret_cast<const FrontCMJob*>(e_jobs)); } break;
             case TR_POLYC: vfo_polyc_body(bid, reinterpret_cast<float2*>(smem), reinterpret_cast<const PolyJob*>(e_jobs), e_aux); break;
             case TR_DEEMP_P0: vfo_deemph_body<0, 0>(bid, smem, reinterpret_cast<const DeempJob*>(e_jobs)); break;
             case TR_DEEMP_P1: vfo_deemph_body<0, 1>(bid, smem, reinterpret_cast<const DeempJob*>(e_jobs)); break;
@@ -360,6 +349,8 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : (SET == 2 ? 4 : 3)) void tick_k
             case TR_DC_P1: vfo_deemph_body<1, 1>(bid, smem, reinterpret_cast<const DeempJob*>(e_jobs)); break;
             case TR_WF_RING: { const TickWf q = e.p.wf; wf_ring_store_body(bid, gdim, q.src, q.n0, q.n1, q.a, q.n2, q.n3); } break;
             case TR_WF_TRACE: { const TickWf q = e.p.wf; wf_trace_body(bid, q.src, q.n0, q.n1, q.a, q.b, q.f0, q.f1, q.c, q.f2); } break;
+            // (the planner never puts TR_PIPE into a tick.  The case stays because the kernel's register allocation depends on it: without it
+            // tick_kernel<0> took 168 registers instead of 167 and cfg 3's tick at 10^6-sample blocks 46.5 instead of 45.7 us)
             case TR_PIPE: vfo_pipe_body<1>(bid, gdim, smem, reinterpret_cast<const PipeJob*>(e_jobs)); break;
             default: break;
             }

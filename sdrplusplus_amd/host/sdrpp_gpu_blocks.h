@@ -476,8 +476,7 @@ public:
             const auto t0 = std::chrono::steady_clock::now();
             // (how long "no new block" is follows the stream: twice what the last blocks took to arrive after the flush — a source that needs 22 us per block
             // must not have its groups sent off after 20 —, at least _kickUs, at most 200 us / the spin window)
-            static const bool kickFixed = getenv("SDRPP_GPU_KICK_FIXED") != nullptr;  // (measurement switch)
-            const long kickUs = std::min<long>(kickFixed ? (long)_kickUs : std::max<long>(_kickUs, std::min<long>(200, (long)(2.0 * arriveEmaUs) + 5)), _spinUs);
+            const long kickUs = std::min<long>(std::max<long>(_kickUs, std::min<long>(200, (long)(2.0 * arriveEmaUs) + 5)), _spinUs);
             unsigned n = 0;
             bool arrived = true;
             while (peekReadBuf(_in) == spinLast) {

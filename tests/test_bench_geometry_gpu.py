@@ -103,7 +103,7 @@ def test_cfg3_pipelined_bench_geometry_vs_oracle(fed):
         assert "fcm16_132_4" in st["roles"] and "fcm_132_4" not in st["roles"], st  # small-block shape of the front end
     else:
         assert "fcm_132_4" in st["roles"] and "fcm16_132_4" not in st["roles"], st  # host-fetched blocks keep the 32 x 32 x 2 shape
-    assert any(k in st["roles"] for k in ("toep_q", "pipe")) and "fft_p1_8" in st["roles"] and "fft_p2_8" in st["roles"], st
+    assert "toep_q" in st["roles"] and "fft_p1_8" in st["roles"] and "fft_p2_8" in st["roles"], st
     spec = S.OracleSpectrum(65536, 65536, 0, capi.design_fft_window(2, 65536))
     nlines = _check_lines(spec, info["view"], x, cuts, results)
     assert nlines == (B * nblk) // 65536
