@@ -206,6 +206,8 @@ int sdrpp_vfo_count(sdrpp_ctx* ctx);
  *   keep & 2: the demodulator behind it lives on (setInSamplerate: the radio's demodulator block is not touched): discriminator and audio low-pass
  *             history, AGC / DC-blocker state, SSB's second translation.  Only where the new description has the same demodulator; a demodulator
  *             SWITCH creates a new demodulator object in the reference too: leave the bit off.
+ *   keep & 4: the IF chain (sdrpp_vfo_set_if) moves to the new handle with its parameters and the blanker's amplitude estimate: the radio module's
+ *             IF-chain blocks are not the demodulator's and outlive a demodulator switch (radio_module.h:84-96).  Without the bit the new handle has no chain.
  * An AF chain (sdrpp_vfo_set_af) is not carried over: attach it to the new handle (it starts cleared, as afChain's blocks do after a restart). */
 int sdrpp_vfo_replace(sdrpp_ctx* ctx, int old_id, const sdrpp_vfo_desc* desc, int keep, int* new_id);
 /* RxVFO::setOffset (rx_vfo.h:72-77): only phaseDelta changes, phase stays continuous; the samples already inside the first
@@ -223,7 +225,7 @@ int sdrpp_vfo_out_count(sdrpp_ctx* ctx, int id);
 int sdrpp_vfo_read(sdrpp_ctx* ctx, int id, float* dst_host, int max);
 /* The same for many VFOs with ONE device-to-host copy (a host block that delivers every VFO stream after each block would otherwise
  * pay one small copy + synchronisation per VFO).  which[i]: 0 = what sdrpp_vfo_read returns, 1 = the complex IF, 2 = the AF chain
- * output (NULL: all 0).  The blocks are packed back to back into dst_host (2 floats per sample); offsets[i] / counts[i] (in samples)
+ * output, 3 = the IF chain's output (sdrpp_vfo_set_if) (NULL: all 0).  The blocks are packed back to back into dst_host (2 floats per sample); offsets[i] / counts[i] (in samples)
  * locate VFO ids[i]'s block.  Returns the total number of samples, SDRPP_ERR_INVALID if max_samples is too small.  dst_host = NULL is
  * a size query: offsets / counts are filled and the total returned, nothing is copied. */
 int sdrpp_vfo_read_many(sdrpp_ctx* ctx, int n, const int* ids, const int* which, float* dst_host, int64_t max_samples, int64_t* offsets, int* counts);
@@ -255,6 +257,31 @@ int sdrpp_vfo_af_count(sdrpp_ctx* ctx, int id);
 int sdrpp_vfo_af_read(sdrpp_ctx* ctx, int id, float* dst_host, int max);
 int sdrpp_vfo_af_device_buffer(sdrpp_ctx* ctx, int id, const float** out, int* n_out);
 int sdrpp_abi_sizeof_af_desc(void);
+
+/* ---- radio IF chain between a VFO's IF stream and its demodulator (decoder_modules/radio/src/radio_module.h:84-96) ------------------
+ * NoiseBlanker (dsp/noise_reduction/noise_blanker.h:38-57) -> PowerSquelch (dsp/noise_reduction/power_squelch.h:33-50), in that order,
+ * on the complex IF; the demodulator (and the AF chain behind it) then reads the chain's output.  RxVFO::out itself (`if_out`, which = 1)
+ * stays the stream IN FRONT of the chain, as vfo->output is in the reference; the chain's own output of the last push has its accessors
+ * below and is which = 3.  A RAW VFO with a chain delivers the chain's output as its `out`.
+ *   blanker: per sample, state amp (1 when the blanker starts, sdrpp_vfo_reset sets it back): inAmp = |x|; if inAmp != 0 { amp = amp * (1 -
+ *            nb_rate) + inAmp * nb_rate; excess = inAmp / amp; if excess > nb_level: x /= excess }.  The radio module uses nb_rate = 500 / IF rate.
+ *   squelch: per REFERENCE BLOCK (sdrpp_set_reference_block; 0: one push = one block) of the blanker's output: the block passes if
+ *            10 * log10(mean |x|) >= squelch_level, else it is zeroed.  No state.
+ * Calling it on a VFO that has a chain changes the parameters and keeps amp (setRate / setLevel keep it); a blanker switched from off to
+ * on starts at amp = 1.  desc == NULL detaches.  With both blocks disabled, or without a chain, nothing is planned for it: every path is
+ * what it is without this call.  VFOs with an active chain do not take part in the one-launch FM back end (sdrpp_set_backend_pipeline).
+ * Not covered: FMIF (the FFT-based IF noise reduction, third block of the reference's IF chain) and the AF-side CTCSS squelch. */
+typedef struct sdrpp_if_desc {
+    int nb_enabled;
+    float nb_rate, nb_level;
+    int squelch_enabled;
+    float squelch_level;                              /* dB                                                                      */
+} sdrpp_if_desc;
+int sdrpp_vfo_set_if(sdrpp_ctx* ctx, int id, const sdrpp_if_desc* desc);
+int sdrpp_vfo_ifc_count(sdrpp_ctx* ctx, int id);
+int sdrpp_vfo_ifc_read(sdrpp_ctx* ctx, int id, float* dst_host, int max);
+int sdrpp_vfo_ifc_device_buffer(sdrpp_ctx* ctx, int id, const float** out, int* n_out);
+int sdrpp_abi_sizeof_if_desc(void);
 
 /* ---- sink-side sample packing: float -> int16 / int8 on the device, before the copy to the host -----------------
  * `which`: 0 = what sdrpp_vfo_read returns (demodulator output, or the IF in RAW mode), 1 = the complex IF (RxVFO::out), 2 = the AF

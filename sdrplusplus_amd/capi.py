@@ -77,6 +77,18 @@ class AfDesc(C.Structure):
     ]
 
 
+class IfDesc(C.Structure):
+    """struct sdrpp_if_desc (include/sdrpp_gpu.h): the radio IF chain (noise blanker -> power squelch) in front of the demodulator."""
+
+    _fields_ = [
+        ("nb_enabled", C.c_int),
+        ("nb_rate", C.c_float),
+        ("nb_level", C.c_float),
+        ("squelch_enabled", C.c_int),
+        ("squelch_level", C.c_float),
+    ]
+
+
 class Result(C.Structure):
     """struct sdrpp_result (include/sdrpp_gpu.h): one block's results in the library's page-locked host memory (pipelined mode)."""
 
@@ -159,6 +171,13 @@ def load():
     L.sdrpp_preproc_out_count.argtypes = [vp]
     L.sdrpp_preproc_read.argtypes = [vp, c_float_p, C.c_int]
     L.sdrpp_preproc_device_buffer.argtypes = [vp, C.POINTER(vp), c_int_p]
+    L.sdrpp_abi_sizeof_if_desc.argtypes = []
+    if L.sdrpp_abi_sizeof_if_desc() != C.sizeof(IfDesc):
+        raise ImportError("sdrpp_if_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_if_desc(), C.sizeof(IfDesc)))
+    L.sdrpp_vfo_set_if.argtypes = [vp, C.c_int, C.POINTER(IfDesc)]
+    L.sdrpp_vfo_ifc_count.argtypes = [vp, C.c_int]
+    L.sdrpp_vfo_ifc_read.argtypes = [vp, C.c_int, c_float_p, C.c_int]
+    L.sdrpp_vfo_ifc_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), c_int_p]
     L.sdrpp_vfo_set_af.argtypes = [vp, C.c_int, C.POINTER(AfDesc)]
     L.sdrpp_vfo_af_count.argtypes = [vp, C.c_int]
     L.sdrpp_vfo_af_read.argtypes = [vp, C.c_int, c_float_p, C.c_int]
@@ -247,6 +266,7 @@ EXPORTED_SYMBOLS = [
     "sdrpp_wf_configure", "sdrpp_wf_set_smoothing", "sdrpp_wf_set_hold", "sdrpp_wf_latest", "sdrpp_wf_raster", "sdrpp_wf_signal_info",
     "sdrpp_preproc_configure", "sdrpp_preproc_reconfigure", "sdrpp_preproc_set_reference_order", "sdrpp_preproc_out_count", "sdrpp_preproc_read", "sdrpp_preproc_device_buffer",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
+    "sdrpp_vfo_set_if", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
     "sdrpp_fft_configure", "sdrpp_fft_disable", "sdrpp_fft_set_view", "sdrpp_fft_lines", "sdrpp_fft_read", "sdrpp_fft_copy_device", "sdrpp_fft_device_buffers",
     "sdrpp_vfo_add", "sdrpp_vfo_remove", "sdrpp_vfo_replace", "sdrpp_vfo_count", "sdrpp_vfo_set_phase_delta", "sdrpp_vfo_set_channel_taps", "sdrpp_vfo_reset",
     "sdrpp_vfo_out_count", "sdrpp_vfo_read", "sdrpp_vfo_device_buffers",
@@ -428,7 +448,7 @@ class Context:
 
     def vfo_replace(self, vid, desc, keep, keepalive=()):
         """sdrpp_vfo_replace: RxVFO::setInSamplerate / setOutSamplerate — a new description, the RxVFO's own state (keep & 1) and the demodulator's
-        (keep & 2) carried over as the reference's objects carry it.  Returns the new handle."""
+        (keep & 2) carried over as the reference's objects carry it; keep & 4 moves the IF chain (sdrpp_vfo_set_if) and its state along.  Returns the new handle."""
         nid = C.c_int()
         self._chk(self.L.sdrpp_vfo_replace(self.h, vid, C.byref(desc), int(keep), C.byref(nid)))
         del keepalive
@@ -556,6 +576,26 @@ class Context:
         out = np.empty((max(n, 1), 2), dtype=np.float32)
         got = self._chk(self.L.sdrpp_vfo_af_read(self.h, vid, out.ctypes.data_as(c_float_p), n))
         return out[:got]
+
+    def vfo_set_if(self, vid, if_desc):
+        """Attach (or, with None, detach) the radio IF chain: noise blanker -> power squelch in front of the demodulator (sdrpp_vfo_set_if).
+        On a VFO that already has one the parameters change and the blanker's amplitude estimate is kept."""
+        self._chk(self.L.sdrpp_vfo_set_if(self.h, vid, C.byref(if_desc) if if_desc is not None else None))
+
+    def vfo_ifc_count(self, vid):
+        return self._chk(self.L.sdrpp_vfo_ifc_count(self.h, vid))
+
+    def vfo_ifc_read(self, vid):
+        """The IF chain's own output of the last push (complex; what the demodulator was fed)."""
+        n = self.vfo_ifc_count(vid)
+        out = np.empty(max(n, 1), dtype=np.complex64)
+        got = self._chk(self.L.sdrpp_vfo_ifc_read(self.h, vid, out.view(np.float32).ctypes.data_as(c_float_p), n))
+        return out[:got]
+
+    def vfo_ifc_device_buffer(self, vid):
+        o, n = C.c_void_p(), C.c_int()
+        self._chk(self.L.sdrpp_vfo_ifc_device_buffer(self.h, vid, C.byref(o), C.byref(n)))
+        return o.value, n.value
 
     def vfo_device_buffers(self, vid):
         o, i = C.c_void_p(), C.c_void_p()

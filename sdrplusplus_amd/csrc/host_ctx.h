@@ -79,7 +79,16 @@ struct Vfo {
     // streams: 0..nstages-1 decimator outputs (index 0 also used by the rotate-only path), then poly, chan, dem, out
     std::vector<Stream> st;
     int i_first = 0, i_poly = -1, i_chan = -1, i_dem = -1, i_out = -1, i_if = 0;
-    int lvl_if = 1, lvl_out = 1, lvl_af = 1;  // levels (do_vfos_plan) at which the IF stream / the demodulator's output / the AF chain's output of the most recent block are written
+    int i_ifc = -1;  // the IF chain's output stream: a slot of `st` from the start, its buffers allocated when a chain is first attached (sdrpp_vfo_set_if)
+    int lvl_if = 1, lvl_out = 1, lvl_af = 1, lvl_ifc = 1;  // levels (do_vfos_plan) at which the IF stream / the demodulator's output / the AF chain's output / the IF chain's output of the most recent block are written
+    // radio IF chain (sdrpp_vfo_set_if): NoiseBlanker -> PowerSquelch between st[i_if] and the demodulator
+    struct Ifc {
+        bool on = false;  // a chain is attached (both blocks may still be disabled: then nothing is planned for it)
+        int nb_on = 0, sq_on = 0;
+        float nb_rate = 0.0f, nb_level = 0.0f, sq_level = 0.0f;
+        float* d_amp = nullptr;  // NoiseBlanker::amp (device, persistent)
+        bool active() const { return on && (nb_on || sq_on); }
+    } ifc;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
     ToepTab tp_stage[SDRPP_MAX_DECIM_STAGES], tp_poly, tp_chan, tp_audio;
     // front end as one filter (what the fused translate + filter kernels evaluate): stages 0 (+ 1) of the plan

@@ -358,6 +358,7 @@ void vfo_free(Vfo& v) {
     dev_free(v.d_state);
     dev_free(v.d_h12);
     dev_free(v.d_rot);
+    dev_free(v.ifc.d_amp);
     for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { toep_free(v.tp_stage[i]); }
     toep_free(v.tp_poly);
     toep_free(v.tp_chan);
@@ -414,6 +415,10 @@ int vfo_reset_state(sdrpp_ctx* c, Vfo& v) {
     HIPCHK(c, hipMemcpy(v.d_state, blob, sizeof(blob), hipMemcpyHostToDevice));
     const float2 unit[2] = { make_float2(1.0f, 0.0f), make_float2(1.0f, 0.0f) };  // frequency_xlator.h:21: phase = (1, 0)
     HIPCHK(c, hipMemcpy(v.d_rot, unit, sizeof(unit), hipMemcpyHostToDevice));
+    if (v.ifc.d_amp) {  // NoiseBlanker::reset (noise_blanker.h:32-36)
+        const float one = 1.0f;
+        HIPCHK(c, hipMemcpy(v.ifc.d_amp, &one, sizeof(float), hipMemcpyHostToDevice));
+    }
     return SDRPP_OK;
 }
 
@@ -499,6 +504,7 @@ void launch_role(sdrpp_ctx* c, const sdrpp_ctx::RoleLaunch& r) {
     case TR_FIRB_Q: hipLaunchKernelGGL((vfo_firb_kernel<1, true, true>), grid, dim3((unsigned)e.aux), r.lds, st, (const FirBJob*)e.jobs); break;
     case TR_PRE: hipLaunchKernelGGL(vfo_demod_pre_kernel, grid, b256, 0, st, (const PreJob*)e.jobs); break;
     case TR_SEQ: hipLaunchKernelGGL(vfo_sequential_kernel, grid, dim3(64), 0, st, (const SeqJob*)e.jobs, e.aux); break;
+    case TR_IFC: hipLaunchKernelGGL(vfo_ifchain_kernel, grid, b256, 0, st, (const IfcJob*)e.jobs, e.aux); break;
     case TR_PIPE: hipLaunchKernelGGL(vfo_pipe_kernel<1>, grid, b256, r.lds, st, (const PipeJob*)e.jobs); break;
     case TR_POLYC: hipLaunchKernelGGL(vfo_polyc_kernel, grid, b256, r.lds, st, (const PolyJob*)e.jobs, e.aux); break;
     case TR_DEEMP_P0: hipLaunchKernelGGL((vfo_deemph_kernel<0, 0>), grid, b256, 0, st, (const DeempJob*)e.jobs); break;

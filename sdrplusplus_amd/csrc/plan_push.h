@@ -6,7 +6,7 @@ namespace {
 
 // ---- streaming state that planning a block changes, for roll-back: a block either happens completely or not at all ----------------------
 struct PlanSnapshot {
-    struct V { int soff[SDRPP_MAX_DECIM_STAGES]; int pphase, poff; double phi, phi2; long long seen; int i_if, lvl_if, lvl_out, lvl_af; int n[24], cur[24]; size_t nrecs;
+    struct V { int soff[SDRPP_MAX_DECIM_STAGES]; int pphase, poff; double phi, phi2; long long seen; int i_if, lvl_if, lvl_out, lvl_af, lvl_ifc; int n[24], cur[24]; size_t nrecs;
                int af_soff[SDRPP_MAX_DECIM_STAGES], af_pphase, af_poff, af_last, af_state; };
     std::vector<V> v;
     int64_t fft_pos, fft_next;
@@ -21,7 +21,7 @@ void plan_snapshot(sdrpp_ctx* c, PlanSnapshot& S, bool rotate = false) {
         Vfo& v = *c->vfo_list[i];
         PlanSnapshot::V& q = S.v[i];
         for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { q.soff[k] = v.soff[k]; q.af_soff[k] = v.af.soff[k]; }
-        q.pphase = v.pphase; q.poff = v.poff; q.phi = v.phi; q.phi2 = v.phi2; q.seen = v.seen; q.i_if = v.i_if; q.lvl_if = v.lvl_if; q.lvl_out = v.lvl_out; q.lvl_af = v.lvl_af;
+        q.pphase = v.pphase; q.poff = v.poff; q.phi = v.phi; q.phi2 = v.phi2; q.seen = v.seen; q.i_if = v.i_if; q.lvl_if = v.lvl_if; q.lvl_out = v.lvl_out; q.lvl_af = v.lvl_af; q.lvl_ifc = v.lvl_ifc;
         q.nrecs = v.recs.size();
         q.af_pphase = v.af.pphase; q.af_poff = v.af.poff; q.af_last = v.af.i_last; q.af_state = v.af.state_cur;
         for (size_t k = 0; k < v.st.size() && k < 24; k++) { q.n[k] = v.st[k].n; q.cur[k] = v.st[k].cur; }
@@ -42,7 +42,7 @@ void plan_restore(sdrpp_ctx* c, const PlanSnapshot& S) {
         Vfo& v = *c->vfo_list[i];
         const PlanSnapshot::V& q = S.v[i];
         for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { v.soff[k] = q.soff[k]; v.af.soff[k] = q.af_soff[k]; }
-        v.pphase = q.pphase; v.poff = q.poff; v.phi = q.phi; v.phi2 = q.phi2; v.seen = q.seen; v.i_if = q.i_if; v.lvl_if = q.lvl_if; v.lvl_out = q.lvl_out; v.lvl_af = q.lvl_af;
+        v.pphase = q.pphase; v.poff = q.poff; v.phi = q.phi; v.phi2 = q.phi2; v.seen = q.seen; v.i_if = q.i_if; v.lvl_if = q.lvl_if; v.lvl_out = q.lvl_out; v.lvl_af = q.lvl_af; v.lvl_ifc = q.lvl_ifc;
         v.af.pphase = q.af_pphase; v.af.poff = q.af_poff; v.af.i_last = q.af_last; v.af.state_cur = q.af_state;
         for (size_t k = 0; k < v.st.size() && k < 24; k++) { v.st[k].n = q.n[k]; v.st[k].cur = q.cur[k]; }
     }

@@ -209,6 +209,7 @@ struct BankPlan {
     Lev<PolyBJob> polyb[4];  // [0]: LMAX 4, [1]: LMAX 8 (de-interleaved tile); [2], [3]: same with odd decimation (linear tile)
     Lev<FirBJob> chan;
     Lev<SeqJob> seq;
+    Lev<IfcJob> ifc;        // radio IF chain (noise blanker, squelch): between the channel filter's level and the demodulator's, for the VFOs that carry one
     Lev<PreJob> pre;
     Lev<FirBJob> audio;     // AM: real stream -> low-pass -> stereo
     Lev<FirBJob> audio_fm;  // WFM/NFM: IF -> discriminator -> low-pass -> stereo, one kernel
@@ -275,7 +276,7 @@ struct BankPlan {
         s1.clear(); rot.clear(); rotx.clear(); retune.clear(); pipes.clear();
         lev_reset(f_dec); lev_reset(poly);
         for (auto& q : polyb) { lev_reset(q); }
-        lev_reset(chan); lev_reset(seq); lev_reset(pre); lev_reset(audio); lev_reset(audio_fm);
+        lev_reset(chan); lev_reset(seq); lev_reset(ifc); lev_reset(pre); lev_reset(audio); lev_reset(audio_fm);
         lev_reset(t_dec); lev_reset(t_poly); lev_reset(t_chan); lev_reset(t_audio); lev_reset(t_audio_fm);
         lev_reset(t_af_dec); lev_reset(t_af_poly); lev_reset(t_af_hpf); lev_reset(af_dec); lev_reset(af_hpf); lev_reset(af_poly); lev_reset(af_deemp);
         lev_reset(ssbx_l); lev_reset(carry);
@@ -314,7 +315,9 @@ struct BankPlan {
         // reference-block ends carried stage by stage down to the demodulator's rate, for the block-dependent operations there
         // (AGC look-ahead, SSB rotator calls)
         const bool agc_mode = v.d.demod == SDRPP_DEMOD_AM || (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_DSB);
-        const bool need_bnd = agc_mode && (blocks || v.nco_exact);
+        // ... and the IF chain's squelch, which decides per reference block (power_squelch.h:33-50)
+        const bool ifc_on = v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base;
+        const bool need_bnd = (agc_mode && (blocks || v.nco_exact)) || (ifc_on && v.ifc.sq_on && blocks);
         std::vector<int> bnd;
         if (need_bnd) { bnd = fb; }
         // a launch group of several pushes (sdrpp_set_pipeline_group): the PUSH ends carried the same way, through every rate change down to the
@@ -457,7 +460,7 @@ struct BankPlan {
         // the FM back end as one pipelined launch (ordinary passes): last decimator, resampler, channel filter, discriminator + audio low-pass all
         // in their matrix form, and the pipeline's LDS layout fits
         const int last_dec = v.d.n_stages - 1;
-        bool piped_be = c->pipe_on && !ticking && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= first_sep && v.tp_stage[last_dec].ok &&
+        bool piped_be = c->pipe_on && !ticking && !ifc_on && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= first_sep && v.tp_stage[last_dec].ok &&
                         v.i_poly >= 0 && v.tp_poly.ok && v.i_chan >= 0 && v.chan_ntaps > 0 && v.tp_chan.ok && v.tp_audio.ok;
         PipeJob pj{};
         size_t pj_lds = 0;
@@ -542,6 +545,21 @@ struct BankPlan {
             if (!d_bnd) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
         }
         const int nbnd = need_bnd ? (int)bnd.size() : 0;
+        if (ifc_on) {
+            // the radio's IF chain: one level of its own between the IF stream (which stays RxVFO::out) and whatever follows — the demodulator's
+            // levels below move down by one for this VFO, and read the chain's buffer in place of the IF
+            Stream& fs = v.st[(size_t)v.i_ifc];
+            lvl++;
+            cur->clevel = lvl;
+            ifc.add(lvl, IfcJob{ (const float2*)cur->data, (float2*)fs.data, v.ifc.d_amp, nif, v.ifc.nb_on, v.ifc.nb_rate, 1.0f - v.ifc.nb_rate, v.ifc.nb_level, v.ifc.sq_on, v.ifc.sq_level,
+                                 (v.ifc.sq_on && blocks) ? d_bnd : nullptr, (v.ifc.sq_on && blocks) ? nbnd : 0 });
+            fs.n = nif;
+            fs.wlevel = lvl;
+            cur = &fs;
+            v.lvl_ifc = lvl;
+            v.lvl_out = lvl;
+        }
+        else if (v.i_ifc >= 0) { v.st[(size_t)v.i_ifc].n = 0; }
         if (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) {
             Stream& out = v.st[(size_t)v.i_out];
             lvl++;
@@ -666,7 +684,7 @@ struct BankPlan {
         // history carries for every stream that has a consumer with memory
         const Stream* phantom = (v.fused_front && v.d.n_stages >= 2 && !v.nco_exact) ? &v.st[(size_t)v.i_first] : nullptr;  // stage-1 output of a fused front end: never written, never read
         for (auto& s : v.st) {
-            if (s.hist_len > 0 && s.data && &s != phantom) {
+            if (s.hist_len > 0 && s.data && &s != phantom && (ifc_on || v.i_ifc < 0 || &s != &v.st[(size_t)v.i_ifc])) {
                 // pipelined: at the level of the consumer (its window of the NEXT block reads the new history one tick later, the carry of
                 // the next block overwrites the old one one tick later still); a stream nobody reads with memory (a consumer may be attached
                 // later: sdrpp_vfo_set_af, a taps change): one level behind the role that WRITES it — not behind the whole chain, which with
@@ -1011,7 +1029,7 @@ struct BankPlan {
             if (!arena_push_lev(c, L)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
         }
         if (!arena_push_lev(c, f_dec) || !arena_push_lev(c, poly) || !arena_push_lev(c, polyb[0]) || !arena_push_lev(c, polyb[1]) || !arena_push_lev(c, polyb[2]) ||
-            !arena_push_lev(c, polyb[3]) || !arena_push_lev(c, chan) || !arena_push_lev(c, seq) || !arena_push_lev(c, pre) || !arena_push_lev(c, audio) ||
+            !arena_push_lev(c, polyb[3]) || !arena_push_lev(c, chan) || !arena_push_lev(c, seq) || !arena_push_lev(c, ifc) || !arena_push_lev(c, pre) || !arena_push_lev(c, audio) ||
             !arena_push_lev(c, audio_fm) || !arena_push_lev(c, af_dec) || !arena_push_lev(c, af_hpf) || !arena_push_lev(c, af_poly) || !arena_push_lev(c, af_deemp) ||
             !arena_push_lev(c, ssbx_l) || !arena_push_lev(c, carry)) {
             return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted");
@@ -1277,7 +1295,7 @@ struct BankPlan {
     int emit_levels() {
         int rc = SDRPP_OK;
         int top = std::max({ t_dec.top, t_poly.top, t_chan.top, t_audio.top, t_audio_fm.top, t_af_dec.top, t_af_poly.top, t_af_hpf.top, f_dec.top, poly.top,
-                             polyb[0].top, polyb[1].top, polyb[2].top, polyb[3].top, chan.top, seq.top, pre.top, audio.top, audio_fm.top, af_dec.top, af_hpf.top,
+                             polyb[0].top, polyb[1].top, polyb[2].top, polyb[3].top, chan.top, seq.top, ifc.top, pre.top, audio.top, audio_fm.top, af_dec.top, af_hpf.top,
                              af_poly.top, af_deemp.top, ssbx_l.top, carry.top, d_pipes ? pipe_lvl + 1 : 0 });
         for (int l = 1; l < top; l++) {
             {
@@ -1314,6 +1332,11 @@ struct BankPlan {
                     rc = launch_fir(l, F_FIR, chan.at[l], chan.dev[l], 2, false);
                     if (rc) { return rc; }
                 }
+            }
+            if (l < ifc.top && !ifc.at[l].empty()) {
+                FamilyTimer t(c, F_DEMOD);
+                const int nj = (int)ifc.at[l].size();
+                emit(c, l, F_DEMOD, TR_IFC, (nj + 3) / 4, 1, 0, ifc.dev[l], nullptr, nj);
             }
             if ((l < pre.top && !pre.at[l].empty()) || (l < seq.top && !seq.at[l].empty()) || (l < ssbx_l.top && !ssbx_l.at[l].empty())) {
                 FamilyTimer t(c, F_DEMOD);

@@ -918,6 +918,9 @@ int sdrpp_vfo_add(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
         v->chan_ntaps = d->chan_ntaps;
     }
     v->d.chan_taps = nullptr;
+    // the IF chain's output (sdrpp_vfo_set_if): only the slot — its buffers come with the first chain, a VFO without one pays nothing
+    v->st.emplace_back();
+    v->i_ifc = (int)v->st.size() - 1;
     if (d->demod != SDRPP_DEMOD_RAW) {
         if (fm || d->demod == SDRPP_DEMOD_AM) {
             static const float unit = 1.0f;  // fm.h:165-168 loadDummyTaps: a single unit tap when the low-pass is off
@@ -991,9 +994,60 @@ static int hist_tail_copy(sdrpp_ctx* c, Stream& to, const Stream& from, int max_
     HIPCHK(c, hipMemcpy(to.hist[to.cur] + (size_t)(to.hist_len - H) * w, from.hist[from.cur] + (size_t)(from.hist_len - H) * w, (size_t)H * w * sizeof(float), hipMemcpyDeviceToDevice));
     return SDRPP_OK;
 }
+// The stream the demodulator would read without an IF chain: the channel filter's output, or its input while the filter is bypassed.
+static Stream& if_feed_stream(Vfo& v) {
+    if (v.chan_ntaps > 0 && v.i_chan >= 0) { return v.st[(size_t)v.i_chan]; }
+    return v.st[(size_t)((v.i_poly >= 0) ? v.i_poly : v.i_first + std::max(v.d.n_stages, 1) - 1)];
+}
+// sdrpp_vfo_set_if on a VFO the caller has looked up (the stream is idle).  What the demodulator remembers of its input (the discriminator's
+// previous sample, the audio low-pass's delay line) moves with the switch: it was fed the IF until a chain becomes active and the chain's
+// output from then on, or the other way round.
+static int ifc_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_if_desc* d) {
+    Vfo::Ifc& f = v.ifc;
+    if (v.i_ifc < 0) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no IF chain slot", v.id); }
+    Stream& fs = v.st[(size_t)v.i_ifc];
+    const bool was_active = f.active() && fs.base, was_nb = f.on && f.nb_on;
+    if (d) {
+        if (d->nb_enabled && !(d->nb_rate > 0.0f && d->nb_rate <= 1.0f && d->nb_level == d->nb_level)) { return fail(c, SDRPP_ERR_INVALID, "noise blanker: rate %g (0 < rate <= 1), level %g", d->nb_rate, d->nb_level); }
+        if (d->squelch_enabled && d->squelch_level != d->squelch_level) { return fail(c, SDRPP_ERR_INVALID, "squelch level is not a number"); }
+        if (!fs.base) {
+            const Stream& like = v.st[(size_t)v.i_chan];  // what the demodulator reads today: same capacity, same history
+            int rc = stream_alloc(c, fs, 2, like.hist_len, like.cap);
+            if (rc) { return rc; }
+        }
+        if (!f.d_amp) {
+            int rc = dev_alloc(c, &f.d_amp, 1);
+            if (rc) { return rc; }
+        }
+        if (d->nb_enabled && !was_nb) {  // a blanker that starts: amp = 1 (noise_blanker.h:75); one that runs keeps it through setRate / setLevel
+            const float one = 1.0f;
+            HIPCHK(c, hipMemcpy(f.d_amp, &one, sizeof(float), hipMemcpyHostToDevice));
+        }
+        f.on = true;
+        f.nb_on = d->nb_enabled != 0;
+        f.nb_rate = d->nb_rate;
+        f.nb_level = d->nb_level;
+        f.sq_on = d->squelch_enabled != 0;
+        f.sq_level = d->squelch_level;
+    }
+    else {
+        f.on = false;
+        f.nb_on = 0;
+        f.sq_on = 0;
+    }
+    const bool now_active = f.active();
+    if (was_active != now_active && fs.base) {
+        Stream& feed = if_feed_stream(v);
+        const int if_need = (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) ? std::max(v.audio_ntaps, 1) + 1 : 1;
+        int rc = now_active ? hist_tail_copy(c, fs, feed, if_need) : hist_tail_copy(c, feed, fs, if_need);
+        if (rc) { return rc; }
+    }
+    if (!now_active) { fs.n = 0; }
+    return SDRPP_OK;
+}
 int sdrpp_vfo_replace(sdrpp_ctx* c, int old_id, const sdrpp_vfo_desc* d, int keep, int* new_id) {
     DeviceScope dev_scope_(c);
-    if (!c || !d || !new_id || keep < 0 || keep > 3) { return SDRPP_ERR_INVALID; }
+    if (!c || !d || !new_id || keep < 0 || keep > 7) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
     if (c->vfos.find(old_id) == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", old_id); }
     int nid = 0;
@@ -1030,7 +1084,8 @@ int sdrpp_vfo_replace(sdrpp_ctx* c, int old_id, const sdrpp_vfo_desc* d, int kee
     }
     if ((keep & 2) && o.d.demod == n.d.demod) {
         // the demodulator's view of the IF stream: the discriminator's previous sample and the audio low-pass's delay line are its newest samples
-        Stream& oif = (o.chan_ntaps > 0 && o.i_chan >= 0) ? o.st[(size_t)o.i_chan] : of;
+        // (behind an IF chain that is what the CHAIN delivered)
+        Stream& oif = (o.ifc.active() && o.i_ifc >= 0 && o.st[(size_t)o.i_ifc].base) ? o.st[(size_t)o.i_ifc] : ((o.chan_ntaps > 0 && o.i_chan >= 0) ? o.st[(size_t)o.i_chan] : of);
         Stream& nif = (n.chan_ntaps > 0 && n.i_chan >= 0) ? n.st[(size_t)n.i_chan] : nf;
         const int if_need = (n.d.demod == SDRPP_DEMOD_WFM || n.d.demod == SDRPP_DEMOD_NFM) ? std::max(n.audio_ntaps, 1) + 1 : 1;
         rc = hist_tail_copy(c, nif, oif, if_need);
@@ -1042,6 +1097,14 @@ int sdrpp_vfo_replace(sdrpp_ctx* c, int old_id, const sdrpp_vfo_desc* d, int kee
         if (o.d_state && n.d_state) { HIPCHK(c, hipMemcpy(n.d_state, o.d_state, 2 * sizeof(AgcState) + sizeof(float), hipMemcpyDeviceToDevice)); }
         n.phi2 = o.phi2;
         if (o.d_rot && n.d_rot) { HIPCHK(c, hipMemcpy(n.d_rot + 1, o.d_rot + 1, sizeof(float2), hipMemcpyDeviceToDevice)); }
+    }
+    if ((keep & 4) && o.ifc.on) {
+        // the radio's IF chain objects are not the demodulator's: they live through a demodulator switch (radio_module.h:84-96, 419-563), the
+        // blanker with its amplitude estimate.  Attaching copies the demodulator's view of the IF (set above) into the chain's history.
+        const sdrpp_if_desc fd{ o.ifc.nb_on, o.ifc.nb_rate, o.ifc.nb_level, o.ifc.sq_on, o.ifc.sq_level };
+        rc = ifc_apply(c, n, &fd);
+        if (rc) { return rc; }
+        if (o.ifc.nb_on && o.ifc.d_amp && n.ifc.d_amp) { HIPCHK(c, hipMemcpy(n.ifc.d_amp, o.ifc.d_amp, sizeof(float), hipMemcpyDeviceToDevice)); }
     }
     rc = sdrpp_vfo_remove(c, old_id);
     if (rc) { return rc; }
@@ -1297,12 +1360,67 @@ int sdrpp_vfo_af_device_buffer(sdrpp_ctx* c, int id, const float** out, int* n_o
 
 int sdrpp_abi_sizeof_af_desc(void) { return (int)sizeof(sdrpp_af_desc); }
 
+// ---- radio IF chain: NoiseBlanker -> PowerSquelch between RxVFO::out and the demodulator (radio_module.h:84-96) ---------------------
+int sdrpp_vfo_set_if(sdrpp_ctx* c, int id, const sdrpp_if_desc* d) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    auto it = c->vfos.find(id);
+    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ifc_apply(c, *it->second, d);
+}
+
+static Stream* ifc_stream(Vfo& v) { return (v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base) ? &v.st[(size_t)v.i_ifc] : nullptr; }
+
+int sdrpp_vfo_ifc_count(sdrpp_ctx* c, int id) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    auto it = c->vfos.find(id);
+    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
+    Stream* s = ifc_stream(*it->second);
+    if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no active IF chain", id); }
+    return s->n;
+}
+
+int sdrpp_vfo_ifc_read(sdrpp_ctx* c, int id, float* dst, int max) {
+    DeviceScope dev_scope_(c);
+    if (!c || !dst || max < 0) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    auto it = c->vfos.find(id);
+    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
+    Stream* s = ifc_stream(*it->second);
+    if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no active IF chain", id); }
+    const int n = std::min(max, s->n);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = pipe_timeouts_check(c)) { return rc; }
+    if (n > 0) { HIPCHK(c, hipMemcpy(dst, s->data, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost)); }
+    return n;
+}
+
+int sdrpp_vfo_ifc_device_buffer(sdrpp_ctx* c, int id, const float** out, int* n_out) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    auto it = c->vfos.find(id);
+    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
+    Stream* s = ifc_stream(*it->second);
+    if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no active IF chain", id); }
+    if (out) { *out = s->data; }
+    if (n_out) { *n_out = s->n; }
+    return SDRPP_OK;
+}
+
+int sdrpp_abi_sizeof_if_desc(void) { return (int)sizeof(sdrpp_if_desc); }
+
 // ---- sink-side sample packing ----------------------------------------------------------------------------------
 static Stream* pick_stream(sdrpp_ctx* c, Vfo& v, int which) {
     (void)c;
-    if (which == 0) { return (v.d.demod == SDRPP_DEMOD_RAW) ? &v.st[(size_t)v.i_if] : &v.st[(size_t)v.i_out]; }
+    if (which == 0) { return (v.d.demod == SDRPP_DEMOD_RAW) ? (ifc_stream(v) ? ifc_stream(v) : &v.st[(size_t)v.i_if]) : &v.st[(size_t)v.i_out]; }
     if (which == 1) { return &v.st[(size_t)v.i_if]; }
     if (which == 2) { return (v.af.on && v.af.i_last >= 0) ? &v.st[(size_t)v.af.i_last] : nullptr; }
+    if (which == 3) { return ifc_stream(v); }
     return nullptr;
 }
 static int pack_scratch(sdrpp_ctx* c, size_t bytes) {
@@ -1481,7 +1599,11 @@ int sdrpp_vfo_reset(sdrpp_ctx* c, int id) {
     return vfo_reset_state(c, *it->second);
 }
 
-static Stream* out_stream(Vfo& v) { return (v.d.demod == SDRPP_DEMOD_RAW) ? &v.st[(size_t)v.i_if] : &v.st[(size_t)v.i_out]; }
+static Stream* out_stream(Vfo& v) {  // (a RAW VFO with an IF chain delivers the chain's output)
+    if (v.d.demod != SDRPP_DEMOD_RAW) { return &v.st[(size_t)v.i_out]; }
+    Stream* f = ifc_stream(v);
+    return f ? f : &v.st[(size_t)v.i_if];
+}
 
 int sdrpp_vfo_out_count(sdrpp_ctx* c, int id) {
     DeviceScope dev_scope_(c);
@@ -2024,7 +2146,7 @@ const char* sdrpp_pipeline_role_name(int role) {
     static const char* const names[] = { "none", "copy", "carry", "rot", "fcm_132_4", "fcm_6", "fcm_10", "fcm_16", "fcm16_132_4", "fcl_0", "fcl_pf", "toep_c", "toep_r", "toep_q",
                                          "firb_c", "firb_r", "firb_s", "firb_q", "pre", "seq", "fft_s10", "fft_s11", "fft_s12", "fft_p1_5", "fft_p1_6", "fft_p1_7", "fft_p1_8", "fft_p1_9",
                                          "fft_p1_10", "fft_p2_7", "fft_p2_8", "fft_p2_9", "fft_p2_10", "fft_p2row", "fft_tr", "zoom_16", "zoom_4", "zoom_1", "polyc", "deemp_p0", "deemp_p1",
-                                         "dc_p0", "dc_p1", "wf_ring", "wf_trace", "pipe", "rotx16", "fird", "ssbx", "s1_1", "s1d_1", "f2_1", "poly" };
+                                         "dc_p0", "dc_p1", "wf_ring", "wf_trace", "pipe", "rotx16", "fird", "ssbx", "s1_1", "s1d_1", "f2_1", "poly", "ifc" };
     static_assert(sizeof(names) / sizeof(names[0]) == TR_COUNT, "role names out of step with TickRole");
     return (role >= 0 && role < TR_COUNT) ? names[role] : nullptr;
 }

@@ -80,7 +80,7 @@ inline int tick_role_weight(int role, bool crowded) {
     switch (role) {
     case TR_FCL_0: case TR_FCL_PF: return 72;
     case TR_FCM_132_4: case TR_FCM_6: case TR_FCM_10: case TR_FCM_16: case TR_FCM16_132_4: case TR_S1_1: case TR_S1D_1: case TR_F2_1: return 90;
-    case TR_SEQ: case TR_SSBX: return 85;
+    case TR_SEQ: case TR_SSBX: case TR_IFC: return 85;  // (one wavefront per VFO walking its whole block: few and long)
     case TR_FIRB_C: case TR_FIRB_R: case TR_FIRB_S: case TR_FIRB_Q: return 70;
     case TR_POLYC: return 55;
     case TR_DEEMP_P1: case TR_DC_P1: return 52;
@@ -236,6 +236,10 @@ const Stream& result_stream(const Vfo& v, int* level = nullptr) {
         return v.st[(size_t)v.af.i_last];
     }
     const bool raw = v.d.demod == SDRPP_DEMOD_RAW;
+    if (raw && v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base) {  // a RAW VFO behind an IF chain: the chain's output
+        if (level) { *level = v.lvl_ifc; }
+        return v.st[(size_t)v.i_ifc];
+    }
     if (level) { *level = raw ? v.lvl_if : v.lvl_out; }
     return raw ? v.st[(size_t)v.i_if] : v.st[(size_t)v.i_out];
 }
@@ -373,7 +377,7 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
             const Vfo& v = *kv.second;
             int lvl = 1;
             const Stream& s = result_stream(v, &lvl);
-            const std::vector<int>& tk = (&s == &v.st[(size_t)v.i_if] || (v.i_out >= 0 && &s == &v.st[(size_t)v.i_out])) ? v.tk_if : v.tk_af;
+            const std::vector<int>& tk = (&s == &v.st[(size_t)v.i_if] || (v.i_out >= 0 && &s == &v.st[(size_t)v.i_out]) || (v.i_ifc >= 0 && &s == &v.st[(size_t)v.i_ifc])) ? v.tk_if : v.tk_af;
             if (split && ((int)tk.size() != k || tk[(size_t)k - 1] != s.n)) { return fail(c, SDRPP_ERR_INVALID, "internal: push ends of VFO %d do not add up (%zu ends, %d samples)", v.id, tk.size(), s.n); }
             for (int j = 0; j < k; j++) {
                 const int lo = (split && j > 0) ? tk[(size_t)j - 1] : 0, hi = split ? tk[(size_t)j] : s.n;

@@ -129,6 +129,12 @@ public:
     // every analog demodulator of the radio module).  detachAF() puts the demodulator output back on `audio`.
     void attachAF(double audioSamplerate = 48000.0, double deempTau = 50e-6, bool highPass = false);
     void detachAF();
+    // The radio module's IF chain in front of the demodulator (radio_module.h:84-96), on the device: NoiseBlanker(500 / IF rate, level) ->
+    // PowerSquelch(level in dB), either switchable while the stream runs (sdrpp_vfo_set_if: the blanker's amplitude estimate lives through
+    // level changes, re-plans and demodulator switches, as the reference's `nb` object does).  `out` stays the stream in front of the chain;
+    // a channel without a demodulator delivers the chain's output on it.  Not on the device: FMIF and the CTCSS squelch.
+    void setNoiseBlanker(bool enabled, double level = 10.0);
+    void setSquelch(bool enabled, double level = -100.0);
     // Parity switch for THIS channel (sdrpp_vfo_desc.nco_mode): true = the reference's float rotator recursion on the device (what an SSB
     // product detector or a raw-IF consumer needs to follow a CPU build's own rounding drift), false = closed-form NCO, the fast path
     void setReferenceRotator(bool enabled);
@@ -140,6 +146,8 @@ public:
     double agcAttack = 50.0, agcDecay = 5.0;
     int ncoMode = 0;  // 0: the front end's mode (IQFrontEnd::setReferenceRotator), 1: closed form, 2: reference rotator
     bool afOn = false, afHighPass = false;
+    bool nbOn = false, squelchOn = false;
+    double nbLevel = 10.0, squelchLevel = -100.0;
     double afAudioRate = 48000.0, afDeempTau = 50e-6;
 
 private:
@@ -1164,9 +1172,24 @@ private:
             const double tr = v.demod == Demod::USB ? dbw / 2.0 : (v.demod == Demod::LSB ? -dbw / 2.0 : 0.0);
             sdrpp_design_phase_delta(tr, v.outSamplerate, &d.ssb_phase_delta_re, &d.ssb_phase_delta_im);
         }
-        int rc = oldId >= 0 ? sdrpp_vfo_replace(ctx, oldId, &d, keep, &v.id) : sdrpp_vfo_add(ctx, &d, &v.id);
+        // (keep | 4: the IF chain and the blanker's amplitude estimate move to the new handle — the radio module's IF-chain blocks outlive every re-plan)
+        int rc = oldId >= 0 ? sdrpp_vfo_replace(ctx, oldId, &d, keep | 4, &v.id) : sdrpp_vfo_add(ctx, &d, &v.id);
         if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_add: ") + sdrpp_last_error(ctx)); }
+        if (v.nbOn || v.squelchOn) { applyIF(v); }  // (the blanker's rate follows the IF rate: radio_module.h:526)
         if (v.afOn && v.demod != Demod::RAW) { applyAF(v); }
+    }
+
+    // radio_module.h:90-91: nb.init(NULL, 500.0 / ifRate, 10.0); powerSquelch.init(NULL, MIN_SQUELCH)
+    void applyIF(RxVFO& v) {
+        sdrpp_if_desc f;
+        memset(&f, 0, sizeof(f));
+        f.nb_enabled = v.nbOn ? 1 : 0;
+        f.nb_rate = (float)(500.0 / v.outSamplerate);
+        f.nb_level = (float)v.nbLevel;
+        f.squelch_enabled = v.squelchOn ? 1 : 0;
+        f.squelch_level = (float)v.squelchLevel;
+        int rc = sdrpp_vfo_set_if(ctx, v.id, &f);
+        if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_if: ") + sdrpp_last_error(ctx)); }
     }
 
     // radio_module.h:98-110: resamp.init(NULL, afRate, audioRate); hpTaps = highPass(300, 100, audioRate); deemp.init(NULL, tau, audioRate)
@@ -1474,6 +1497,22 @@ inline void RxVFO::detachAF() {
     fe->tempStop();
     afOn = false;
     if (id >= 0) { sdrpp_vfo_set_af(fe->ctx, id, nullptr); }
+    fe->tempStart();
+}
+inline void RxVFO::setNoiseBlanker(bool enabled, double level) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    fe->tempStop();
+    nbOn = enabled;
+    nbLevel = level;
+    if (id >= 0) { fe->applyIF(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::setSquelch(bool enabled, double level) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    fe->tempStop();
+    squelchOn = enabled;
+    squelchLevel = level;
+    if (id >= 0) { fe->applyIF(*this); }
     fe->tempStart();
 }
 

@@ -13,8 +13,12 @@
 //   using GpuWFM = sdrpp_gpu::FusedDemodulator<demod::Demodulator, sdrpp_gpu::Demod::WFM>;
 //   ... demod = new GpuWFM(&sigpath::iqFrontEnd);  demod->init(name, &config, vfo->output, bw, audioSR);
 //
-// Not covered (a fused VFO cannot have CPU blocks between channeliser and demodulator): the radio module's IF chain (noise
-// blanker, FM IF noise reduction, squelch; radio_module.h:84-96) must stay disabled — init() throws if `input` is not a VFO output.
+// The radio module's IF chain (radio_module.h:84-96) sits between the VFO and the demodulator; a fused VFO has no place for CPU blocks
+// there, so its two cheap blocks run on the device: the noise blanker and the power squelch (setNBEnabled / setNBLevel /
+// setSquelchEnabled / setSquelchLevel below, with the radio module's clamps; sdrpp_vfo_set_if).  The radio module keeps its own
+// `nb` / `powerSquelch` blocks disabled and forwards its menu / interface commands to these setters.
+// Not covered: FMIF (the FFT-based FM IF noise reduction) and the AF-side CTCSS squelch — with one of them enabled the demodulator's
+// input is no longer a VFO's own stream and init() / setInput() throw, as before.
 // showMenu() draws nothing (GUI is out of scope); the options it would toggle are setLowPass / setAGC* / setCarrierAgc below.
 #pragma once
 #include <stdexcept>
@@ -102,6 +106,11 @@ public:
     void setAGCAttack(double attack) { _agcAttack = attack; apply(); }
     void setAGCDecay(double decay) { _agcDecay = decay; apply(); }
     void setCarrierAgc(bool enabled) { _carrierAgc = enabled; apply(); }
+    // the radio module's IF chain on the device (radio_module.h:633-713; clamps :908-911: MIN_NB 1, MAX_NB 10, MIN_SQUELCH -100, MAX_SQUELCH 0)
+    void setNBEnabled(bool enabled) { _nbEnabled = enabled; applyIF(); }
+    void setNBLevel(float level) { _nbLevel = level < 1.0f ? 1.0f : (level > 10.0f ? 10.0f : level); applyIF(); }
+    void setSquelchEnabled(bool enabled) { _squelchEnabled = enabled; applyIF(); }
+    void setSquelchLevel(float level) { _squelchLevel = level < -100.0f ? -100.0f : (level > 0.0f ? 0.0f : level); applyIF(); }
     RxVFO* channel() { return vfo; }
 
 private:
@@ -109,16 +118,28 @@ private:
         RxVFO* v = fe ? fe->vfoOfStream(input) : nullptr;
         if (!v) {
             throw std::runtime_error("[sdrpp_gpu::FusedDemodulator] the input is not the output stream of a VFO of this front end "
-                                     "(the radio module's IF chain blocks must stay disabled: the demodulator is fused behind the channeliser)");
+                                     "(noise blanker and squelch run on the device — setNBEnabled / setSquelchEnabled; FMIF and the CTCSS squelch must stay disabled: "
+                                     "the demodulator is fused behind the channeliser)");
         }
-        if (vfo && vfo != v) { vfo->attachDemod(Demod::RAW); }  // the previous channel goes back to delivering its IF
+        if (vfo && vfo != v) {  // the previous channel goes back to delivering its IF
+            vfo->setNoiseBlanker(false, _nbLevel);
+            vfo->setSquelch(false, _squelchLevel);
+            vfo->attachDemod(Demod::RAW);
+        }
         vfo = v;
         apply();
+        applyIF();
     }
     void apply() {
         if (!vfo) { return; }
         vfo->demodBandwidth = _bandwidth;
         vfo->attachDemod(MODE, _lowPass, _agcAttack, _agcDecay, _carrierAgc);
+    }
+
+    void applyIF() {
+        if (!vfo) { return; }
+        if (vfo->nbOn != _nbEnabled || vfo->nbLevel != (double)_nbLevel) { vfo->setNoiseBlanker(_nbEnabled, _nbLevel); }
+        if (vfo->squelchOn != _squelchEnabled || vfo->squelchLevel != (double)_squelchLevel) { vfo->setSquelch(_squelchEnabled, _squelchLevel); }
     }
 
     IQFrontEnd* fe;
@@ -127,6 +148,8 @@ private:
     double _bandwidth = 0.0;
     bool _lowPass = true, _carrierAgc = false;
     double _agcAttack = 50.0, _agcDecay = 5.0;  // am.h:98-99, usb.h:92-93
+    bool _nbEnabled = false, _squelchEnabled = false;
+    float _nbLevel = 10.0f, _squelchLevel = -100.0f;  // radio_module.h:906, :446
 };
 
 }  // namespace sdrpp_gpu

@@ -182,3 +182,15 @@ def af_desc(af_rate, audio_rate=48000.0, deemp_tau=50e-6, high_pass=False):
         a.hpf_taps = _fp(ht)
     a.deemph_alpha = capi.design_deemphasis_alpha(deemp_tau, audio_rate) if deemp_tau else 0.0
     return a, keep
+
+
+def if_desc(if_rate, nb=False, nb_level=10.0, squelch=None):
+    """sdrpp_if_desc for the radio module's IF chain (radio_module.h:84-96): NoiseBlanker(rate = 500 / if_rate, level; :90, :526) ->
+    PowerSquelch(level in dB; None = off).  FMIF and the CTCSS squelch are not on the device."""
+    f = capi.IfDesc()
+    f.nb_enabled = int(bool(nb))
+    f.nb_rate = 500.0 / float(if_rate)
+    f.nb_level = float(nb_level)
+    f.squelch_enabled = int(squelch is not None)
+    f.squelch_level = float(squelch) if squelch is not None else 0.0
+    return f
