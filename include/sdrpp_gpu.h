@@ -40,7 +40,10 @@ typedef struct sdrpp_ctx sdrpp_ctx;
 /* ---- lifecycle ----------------------------------------------------------------------------------------------------- */
 /* Replaces IQFrontEnd::init's allocation half (iq_frontend.cpp:17-71).  `max_push` = largest sample count one
  * sdrpp_push* call will carry (the reference's streams carry <= 1 000 000, core/src/dsp/stream.h:9; device-resident
- * callers may use larger batches). */
+ * callers may use larger batches).
+ * The SDRPP_GPU_* environment variables the library reads when a context is created (grid rules of the ticks, SDRPP_GPU_FRONT_WAVES, ...)
+ * are test and measurement switches: results are bit-identical with or without them, only the shape of the launches changes.  A host
+ * does not set them; unset is the tuned configuration. */
 int sdrpp_device_count(void);   /* usable devices (0: none — nothing here runs without one) */
 int sdrpp_create(int device, int64_t max_push, sdrpp_ctx** ctx);
 int sdrpp_destroy(sdrpp_ctx* ctx);
@@ -498,6 +501,14 @@ int sdrpp_result_take_lines(sdrpp_ctx* ctx, uint64_t ticket, float* zoomed_dst, 
 #define SDRPP_PIPELINE_STATS_HEAD 8
 int sdrpp_pipeline_stats(sdrpp_ctx* ctx, int64_t* out, int max);
 const char* sdrpp_pipeline_role_name(int role);
+/* Which kernel forms the ORDINARY pass launched (sdrpp_push outside pipelined mode, and the blocks of a pipelined run that fell back to a
+ * pass) — for tests, which assert the kernel they mean to test.  out[f] = launches of form f since sdrpp_create, names[f] its name (static
+ * strings): f < R (sdrpp_pipeline_stats out[5]) are the forms that are also roles, named as sdrpp_pipeline_role_name(f); behind them the forms
+ * an ordinary pass alone has: "polyb_4", "polyb_8", "polyb_4_odd", "polyb_8_odd" (the resampler with up to 4 / 8 phases whose Toeplitz table
+ * does not fit, even / odd decimation), "s1_8|4|2", "s1d_8|4|2", "f2_8_44_3", "f2_8|4|2" (the VALU front ends with 8 / 4 / 2 VFOs per job), "rotx_1" (the one-wavefront reference rotator).
+ * Either array may be NULL (ctx may be NULL when out is).  Returns the number of entries written (<= max); a launch of an FFT-branch kernel is
+ * not counted. */
+int sdrpp_pass_form_stats(sdrpp_ctx* ctx, int64_t* out, const char** names, int max);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------------------- */
 /* Cumulative per-kernel-family device time measured with HIP events on the context's stream while timing is enabled.

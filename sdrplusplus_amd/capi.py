@@ -249,6 +249,7 @@ def load():
     L.sdrpp_pipeline_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     L.sdrpp_pipeline_role_name.restype = C.c_char_p
     L.sdrpp_pipeline_role_name.argtypes = [C.c_int]
+    L.sdrpp_pass_form_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_char_p), C.c_int]
     L.sdrpp_timing_enable.argtypes = [vp, C.c_int]
     L.sdrpp_timing_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.sdrpp_kernel_family_name.restype = C.c_char_p
@@ -272,12 +273,19 @@ EXPORTED_SYMBOLS = [
     "sdrpp_vfo_out_count", "sdrpp_vfo_read", "sdrpp_vfo_device_buffers",
     "sdrpp_set_reference_block", "sdrpp_set_nco_mode", "sdrpp_set_backend_pipeline", "sdrpp_vfo_set_ssb_phase_delta", "sdrpp_vfo_read_many", "sdrpp_set_deferred", "sdrpp_push_pinned_async", "sdrpp_push_wait", "sdrpp_pending", "sdrpp_host_alloc", "sdrpp_host_free", "sdrpp_device_alloc", "sdrpp_device_free", "sdrpp_device_copy", "sdrpp_device_count",
     "sdrpp_push", "sdrpp_push_device", "sdrpp_push_int16", "sdrpp_push_stage", "sdrpp_push_staged", "sdrpp_push_staged_when",
-    "sdrpp_set_pipelined", "sdrpp_set_pipeline_group", "sdrpp_pipeline_group_stats", "sdrpp_ticket", "sdrpp_pipeline_flush", "sdrpp_pipeline_launch_held", "sdrpp_result_ready", "sdrpp_result_wait", "sdrpp_result_release", "sdrpp_result_take_lines", "sdrpp_pipeline_stats", "sdrpp_pipeline_role_name",
+    "sdrpp_set_pipelined", "sdrpp_set_pipeline_group", "sdrpp_pipeline_group_stats", "sdrpp_ticket", "sdrpp_pipeline_flush", "sdrpp_pipeline_launch_held", "sdrpp_result_ready", "sdrpp_result_wait", "sdrpp_result_release", "sdrpp_result_take_lines", "sdrpp_pipeline_stats", "sdrpp_pipeline_role_name", "sdrpp_pass_form_stats",
     "sdrpp_timing_enable", "sdrpp_timing_read", "sdrpp_kernel_family_name",
 ]
 
 
 # ---- host-side design helpers (pure CPU maths inside the library) ---------------------------------------------------------
+def pass_form_names():
+    """Every form sdrpp_pass_form_stats counts, in its order: the tick kernel's roles, then the forms only an ordinary pass has."""
+    names = (C.c_char_p * 128)()
+    n = load().sdrpp_pass_form_stats(None, None, names, 128)
+    return [names[i].decode() for i in range(n)]
+
+
 def design_low_pass(cutoff, trans_width, sample_rate, odd=False):
     L = load()
     n = L.sdrpp_design_low_pass(cutoff, trans_width, sample_rate, int(odd), None, 0)
@@ -746,6 +754,13 @@ class Context:
             if 8 + r < n and buf[8 + r]:
                 roles[self.L.sdrpp_pipeline_role_name(r).decode()] = int(buf[8 + r])
         return dict(ticks=int(buf[0]), tick_blocks=int(buf[1]), pass_blocks=int(buf[2]), crowded_ticks=int(buf[3]), depth=int(buf[4]), table_bytes=int(buf[7]), roles=roles)
+
+    def pass_form_stats(self):
+        """sdrpp_pass_form_stats -> {form name: launches} of the forms the ordinary pass has launched so far."""
+        buf = (C.c_int64 * 128)()
+        names = (C.c_char_p * 128)()
+        n = self._chk(self.L.sdrpp_pass_form_stats(self.h, buf, names, 128))
+        return {names[i].decode(): int(buf[i]) for i in range(n) if buf[i]}
 
     # measurement
     def timing_enable(self, on=True, families=None):

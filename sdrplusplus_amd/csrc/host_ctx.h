@@ -294,6 +294,9 @@ struct sdrpp_ctx {
     int fft_tick_grid = getenv("SDRPP_GPU_FFT_TICK_GRID") ? atoi(getenv("SDRPP_GPU_FFT_TICK_GRID")) : 0;  // ... of a pass-1 / pass-2 role inside a tick (a shared GPU: 18.4 / 16.2 / 18.8 / 18.5 GS/s at 0 / 64 / 128 / 256; cfg 2: 61.7 / - / 57.0)
     int tick_zoom_groups = getenv("SDRPP_GPU_TICK_ZOOM_GROUPS") ? atoi(getenv("SDRPP_GPU_TICK_ZOOM_GROUPS")) : 8;
     int tick_fcm_waves = getenv("SDRPP_GPU_TICK_FCM_WAVES") ? atoi(getenv("SDRPP_GPU_TICK_FCM_WAVES")) : 768;
+    // wavefronts the tiles of ONE matrix front-end job (vfo_frontcm / vfo_frontcl) are dealt out over, in a pass and in a tick alike; 0: the rules of
+    // group_front / upload.  TEST-ONLY (a host never sets it: N wavefronts per job leave the device idle): small blocks then walk many tiles per wavefront, as 10^6-sample blocks do under the rules.
+    int front_walk_waves = getenv("SDRPP_GPU_FRONT_WAVES") ? std::max(0, atoi(getenv("SDRPP_GPU_FRONT_WAVES"))) : 0;
     int tick_toep_blocks = getenv("SDRPP_GPU_TICK_TOEP_BLOCKS") ? atoi(getenv("SDRPP_GPU_TICK_TOEP_BLOCKS")) : 256;
     int tick_land_blocks = getenv("SDRPP_GPU_TICK_LAND_BLOCKS") ? std::max(1, atoi(getenv("SDRPP_GPU_TICK_LAND_BLOCKS"))) : 64;  // workgroups of a tick's landing copy (host-fed blocks), at most
     int tick_lds_cap = 24 * 1024;       // LDS window of the many-phase resampler as a role of a tick (launch_polyc)
@@ -385,6 +388,7 @@ struct sdrpp_ctx {
     // how the blocks of a pipelined run were executed (sdrpp_pipeline_stats: tests and bench.py assert the mode they mean to measure)
     int64_t stat_tick_blocks = 0, stat_pass_blocks = 0, stat_crowded = 0, stat_last_depth = 0, stat_last_table_bytes = 0;
     int64_t stat_role_wgs[64] = {};
+    int64_t stat_pass_forms[96] = {};  // launches of an ordinary pass per form (sdrpp_pass_form_stats): [role] for the forms that are roles, then the PassForm extras (host_util.h)
 
     // timing
     bool timing = false;

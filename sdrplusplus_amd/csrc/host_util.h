@@ -478,6 +478,21 @@ void launch(sdrpp_ctx* c, K kernel, dim3 grid, dim3 block, size_t lds, A... args
     hipLaunchKernelGGL(kernel, grid, block, lds, c->launch_stream, args...);
 }
 
+// Forms that exist only as launches of an ordinary pass (no role of the tick kernel): counted behind the roles in sdrpp_pass_form_stats.
+enum PassForm : int {
+    PF_POLYB_4 = TR_COUNT, PF_POLYB_8, PF_POLYB_4_ODD, PF_POLYB_8_ODD,  // vfo_polyb_kernel<4 | 8, false | true>
+    PF_S1_8, PF_S1_4, PF_S1_2,                                         // vfo_stage1_kernel<8 | 4 | 2>
+    PF_S1D_8, PF_S1D_4, PF_S1D_2,                                      // vfo_stage1_direct_kernel<8 | 4 | 2>
+    PF_F2_8_44_3, PF_F2_8, PF_F2_4, PF_F2_2,                           // vfo_front2_kernel<8, 44, 3>, <8 | 4 | 2, 0, 0>
+    PF_ROTX_1,                                                         // vfo_rotate_exact_kernel (the one-wavefront reference rotator: SDRPP_GPU_ROT_EXACT_SINGLE)
+    PF_COUNT
+};
+static_assert(PF_COUNT <= 96, "sdrpp_ctx::stat_pass_forms too short");
+// one launch of `form` (a TickRole or a PassForm) in an ordinary pass; while a tick is being planned nothing is launched here
+inline void count_form(sdrpp_ctx* c, int form) {
+    if (!c->tick_planning && form >= 0 && form < PF_COUNT) { c->stat_pass_forms[form]++; }
+}
+
 // ---- roles: kernels that exist both as a launch of their own and as a role of the tick kernel ------------------------------------------
 void launch_role(sdrpp_ctx* c, const sdrpp_ctx::RoleLaunch& r) {
     const TickEntry& e = r.e;
@@ -530,7 +545,10 @@ void emit(sdrpp_ctx* c, int level, int fam, int role, int gx, int gy, size_t lds
     r.level = level;
     r.fam = fam;
     if (c->tick_planning) { c->emits.push_back(r); }
-    else { launch_role(c, r); }
+    else {
+        count_form(c, role);
+        launch_role(c, r);
+    }
 }
 
 // ... the same for a role whose parameters travel in the entry itself (TickWf)
@@ -544,7 +562,10 @@ void emit_wf(sdrpp_ctx* c, int level, int fam, int role, int gx, int gy, const T
     r.level = level;
     r.fam = fam;
     if (c->tick_planning) { c->emits.push_back(r); }
-    else { launch_role(c, r); }
+    else {
+        count_form(c, role);
+        launch_role(c, r);
+    }
 }
 
 int pick_tile(int D, int K, int width_bytes) {

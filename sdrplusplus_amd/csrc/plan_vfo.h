@@ -817,6 +817,7 @@ struct BankPlan {
                 const int nsub = std::max<int>(1, (int)c->grp_ends.size());
                 const int resident = std::max(64, (m_long ? 256 * long_blocks * fcl_nw : (c->tick_planning ? std::min(3072, c->tick_fcm_waves) : 3072)) / nsub);
                 job.tiles_per_wave = std::max(1, (ntiles + resident - 1) / resident);
+                if (c->front_walk_waves > 0) { job.tiles_per_wave = std::max(1, (ntiles + c->front_walk_waves - 1) / c->front_walk_waves); }
                 job.atab = reinterpret_cast<const float*>(d_taps);
                 job.ptab = d_taps + (size_t)NP4 * 32;
                 for (int m = 0; m < SDRPP_FCM_VT; m++) {
@@ -980,6 +981,7 @@ struct BankPlan {
                 const int resident = 256 * long_blocks * fcl_nw;
                 int tpw = ticking ? std::max(1, (int)((double)ntiles * (double)fcl.jobs.size() / target + 0.75)) : std::max(1, (ntiles + resident - 1) / resident);
                 if (ticking && fcl.jobs.size() > 1) { tpw = std::max(1, (int)(per_wave / tile_cost(jb) + 0.5)); }
+                if (c->front_walk_waves > 0) { tpw = std::max(1, (ntiles + c->front_walk_waves - 1) / c->front_walk_waves); }
                 jb.tiles_per_wave = tpw;
                 fcl.max_blocks = std::max(fcl.max_blocks, (ntiles + fcl_nw * tpw - 1) / (fcl_nw * tpw));
             }
@@ -1048,13 +1050,17 @@ struct BankPlan {
         {
             FamilyTimer t(c, F_S1);
             if (!rotx.empty() && n_in > 0) {
-                if (c->rot_exact_single) { launch(c, vfo_rotate_exact_kernel, dim3(((unsigned)rotx.size() + 63) / 64), dim3(64), (size_t)64 * 65 * sizeof(float2), src, (const RotXJob*)d_rotx, (int)rotx.size(), d_fb, (int)fb.size()); }
+                if (c->rot_exact_single) {
+                    count_form(c, PF_ROTX_1);
+                    launch(c, vfo_rotate_exact_kernel, dim3(((unsigned)rotx.size() + 63) / 64), dim3(64), (size_t)64 * 65 * sizeof(float2), src, (const RotXJob*)d_rotx, (int)rotx.size(), d_fb, (int)fb.size());
+                }
                 else if (c->tick_planning) {  // pipelined: the chain as a role of the tick (level 1: its VFOs' first stages follow at level 2)
                     emit(c, L0 + 1, F_S1, TR_ROTX16, ((int)rotx.size() + c->rot_exact_vpw - 1) / c->rot_exact_vpw, 1, SDRPP_ROTX4_LDS_BYTES, d_rotx_head, &src);
                 }
                 else {
                     const int vpw = c->rot_exact_vpw;
                     const dim3 grid(((unsigned)rotx.size() + vpw - 1) / vpw);
+                    count_form(c, TR_ROTX16);
                     launch(c, vfo_rotate_exact4_kernel<16>, grid, dim3(256), SDRPP_ROTX4_LDS_BYTES, src, (const RotXJob*)d_rotx, (int)rotx.size(), d_fb, (int)fb.size(), vpw);
                 }
             }
@@ -1068,6 +1074,7 @@ struct BankPlan {
                         continue;
                     }
                     const dim3 grid((s1l[k].max_nout + 255) / 256, (unsigned)s1l[k].jobs.size());
+                    count_form(c, s1l[k].vt == 8 ? (int)PF_S1D_8 : (s1l[k].vt == 4 ? (int)PF_S1D_4 : (s1l[k].vt == 2 ? (int)PF_S1D_2 : (int)TR_S1D_1)));
                     switch (s1l[k].vt) {
                     case 8: launch(c, vfo_stage1_direct_kernel<8>, grid, dim3(256), 0, src, (const Stage1Job*)d_s1[k]); break;
                     case 4: launch(c, vfo_stage1_direct_kernel<4>, grid, dim3(256), 0, src, (const Stage1Job*)d_s1[k]); break;
@@ -1082,6 +1089,7 @@ struct BankPlan {
                 }
                 const dim3 grid((s1l[k].max_nout + s1l[k].tile - 1) / s1l[k].tile, (unsigned)s1l[k].jobs.size());
                 const dim3 block(s1l[k].tile);
+                count_form(c, s1l[k].vt == 8 ? (int)PF_S1_8 : (s1l[k].vt == 4 ? (int)PF_S1_4 : (s1l[k].vt == 2 ? (int)PF_S1_2 : (int)TR_S1_1)));
                 switch (s1l[k].vt) {
                 case 8: launch(c, vfo_stage1_kernel<8>, grid, block, s1l[k].lds, src, (const Stage1Job*)d_s1[k]); break;
                 case 4: launch(c, vfo_stage1_kernel<4>, grid, block, s1l[k].lds, src, (const Stage1Job*)d_s1[k]); break;
@@ -1101,6 +1109,7 @@ struct BankPlan {
                 // fully unrolled instance, everything else runs the generic loop
                 bool all_44_3 = true;
                 for (auto& jb : f2l[k].jobs) { all_44_3 = all_44_3 && jb.ntaps1 == 44 && jb.log2_decim1 == 3; }
+                count_form(c, f2l[k].vt == 8 ? (int)(all_44_3 ? PF_F2_8_44_3 : PF_F2_8) : (f2l[k].vt == 4 ? (int)PF_F2_4 : (f2l[k].vt == 2 ? (int)PF_F2_2 : (int)TR_F2_1)));
                 switch (f2l[k].vt) {
                 case 8:
                     if (all_44_3) { launch(c, vfo_front2_kernel<8, 44, 3>, grid, block, f2l[k].lds, src, (const Front2Job*)d_f2[k]); }
@@ -1173,7 +1182,10 @@ struct BankPlan {
                 for (auto& jb : jobs) { max_nout = std::max(max_nout, jb.nout); }
                 if (max_nout > 0) {
                     if (c->tick_planning) { emit(c, level, fam, TR_FIRD, std::min((max_nout + 255) / 256, 1024), (int)jobs.size(), 0, d_jobs); }
-                    else { launch(c, vfo_fir_direct_kernel<false>, dim3((unsigned)std::min((max_nout + 255) / 256, 1024), (unsigned)jobs.size()), dim3(256), 0, (const FirBJob*)d_jobs); }
+                    else {
+                        count_form(c, TR_FIRD);
+                        launch(c, vfo_fir_direct_kernel<false>, dim3((unsigned)std::min((max_nout + 255) / 256, 1024), (unsigned)jobs.size()), dim3(256), 0, (const FirBJob*)d_jobs);
+                    }
                 }
                 return SDRPP_OK;
             }
@@ -1229,7 +1241,10 @@ struct BankPlan {
             }
             if (lds > (size_t)kMaxLds) { return fail(c, SDRPP_ERR_UNSUPPORTED, "polyphase tile does not fit in LDS"); }
             if (c->tick_planning) { emit(c, level, fam, TR_POLY, (max_nout + tile - 1) / tile, (int)jobs.size(), lds, d_jobs); }
-            else { launch(c, vfo_poly_kernel, dim3((max_nout + tile - 1) / tile, (unsigned)jobs.size()), dim3(tile), lds, (const PolyJob*)d_jobs); }
+            else {
+                count_form(c, TR_POLY);
+                launch(c, vfo_poly_kernel, dim3((max_nout + tile - 1) / tile, (unsigned)jobs.size()), dim3(tile), lds, (const PolyJob*)d_jobs);
+            }
             return SDRPP_OK;
     }
     int launch_polyb(int li, std::vector<PolyBJob>& jobs, PolyBJob* d_jobs) {
@@ -1248,6 +1263,7 @@ struct BankPlan {
             while (threads > 64 && (size_t)((max_cycles + threads - 1) / threads) * jobs.size() < 2048) { threads >>= 1; }
             for (auto& jb : jobs) { lds = std::max(lds, lds_for(jb, threads)); }
             const dim3 grid((max_cycles + threads - 1) / threads, (unsigned)jobs.size());
+            count_form(c, PF_POLYB_4 + li);
             if (li == 0) { launch(c, vfo_polyb_kernel<4, false>, grid, dim3(threads), lds, (const PolyBJob*)d_jobs); }
             else if (li == 1) { launch(c, vfo_polyb_kernel<8, false>, grid, dim3(threads), lds, (const PolyBJob*)d_jobs); }
             else if (li == 2) { launch(c, vfo_polyb_kernel<4, true>, grid, dim3(threads), lds, (const PolyBJob*)d_jobs); }
@@ -1343,7 +1359,10 @@ struct BankPlan {
                 if (l < ssbx_l.top && !ssbx_l.at[l].empty()) {
                     const int nj = (int)ssbx_l.at[l].size();
                     if (c->tick_planning) { emit(c, l, F_DEMOD, TR_SSBX, (nj + 3) / 4, 1, 0, ssbx_l.dev[l], nullptr, nj); }
-                    else { launch(c, vfo_ssb_rotate_exact_kernel, dim3((unsigned)nj), dim3(64), 0, (const SsbRotXJob*)ssbx_l.dev[l]); }
+                    else {
+                        count_form(c, TR_SSBX);
+                        launch(c, vfo_ssb_rotate_exact_kernel, dim3((unsigned)nj), dim3(64), 0, (const SsbRotXJob*)ssbx_l.dev[l]);
+                    }
                 }
                 if (l < pre.top && !pre.at[l].empty()) {
                     int mx = 0;

@@ -2150,6 +2150,17 @@ const char* sdrpp_pipeline_role_name(int role) {
     static_assert(sizeof(names) / sizeof(names[0]) == TR_COUNT, "role names out of step with TickRole");
     return (role >= 0 && role < TR_COUNT) ? names[role] : nullptr;
 }
+int sdrpp_pass_form_stats(sdrpp_ctx* c, int64_t* out, const char** names, int max) {
+    static const char* const extra[] = { "polyb_4", "polyb_8", "polyb_4_odd", "polyb_8_odd", "s1_8", "s1_4", "s1_2", "s1d_8", "s1d_4", "s1d_2", "f2_8_44_3", "f2_8", "f2_4", "f2_2", "rotx_1" };
+    static_assert(sizeof(extra) / sizeof(extra[0]) == PF_COUNT - TR_COUNT, "form names out of step with PassForm");
+    if (max < 0 || (out && !c)) { return SDRPP_ERR_INVALID; }
+    int n = 0;
+    for (; n < PF_COUNT && n < max; n++) {
+        if (out) { out[n] = c->stat_pass_forms[n]; }
+        if (names) { names[n] = n < TR_COUNT ? sdrpp_pipeline_role_name(n) : extra[n - TR_COUNT]; }
+    }
+    return n;
+}
 
 // ---- measurement ---------------------------------------------------------------------------------------------------------------------
 int sdrpp_timing_enable(sdrpp_ctx* c, int on) {

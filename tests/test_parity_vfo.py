@@ -343,6 +343,8 @@ def test_reference_rotator_four_wavefront_kernel_is_bit_identical(backend, monke
             pos += n
             got.append([a.copy() for a in ctx.vfo_read_many(vids)] + [a.copy() for a in ctx.vfo_read_many(vids, which=[1] * len(vids))])
         outs.append(got)
+        forms = ctx.pass_form_stats()  # each leg ran the kernel it names
+        assert (forms.get("rotx_1", 0) > 0 and "rotx16" not in forms) if single else (forms.get("rotx16", 0) > 0 and "rotx_1" not in forms), forms
         ctx.close()
     for ga, gb in zip(*outs):
         for a, b in zip(ga, gb):
