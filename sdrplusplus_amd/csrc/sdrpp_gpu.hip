@@ -35,6 +35,7 @@ using namespace sdrpp_k;
 #include "plan_pre.h"
 #include "plan_push.h"
 #include "tick_host.h"
+#include "vfo_ctl.h"
 
 // =====================================================================================================================
 // C ABI
@@ -65,6 +66,10 @@ struct DeviceScope {
         int frc_ = flush_pending(c);              \
         if (frc_) { return frc_; }                \
     } while (0)
+// ... and every call that takes a VFO id then looks it up (vfo_lookup has set the message)
+#define LOOKUP_VFO(v, c, id)    \
+    Vfo* v = vfo_lookup(c, id); \
+    if (!v) { return SDRPP_ERR_NOT_FOUND; }
 
 extern "C" {
 
@@ -434,20 +439,6 @@ int sdrpp_destroy(sdrpp_ctx* c) {
 
 const char* sdrpp_last_error(const sdrpp_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
-// A pipelined back-end launch whose wavefronts gave up waiting for each other (never seen; a hang would be worse) counted that in THIS context's
-// page-locked word.  Called wherever the host has just synchronised with the stream and is about to hand out results.
-static int pipe_timeouts_check(sdrpp_ctx* c) {
-    if (!c->pipe_launched || !c->h_tick_flag) { return SDRPP_OK; }
-    c->pipe_launched = false;
-    const int n = *(const volatile int*)(c->h_tick_flag + 8);
-    if (n != c->timeouts_seen) {
-        const int d = n - c->timeouts_seen;
-        c->timeouts_seen = n;
-        return fail(c, SDRPP_ERR_HIP, "pipelined back end: %d wavefront waits timed out (results of the last pushes are invalid)", d);
-    }
-    return SDRPP_OK;
-}
-
 int sdrpp_set_stream(sdrpp_ctx* c, void* s) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
@@ -746,29 +737,21 @@ int sdrpp_preproc_out_count(sdrpp_ctx* c) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    if (!c->pre.on) { return fail(c, SDRPP_ERR_INVALID, "no pre-processing chain configured"); }
-    return c->pre.last_n;
+    return out_count(c, out_of_preproc(c), kNoPreproc, 0);
 }
 
 int sdrpp_preproc_read(sdrpp_ctx* c, float* dst, int max) {
     DeviceScope dev_scope_(c);
     if (!c || !dst || max < 0) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    if (!c->pre.on) { return fail(c, SDRPP_ERR_INVALID, "no pre-processing chain configured"); }
-    const int n = std::min(max, c->pre.last_n);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (n > 0) { HIPCHK(c, hipMemcpy(dst, c->pre.last, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost)); }
-    return n;
+    return out_read(c, out_of_preproc(c), kNoPreproc, 0, dst, max, false);
 }
 
 int sdrpp_preproc_device_buffer(sdrpp_ctx* c, const float** iq, int* n) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    if (!c->pre.on) { return fail(c, SDRPP_ERR_INVALID, "no pre-processing chain configured"); }
-    if (iq) { *iq = c->pre.last; }
-    if (n) { *n = c->pre.last_n; }
-    return SDRPP_OK;
+    return out_hand(c, out_of_preproc(c), kNoPreproc, 0, iq, n);
 }
 
 // ---- VFOs ----------------------------------------------------------------------------------------------------------------------
@@ -776,338 +759,34 @@ int sdrpp_vfo_add(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
     DeviceScope dev_scope_(c);
     if (!c || !d || !id) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    if (d->n_stages < 0 || d->n_stages > SDRPP_MAX_DECIM_STAGES) { return fail(c, SDRPP_ERR_INVALID, "n_stages %d", d->n_stages); }
-    for (int s = 0; s < d->n_stages; s++) {
-        if (!is_pow2(d->stage_decim[s]) || d->stage_ntaps[s] <= 0 || !d->stage_taps[s]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "stage %d: decimation must be a power of two with taps", s); }
-    }
-    if (d->n_stages > 0) {  // the fused translation + FIR kernel uses the linear-phase pairing (all reference plans are symmetric)
-        const float* h = d->stage_taps[0];
-        for (int k = 0; k < d->stage_ntaps[0] / 2; k++) {
-            if (h[k] != h[d->stage_ntaps[0] - 1 - k]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "first decimation stage must have symmetric (linear-phase) taps"); }
-        }
-    }
-    const bool has_poly = (d->interp != d->decim);
-    if (has_poly && (d->interp <= 0 || d->decim <= 0 || d->resamp_ntaps <= 0 || !d->resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad polyphase description"); }
-    if (d->chan_ntaps < 0 || d->chan_ntaps > kChanHistCap + 1) { return fail(c, SDRPP_ERR_UNSUPPORTED, "channel filter of %d taps (max %d)", d->chan_ntaps, kChanHistCap + 1); }
-    if (d->demod < SDRPP_DEMOD_RAW || d->demod > SDRPP_DEMOD_DSB) { return fail(c, SDRPP_ERR_INVALID, "demod %d", d->demod); }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    // every early return below gives the device allocations made so far back (vfo_free); only a fully built VFO is handed to the context
-    struct VfoFreer {
-        void operator()(Vfo* p) const {
-            if (p) {
-                vfo_free(*p);
-                delete p;
-            }
-        }
-    };
-    std::unique_ptr<Vfo, VfoFreer> v(new Vfo);
-    v->id = c->next_id++;
-    v->d = *d;
-    if (d->nco_mode < 0 || d->nco_mode > 2) { return fail(c, SDRPP_ERR_INVALID, "nco_mode %d: 0 (context), 1 (closed form) or 2 (reference rotator)", d->nco_mode); }
-    v->nco_exact = d->nco_mode == 0 ? (c->nco_exact != 0) : (d->nco_mode == 2);
-    int rc;
-    // capacities
-    size_t cap = (size_t)c->max_push;
-    auto add_stream = [&](int width, int hist, size_t capn) -> int {
-        v->st.emplace_back();
-        int r = stream_alloc(c, v->st.back(), width, hist, capn);
-        return r ? -1 : (int)v->st.size() - 1;
-    };
-    // what consumes the decimator / rotator output
-    const int tpp = has_poly ? (d->resamp_ntaps + d->interp - 1) / d->interp : 0;
-    const bool fm = (d->demod == SDRPP_DEMOD_WFM || d->demod == SDRPP_DEMOD_NFM);
-    const bool fm_mode = (d->demod == SDRPP_DEMOD_WFM || d->demod == SDRPP_DEMOD_NFM);
-    const int if_hist = fm_mode ? std::max(d->audio_ntaps, 1) + 1 : 1;  // fused discriminator + audio FIR re-reads the IF history
-    const int chan_hist = ((std::max(std::max(d->chan_ntaps - 1, 1), if_hist) + 63) / 64) * 64;  // grown on demand by sdrpp_vfo_set_channel_taps
-    auto hist_after_decim = [&]() -> int {
-        if (has_poly) { return tpp - 1; }
-        return chan_hist;  // channel filter or the discriminator
-    };
-    for (int s = 0; s < d->n_stages; s++) {
-        v->staps[s].assign(d->stage_taps[s], d->stage_taps[s] + d->stage_ntaps[s]);
-        v->d.stage_taps[s] = nullptr;
-        rc = upload_blocked(c, &v->d_staps[s], v->staps[s].data(), (int)v->staps[s].size(), d->stage_decim[s], &v->s_kp[s]);
-        if (rc) { return rc; }
-        rc = upload(c, &v->d_staps_nat[s], v->staps[s].data(), v->staps[s].size());
-        if (rc) { return rc; }
-        if (s >= 1 || v->nco_exact) {  // stage 0 runs as a plain FIR only behind the reference rotator
-            rc = toep_build_fir(c, v->tp_stage[s], v->staps[s].data(), (int)v->staps[s].size(), d->stage_decim[s]);
-            if (rc) { return rc; }
-        }
-        cap = cap / (size_t)d->stage_decim[s] + 2;
-        const int hist = (s + 1 < d->n_stages) ? d->stage_ntaps[s + 1] - 1 : hist_after_decim();
-        if (add_stream(2, hist, cap) < 0) { return SDRPP_ERR_NOMEM; }
-    }
-    if (d->n_stages == 0) {
-        if (add_stream(2, hist_after_decim(), cap) < 0) { return SDRPP_ERR_NOMEM; }
-    }
-    v->i_first = 0;
-    {   // the front end as one filter: fusion decision (geometry only), tap identity, composite taps for the retune hand-over
-        unsigned long long hsh = 1469598103934665603ull;  // FNV-1a over the taps of stages 0 and 1
-        for (int s = 0; s < std::min(d->n_stages, 2); s++) {
-            for (float t : v->staps[s]) {
-                unsigned u;
-                memcpy(&u, &t, 4);
-                hsh = (hsh ^ u) * 1099511628211ull;
-            }
-        }
-        v->tap_hash = hsh;
-        if (d->n_stages >= 2) {  // the composite forms pair taps k and K-1-k: stage 1 must be linear phase as well
-            const std::vector<float>& h2 = v->staps[1];
-            for (size_t k = 0; k < h2.size() / 2; k++) { v->no_fuse = v->no_fuse || (h2[k] != h2[h2.size() - 1 - k]); }
-        }
-        v->fused_front = !v->nco_exact && !v->no_fuse && d->n_stages >= 2 && front2_t2(d->stage_ntaps[0], d->stage_decim[0], d->stage_ntaps[1], d->stage_decim[1], 8) > 0;
-        if (d->n_stages >= 1 && !v->nco_exact) {
-            const int K0 = d->stage_ntaps[0], D1 = d->stage_decim[0], K2 = v->fused_front ? d->stage_ntaps[1] : 1;
-            const int K = K0 + (K2 - 1) * D1;
-            std::vector<double> h12((size_t)K, 0.0);
-            for (int k2 = 0; k2 < K2; k2++) {
-                const double w2 = v->fused_front ? (double)v->staps[1][(size_t)k2] : 1.0;
-                for (int k1 = 0; k1 < K0; k1++) { h12[(size_t)k2 * D1 + k1] += w2 * (double)v->staps[0][(size_t)k1]; }
-            }
-            std::vector<float> hf(h12.begin(), h12.end());
-            rc = upload(c, &v->d_h12, hf.data(), hf.size());
-            if (rc) { return rc; }
-            v->h12_K = K;
-            v->h12_lgD = ilog2(D1) + (v->fused_front ? ilog2(d->stage_decim[1]) : 0);
-        }
-        if (v->nco_exact && d->n_stages >= 1) {  // reference-rotator mode: the rotated full-rate stream feeds stage 0
-            v->i_rot = add_stream(2, d->stage_ntaps[0] - 1, (size_t)c->max_push);
-            if (v->i_rot < 0) { return SDRPP_ERR_NOMEM; }
-        }
-    }
-    if (has_poly) {
-        v->rtaps.assign(d->resamp_taps, d->resamp_taps + d->resamp_ntaps);
-        v->d.resamp_taps = nullptr;
-        v->tpp = tpp;
-        std::vector<float> bank((size_t)d->interp * tpp, 0.0f);
-        const int tot = d->interp * tpp;
-        for (int i = 0; i < tot; i++) { bank[(size_t)((d->interp - 1) - (i % d->interp)) * tpp + (size_t)(i / d->interp)] = (i < d->resamp_ntaps) ? v->rtaps[(size_t)i] : 0.0f; }  // polyphase_bank.h:31-34
-        rc = upload(c, &v->d_bank, bank.data(), bank.size());
-        if (rc) { return rc; }
-        rc = toep_build_poly(c, v->tp_poly, bank, d->interp, d->decim, tpp);
-        if (rc) { return rc; }
-        if (d->interp <= 8) {  // register-blocked kernel: per carried phase, taps of one full phase cycle
-            const int L = d->interp, M = d->decim, lmax = (L <= 4) ? 4 : 8, rows = tpp + M;
-            std::vector<float> cyc((size_t)L * rows * lmax, 0.0f);
-            for (int ph0 = 0; ph0 < L; ph0++) {
-                for (int r = 0; r < L; r++) {
-                    const int A = ph0 + r * M, ph = A % L, o = A / L;
-                    for (int k = 0; k < tpp; k++) { cyc[((size_t)ph0 * rows + (size_t)(k + o)) * lmax + r] = bank[(size_t)ph * tpp + k]; }
-                }
-            }
-            rc = upload(c, &v->d_cyc, cyc.data(), cyc.size());
-            if (rc) { return rc; }
-            v->cyc_rows = rows;
-            v->cyc_lmax = lmax;
-        }
-        cap = cap * (size_t)d->interp / (size_t)d->decim + 4;
-        v->i_poly = add_stream(2, chan_hist, cap);
-        if (v->i_poly < 0) { return SDRPP_ERR_NOMEM; }
-    }
-    // channel-filter output stream always exists (taps may be enabled later); its consumer is the demodulator
-    v->i_chan = add_stream(2, if_hist, cap);
-    if (v->i_chan < 0) { return SDRPP_ERR_NOMEM; }
-    if (d->chan_ntaps > 0) {
-        if (!d->chan_taps) { return fail(c, SDRPP_ERR_INVALID, "chan_taps null"); }
-        v->ctaps_chan.assign(d->chan_taps, d->chan_taps + d->chan_ntaps);
-        rc = upload_blocked(c, &v->d_chan, v->ctaps_chan.data(), (int)v->ctaps_chan.size(), 1, &v->chan_kp);
-        if (rc) { return rc; }
-        rc = toep_build_fir(c, v->tp_chan, v->ctaps_chan.data(), (int)v->ctaps_chan.size(), 1);
-        if (rc) { return rc; }
-        v->chan_ntaps = d->chan_ntaps;
-    }
-    v->d.chan_taps = nullptr;
-    // the IF chain's output (sdrpp_vfo_set_if): only the slot — its buffers come with the first chain, a VFO without one pays nothing
-    v->st.emplace_back();
-    v->i_ifc = (int)v->st.size() - 1;
-    if (d->demod != SDRPP_DEMOD_RAW) {
-        if (fm || d->demod == SDRPP_DEMOD_AM) {
-            static const float unit = 1.0f;  // fm.h:165-168 loadDummyTaps: a single unit tap when the low-pass is off
-            const float* at = d->audio_ntaps > 0 ? d->audio_taps : &unit;
-            const int an = d->audio_ntaps > 0 ? d->audio_ntaps : 1;
-            if (d->audio_ntaps > 0 && !d->audio_taps) { return fail(c, SDRPP_ERR_INVALID, "audio_taps null"); }
-            v->ataps.assign(at, at + an);
-            v->audio_ntaps = an;
-            rc = upload_blocked(c, &v->d_audio, v->ataps.data(), (int)v->ataps.size(), 1, &v->audio_kp);
-            if (rc) { return rc; }
-            rc = toep_build_fir(c, v->tp_audio, v->ataps.data(), (int)v->ataps.size(), 1);
-            if (rc) { return rc; }
-            if (!fm) {  // AM: the sequential envelope/AGC kernel writes a real stream for the low-pass; FM demodulates inside the FIR kernel
-                v->i_dem = add_stream(1, std::max(an - 1, 1), cap);
-                if (v->i_dem < 0) { return SDRPP_ERR_NOMEM; }
-            }
-        }
-        if (d->demod >= SDRPP_DEMOD_USB) {  // SSB: real scratch between the parallel translation and the sequential AGC
-            v->i_dem = add_stream(1, 0, cap);
-            if (v->i_dem < 0) { return SDRPP_ERR_NOMEM; }
-        }
-        v->i_out = add_stream(2, 0, cap);
-        if (v->i_out < 0) { return SDRPP_ERR_NOMEM; }
-    }
-    v->d.audio_taps = nullptr;
-    rc = dev_alloc(c, &v->d_state, 2 * sizeof(AgcState) + sizeof(float));
-    if (rc) { return rc; }
-    rc = dev_alloc(c, &v->d_rot, 2);
-    if (rc) { return rc; }
-    v->theta = sdrpp_host::turnsPerSample(d->phase_delta_re, d->phase_delta_im);
-    v->theta2 = sdrpp_host::turnsPerSample(d->ssb_phase_delta_re, d->ssb_phase_delta_im);
-    if (d->demod < SDRPP_DEMOD_USB) { v->theta2 = 0.0; }
-    v->modtaps_dirty = true;
-    rc = vfo_reset_state(c, *v);
-    if (rc) { return rc; }
-    const int vid = v->id;  // (the right-hand side of the assignment below is evaluated first)
-    *id = vid;
-    c->vfos[vid] = std::unique_ptr<Vfo>(v.release());
-    vfo_list_rebuild(c);
-    return SDRPP_OK;
+    return vfo_build(c, d, id);
 }
 
 int sdrpp_vfo_remove(sdrpp_ctx* c, int id) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
+    LOOKUP_VFO(v, c, id);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    vfo_free(*it->second);
-    c->vfos.erase(it);
+    vfo_free(*v);
+    c->vfos.erase(id);
     vfo_list_rebuild(c);
     return SDRPP_OK;
 }
 
 int sdrpp_vfo_count(sdrpp_ctx* c) { return c ? (int)c->vfos.size() : SDRPP_ERR_INVALID; }
 
-// RxVFO::setInSamplerate / setOutSamplerate (rx_vfo.h:35-58): the channeliser is re-planned, but not everything starts over.  The reference keeps
-//   * the translation's phase (FrequencyXlator::setOffset only swaps phaseDelta, frequency_xlator.h:24-30) and
-//   * the channel filter's delay line (setOutSamplerate: FIR::setTaps moves it under the new tap count, fir.h:31-52; setInSamplerate does not touch the
-//     filter at all; a filter that is bypassed under the new settings keeps what it held, one that wakes up continues from that)          -> keep bit 0
-// while its decimator stages are new objects and the polyphase resampler is reset (power_decimator.h:91-108, polyphase_resampler.h:38-67), and
-//   * the demodulator behind it is a separate block that setInSamplerate leaves alone: discriminator / audio low-pass history, AGC and DC-blocker
-//     states, SSB's second translation                                                                                                     -> keep bit 1
-// (a demodulator SWITCH deletes and creates it, radio_module.h:419-563: bit 1 off).  The AF chain is re-attached by the caller and starts cleared.
-static int hist_tail_copy(sdrpp_ctx* c, Stream& to, const Stream& from, int max_samples) {
-    if (!to.hist[to.cur] || !from.hist[from.cur] || to.width != from.width) { return SDRPP_OK; }
-    const int H = std::min(std::min(from.hist_len, to.hist_len), max_samples);
-    if (H <= 0) { return SDRPP_OK; }
-    const size_t w = (size_t)to.width;
-    HIPCHK(c, hipMemcpy(to.hist[to.cur] + (size_t)(to.hist_len - H) * w, from.hist[from.cur] + (size_t)(from.hist_len - H) * w, (size_t)H * w * sizeof(float), hipMemcpyDeviceToDevice));
-    return SDRPP_OK;
-}
-// The stream the demodulator would read without an IF chain: the channel filter's output, or its input while the filter is bypassed.
-static Stream& if_feed_stream(Vfo& v) {
-    if (v.chan_ntaps > 0 && v.i_chan >= 0) { return v.st[(size_t)v.i_chan]; }
-    return v.st[(size_t)((v.i_poly >= 0) ? v.i_poly : v.i_first + std::max(v.d.n_stages, 1) - 1)];
-}
-// sdrpp_vfo_set_if on a VFO the caller has looked up (the stream is idle).  What the demodulator remembers of its input (the discriminator's
-// previous sample, the audio low-pass's delay line) moves with the switch: it was fed the IF until a chain becomes active and the chain's
-// output from then on, or the other way round.
-static int ifc_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_if_desc* d) {
-    Vfo::Ifc& f = v.ifc;
-    if (v.i_ifc < 0) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no IF chain slot", v.id); }
-    Stream& fs = v.st[(size_t)v.i_ifc];
-    const bool was_active = f.active() && fs.base, was_nb = f.on && f.nb_on;
-    if (d) {
-        if (d->nb_enabled && !(d->nb_rate > 0.0f && d->nb_rate <= 1.0f && d->nb_level == d->nb_level)) { return fail(c, SDRPP_ERR_INVALID, "noise blanker: rate %g (0 < rate <= 1), level %g", d->nb_rate, d->nb_level); }
-        if (d->squelch_enabled && d->squelch_level != d->squelch_level) { return fail(c, SDRPP_ERR_INVALID, "squelch level is not a number"); }
-        if (!fs.base) {
-            const Stream& like = v.st[(size_t)v.i_chan];  // what the demodulator reads today: same capacity, same history
-            int rc = stream_alloc(c, fs, 2, like.hist_len, like.cap);
-            if (rc) { return rc; }
-        }
-        if (!f.d_amp) {
-            int rc = dev_alloc(c, &f.d_amp, 1);
-            if (rc) { return rc; }
-        }
-        if (d->nb_enabled && !was_nb) {  // a blanker that starts: amp = 1 (noise_blanker.h:75); one that runs keeps it through setRate / setLevel
-            const float one = 1.0f;
-            HIPCHK(c, hipMemcpy(f.d_amp, &one, sizeof(float), hipMemcpyHostToDevice));
-        }
-        f.on = true;
-        f.nb_on = d->nb_enabled != 0;
-        f.nb_rate = d->nb_rate;
-        f.nb_level = d->nb_level;
-        f.sq_on = d->squelch_enabled != 0;
-        f.sq_level = d->squelch_level;
-    }
-    else {
-        f.on = false;
-        f.nb_on = 0;
-        f.sq_on = 0;
-    }
-    const bool now_active = f.active();
-    if (was_active != now_active && fs.base) {
-        Stream& feed = if_feed_stream(v);
-        const int if_need = (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) ? std::max(v.audio_ntaps, 1) + 1 : 1;
-        int rc = now_active ? hist_tail_copy(c, fs, feed, if_need) : hist_tail_copy(c, feed, fs, if_need);
-        if (rc) { return rc; }
-    }
-    if (!now_active) { fs.n = 0; }
-    return SDRPP_OK;
-}
 int sdrpp_vfo_replace(sdrpp_ctx* c, int old_id, const sdrpp_vfo_desc* d, int keep, int* new_id) {
     DeviceScope dev_scope_(c);
     if (!c || !d || !new_id || keep < 0 || keep > 7) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    if (c->vfos.find(old_id) == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", old_id); }
+    LOOKUP_VFO(o, c, old_id);
     int nid = 0;
-    int rc = sdrpp_vfo_add(c, d, &nid);
+    int rc = vfo_build(c, d, &nid);
     if (rc) { return rc; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    Vfo& o = *c->vfos[old_id];
-    Vfo& n = *c->vfos[nid];
-    auto feed_idx = [](const Vfo& v) { return (v.i_poly >= 0) ? v.i_poly : v.i_first + std::max(v.d.n_stages, 1) - 1; };  // the stream the channel filter reads
-    Stream& of = o.st[(size_t)feed_idx(o)];
-    Stream& nf = n.st[(size_t)feed_idx(n)];
-    if (keep & 1) {
-        if (o.nco_exact == n.nco_exact) {
-            n.phi = o.phi;
-            if (o.d_rot && n.d_rot) { HIPCHK(c, hipMemcpy(n.d_rot, o.d_rot, sizeof(float2), hipMemcpyDeviceToDevice)); }
-        }
-        // the channel filter's delay line as the reference's FIR object holds it now: the newest old_taps - 1 samples it was fed, or what it held
-        // when it was last bypassed
-        const int w = of.width;
-        std::vector<float> line;
-        if (o.chan_ntaps > 1 && of.hist[of.cur] && of.hist_len >= o.chan_ntaps - 1) {
-            line.resize((size_t)(o.chan_ntaps - 1) * (size_t)w);
-            HIPCHK(c, hipMemcpy(line.data(), of.hist[of.cur] + (size_t)(of.hist_len - (o.chan_ntaps - 1)) * w, line.size() * sizeof(float), hipMemcpyDeviceToHost));
-        }
-        else if (o.chan_ntaps == 0) { line = o.chan_stale; }
-        if (n.chan_ntaps > 0 && nf.width == w) {  // FIR::setTaps: the newest min(old, new) - 1 samples stay, zeros in front of them
-            if (nf.hist[nf.cur]) {
-                HIPCHK(c, hipMemset(nf.hist[nf.cur], 0, (size_t)nf.hist_len * (size_t)w * sizeof(float)));
-                const int have = (int)(line.size() / (size_t)w), m = std::min(have, std::min(n.chan_ntaps - 1, nf.hist_len));
-                if (m > 0) { HIPCHK(c, hipMemcpy(nf.hist[nf.cur] + (size_t)(nf.hist_len - m) * w, line.data() + (size_t)(have - m) * w, (size_t)m * w * sizeof(float), hipMemcpyHostToDevice)); }
-            }
-        }
-        else if (n.chan_ntaps == 0) { n.chan_stale = line; }  // bypassed under the new settings: the filter object keeps what it held
-    }
-    if ((keep & 2) && o.d.demod == n.d.demod) {
-        // the demodulator's view of the IF stream: the discriminator's previous sample and the audio low-pass's delay line are its newest samples
-        // (behind an IF chain that is what the CHAIN delivered)
-        Stream& oif = (o.ifc.active() && o.i_ifc >= 0 && o.st[(size_t)o.i_ifc].base) ? o.st[(size_t)o.i_ifc] : ((o.chan_ntaps > 0 && o.i_chan >= 0) ? o.st[(size_t)o.i_chan] : of);
-        Stream& nif = (n.chan_ntaps > 0 && n.i_chan >= 0) ? n.st[(size_t)n.i_chan] : nf;
-        const int if_need = (n.d.demod == SDRPP_DEMOD_WFM || n.d.demod == SDRPP_DEMOD_NFM) ? std::max(n.audio_ntaps, 1) + 1 : 1;
-        rc = hist_tail_copy(c, nif, oif, if_need);
-        if (rc) { return rc; }
-        if (o.i_dem >= 0 && n.i_dem >= 0) {
-            rc = hist_tail_copy(c, n.st[(size_t)n.i_dem], o.st[(size_t)o.i_dem], 1 << 30);
-            if (rc) { return rc; }
-        }
-        if (o.d_state && n.d_state) { HIPCHK(c, hipMemcpy(n.d_state, o.d_state, 2 * sizeof(AgcState) + sizeof(float), hipMemcpyDeviceToDevice)); }
-        n.phi2 = o.phi2;
-        if (o.d_rot && n.d_rot) { HIPCHK(c, hipMemcpy(n.d_rot + 1, o.d_rot + 1, sizeof(float2), hipMemcpyDeviceToDevice)); }
-    }
-    if ((keep & 4) && o.ifc.on) {
-        // the radio's IF chain objects are not the demodulator's: they live through a demodulator switch (radio_module.h:84-96, 419-563), the
-        // blanker with its amplitude estimate.  Attaching copies the demodulator's view of the IF (set above) into the chain's history.
-        const sdrpp_if_desc fd{ o.ifc.nb_on, o.ifc.nb_rate, o.ifc.nb_level, o.ifc.sq_on, o.ifc.sq_level };
-        rc = ifc_apply(c, n, &fd);
-        if (rc) { return rc; }
-        if (o.ifc.nb_on && o.ifc.d_amp && n.ifc.d_amp) { HIPCHK(c, hipMemcpy(n.ifc.d_amp, o.ifc.d_amp, sizeof(float), hipMemcpyDeviceToDevice)); }
-    }
-    rc = sdrpp_vfo_remove(c, old_id);
-    if (rc) { return rc; }
+    if ((rc = vfo_hand_over(c, *o, *c->vfos[nid], keep))) { return rc; }
+    if ((rc = sdrpp_vfo_remove(c, old_id))) { return rc; }
     *new_id = nid;
     return SDRPP_OK;
 }
@@ -1116,20 +795,18 @@ int sdrpp_vfo_set_phase_delta(sdrpp_ctx* c, int id, float re, float im) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Vfo& v = *it->second;
+    LOOKUP_VFO(v, c, id);
     const double th = sdrpp_host::turnsPerSample(re, im);
     // the samples already in the first decimator's delay line stay rotated with the old increment (rx_vfo.h:72-77 only swaps
     // phaseDelta): remember where it changed so the first outputs of the next pushes can be handed over exactly (do_vfos)
-    if (!v.nco_exact && v.d.n_stages > 0 && th != v.theta) {
-        if (!v.recs.empty() && v.recs.back().pos == v.seen) { /* retuned twice between pushes: the older increment stays the one before */ }
-        else { v.recs.push_back(Vfo::Retune{ v.seen, v.theta }); }
+    if (!v->nco_exact && v->d.n_stages > 0 && th != v->theta) {
+        if (!v->recs.empty() && v->recs.back().pos == v->seen) { /* retuned twice between pushes: the older increment stays the one before */ }
+        else { v->recs.push_back(Vfo::Retune{ v->seen, v->theta }); }
     }
-    v.d.phase_delta_re = re;
-    v.d.phase_delta_im = im;
-    v.theta = th;
-    v.modtaps_dirty = true;
+    v->d.phase_delta_re = re;
+    v->d.phase_delta_im = im;
+    v->theta = th;
+    v->modtaps_dirty = true;
     return SDRPP_OK;
 }
 
@@ -1137,225 +814,40 @@ int sdrpp_vfo_set_channel_taps(sdrpp_ctx* c, int id, const float* taps, int n) {
     DeviceScope dev_scope_(c);
     if (!c || n < 0 || n > kChanHistCap + 1 || (n > 0 && !taps)) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Vfo& v = *it->second;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    {   // the stream that feeds the channel filter must remember n-1 samples
-        const int idx = (v.i_poly >= 0) ? v.i_poly : v.i_first + std::max(v.d.n_stages, 1) - 1;
-        Stream& fs = v.st[(size_t)idx];
-        const int old_n = v.chan_ntaps, w = fs.width;
-        const bool was_on = old_n > 0, now_on = n > 0;
-        // ---- the filter's BYPASS switched (bandwidth == IF rate exactly, rx_vfo.h:60-70 / :89-100) ----
-        // (a) The consumers behind the filter read "the IF stream" with memory (the demodulator's audio low-pass): their delay line holds the last
-        //     samples they were FED — the filter's outputs until now, its input from now on, or the other way round.  The IF stream changes its
-        //     identity here (st[i_chan] <-> the filter's input stream), so the newest history goes with it.
-        // (b) The reference does not touch a bypassed filter: its delay line keeps what it held when it last ran, and a filter switched on again
-        //     continues from that stale content (FIR::setTaps moves it like any other change of the tap count, fir.h:31-52).  The stream's side
-        //     buffer here keeps being refreshed for consumer (a), so the filter's own last history is set aside when it goes to sleep and put
-        //     back — under the new tap count — when it wakes up.
-        if (was_on != now_on && v.i_chan >= 0) {
-            Stream& cs = v.st[(size_t)v.i_chan];
-            if (was_on) {  // going to sleep: (b) first, (a) overwrites the buffer
-                // exactly the old filter's old_n - 1 samples, whatever an EARLIER bypass left here (a one-tap filter has no delay line: nothing; a
-                // stream without history yet: zeros, which is what FIR's cleared buffer holds, fir.h:24-26)
-                v.chan_stale.assign((size_t)std::max(old_n - 1, 0) * (size_t)w, 0.0f);
-                if (old_n > 1 && fs.hist[fs.cur] && fs.hist_len >= old_n - 1) {
-                    HIPCHK(c, hipMemcpy(v.chan_stale.data(), fs.hist[fs.cur] + (size_t)(fs.hist_len - (old_n - 1)) * w, v.chan_stale.size() * sizeof(float), hipMemcpyDeviceToHost));
-                }
-            }
-            if (now_on) {  // waking up: the buffer must be long enough for the new filter before anything is put into it
-                int rc = stream_grow_hist(c, fs, n - 1);
-                if (rc) { return rc; }
-            }
-            Stream& from = was_on ? cs : fs;
-            Stream& to = was_on ? fs : cs;
-            const int H = std::min(from.hist_len, to.hist_len);
-            if (H > 0 && from.hist[from.cur] && to.hist[to.cur] && from.width == to.width) {
-                HIPCHK(c, hipMemcpy(to.hist[to.cur] + (size_t)(to.hist_len - H) * w, from.hist[from.cur] + (size_t)(from.hist_len - H) * w, (size_t)H * w * sizeof(float), hipMemcpyDeviceToDevice));
-            }
-            if (now_on && fs.hist[fs.cur]) {  // (b): zeros, then the newest part of what the filter held when it last ran (all zeros for one that never ran)
-                HIPCHK(c, hipMemset(fs.hist[fs.cur], 0, (size_t)fs.hist_len * (size_t)w * sizeof(float)));
-                const int have = (int)(v.chan_stale.size() / (size_t)w), m = std::min(have, std::min(n - 1, fs.hist_len));
-                if (m > 0) {
-                    HIPCHK(c, hipMemcpy(fs.hist[fs.cur] + (size_t)(fs.hist_len - m) * w, v.chan_stale.data() + (size_t)(have - m) * w, (size_t)m * w * sizeof(float), hipMemcpyHostToDevice));
-                }
-            }
-        }
-        else {
-            int rc = stream_grow_hist(c, fs, n - 1);
-            if (rc) { return rc; }
-            // FIR::setTaps (dsp/filter/fir.h:31-52): a LONGER filter starts with zeros in front of the old delay line — its old_n - 1 samples are
-            // all the reference kept, whatever the stream held before them.  The side buffer here holds the stream's true tail (newest last):
-            // everything older than the old filter's reach is cleared.
-            const int keep = std::max(old_n - 1, 0);
-            if (n > old_n && fs.hist_len > keep && fs.hist[fs.cur]) {
-                HIPCHK(c, hipMemset(fs.hist[fs.cur], 0, (size_t)(fs.hist_len - keep) * (size_t)w * sizeof(float)));
-            }
-        }
-    }
-    v.ctaps_chan.assign(taps, taps + n);
-    v.chan_ntaps = n;
-    v.d.chan_ntaps = n;
-    if (n > 0) {
-        int rc = upload_blocked(c, &v.d_chan, v.ctaps_chan.data(), n, 1, &v.chan_kp);
-        if (rc) { return rc; }
-        rc = toep_build_fir(c, v.tp_chan, v.ctaps_chan.data(), n, 1);
-        if (rc) { return rc; }
-    }
-    return SDRPP_OK;
-}
-
-static void af_detach(Vfo& v) {
-    Vfo::Af& a = v.af;
-    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) {
-        dev_free(a.d_staps[i]);
-        toep_free(a.tp_stage[i]);
-    }
-    toep_free(a.tp_poly);
-    toep_free(a.tp_hpf);
-    dev_free(a.d_bank);
-    dev_free(a.d_hpf);
-    dev_free(a.d_last);
-    dev_free(a.d_seg);
-    if (a.base >= 0) {
-        for (size_t i = (size_t)a.base; i < v.st.size(); i++) { stream_free(v.st[i]); }
-        v.st.resize((size_t)a.base);
-    }
-    a = Vfo::Af{};
+    LOOKUP_VFO(v, c, id);
+    return vfo_set_chan_taps(c, *v, taps, n);
 }
 
 int sdrpp_vfo_set_af(sdrpp_ctx* c, int id, const sdrpp_af_desc* af) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Vfo& v = *it->second;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    af_detach(v);
-    if (!af) { return SDRPP_OK; }
-    if (v.d.demod == SDRPP_DEMOD_RAW || v.i_out < 0) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the AF chain needs a demodulating VFO"); }
-    if (af->n_stages < 0 || af->n_stages > SDRPP_MAX_DECIM_STAGES) { return fail(c, SDRPP_ERR_INVALID, "af n_stages %d", af->n_stages); }
-    for (int s = 0; s < af->n_stages; s++) {
-        if (!is_pow2(af->stage_decim[s]) || af->stage_ntaps[s] <= 0 || !af->stage_taps[s]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "af stage %d: decimation must be a power of two with taps", s); }
-    }
-    const bool has_poly = af->interp != af->decim;
-    if (has_poly && (af->interp <= 0 || af->decim <= 0 || af->resamp_ntaps <= 0 || !af->resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af polyphase description"); }
-    if (af->hpf_ntaps < 0 || af->hpf_ntaps > kChanHistCap + 1 || (af->hpf_ntaps > 0 && !af->hpf_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af high-pass description"); }
-    Vfo::Af& a = v.af;
-    a.base = (int)v.st.size();
-    a.n_stages = af->n_stages;
-    a.interp = has_poly ? af->interp : 1;
-    a.decim = has_poly ? af->decim : 1;
-    a.tpp = has_poly ? (af->resamp_ntaps + af->interp - 1) / af->interp : 0;
-    a.alpha = af->deemph_alpha;
-    int rc;
-    // history a stream must keep = (taps - 1) of its consumer; `stage` = first block that can be the consumer
-    // (0..n_stages-1 decimators, n_stages polyphase, n_stages+1 high-pass; de-emphasis needs none)
-    auto need_of = [&](int stage) -> int {
-        if (stage < a.n_stages) { return af->stage_ntaps[stage] - 1; }
-        if (stage <= a.n_stages && has_poly) { return a.tpp - 1; }
-        if (stage <= a.n_stages + 1 && af->hpf_ntaps > 0) { return af->hpf_ntaps - 1; }
-        return 0;
-    };
-    rc = stream_grow_hist(c, v.st[(size_t)v.i_out], need_of(0));
-    if (rc) { return rc; }
-    size_t cap = v.st[(size_t)v.i_out].cap;
-    auto add_stream = [&](int hist, size_t capn) -> int {
-        v.st.emplace_back();
-        int r = stream_alloc(c, v.st.back(), 2, hist, capn);
-        return r ? -1 : (int)v.st.size() - 1;
-    };
-    for (int s = 0; s < a.n_stages; s++) {
-        a.decim_s[s] = af->stage_decim[s];
-        a.staps[s].assign(af->stage_taps[s], af->stage_taps[s] + af->stage_ntaps[s]);
-        rc = upload_blocked(c, &a.d_staps[s], a.staps[s].data(), (int)a.staps[s].size(), a.decim_s[s], &a.s_kp[s]);
-        if (rc) { return rc; }
-        rc = toep_build_fir(c, a.tp_stage[s], a.staps[s].data(), (int)a.staps[s].size(), a.decim_s[s]);
-        if (rc) { return rc; }
-        cap = cap / (size_t)a.decim_s[s] + 2;
-        const int idx = add_stream(need_of(s + 1), cap);
-        if (idx < 0) { return SDRPP_ERR_NOMEM; }
-        if (s == 0) { a.i_stage0 = idx; }
-    }
-    if (has_poly) {
-        a.rtaps.assign(af->resamp_taps, af->resamp_taps + af->resamp_ntaps);
-        std::vector<float> bank((size_t)a.interp * a.tpp, 0.0f);
-        const int tot = a.interp * a.tpp;
-        for (int i = 0; i < tot; i++) { bank[(size_t)((a.interp - 1) - (i % a.interp)) * a.tpp + (size_t)(i / a.interp)] = (i < af->resamp_ntaps) ? a.rtaps[(size_t)i] : 0.0f; }  // polyphase_bank.h:31-34
-        rc = upload(c, &a.d_bank, bank.data(), bank.size());
-        if (rc) { return rc; }
-        rc = toep_build_poly(c, a.tp_poly, bank, a.interp, a.decim, a.tpp);
-        if (rc) { return rc; }
-        cap = cap * (size_t)a.interp / (size_t)a.decim + 4;
-        a.i_poly = add_stream(need_of(a.n_stages + 1), cap);
-        if (a.i_poly < 0) { return SDRPP_ERR_NOMEM; }
-    }
-    if (af->hpf_ntaps > 0) {
-        a.htaps.assign(af->hpf_taps, af->hpf_taps + af->hpf_ntaps);
-        rc = upload_blocked(c, &a.d_hpf, a.htaps.data(), (int)a.htaps.size(), 1, &a.hpf_kp);
-        if (rc) { return rc; }
-        rc = toep_build_fir(c, a.tp_hpf, a.htaps.data(), (int)a.htaps.size(), 1);
-        if (rc) { return rc; }
-        a.i_hpf = add_stream(0, cap);
-        if (a.i_hpf < 0) { return SDRPP_ERR_NOMEM; }
-    }
-    if (a.alpha != 0.0f) {
-        rc = dev_alloc(c, &a.d_last, 2);
-        if (rc) { return rc; }
-        HIPCHK(c, hipMemset(a.d_last, 0, 2 * sizeof(float2)));
-        a.state_cur = 0;
-        a.seg_cap = (int)(cap / SDRPP_DEEMP_SEG) + 2;
-        rc = dev_alloc(c, &a.d_seg, 2 * ((size_t)a.seg_cap + 1));
-        if (rc) { return rc; }
-        a.i_deemp = add_stream(0, cap);
-        if (a.i_deemp < 0) { return SDRPP_ERR_NOMEM; }
-    }
-    a.i_last = v.i_out;
-    a.on = true;
-    return SDRPP_OK;
+    LOOKUP_VFO(v, c, id);
+    return af_apply(c, *v, af);
 }
-
-static Stream* af_stream(Vfo& v) { return (v.af.on && v.af.i_last >= 0) ? &v.st[(size_t)v.af.i_last] : nullptr; }
 
 int sdrpp_vfo_af_count(sdrpp_ctx* c, int id) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Stream* s = af_stream(*it->second);
-    if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no AF chain", id); }
-    return s->n;
+    LOOKUP_VFO(v, c, id);
+    return out_count(c, out_of(delivered(*v, 2)), kNoAf, id);
 }
 
 int sdrpp_vfo_af_read(sdrpp_ctx* c, int id, float* dst, int max) {
     DeviceScope dev_scope_(c);
     if (!c || !dst || max < 0) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Stream* s = af_stream(*it->second);
-    if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no AF chain", id); }
-    const int n = std::min(max, s->n);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (int rc = pipe_timeouts_check(c)) { return rc; }
-    if (n > 0) { HIPCHK(c, hipMemcpy(dst, s->data, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost)); }
-    return n;
+    LOOKUP_VFO(v, c, id);
+    return out_read(c, out_of(delivered(*v, 2)), kNoAf, id, dst, max, true);
 }
 
 int sdrpp_vfo_af_device_buffer(sdrpp_ctx* c, int id, const float** out, int* n_out) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Stream* s = af_stream(*it->second);
-    if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no AF chain", id); }
-    if (out) { *out = s->data; }
-    if (n_out) { *n_out = s->n; }
-    return SDRPP_OK;
+    LOOKUP_VFO(v, c, id);
+    return out_hand(c, out_of(delivered(*v, 2)), kNoAf, id, out, n_out);
 }
 
 int sdrpp_abi_sizeof_af_desc(void) { return (int)sizeof(sdrpp_af_desc); }
@@ -1365,126 +857,63 @@ int sdrpp_vfo_set_if(sdrpp_ctx* c, int id, const sdrpp_if_desc* d) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
+    LOOKUP_VFO(v, c, id);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ifc_apply(c, *it->second, d);
+    return ifc_apply(c, *v, d);
 }
-
-static Stream* ifc_stream(Vfo& v) { return (v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base) ? &v.st[(size_t)v.i_ifc] : nullptr; }
 
 int sdrpp_vfo_ifc_count(sdrpp_ctx* c, int id) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Stream* s = ifc_stream(*it->second);
-    if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no active IF chain", id); }
-    return s->n;
+    LOOKUP_VFO(v, c, id);
+    return out_count(c, out_of(delivered(*v, 3)), kNoIfc, id);
 }
 
 int sdrpp_vfo_ifc_read(sdrpp_ctx* c, int id, float* dst, int max) {
     DeviceScope dev_scope_(c);
     if (!c || !dst || max < 0) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Stream* s = ifc_stream(*it->second);
-    if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no active IF chain", id); }
-    const int n = std::min(max, s->n);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (int rc = pipe_timeouts_check(c)) { return rc; }
-    if (n > 0) { HIPCHK(c, hipMemcpy(dst, s->data, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost)); }
-    return n;
+    LOOKUP_VFO(v, c, id);
+    return out_read(c, out_of(delivered(*v, 3)), kNoIfc, id, dst, max, true);
 }
 
 int sdrpp_vfo_ifc_device_buffer(sdrpp_ctx* c, int id, const float** out, int* n_out) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Stream* s = ifc_stream(*it->second);
-    if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no active IF chain", id); }
-    if (out) { *out = s->data; }
-    if (n_out) { *n_out = s->n; }
-    return SDRPP_OK;
+    LOOKUP_VFO(v, c, id);
+    return out_hand(c, out_of(delivered(*v, 3)), kNoIfc, id, out, n_out);
 }
 
 int sdrpp_abi_sizeof_if_desc(void) { return (int)sizeof(sdrpp_if_desc); }
-
-// ---- sink-side sample packing ----------------------------------------------------------------------------------
-static Stream* pick_stream(sdrpp_ctx* c, Vfo& v, int which) {
-    (void)c;
-    if (which == 0) { return (v.d.demod == SDRPP_DEMOD_RAW) ? (ifc_stream(v) ? ifc_stream(v) : &v.st[(size_t)v.i_if]) : &v.st[(size_t)v.i_out]; }
-    if (which == 1) { return &v.st[(size_t)v.i_if]; }
-    if (which == 2) { return (v.af.on && v.af.i_last >= 0) ? &v.st[(size_t)v.af.i_last] : nullptr; }
-    if (which == 3) { return ifc_stream(v); }
-    return nullptr;
-}
-static int pack_scratch(sdrpp_ctx* c, size_t bytes) {
-    if (bytes <= c->pack_cap) { return SDRPP_OK; }
-    dev_free(c->d_pack);
-    c->pack_cap = 0;
-    int rc = dev_alloc(c, &c->d_pack, bytes + 1024);
-    if (rc) { return rc; }
-    c->pack_cap = bytes + 1024;
-    return SDRPP_OK;
-}
 
 int sdrpp_vfo_read_pcm(sdrpp_ctx* c, int id, int which, int pcm_type, float scale, void* dst_host, int max_frames) {
     DeviceScope dev_scope_(c);
     if (!c || !dst_host || max_frames < 0 || (pcm_type != 0 && pcm_type != 1)) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Stream* s = pick_stream(c, *it->second, which);
+    LOOKUP_VFO(v, c, id);
+    Stream* s = delivered(*v, which);
     if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no such stream (%d)", id, which); }
-    const int n = std::min(max_frames, s->n);
-    if (n == 0) { return 0; }
-    const long long nv = (long long)n * 2;
-    const size_t esz = pcm_type == 1 ? 2 : 1;
-    int rc = pack_scratch(c, (size_t)nv * esz);
-    if (rc) { return rc; }
-    const dim3 grid((unsigned)std::min<long long>((nv + 255) / 256, 4096));
-    if (pcm_type == 1) { hipLaunchKernelGGL(pack_convert_kernel<int16_t>, grid, dim3(256), 0, c->stream, (const float*)s->data, scale, nv, (int16_t*)c->d_pack); }
-    else { hipLaunchKernelGGL(pack_convert_kernel<int8_t>, grid, dim3(256), 0, c->stream, (const float*)s->data, scale, nv, (int8_t*)c->d_pack); }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (int rc = pipe_timeouts_check(c)) { return rc; }
-    HIPCHK(c, hipMemcpy(dst_host, c->d_pack, (size_t)nv * esz, hipMemcpyDeviceToHost));
-    return n;
+    return pcm_read(c, s->data, s->n, pcm_type, scale, dst_host, max_frames);
 }
 
 // the pre-processed wideband IQ of the most recent push as int16 / int8: what the recorder's baseband mode writes (bindIQStream consumer ->
-// wav::Writer::write, utils/wav.cpp:158-167), converted on the device so that the copy to the host carries 4 (2) bytes per sample
+// wav::Writer::write, utils/wav.cpp:158-167)
 int sdrpp_preproc_read_pcm(sdrpp_ctx* c, int pcm_type, float scale, void* dst_host, int max_samples) {
     DeviceScope dev_scope_(c);
     if (!c || !dst_host || max_samples < 0 || (pcm_type != 0 && pcm_type != 1)) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    if (!c->pre.on) { return fail(c, SDRPP_ERR_INVALID, "no pre-processing chain configured"); }
-    const int n = std::min(max_samples, c->pre.last_n);
-    if (n == 0) { return 0; }
-    const long long nv = (long long)n * 2;
-    const size_t esz = pcm_type == 1 ? 2 : 1;
-    int rc = pack_scratch(c, (size_t)nv * esz);
-    if (rc) { return rc; }
-    const dim3 grid((unsigned)std::min<long long>((nv + 255) / 256, 4096));
-    if (pcm_type == 1) { hipLaunchKernelGGL(pack_convert_kernel<int16_t>, grid, dim3(256), 0, c->stream, (const float*)c->pre.last, scale, nv, (int16_t*)c->d_pack); }
-    else { hipLaunchKernelGGL(pack_convert_kernel<int8_t>, grid, dim3(256), 0, c->stream, (const float*)c->pre.last, scale, nv, (int8_t*)c->d_pack); }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (int rc = pipe_timeouts_check(c)) { return rc; }
-    HIPCHK(c, hipMemcpy(dst_host, c->d_pack, (size_t)nv * esz, hipMemcpyDeviceToHost));
-    return n;
+    if (!c->pre.on) { return fail(c, SDRPP_ERR_INVALID, kNoPreproc); }
+    return pcm_read(c, c->pre.last, c->pre.last_n, pcm_type, scale, dst_host, max_samples);
 }
 
 int sdrpp_vfo_read_compressed(sdrpp_ctx* c, int id, int which, int pcm_type, unsigned char* dst_host, int max_bytes) {
     DeviceScope dev_scope_(c);
     if (!c || !dst_host || pcm_type < 0 || pcm_type > 2) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Stream* s = pick_stream(c, *it->second, which);
+    LOOKUP_VFO(v, c, id);
+    Stream* s = delivered(*v, which);
     if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no such stream (%d)", id, which); }
     const int n = s->n;
     const long long nv = (long long)n * 2;
@@ -1516,9 +945,7 @@ int sdrpp_vfo_read_compressed(sdrpp_ctx* c, int id, int which, int pcm_type, uns
     }
     scaler = maxVal;
     memcpy(dst_host + 4, &scaler, 4);
-    const dim3 grid((unsigned)std::min<long long>((nv + 255) / 256, 4096));
-    if (pcm_type == 1) { hipLaunchKernelGGL(pack_convert_kernel<int16_t>, grid, dim3(256), 0, c->stream, (const float*)s->data, 32768.0f / maxVal, nv, (int16_t*)d_data); }
-    else { hipLaunchKernelGGL(pack_convert_kernel<int8_t>, grid, dim3(256), 0, c->stream, (const float*)s->data, 128.0f / maxVal, nv, (int8_t*)d_data); }
+    pack_convert(c, s->data, nv, (pcm_type == 1 ? 32768.0f : 128.0f) / maxVal, pcm_type, d_data);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(dst_host + 8, d_data, (size_t)nv * esz, hipMemcpyDeviceToHost));
     return (int)total;
@@ -1580,13 +1007,11 @@ int sdrpp_vfo_set_ssb_phase_delta(sdrpp_ctx* c, int id, float re, float im) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Vfo& v = *it->second;
-    if (v.d.demod < SDRPP_DEMOD_USB) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no SSB demodulator", id); }
-    v.d.ssb_phase_delta_re = re;
-    v.d.ssb_phase_delta_im = im;
-    v.theta2 = sdrpp_host::turnsPerSample(re, im);  // the translation is sample-wise: nothing to hand over, the phase stays continuous
+    LOOKUP_VFO(v, c, id);
+    if (v->d.demod < SDRPP_DEMOD_USB) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no SSB demodulator", id); }
+    v->d.ssb_phase_delta_re = re;
+    v->d.ssb_phase_delta_im = im;
+    v->theta2 = sdrpp_host::turnsPerSample(re, im);  // the translation is sample-wise: nothing to hand over, the phase stays continuous
     return SDRPP_OK;
 }
 
@@ -1594,41 +1019,24 @@ int sdrpp_vfo_reset(sdrpp_ctx* c, int id) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    return vfo_reset_state(c, *it->second);
-}
-
-static Stream* out_stream(Vfo& v) {  // (a RAW VFO with an IF chain delivers the chain's output)
-    if (v.d.demod != SDRPP_DEMOD_RAW) { return &v.st[(size_t)v.i_out]; }
-    Stream* f = ifc_stream(v);
-    return f ? f : &v.st[(size_t)v.i_if];
+    LOOKUP_VFO(v, c, id);
+    return vfo_reset_state(c, *v);
 }
 
 int sdrpp_vfo_out_count(sdrpp_ctx* c, int id) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
-    {
-        int frc = flush_pending_opt(c, 0);
-        if (frc) { return frc; }
-    }
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    return out_stream(*it->second)->n;
+    if (int frc = flush_pending_opt(c, 0)) { return frc; }  // (non-draining: a count is what the HOST knows)
+    LOOKUP_VFO(v, c, id);
+    return delivered(*v, 0)->n;
 }
 
 int sdrpp_vfo_read(sdrpp_ctx* c, int id, float* dst, int max) {
     DeviceScope dev_scope_(c);
     if (!c || !dst || max < 0) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Stream* s = out_stream(*it->second);
-    const int n = std::min(max, s->n);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (int rc = pipe_timeouts_check(c)) { return rc; }
-    if (n > 0) { HIPCHK(c, hipMemcpy(dst, s->data, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost)); }
-    return n;
+    LOOKUP_VFO(v, c, id);
+    return out_read(c, out_of(delivered(*v, 0)), kNoOut, id, dst, max, true);
 }
 
 int sdrpp_vfo_read_many(sdrpp_ctx* c, int n, const int* ids, const int* which, float* dst_host, int64_t max_samples, int64_t* offsets, int* counts) {
@@ -1639,9 +1047,8 @@ int sdrpp_vfo_read_many(sdrpp_ctx* c, int n, const int* ids, const int* which, f
     int64_t total = 0;
     int mx = 0;
     for (int i = 0; i < n; i++) {
-        auto it = c->vfos.find(ids[i]);
-        if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", ids[i]); }
-        Stream* s = pick_stream(c, *it->second, which ? which[i] : 0);
+        LOOKUP_VFO(v, c, ids[i]);
+        Stream* s = delivered(*v, which ? which[i] : 0);
         if (!s) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no such stream (%d)", ids[i], which ? which[i] : 0); }
         offsets[i] = total;
         counts[i] = s->n;
@@ -1689,15 +1096,9 @@ int sdrpp_vfo_device_buffers(sdrpp_ctx* c, int id, const float** out, int* n_out
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    auto it = c->vfos.find(id);
-    if (it == c->vfos.end()) { return fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id); }
-    Vfo& v = *it->second;
-    Stream* o = out_stream(v);
-    if (out) { *out = o->data; }
-    if (n_out) { *n_out = o->n; }
-    if (if_out) { *if_out = v.st[(size_t)v.i_if].data; }
-    if (n_if) { *n_if = v.st[(size_t)v.i_if].n; }
-    return SDRPP_OK;
+    LOOKUP_VFO(v, c, id);
+    (void)out_hand(c, out_of(delivered(*v, 0)), kNoOut, id, out, n_out);
+    return out_hand(c, out_of(delivered(*v, 1)), kNoOut, id, if_out, n_if);
 }
 
 // ---- data path --------------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,593 @@
+// The per-VFO control surface behind the C-ABI: lookup, which stream is what, building / re-planning / replacing a VFO with the reference's hand-overs,
+// its IF and AF chains, read-out.  The extern "C" entry points in sdrpp_gpu.hip check their arguments, flush, look the VFO up and call one of these.
+// Part of the one translation unit sdrpp_gpu.hip (included there, in order; not a stand-alone header).
+#pragma once
+
+namespace {
+
+// The VFO behind a caller's id; nullptr for an id the context does not know, with the message of SDRPP_ERR_NOT_FOUND set (LOOKUP_VFO returns the code).
+Vfo* vfo_lookup(sdrpp_ctx* c, int id) {
+    auto it = c->vfos.find(id);
+    if (it != c->vfos.end()) { return it->second.get(); }
+    fail(c, SDRPP_ERR_NOT_FOUND, "no VFO %d", id);
+    return nullptr;
+}
+
+// ---- which stream is what -----------------------------------------------------------------------------------------------------------
+// The stream the channel filter reads: the resampler's output, else the last decimator stage's (stream 0 of a VFO without stages).
+Stream& chan_feed(Vfo& v) { return v.st[(size_t)((v.i_poly >= 0) ? v.i_poly : v.i_first + std::max(v.d.n_stages, 1) - 1)]; }
+// RxVFO::out as the VFO is configured NOW: the channel filter's output, or its input while the filter is bypassed (st[i_if]: where the last push's lies).
+Stream& rx_out(Vfo& v) { return (v.chan_ntaps > 0 && v.i_chan >= 0) ? v.st[(size_t)v.i_chan] : chan_feed(v); }
+// What a read-out call names with `which` (sdrpp_vfo_read_many / _read_pcm / _read_compressed); nullptr: the VFO has no such stream.
+//   0: what the VFO delivers — the demodulator's output; a RAW VFO's IF stream, behind an active IF chain the chain's output
+//   1: the IF stream in front of the IF chain      2: the AF chain's output      3: the IF chain's output (a chain with a block switched on)
+Stream* delivered(Vfo& v, int which) {
+    Stream* ifc = (v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base) ? &v.st[(size_t)v.i_ifc] : nullptr;
+    switch (which) {
+    case 0: return (v.d.demod != SDRPP_DEMOD_RAW) ? &v.st[(size_t)v.i_out] : (ifc ? ifc : &v.st[(size_t)v.i_if]);
+    case 1: return &v.st[(size_t)v.i_if];
+    case 2: return (v.af.on && v.af.i_last >= 0) ? &v.st[(size_t)v.af.i_last] : nullptr;
+    case 3: return ifc;
+    default: return nullptr;
+    }
+}
+// The stream the demodulator reads: the IF chain's output while a chain is active, else RxVFO::out.
+Stream& demod_feed(Vfo& v) { return delivered(v, 3) ? *delivered(v, 3) : rx_out(v); }
+// How much of its input the demodulator remembers: the fused discriminator + audio FIR re-reads the IF history.
+int demod_if_need(const Vfo& v) { return (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) ? std::max(v.audio_ntaps, 1) + 1 : 1; }
+
+// ---- delay-line hand-overs ----------------------------------------------------------------------------------------------------------
+// the newest min(both histories, max_samples) samples of `from`'s history become the newest of `to`'s
+int hist_tail_copy(sdrpp_ctx* c, Stream& to, const Stream& from, int max_samples) {
+    if (!to.hist[to.cur] || !from.hist[from.cur] || to.width != from.width) { return SDRPP_OK; }
+    const int H = std::min(std::min(from.hist_len, to.hist_len), max_samples);
+    if (H <= 0) { return SDRPP_OK; }
+    const size_t w = (size_t)to.width;
+    HIPCHK(c, hipMemcpy(to.hist[to.cur] + (size_t)(to.hist_len - H) * w, from.hist[from.cur] + (size_t)(from.hist_len - H) * w, (size_t)H * w * sizeof(float), hipMemcpyDeviceToDevice));
+    return SDRPP_OK;
+}
+// The delay line of a FIR of `ntaps` taps that reads stream `s`: exactly the newest ntaps - 1 samples it was fed, whatever the stream's longer history holds
+// in front of them (a one-tap filter has no delay line: nothing; a stream without history yet: zeros, which is what FIR's cleared buffer holds, fir.h:24-26).
+int fir_line_save(sdrpp_ctx* c, const Stream& s, int ntaps, std::vector<float>& line) {
+    const size_t w = (size_t)s.width;
+    line.assign((size_t)std::max(ntaps - 1, 0) * w, 0.0f);
+    if (ntaps > 1 && s.hist[s.cur] && s.hist_len >= ntaps - 1) {
+        HIPCHK(c, hipMemcpy(line.data(), s.hist[s.cur] + (size_t)(s.hist_len - (ntaps - 1)) * w, line.size() * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return SDRPP_OK;
+}
+// FIR::setTaps (dsp/filter/fir.h:31-52) on a filter that held `line` and has `ntaps` taps from now on: the newest min(old, new) - 1 samples stay,
+// zeros in front of them (all zeros for a filter that never ran).
+int fir_line_restore(sdrpp_ctx* c, Stream& s, int ntaps, const std::vector<float>& line) {
+    if (!s.hist[s.cur]) { return SDRPP_OK; }
+    const size_t w = (size_t)s.width;
+    HIPCHK(c, hipMemset(s.hist[s.cur], 0, (size_t)s.hist_len * w * sizeof(float)));
+    const int have = (int)(line.size() / w), m = std::min(have, std::min(ntaps - 1, s.hist_len));
+    if (m > 0) { HIPCHK(c, hipMemcpy(s.hist[s.cur] + (size_t)(s.hist_len - m) * w, line.data() + (size_t)(have - m) * w, (size_t)m * w * sizeof(float), hipMemcpyHostToDevice)); }
+    return SDRPP_OK;
+}
+
+// ---- building a VFO -----------------------------------------------------------------------------------------------------------------
+// bank[(L-1) - (i mod L)][i div L] = taps[i], zero-padded to L x tpp (polyphase_bank.h:31-34), laid out [phase][tpp]
+std::vector<float> polyphase_bank(const float* taps, int n, int interp, int tpp) {
+    std::vector<float> bank((size_t)interp * tpp, 0.0f);
+    for (int i = 0; i < std::min(n, interp * tpp); i++) { bank[(size_t)((interp - 1) - (i % interp)) * tpp + (size_t)(i / interp)] = taps[i]; }
+    return bank;
+}
+
+// sdrpp_vfo_add behind its argument check and flush: validates the description, builds the VFO and hands it to the context
+int vfo_build(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
+    if (d->n_stages < 0 || d->n_stages > SDRPP_MAX_DECIM_STAGES) { return fail(c, SDRPP_ERR_INVALID, "n_stages %d", d->n_stages); }
+    for (int s = 0; s < d->n_stages; s++) {
+        if (!is_pow2(d->stage_decim[s]) || d->stage_ntaps[s] <= 0 || !d->stage_taps[s]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "stage %d: decimation must be a power of two with taps", s); }
+    }
+    if (d->n_stages > 0) {  // the fused translation + FIR kernel uses the linear-phase pairing (all reference plans are symmetric)
+        const float* h = d->stage_taps[0];
+        for (int k = 0; k < d->stage_ntaps[0] / 2; k++) {
+            if (h[k] != h[d->stage_ntaps[0] - 1 - k]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "first decimation stage must have symmetric (linear-phase) taps"); }
+        }
+    }
+    const bool has_poly = (d->interp != d->decim);
+    if (has_poly && (d->interp <= 0 || d->decim <= 0 || d->resamp_ntaps <= 0 || !d->resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad polyphase description"); }
+    if (d->chan_ntaps < 0 || d->chan_ntaps > kChanHistCap + 1) { return fail(c, SDRPP_ERR_UNSUPPORTED, "channel filter of %d taps (max %d)", d->chan_ntaps, kChanHistCap + 1); }
+    if (d->demod < SDRPP_DEMOD_RAW || d->demod > SDRPP_DEMOD_DSB) { return fail(c, SDRPP_ERR_INVALID, "demod %d", d->demod); }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // every early return below gives the device allocations made so far back (vfo_free); only a fully built VFO is handed to the context
+    struct VfoFreer {
+        void operator()(Vfo* p) const {
+            if (p) {
+                vfo_free(*p);
+                delete p;
+            }
+        }
+    };
+    std::unique_ptr<Vfo, VfoFreer> v(new Vfo);
+    v->id = c->next_id++;
+    v->d = *d;
+    if (d->nco_mode < 0 || d->nco_mode > 2) { return fail(c, SDRPP_ERR_INVALID, "nco_mode %d: 0 (context), 1 (closed form) or 2 (reference rotator)", d->nco_mode); }
+    v->nco_exact = d->nco_mode == 0 ? (c->nco_exact != 0) : (d->nco_mode == 2);
+    int rc;
+    // capacities
+    size_t cap = (size_t)c->max_push;
+    auto add_stream = [&](int width, int hist, size_t capn) -> int {
+        v->st.emplace_back();
+        int r = stream_alloc(c, v->st.back(), width, hist, capn);
+        return r ? -1 : (int)v->st.size() - 1;
+    };
+    // what consumes the decimator / rotator output
+    const int tpp = has_poly ? (d->resamp_ntaps + d->interp - 1) / d->interp : 0;
+    const bool fm = (d->demod == SDRPP_DEMOD_WFM || d->demod == SDRPP_DEMOD_NFM);
+    if (fm || d->demod == SDRPP_DEMOD_AM) { v->audio_ntaps = std::max(d->audio_ntaps, 1); }  // fm.h:165-168 loadDummyTaps: a single unit tap when the low-pass is off
+    const int if_hist = demod_if_need(*v);
+    const int chan_hist = ((std::max(std::max(d->chan_ntaps - 1, 1), if_hist) + 63) / 64) * 64;  // grown on demand by sdrpp_vfo_set_channel_taps
+    auto hist_after_decim = [&]() -> int {
+        if (has_poly) { return tpp - 1; }
+        return chan_hist;  // channel filter or the discriminator
+    };
+    for (int s = 0; s < d->n_stages; s++) {
+        v->staps[s].assign(d->stage_taps[s], d->stage_taps[s] + d->stage_ntaps[s]);
+        v->d.stage_taps[s] = nullptr;
+        rc = upload_blocked(c, &v->d_staps[s], v->staps[s].data(), (int)v->staps[s].size(), d->stage_decim[s], &v->s_kp[s]);
+        if (rc) { return rc; }
+        rc = upload(c, &v->d_staps_nat[s], v->staps[s].data(), v->staps[s].size());
+        if (rc) { return rc; }
+        if (s >= 1 || v->nco_exact) {  // stage 0 runs as a plain FIR only behind the reference rotator
+            rc = toep_build_fir(c, v->tp_stage[s], v->staps[s].data(), (int)v->staps[s].size(), d->stage_decim[s]);
+            if (rc) { return rc; }
+        }
+        cap = cap / (size_t)d->stage_decim[s] + 2;
+        const int hist = (s + 1 < d->n_stages) ? d->stage_ntaps[s + 1] - 1 : hist_after_decim();
+        if (add_stream(2, hist, cap) < 0) { return SDRPP_ERR_NOMEM; }
+    }
+    if (d->n_stages == 0) {
+        if (add_stream(2, hist_after_decim(), cap) < 0) { return SDRPP_ERR_NOMEM; }
+    }
+    v->i_first = 0;
+    {   // the front end as one filter: fusion decision (geometry only), tap identity, composite taps for the retune hand-over
+        unsigned long long hsh = 1469598103934665603ull;  // FNV-1a over the taps of stages 0 and 1
+        for (int s = 0; s < std::min(d->n_stages, 2); s++) {
+            for (float t : v->staps[s]) {
+                unsigned u;
+                memcpy(&u, &t, 4);
+                hsh = (hsh ^ u) * 1099511628211ull;
+            }
+        }
+        v->tap_hash = hsh;
+        if (d->n_stages >= 2) {  // the composite forms pair taps k and K-1-k: stage 1 must be linear phase as well
+            const std::vector<float>& h2 = v->staps[1];
+            for (size_t k = 0; k < h2.size() / 2; k++) { v->no_fuse = v->no_fuse || (h2[k] != h2[h2.size() - 1 - k]); }
+        }
+        v->fused_front = !v->nco_exact && !v->no_fuse && d->n_stages >= 2 && front2_t2(d->stage_ntaps[0], d->stage_decim[0], d->stage_ntaps[1], d->stage_decim[1], 8) > 0;
+        if (d->n_stages >= 1 && !v->nco_exact) {
+            const int K0 = d->stage_ntaps[0], D1 = d->stage_decim[0], K2 = v->fused_front ? d->stage_ntaps[1] : 1;
+            const int K = K0 + (K2 - 1) * D1;
+            std::vector<double> h12((size_t)K, 0.0);
+            for (int k2 = 0; k2 < K2; k2++) {
+                const double w2 = v->fused_front ? (double)v->staps[1][(size_t)k2] : 1.0;
+                for (int k1 = 0; k1 < K0; k1++) { h12[(size_t)k2 * D1 + k1] += w2 * (double)v->staps[0][(size_t)k1]; }
+            }
+            std::vector<float> hf(h12.begin(), h12.end());
+            rc = upload(c, &v->d_h12, hf.data(), hf.size());
+            if (rc) { return rc; }
+            v->h12_K = K;
+            v->h12_lgD = ilog2(D1) + (v->fused_front ? ilog2(d->stage_decim[1]) : 0);
+        }
+        if (v->nco_exact && d->n_stages >= 1) {  // reference-rotator mode: the rotated full-rate stream feeds stage 0
+            v->i_rot = add_stream(2, d->stage_ntaps[0] - 1, (size_t)c->max_push);
+            if (v->i_rot < 0) { return SDRPP_ERR_NOMEM; }
+        }
+    }
+    if (has_poly) {
+        v->rtaps.assign(d->resamp_taps, d->resamp_taps + d->resamp_ntaps);
+        v->d.resamp_taps = nullptr;
+        v->tpp = tpp;
+        const std::vector<float> bank = polyphase_bank(v->rtaps.data(), d->resamp_ntaps, d->interp, tpp);
+        rc = upload(c, &v->d_bank, bank.data(), bank.size());
+        if (rc) { return rc; }
+        rc = toep_build_poly(c, v->tp_poly, bank, d->interp, d->decim, tpp);
+        if (rc) { return rc; }
+        if (d->interp <= 8) {  // register-blocked kernel: per carried phase, taps of one full phase cycle
+            const int L = d->interp, M = d->decim, lmax = (L <= 4) ? 4 : 8, rows = tpp + M;
+            std::vector<float> cyc((size_t)L * rows * lmax, 0.0f);
+            for (int ph0 = 0; ph0 < L; ph0++) {
+                for (int r = 0; r < L; r++) {
+                    const int A = ph0 + r * M, ph = A % L, o = A / L;
+                    for (int k = 0; k < tpp; k++) { cyc[((size_t)ph0 * rows + (size_t)(k + o)) * lmax + r] = bank[(size_t)ph * tpp + k]; }
+                }
+            }
+            rc = upload(c, &v->d_cyc, cyc.data(), cyc.size());
+            if (rc) { return rc; }
+            v->cyc_rows = rows;
+            v->cyc_lmax = lmax;
+        }
+        cap = cap * (size_t)d->interp / (size_t)d->decim + 4;
+        v->i_poly = add_stream(2, chan_hist, cap);
+        if (v->i_poly < 0) { return SDRPP_ERR_NOMEM; }
+    }
+    // channel-filter output stream always exists (taps may be enabled later); its consumer is the demodulator
+    v->i_chan = add_stream(2, if_hist, cap);
+    if (v->i_chan < 0) { return SDRPP_ERR_NOMEM; }
+    if (d->chan_ntaps > 0) {
+        if (!d->chan_taps) { return fail(c, SDRPP_ERR_INVALID, "chan_taps null"); }
+        v->ctaps_chan.assign(d->chan_taps, d->chan_taps + d->chan_ntaps);
+        rc = upload_blocked(c, &v->d_chan, v->ctaps_chan.data(), (int)v->ctaps_chan.size(), 1, &v->chan_kp);
+        if (rc) { return rc; }
+        rc = toep_build_fir(c, v->tp_chan, v->ctaps_chan.data(), (int)v->ctaps_chan.size(), 1);
+        if (rc) { return rc; }
+        v->chan_ntaps = d->chan_ntaps;
+    }
+    v->d.chan_taps = nullptr;
+    // the IF chain's output (sdrpp_vfo_set_if): only the slot — its buffers come with the first chain, a VFO without one pays nothing
+    v->st.emplace_back();
+    v->i_ifc = (int)v->st.size() - 1;
+    if (d->demod != SDRPP_DEMOD_RAW) {
+        if (fm || d->demod == SDRPP_DEMOD_AM) {
+            static const float unit = 1.0f;
+            const float* at = d->audio_ntaps > 0 ? d->audio_taps : &unit;
+            const int an = v->audio_ntaps;
+            if (d->audio_ntaps > 0 && !d->audio_taps) { return fail(c, SDRPP_ERR_INVALID, "audio_taps null"); }
+            v->ataps.assign(at, at + an);
+            rc = upload_blocked(c, &v->d_audio, v->ataps.data(), (int)v->ataps.size(), 1, &v->audio_kp);
+            if (rc) { return rc; }
+            rc = toep_build_fir(c, v->tp_audio, v->ataps.data(), (int)v->ataps.size(), 1);
+            if (rc) { return rc; }
+            if (!fm) {  // AM: the sequential envelope/AGC kernel writes a real stream for the low-pass; FM demodulates inside the FIR kernel
+                v->i_dem = add_stream(1, std::max(an - 1, 1), cap);
+                if (v->i_dem < 0) { return SDRPP_ERR_NOMEM; }
+            }
+        }
+        if (d->demod >= SDRPP_DEMOD_USB) {  // SSB: real scratch between the parallel translation and the sequential AGC
+            v->i_dem = add_stream(1, 0, cap);
+            if (v->i_dem < 0) { return SDRPP_ERR_NOMEM; }
+        }
+        v->i_out = add_stream(2, 0, cap);
+        if (v->i_out < 0) { return SDRPP_ERR_NOMEM; }
+    }
+    v->d.audio_taps = nullptr;
+    rc = dev_alloc(c, &v->d_state, 2 * sizeof(AgcState) + sizeof(float));
+    if (rc) { return rc; }
+    rc = dev_alloc(c, &v->d_rot, 2);
+    if (rc) { return rc; }
+    v->theta = sdrpp_host::turnsPerSample(d->phase_delta_re, d->phase_delta_im);
+    v->theta2 = sdrpp_host::turnsPerSample(d->ssb_phase_delta_re, d->ssb_phase_delta_im);
+    if (d->demod < SDRPP_DEMOD_USB) { v->theta2 = 0.0; }
+    v->modtaps_dirty = true;
+    rc = vfo_reset_state(c, *v);
+    if (rc) { return rc; }
+    const int vid = v->id;  // (the right-hand side of the assignment below is evaluated first)
+    *id = vid;
+    c->vfos[vid] = std::unique_ptr<Vfo>(v.release());
+    vfo_list_rebuild(c);
+    return SDRPP_OK;
+}
+
+// ---- radio IF chain -----------------------------------------------------------------------------------------------------------------
+// sdrpp_vfo_set_if on a VFO the caller has looked up (the stream is idle).  What the demodulator remembers of its input (the discriminator's
+// previous sample, the audio low-pass's delay line) moves with the switch: it was fed the IF until a chain becomes active and the chain's
+// output from then on, or the other way round.
+int ifc_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_if_desc* d) {
+    Vfo::Ifc& f = v.ifc;
+    if (v.i_ifc < 0) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no IF chain slot", v.id); }
+    Stream& fs = v.st[(size_t)v.i_ifc];
+    const bool was_active = f.active() && fs.base, was_nb = f.on && f.nb_on;
+    if (d) {
+        if (d->nb_enabled && !(d->nb_rate > 0.0f && d->nb_rate <= 1.0f && d->nb_level == d->nb_level)) { return fail(c, SDRPP_ERR_INVALID, "noise blanker: rate %g (0 < rate <= 1), level %g", d->nb_rate, d->nb_level); }
+        if (d->squelch_enabled && d->squelch_level != d->squelch_level) { return fail(c, SDRPP_ERR_INVALID, "squelch level is not a number"); }
+        if (!fs.base) {
+            const Stream& like = v.st[(size_t)v.i_chan];  // what the demodulator reads today: same capacity, same history
+            int rc = stream_alloc(c, fs, 2, like.hist_len, like.cap);
+            if (rc) { return rc; }
+        }
+        if (!f.d_amp) {
+            int rc = dev_alloc(c, &f.d_amp, 1);
+            if (rc) { return rc; }
+        }
+        if (d->nb_enabled && !was_nb) {  // a blanker that starts: amp = 1 (noise_blanker.h:75); one that runs keeps it through setRate / setLevel
+            const float one = 1.0f;
+            HIPCHK(c, hipMemcpy(f.d_amp, &one, sizeof(float), hipMemcpyHostToDevice));
+        }
+        f.on = true;
+        f.nb_on = d->nb_enabled != 0;
+        f.nb_rate = d->nb_rate;
+        f.nb_level = d->nb_level;
+        f.sq_on = d->squelch_enabled != 0;
+        f.sq_level = d->squelch_level;
+    }
+    else {
+        f.on = false;
+        f.nb_on = 0;
+        f.sq_on = 0;
+    }
+    const bool now_active = f.active();
+    if (was_active != now_active && fs.base) {
+        Stream& feed = rx_out(v);
+        const int if_need = demod_if_need(v);
+        int rc = now_active ? hist_tail_copy(c, fs, feed, if_need) : hist_tail_copy(c, feed, fs, if_need);
+        if (rc) { return rc; }
+    }
+    if (!now_active) { fs.n = 0; }
+    return SDRPP_OK;
+}
+
+// ---- sdrpp_vfo_replace: what of the old VFO lives on in the new one -----------------------------------------------------------------
+// RxVFO::setInSamplerate / setOutSamplerate (rx_vfo.h:35-58): the channeliser is re-planned, but not everything starts over.  The reference keeps
+//   * the translation's phase (FrequencyXlator::setOffset only swaps phaseDelta, frequency_xlator.h:24-30) and
+//   * the channel filter's delay line (setOutSamplerate: FIR::setTaps moves it under the new tap count, fir.h:31-52; setInSamplerate does not touch the
+//     filter at all; a filter that is bypassed under the new settings keeps what it held, one that wakes up continues from that)          -> keep bit 0
+// while its decimator stages are new objects and the polyphase resampler is reset (power_decimator.h:91-108, polyphase_resampler.h:38-67), and
+//   * the demodulator behind it is a separate block that setInSamplerate leaves alone: discriminator / audio low-pass history, AGC and DC-blocker
+//     states, SSB's second translation                                                                                                     -> keep bit 1
+// (a demodulator SWITCH deletes and creates it, radio_module.h:419-563: bit 1 off).  The AF chain is re-attached by the caller and starts cleared.
+int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
+    Stream& of = chan_feed(o);
+    Stream& nf = chan_feed(n);
+    int rc;
+    if (keep & 1) {
+        if (o.nco_exact == n.nco_exact) {
+            n.phi = o.phi;
+            if (o.d_rot && n.d_rot) { HIPCHK(c, hipMemcpy(n.d_rot, o.d_rot, sizeof(float2), hipMemcpyDeviceToDevice)); }
+        }
+        // the channel filter's delay line as the reference's FIR object holds it now: the newest old_taps - 1 samples it was fed, or what it held
+        // when it was last bypassed
+        std::vector<float> line = o.chan_stale;
+        if (o.chan_ntaps > 0 && (rc = fir_line_save(c, of, o.chan_ntaps, line))) { return rc; }
+        if (n.chan_ntaps > 0 && nf.width == of.width) {
+            if ((rc = fir_line_restore(c, nf, n.chan_ntaps, line))) { return rc; }
+        }
+        else if (n.chan_ntaps == 0) { n.chan_stale = line; }  // bypassed under the new settings: the filter object keeps what it held
+    }
+    if ((keep & 2) && o.d.demod == n.d.demod) {
+        // the demodulator's view of the IF stream: the discriminator's previous sample and the audio low-pass's delay line are its newest samples
+        // (behind an IF chain that is what the CHAIN delivered)
+        rc = hist_tail_copy(c, demod_feed(n), demod_feed(o), demod_if_need(n));  // (the new VFO has no chain yet: its RxVFO::out)
+        if (rc) { return rc; }
+        if (o.i_dem >= 0 && n.i_dem >= 0) {
+            rc = hist_tail_copy(c, n.st[(size_t)n.i_dem], o.st[(size_t)o.i_dem], 1 << 30);
+            if (rc) { return rc; }
+        }
+        if (o.d_state && n.d_state) { HIPCHK(c, hipMemcpy(n.d_state, o.d_state, 2 * sizeof(AgcState) + sizeof(float), hipMemcpyDeviceToDevice)); }
+        n.phi2 = o.phi2;
+        if (o.d_rot && n.d_rot) { HIPCHK(c, hipMemcpy(n.d_rot + 1, o.d_rot + 1, sizeof(float2), hipMemcpyDeviceToDevice)); }
+    }
+    if ((keep & 4) && o.ifc.on) {
+        // the radio's IF chain objects are not the demodulator's: they live through a demodulator switch (radio_module.h:84-96, 419-563), the
+        // blanker with its amplitude estimate.  Attaching copies the demodulator's view of the IF (set above) into the chain's history.
+        const sdrpp_if_desc fd{ o.ifc.nb_on, o.ifc.nb_rate, o.ifc.nb_level, o.ifc.sq_on, o.ifc.sq_level };
+        rc = ifc_apply(c, n, &fd);
+        if (rc) { return rc; }
+        if (o.ifc.nb_on && o.ifc.d_amp && n.ifc.d_amp) { HIPCHK(c, hipMemcpy(n.ifc.d_amp, o.ifc.d_amp, sizeof(float), hipMemcpyDeviceToDevice)); }
+    }
+    return SDRPP_OK;
+}
+
+// ---- sdrpp_vfo_set_channel_taps -----------------------------------------------------------------------------------------------------
+int vfo_set_chan_taps(sdrpp_ctx* c, Vfo& v, const float* taps, int n) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    Stream& fs = chan_feed(v);  // must remember n - 1 samples
+    const int old_n = v.chan_ntaps, w = fs.width;
+    const bool was_on = old_n > 0, now_on = n > 0;
+    // ---- the filter's BYPASS switched (bandwidth == IF rate exactly, rx_vfo.h:60-70 / :89-100) ----
+    // (a) The consumers behind the filter read "the IF stream" with memory (the demodulator's audio low-pass): their delay line holds the last
+    //     samples they were FED — the filter's outputs until now, its input from now on, or the other way round.  The IF stream changes its
+    //     identity here (st[i_chan] <-> the filter's input stream), so the newest history goes with it.
+    // (b) The reference does not touch a bypassed filter: its delay line keeps what it held when it last ran, and a filter switched on again
+    //     continues from that stale content (FIR::setTaps moves it like any other change of the tap count, fir.h:31-52).  The stream's side
+    //     buffer here keeps being refreshed for consumer (a), so the filter's own last history is set aside when it goes to sleep and put
+    //     back — under the new tap count — when it wakes up.
+    if (was_on != now_on && v.i_chan >= 0) {
+        Stream& cs = v.st[(size_t)v.i_chan];
+        if (was_on) {  // going to sleep: (b) first, (a) overwrites the buffer
+            if (int rc = fir_line_save(c, fs, old_n, v.chan_stale)) { return rc; }
+        }
+        if (now_on) {  // waking up: the buffer must be long enough for the new filter before anything is put into it
+            int rc = stream_grow_hist(c, fs, n - 1);
+            if (rc) { return rc; }
+        }
+        if (int rc = was_on ? hist_tail_copy(c, fs, cs, 1 << 30) : hist_tail_copy(c, cs, fs, 1 << 30)) { return rc; }  // (a)
+        if (now_on) {  // (b): what the filter held when it last ran, under the new tap count
+            if (int rc = fir_line_restore(c, fs, n, v.chan_stale)) { return rc; }
+        }
+    }
+    else {
+        int rc = stream_grow_hist(c, fs, n - 1);
+        if (rc) { return rc; }
+        // FIR::setTaps (dsp/filter/fir.h:31-52): a LONGER filter starts with zeros in front of the old delay line — its old_n - 1 samples are
+        // all the reference kept, whatever the stream held before them.  The side buffer here holds the stream's true tail (newest last):
+        // everything older than the old filter's reach is cleared.
+        const int keep = std::max(old_n - 1, 0);
+        if (n > old_n && fs.hist_len > keep && fs.hist[fs.cur]) {
+            HIPCHK(c, hipMemset(fs.hist[fs.cur], 0, (size_t)(fs.hist_len - keep) * (size_t)w * sizeof(float)));
+        }
+    }
+    v.ctaps_chan.assign(taps, taps + n);
+    v.chan_ntaps = n;
+    v.d.chan_ntaps = n;
+    if (n > 0) {
+        int rc = upload_blocked(c, &v.d_chan, v.ctaps_chan.data(), n, 1, &v.chan_kp);
+        if (rc) { return rc; }
+        rc = toep_build_fir(c, v.tp_chan, v.ctaps_chan.data(), n, 1);
+        if (rc) { return rc; }
+    }
+    return SDRPP_OK;
+}
+
+// ---- radio AF chain -----------------------------------------------------------------------------------------------------------------
+void af_detach(Vfo& v) {
+    Vfo::Af& a = v.af;
+    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) {
+        dev_free(a.d_staps[i]);
+        toep_free(a.tp_stage[i]);
+    }
+    toep_free(a.tp_poly);
+    toep_free(a.tp_hpf);
+    dev_free(a.d_bank);
+    dev_free(a.d_hpf);
+    dev_free(a.d_last);
+    dev_free(a.d_seg);
+    if (a.base >= 0) {
+        for (size_t i = (size_t)a.base; i < v.st.size(); i++) { stream_free(v.st[i]); }
+        v.st.resize((size_t)a.base);
+    }
+    a = Vfo::Af{};
+}
+
+// sdrpp_vfo_set_af on a VFO the caller has looked up: the old chain goes, `af` (if any) is built behind st[i_out]
+int af_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_af_desc* af) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    af_detach(v);
+    if (!af) { return SDRPP_OK; }
+    if (v.d.demod == SDRPP_DEMOD_RAW || v.i_out < 0) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the AF chain needs a demodulating VFO"); }
+    if (af->n_stages < 0 || af->n_stages > SDRPP_MAX_DECIM_STAGES) { return fail(c, SDRPP_ERR_INVALID, "af n_stages %d", af->n_stages); }
+    for (int s = 0; s < af->n_stages; s++) {
+        if (!is_pow2(af->stage_decim[s]) || af->stage_ntaps[s] <= 0 || !af->stage_taps[s]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "af stage %d: decimation must be a power of two with taps", s); }
+    }
+    const bool has_poly = af->interp != af->decim;
+    if (has_poly && (af->interp <= 0 || af->decim <= 0 || af->resamp_ntaps <= 0 || !af->resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af polyphase description"); }
+    if (af->hpf_ntaps < 0 || af->hpf_ntaps > kChanHistCap + 1 || (af->hpf_ntaps > 0 && !af->hpf_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af high-pass description"); }
+    Vfo::Af& a = v.af;
+    a.base = (int)v.st.size();
+    a.n_stages = af->n_stages;
+    a.interp = has_poly ? af->interp : 1;
+    a.decim = has_poly ? af->decim : 1;
+    a.tpp = has_poly ? (af->resamp_ntaps + af->interp - 1) / af->interp : 0;
+    a.alpha = af->deemph_alpha;
+    int rc;
+    // history a stream must keep = (taps - 1) of its consumer; `stage` = first block that can be the consumer
+    // (0..n_stages-1 decimators, n_stages polyphase, n_stages+1 high-pass; de-emphasis needs none)
+    auto need_of = [&](int stage) -> int {
+        if (stage < a.n_stages) { return af->stage_ntaps[stage] - 1; }
+        if (stage <= a.n_stages && has_poly) { return a.tpp - 1; }
+        if (stage <= a.n_stages + 1 && af->hpf_ntaps > 0) { return af->hpf_ntaps - 1; }
+        return 0;
+    };
+    rc = stream_grow_hist(c, v.st[(size_t)v.i_out], need_of(0));
+    if (rc) { return rc; }
+    size_t cap = v.st[(size_t)v.i_out].cap;
+    auto add_stream = [&](int hist, size_t capn) -> int {
+        v.st.emplace_back();
+        int r = stream_alloc(c, v.st.back(), 2, hist, capn);
+        return r ? -1 : (int)v.st.size() - 1;
+    };
+    for (int s = 0; s < a.n_stages; s++) {
+        a.decim_s[s] = af->stage_decim[s];
+        a.staps[s].assign(af->stage_taps[s], af->stage_taps[s] + af->stage_ntaps[s]);
+        rc = upload_blocked(c, &a.d_staps[s], a.staps[s].data(), (int)a.staps[s].size(), a.decim_s[s], &a.s_kp[s]);
+        if (rc) { return rc; }
+        rc = toep_build_fir(c, a.tp_stage[s], a.staps[s].data(), (int)a.staps[s].size(), a.decim_s[s]);
+        if (rc) { return rc; }
+        cap = cap / (size_t)a.decim_s[s] + 2;
+        const int idx = add_stream(need_of(s + 1), cap);
+        if (idx < 0) { return SDRPP_ERR_NOMEM; }
+        if (s == 0) { a.i_stage0 = idx; }
+    }
+    if (has_poly) {
+        a.rtaps.assign(af->resamp_taps, af->resamp_taps + af->resamp_ntaps);
+        const std::vector<float> bank = polyphase_bank(a.rtaps.data(), af->resamp_ntaps, a.interp, a.tpp);
+        rc = upload(c, &a.d_bank, bank.data(), bank.size());
+        if (rc) { return rc; }
+        rc = toep_build_poly(c, a.tp_poly, bank, a.interp, a.decim, a.tpp);
+        if (rc) { return rc; }
+        cap = cap * (size_t)a.interp / (size_t)a.decim + 4;
+        a.i_poly = add_stream(need_of(a.n_stages + 1), cap);
+        if (a.i_poly < 0) { return SDRPP_ERR_NOMEM; }
+    }
+    if (af->hpf_ntaps > 0) {
+        a.htaps.assign(af->hpf_taps, af->hpf_taps + af->hpf_ntaps);
+        rc = upload_blocked(c, &a.d_hpf, a.htaps.data(), (int)a.htaps.size(), 1, &a.hpf_kp);
+        if (rc) { return rc; }
+        rc = toep_build_fir(c, a.tp_hpf, a.htaps.data(), (int)a.htaps.size(), 1);
+        if (rc) { return rc; }
+        a.i_hpf = add_stream(0, cap);
+        if (a.i_hpf < 0) { return SDRPP_ERR_NOMEM; }
+    }
+    if (a.alpha != 0.0f) {
+        rc = dev_alloc(c, &a.d_last, 2);
+        if (rc) { return rc; }
+        HIPCHK(c, hipMemset(a.d_last, 0, 2 * sizeof(float2)));
+        a.state_cur = 0;
+        a.seg_cap = (int)(cap / SDRPP_DEEMP_SEG) + 2;
+        rc = dev_alloc(c, &a.d_seg, 2 * ((size_t)a.seg_cap + 1));
+        if (rc) { return rc; }
+        a.i_deemp = add_stream(0, cap);
+        if (a.i_deemp < 0) { return SDRPP_ERR_NOMEM; }
+    }
+    a.i_last = v.i_out;
+    a.on = true;
+    return SDRPP_OK;
+}
+
+// ---- read-out -----------------------------------------------------------------------------------------------------------------------
+// A pipelined back-end launch whose wavefronts gave up waiting for each other (never seen; a hang would be worse) counted that in THIS context's
+// page-locked word.  Called wherever the host has just synchronised with the stream and is about to hand out results.
+int pipe_timeouts_check(sdrpp_ctx* c) {
+    if (!c->pipe_launched || !c->h_tick_flag) { return SDRPP_OK; }
+    c->pipe_launched = false;
+    const int n = *(const volatile int*)(c->h_tick_flag + 8);
+    if (n != c->timeouts_seen) {
+        const int d = n - c->timeouts_seen;
+        c->timeouts_seen = n;
+        return fail(c, SDRPP_ERR_HIP, "pipelined back end: %d wavefront waits timed out (results of the last pushes are invalid)", d);
+    }
+    return SDRPP_OK;
+}
+
+// What the last push left in one of the context's output buffers: a VFO's stream (delivered) or the pre-processing chain's output.  `ok` false: there is
+// no such output, and the read-out call refuses with its family's own message (`missing`, a format for the id).
+struct OutBuf { const float* data; int n; bool ok; };
+OutBuf out_of(const Stream* s) { return s ? OutBuf{ s->data, s->n, true } : OutBuf{ nullptr, 0, false }; }
+OutBuf out_of_preproc(const sdrpp_ctx* c) { return c->pre.on ? OutBuf{ c->pre.last, c->pre.last_n, true } : OutBuf{ nullptr, 0, false }; }
+const char* const kNoAf = "VFO %d has no AF chain";
+const char* const kNoIfc = "VFO %d has no active IF chain";
+const char* const kNoPreproc = "no pre-processing chain configured";  // (takes no id)
+const char* const kNoOut = "VFO %d has no output stream";                 // (never seen: what a VFO delivers and its IF stream always exist)
+int out_count(sdrpp_ctx* c, OutBuf o, const char* missing, int id) {
+    if (!o.ok) { return fail(c, SDRPP_ERR_INVALID, missing, id); }
+    return o.n;
+}
+// min(max, n) complex samples to the host.  pipe_check: off for the pre-processing chain's output, which the pipelined back end never writes.
+int out_read(sdrpp_ctx* c, OutBuf o, const char* missing, int id, float* dst, int max, bool pipe_check) {
+    if (!o.ok) { return fail(c, SDRPP_ERR_INVALID, missing, id); }
+    const int n = std::min(max, o.n);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = pipe_check ? pipe_timeouts_check(c) : SDRPP_OK) { return rc; }
+    if (n > 0) { HIPCHK(c, hipMemcpy(dst, o.data, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost)); }
+    return n;
+}
+int out_hand(sdrpp_ctx* c, OutBuf o, const char* missing, int id, const float** data, int* n) {
+    if (!o.ok) { return fail(c, SDRPP_ERR_INVALID, missing, id); }
+    if (data) { *data = o.data; }
+    if (n) { *n = o.n; }
+    return SDRPP_OK;
+}
+
+// ---- sink-side sample packing ----------------------------------------------------------------------------------
+int pack_scratch(sdrpp_ctx* c, size_t bytes) {
+    if (bytes <= c->pack_cap) { return SDRPP_OK; }
+    dev_free(c->d_pack);
+    c->pack_cap = 0;
+    int rc = dev_alloc(c, &c->d_pack, bytes + 1024);
+    if (rc) { return rc; }
+    c->pack_cap = bytes + 1024;
+    return SDRPP_OK;
+}
+// nv floats at `src` -> int16 (pcm_type 1) / int8 (0) at `dst`, on the context's stream
+void pack_convert(sdrpp_ctx* c, const float* src, long long nv, float scale, int pcm_type, void* dst) {
+    const dim3 grid((unsigned)std::min<long long>((nv + 255) / 256, 4096));
+    if (pcm_type == 1) { hipLaunchKernelGGL(pack_convert_kernel<int16_t>, grid, dim3(256), 0, c->stream, src, scale, nv, (int16_t*)dst); }
+    else { hipLaunchKernelGGL(pack_convert_kernel<int8_t>, grid, dim3(256), 0, c->stream, src, scale, nv, (int8_t*)dst); }
+}
+// the first min(max, count) complex samples at `src`, converted on the device so that the copy to the host carries 4 (2) bytes per sample
+int pcm_read(sdrpp_ctx* c, const float* src, int count, int pcm_type, float scale, void* dst_host, int max) {
+    const int n = std::min(max, count);
+    if (n == 0) { return 0; }
+    const long long nv = (long long)n * 2;
+    const size_t esz = pcm_type == 1 ? 2 : 1;
+    if (int rc = pack_scratch(c, (size_t)nv * esz)) { return rc; }
+    pack_convert(c, src, nv, scale, pcm_type, c->d_pack);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = pipe_timeouts_check(c)) { return rc; }
+    HIPCHK(c, hipMemcpy(dst_host, c->d_pack, (size_t)nv * esz, hipMemcpyDeviceToHost));
+    return n;
+}
+
+}  // namespace
