@@ -58,11 +58,11 @@ int run_preproc(sdrpp_ctx* c, const float** d_iq, int64_t* count) {
         tp[s] = toep_plan(tj[s], 2, ticking ? c->tick_toep_blocks : 2048);
         d_tj[s] = arena_push(c, tj[s]);
         d_fj[s] = arena_push(c, fj[s]);
-        if ((!tj[s].empty() && !d_tj[s]) || (!fj[s].empty() && !d_fj[s])) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
+        if ((!tj[s].empty() && !d_tj[s]) || (!fj[s].empty() && !d_fj[s])) { return arena_fail(c); }
     }
     DeempJob* d_dc = arena_push(c, dc);
     CopyJob* d_conj = arena_push(c, conj);
-    if ((!dc.empty() && !d_dc) || (!conj.empty() && !d_conj) || !arena_push_lev(c, carry)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
+    if ((!dc.empty() && !d_dc) || (!conj.empty() && !d_conj) || !arena_push_lev(c, carry)) { return arena_fail(c); }
     int rc = arena_commit(c);
     if (rc) { return rc; }
     auto emit_carries = [&](int level) {

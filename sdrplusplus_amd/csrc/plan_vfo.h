@@ -181,20 +181,24 @@ bool arena_push_lev(sdrpp_ctx* c, Lev<T>& L) {
     }
     return true;
 }
+// the job tables of a block do not fit the arena (arena_push returned null for a list that has jobs)
+int arena_fail(sdrpp_ctx* c) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
 
-// One block of the VFO bank, planned in steps: every VFO's chain is walked once (chain: stage by stage — outputs per stage from the integer
-// streaming state, one job per stage in the list of its kind and LEVEL), the first stages are grouped into front-end jobs (group_front),
-// the job tables go into the arena in one piece (upload), then the launches — or, in pipelined mode, the roles — are emitted level by level
-// (emit_front, emit_levels).  Every job carries the LEVEL of its launch in the block's data flow (level L reads what level L - 1 wrote): the
-// front end is level 1 (level 0 = the block's arrival), every filter behind it one more.  A pass launches level by level; in pipelined mode
-// level L of this block runs L ticks from now (tick_kernels.h).
+// One block of the VFO bank, planned in steps: every VFO's chain is walked once (chain: a sequence of named parts — front_end, pipe_decide, the
+// stage steps decim_step / poly_step / fir_step, if_chain, demod_fm / demod_am / demod_ssb, af_chain, phase_advance, history_carries — with
+// outputs per stage from the integer streaming state and one job per stage in the list of its kind and LEVEL; a ChainCursor does every
+// hand-over from one stream to the next), the first stages are grouped into front-end jobs (group_front), the job tables go into the arena in
+// one piece (upload), then the launches — or, in pipelined mode, the roles — are emitted level by level (emit_front, emit_levels).  Every job
+// carries the LEVEL of its launch in the block's data flow (level L reads what level L - 1 wrote): the front end is level 1 (level 0 = the
+// block's arrival), every filter behind it one more.  A pass launches level by level; in pipelined mode level L of this block runs L ticks
+// from now (tick_kernels.h).  Every Lev<> job list is named once, in for_each_list.
 // One BankPlan lives with its context and is re-used block after block (begin() empties the lists and keeps their storage: with 128 VFOs a
 // fresh plan per block was ~1 000 small allocations, a third of the 225 us of host time that had become cfg 4's limit once its tick took 135 us).
 struct BankPlan {
     sdrpp_ctx* c;
     IqSrc src{};
     int n_in = 0;
-    bool ticking = false;
+    bool ticking = false;  // this block is planned for the tick queue (c->tick_planning when begin() ran; it does not change during a plan)
     int L0 = 0;  // levels the pre-processing chain takes in front (pipelined mode): the front end runs at level L0 + 1
     static constexpr int carry_last = kLevels - 1;
     static constexpr int carry_wave_max = 8192;  // floats: up to four rounds of a wavefront
@@ -255,6 +259,18 @@ struct BankPlan {
                                     { &t_af_poly, 2, 2, false, F_AF, TR_TOEP_C },     { &t_af_hpf, 2, 2, false, F_AF, TR_TOEP_C } };
     ToepPlan tplan[kToepLists][kLevels];
 
+    // THE enumeration of the Lev<> job lists, in the order their tables lie in the arena (the matrix-core lists of tlists[] first), for begin(),
+    // upload() and emit_levels().  A new list is one more f(...) here (a matrix-core list: one more row of tlists[]).
+    template <class F>
+    void for_each_list(F&& f) {
+        for (auto& t : tlists) { f(*t.L); }
+        f(f_dec); f(poly);
+        for (auto& q : polyb) { f(q); }
+        f(chan); f(seq); f(ifc); f(pre); f(audio); f(audio_fm);
+        f(af_dec); f(af_hpf); f(af_poly); f(af_deemp);
+        f(ssbx_l); f(carry);
+    }
+
     explicit BankPlan(sdrpp_ctx* c_) : c(c_), fb(c_->vfo_bounds) {
         for (int i = 0; i < 4; i++) { s1l[i].vt = vts[i]; f2l[i].vt = vts[i]; }
     }
@@ -274,12 +290,7 @@ struct BankPlan {
         L0 = ticking ? c->plan_lvl0 : 0;
         blocks = fb.size() > 1;
         s1.clear(); rot.clear(); rotx.clear(); retune.clear(); pipes.clear();
-        lev_reset(f_dec); lev_reset(poly);
-        for (auto& q : polyb) { lev_reset(q); }
-        lev_reset(chan); lev_reset(seq); lev_reset(ifc); lev_reset(pre); lev_reset(audio); lev_reset(audio_fm);
-        lev_reset(t_dec); lev_reset(t_poly); lev_reset(t_chan); lev_reset(t_audio); lev_reset(t_audio_fm);
-        lev_reset(t_af_dec); lev_reset(t_af_poly); lev_reset(t_af_hpf); lev_reset(af_dec); lev_reset(af_hpf); lev_reset(af_poly); lev_reset(af_deemp);
-        lev_reset(ssbx_l); lev_reset(carry);
+        for_each_list([](auto& L) { lev_reset(L); });
         pipe_lds = 0;
         d_pipes = nullptr;
         pipe_seg = 0;
@@ -307,393 +318,576 @@ struct BankPlan {
     BankPlan& operator=(const BankPlan&) = delete;
 
     // ---- one VFO's chain: stage by stage, a job per stage in the list of its kind and level ----
-    int chain(Vfo& v) {
-        Stream* cur = &v.st[(size_t)v.i_first];
-        int lvl = L0 + 1;  // level at which `cur` is written
-        for (auto& s : v.st) { s.clevel = 0; s.wlevel = 0; }
-        cur->wlevel = lvl;
-        // reference-block ends carried stage by stage down to the demodulator's rate, for the block-dependent operations there
-        // (AGC look-ahead, SSB rotator calls)
-        const bool agc_mode = v.d.demod == SDRPP_DEMOD_AM || (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_DSB);
-        // ... and the IF chain's squelch, which decides per reference block (power_squelch.h:33-50)
-        const bool ifc_on = v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base;
-        const bool need_bnd = (agc_mode && (blocks || v.nco_exact)) || (ifc_on && v.ifc.sq_on && blocks);
-        std::vector<int> bnd;
-        if (need_bnd) { bnd = fb; }
-        // a launch group of several pushes (sdrpp_set_pipeline_group): the PUSH ends carried the same way, through every rate change down to the
-        // stream the results are read from — which samples of the group's output block belong to which push (tick_results_describe)
-        const bool split = c->grp_ends.size() > 1;
-        std::vector<int>& tk = v.tk_if;
-        tk.clear();
-        v.tk_af.clear();
-        if (split) { tk = c->grp_ends; }
+    // Where the walk down a chain stands: the stream the next stage reads and the level at which that stream is written.
+    struct ChainCursor {
+        Stream* cur;
+        int lvl;
+        // The hand-over of a stage that runs `levels` levels behind the writer of `cur`: it is `cur`'s consumer (in pipelined mode the history
+        // carry of `cur` runs at that level, history_carries) and writes n_out samples of `nxt`, which the next stage reads.
+        void step(Stream& nxt, int n_out, int levels = 1) {
+            lvl += levels;
+            cur->clevel = lvl;
+            nxt.n = n_out;
+            nxt.wlevel = lvl;
+            cur = &nxt;
+        }
+    };
+    // What the parts of one chain() call share.
+    struct ChainCtx {
+        Vfo& v;
+        ChainCursor at;
+        bool ifc_on = false;    // the radio's IF chain runs for this VFO
+        std::vector<int> bnd;   // reference-block ends, carried down to the demodulator's rate for the block-dependent operations there; empty where none runs
+        const int* d_bnd = nullptr;  // their copy in the arena once that rate is reached
+        int nbnd = 0;
+        bool split = false;     // a launch group of several pushes (sdrpp_set_pipeline_group)
+        std::vector<int>* tk;   // its PUSH ends, carried down to the stream the results are read from (tick_results_describe): v.tk_if, then v.tk_af; empty unless `split`
+        S1Member mem{};
         int first_sep = 0;  // first decimator stage that runs as its own FIR launch
         double phi_end = 0.0;
         bool have_phi_end = false;  // (a launch group: the NCO phase after its last push, advanced push by push as block-by-block processing does)
+        // the FM back end as one pipelined launch (pipe_decide): the stage steps collect their matrix-form jobs here instead of in the lists
+        bool piped = false;
+        PipeJob pj;  // INDETERMINATE unless `piped`: pipe_decide sets it up for a candidate only (clearing it for every VFO of every block is host time)
+        size_t pj_lds = 0;
+        ChainCtx(Vfo& v_, int lvl) : v(v_), at{ &v_.st[(size_t)v_.i_first], lvl }, tk(&v_.tk_if) {}
+        ToepJob* pipe(int s) { return piped ? &pj.st[s] : nullptr; }
+        void through_decim(int off, int D) { bounds_decim(bnd, off, D); bounds_decim(*tk, off, D); }  // (an empty list: nothing to do)
+        void through_poly(int poff, int pphase, int L, int M) { bounds_poly(bnd, poff, pphase, L, M); bounds_poly(*tk, poff, pphase, L, M); }
+    };
+
+    // ---- one step per stage kind, for the VFO's chain and the AF chain alike: it advances the stage's `off` / `phase`.  `toep` is the list of the matrix form
+    // (taken whenever the stage has a tap table), the other list that of the VALU form; with `pipe` set the matrix-form job goes there instead of into `toep`.
+    // (Forced inline: as calls the three steps cost a 128-VFO bank 3 - 4 us of the 34 us its chains take per block, profiles/planner_split_host_time.md.) ----
+    static void place(Lev<ToepJob>& toep, ToepJob* pipe, int l, const ToepJob& j) {
+        if (pipe) { *pipe = j; }
+        else { toep.add(l, j); }
+    }
+    __attribute__((always_inline)) void decim_step(ChainCtx& x, Stream& nxt, const ToepTab& tp, const float* d_taps, int K, int D, int kp, int& off, Lev<ToepJob>& toep, Lev<FirBJob>& firb, ToepJob* pipe = nullptr) {
+        const Stream& in = *x.at.cur;
+        const int l = x.at.lvl + 1;
+        const int no = decim_nout(in.n, off, D);
+        x.through_decim(off, D);
+        if (tp.ok) { place(toep, pipe, l, toep_job(tp, 0, stream_in(in), nxt.data, off - (K - 1), no, 0.0f)); }
+        else { firb.add(l, FirBJob{ stream_in(in), nxt.data, d_taps, K, ilog2(D), off, no, kp }); }
+        off = off + no * D - in.n;
+        x.at.step(nxt, no);
+    }
+    __attribute__((always_inline)) void poly_step(ChainCtx& x, Stream& nxt, const ToepTab& tp, int L, int M, int tpp, int& phase, int& off, const float* d_bank, const float* d_cyc, int cyc_rows, int cyc_lmax, Lev<ToepJob>& toep, Lev<PolyJob>& valu, ToepJob* pipe = nullptr) {
+        const Stream& in = *x.at.cur;
+        const int l = x.at.lvl + 1;
+        const int no = poly_nout(in.n, off, phase, L, M);
+        x.through_poly(off, phase, L, M);
+        if (tp.ok) { place(toep, pipe, l, toep_job(tp, phase, stream_in(in), nxt.data, off - (tpp - 1), no, 0.0f)); }
+        else if (d_cyc) {
+            polyb[(cyc_lmax == 4 ? 0 : 1) + ((M & 1) ? 2 : 0)].add(l, PolyBJob{ stream_in(in), (float2*)nxt.data, d_cyc + (size_t)phase * cyc_rows * cyc_lmax, L, M,
+                                                                                      tpp, off, no, cyc_rows });
+        }
+        else { valu.add(l, PolyJob{ stream_in(in), (float2*)nxt.data, d_bank, L, M, tpp, phase, off, no }); }
+        const long long A = (long long)phase + (long long)no * M;
+        phase = (int)(A % L);
+        off = off + (int)(A / L) - in.n;
+        x.at.step(nxt, no);
+    }
+    __attribute__((always_inline)) void fir_step(ChainCtx& x, Stream& nxt, const ToepTab& tp, const float* d_taps, int K, int kp, float inv_dev, Lev<ToepJob>& toep, Lev<FirBJob>& firb, ToepJob* pipe = nullptr) {
+        const Stream& in = *x.at.cur;
+        const int l = x.at.lvl + 1;
+        if (tp.ok) { place(toep, pipe, l, toep_job(tp, 0, stream_in(in), nxt.data, -(K - 1), in.n, inv_dev)); }
+        else { firb.add(l, FirBJob{ stream_in(in), nxt.data, d_taps, K, 0, 0, in.n, kp, inv_dev }); }
+        x.at.step(nxt, in.n);
+    }
+
+    int chain(Vfo& v) {
+        ChainCtx x(v, L0 + 1);
+        for (auto& s : v.st) { s.clevel = 0; s.wlevel = 0; }
+        x.at.cur->wlevel = x.at.lvl;
+        const bool agc_mode = v.d.demod == SDRPP_DEMOD_AM || (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_DSB);
+        x.ifc_on = v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base;
+        const bool need_bnd = (agc_mode && (blocks || v.nco_exact)) || (x.ifc_on && v.ifc.sq_on && blocks);
+        if (need_bnd) { x.bnd = fb; }
+        x.split = c->grp_ends.size() > 1;
+        v.tk_if.clear();
+        v.tk_af.clear();
+        if (x.split) { v.tk_if = c->grp_ends; }
+        front_end(x);
+        pipe_decide(x);
+        const int last_dec = v.d.n_stages - 1;
+        for (int s = x.first_sep; s < v.d.n_stages; s++) {
+            Stream& nxt = v.st[(size_t)v.i_first + s];
+            const bool to_pipe = x.piped && s == last_dec;
+            decim_step(x, nxt, v.tp_stage[s], v.d_staps[s], v.d.stage_ntaps[s], v.d.stage_decim[s], v.s_kp[s], v.soff[s], t_dec, f_dec, to_pipe ? x.pipe(0) : nullptr);
+            if (to_pipe) {
+                x.pj.keep[0] = std::max(0, nxt.n - nxt.hist_len);
+                x.pj.dec_stage = s;
+                x.pj.lvl = x.at.lvl;
+            }
+        }
+        if (v.i_poly >= 0) {
+            Stream& nxt = v.st[(size_t)v.i_poly];
+            poly_step(x, nxt, v.tp_poly, v.d.interp, v.d.decim, v.tpp, v.pphase, v.poff, v.d_bank, v.d_cyc, v.cyc_rows, v.cyc_lmax, t_poly, poly, x.pipe(1));
+            if (x.piped) { x.pj.keep[1] = std::max(0, nxt.n - nxt.hist_len); }
+        }
+        if (v.i_chan >= 0 && v.chan_ntaps > 0) {
+            fir_step(x, v.st[(size_t)v.i_chan], v.tp_chan, v.d_chan, v.chan_ntaps, v.chan_kp, 0.0f, t_chan, chan, x.pipe(2));
+            if (x.piped) { x.pj.keep[2] = 0; }  // the IF stream is the RxVFO's output: all of it
+        }
+        v.i_if = (int)(x.at.cur - &v.st[0]);
+        v.lvl_if = x.at.lvl;
+        v.lvl_out = x.at.lvl;
+        if (need_bnd) {
+            x.d_bnd = arena_push(c, x.bnd);
+            if (!x.d_bnd) { return arena_fail(c); }
+            x.nbnd = (int)x.bnd.size();
+        }
+        if_chain(x);
+        if (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) { demod_fm(x); }
+        else if (v.d.demod == SDRPP_DEMOD_AM) { demod_am(x); }
+        else if (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_DSB) { demod_ssb(x); }
+        if (v.af.on && v.i_out >= 0) { af_chain(x); }
+        phase_advance(x);
+        history_carries(x);
+        c->plan_top = std::max(c->plan_top, x.at.lvl + 2);
+        return SDRPP_OK;
+    }
+
+    // The front end of one VFO: its membership of a front-end job (group_front builds the jobs), or the translation alone.  Leaves the cursor on
+    // the first stream a separate stage reads.
+    void front_end(ChainCtx& x) {
+        Vfo& v = x.v;
+        Stream* cur = x.at.cur;
         if (v.nco_exact) {
             // the reference's own data flow: rotate at the full rate (float recursion), then every stage of the plan as a plain FIR
             Stream* tgt = (v.d.n_stages == 0) ? cur : &v.st[(size_t)v.i_rot];
             rotx.push_back(RotXJob{ (float2*)tgt->data, v.d_rot, v.d.phase_delta_re, v.d.phase_delta_im });
             tgt->n = n_in;
-            tgt->wlevel = lvl;
-            cur = tgt;
+            tgt->wlevel = x.at.lvl;
+            x.at.cur = tgt;
+            return;
         }
-        else if (v.d.n_stages == 0) {
+        if (v.d.n_stages == 0) {
             rot.push_back(RotJob{ v.theta, v.phi, (float2*)cur->data, n_in });
             cur->n = n_in;
             max_rot = std::max(max_rot, n_in);
+            return;
         }
-        else {
-            const int D = v.d.stage_decim[0];
-            const int nout = decim_nout(n_in, v.soff[0], D);
-            if (v.modtaps_dirty) { build_modtaps(v); }
-            const int K0 = v.d.stage_ntaps[0];
-            S1Member mem{ &v, K0, ilog2(D), v.soff[0], nout, v.phi, 0, 0, 0, 0, 0, 0, v.tap_hash };
-            int need = K0 - 1;
-            first_sep = 1;
-            if (need_bnd) { bounds_decim(bnd, v.soff[0], D); }
-            if (split) { bounds_decim(tk, v.soff[0], D); }
-            if (v.fused_front) {
-                const int D2 = v.d.stage_decim[1];
-                mem.fused = 1;
-                mem.K2 = v.d.stage_ntaps[1];
-                mem.lgD2 = ilog2(D2);
-                mem.off2 = v.soff[1];
-                mem.nout2 = decim_nout(nout, v.soff[1], D2);
-                need = K0 - 1 + D * (mem.K2 - 1);
-                first_sep = 2;
-                if (need_bnd) { bounds_decim(bnd, v.soff[1], D2); }
-                if (split) { bounds_decim(tk, v.soff[1], D2); }
-            }
-            mem.min_idx = (v.seen >= need) ? -need : -(int)v.seen;  // older samples predate this VFO: zero
-            if (!split) { s1.push_back(mem); }
-            else {
-                // A launch group: ONE front-end job per push, with the offsets, the NCO phase and the history bound block-by-block processing would
-                // have given that push (the closed-form NCO is anchored at the start of a job: tile phasor x in-tile table — one job over the whole
-                // group would round the same samples differently), reading its samples where they lie in the group's block and writing its outputs
-                // behind those of the pushes in front.  Everything behind the front end is a plain FIR over the stream, indifferent to the cuts.
-                int so0 = v.soff[0], so1 = v.soff[1], prev_e = 0, oshift = 0;
-                long long seen = v.seen;
-                double ph = v.phi;
-                for (size_t j = 0; j < c->grp_ends.size(); j++) {
-                    const int nj = c->grp_ends[j] - prev_e;
-                    S1Member m = mem;
-                    m.off0 = so0;
-                    m.nout = decim_nout(nj, so0, D);
-                    m.phi0 = ph;
-                    int outs = m.nout;
-                    if (mem.fused) {
-                        m.off2 = so1;
-                        m.nout2 = decim_nout(m.nout, so1, v.d.stage_decim[1]);
-                        outs = m.nout2;
-                    }
-                    m.min_idx = ((seen >= need) ? -need : -(int)seen) + prev_e;
-                    m.shift = prev_e;
-                    m.oshift = oshift;
-                    if (outs > 0) { s1.push_back(m); }
-                    so0 = so0 + m.nout * D - nj;
-                    if (mem.fused) { so1 = so1 + m.nout2 * v.d.stage_decim[1] - m.nout; }
-                    const double pj = ph + (double)nj * v.theta;
-                    ph = pj - std::floor(pj);
-                    seen += nj;
-                    oshift += outs;
-                    prev_e = c->grp_ends[j];
-                }
-                phi_end = ph;
-                have_phi_end = true;
-            }
-            // setOffset hand-over: outputs whose window still reaches in front of the latest retune point are recomputed with the
-            // piecewise phase (vfo_retune_fix_kernel); retune points no window can reach any more are forgotten
-            {
-                const int D1 = D, Kc = v.h12_K;
-                const int off = mem.fused ? mem.off0 + (mem.off2 - (mem.K2 - 1)) * D1 - (K0 - 1) : mem.off0 - (K0 - 1);
-                const int nout_f = mem.fused ? mem.nout2 : nout;
-                while (!v.recs.empty() && v.recs.front().pos - v.seen <= (long long)off) { v.recs.erase(v.recs.begin()); }
-                while (v.recs.size() > SDRPP_RETUNE_MAX_SEG - 1) { v.recs.erase(v.recs.begin()); }
-                if (!v.recs.empty() && nout_f > 0) {
-                    const long long r_last = v.recs.back().pos - v.seen;  // push-relative, <= 0
-                    const long long Dc = 1ll << v.h12_lgD;
-                    const int nfix = (int)std::min<long long>((long long)nout_f, (r_last - off + Dc - 1) / Dc);  // outputs m with off + m * Dc < r_last
-                    if (nfix > 0) {
-                        RetuneJob rj{};
-                        rj.out = (float2*)v.st[(size_t)v.i_first + (mem.fused ? 1 : 0)].data;
-                        rj.taps = v.d_h12;
-                        rj.K = Kc;
-                        rj.log2_decim = v.h12_lgD;
-                        rj.off = off;
-                        rj.nfix = nfix;
-                        rj.min_idx = mem.min_idx;
-                        const int nr = (int)v.recs.size();
-                        rj.nseg = nr + 1;
-                        // segment q >= 1 starts at retune point q - 1 and runs with the increment that was in effect from there on (the
-                        // newest with the current one); segment 0 = everything in front of the oldest remembered point, anchored there.
-                        // Phases are continuous across the points, evaluated backwards from the current phase.
-                        double P = v.phi + v.theta * (double)r_last;  // phase at the newest point
-                        for (int q = nr; q >= 1; q--) {
-                            const long long Sq = v.recs[(size_t)q - 1].pos - v.seen;
-                            rj.start[q] = (int)std::max<long long>(Sq, -2000000000ll);
-                            rj.theta[q] = (q == nr) ? v.theta : v.recs[(size_t)q].theta_before;
-                            rj.phi[q] = P - std::floor(P);
-                            if (q >= 2) {  // phase at the start of the segment in front: back along ITS increment
-                                const long long Sp = v.recs[(size_t)q - 2].pos - v.seen;
-                                P = P + v.recs[(size_t)q - 1].theta_before * (double)(Sp - Sq);
-                            }
-                        }
-                        rj.start[0] = rj.start[1];
-                        rj.theta[0] = v.recs[0].theta_before;
-                        rj.phi[0] = rj.phi[1];
-                        retune.push_back(rj);
-                    }
-                }
-            }
-            v.soff[0] = v.soff[0] + nout * D - n_in;
-            cur->n = nout;
+        const int D = v.d.stage_decim[0];
+        const int nout = decim_nout(n_in, v.soff[0], D);
+        if (v.modtaps_dirty) { build_modtaps(v); }
+        const int K0 = v.d.stage_ntaps[0];
+        S1Member& mem = x.mem;
+        mem = S1Member{ &v, K0, ilog2(D), v.soff[0], nout, v.phi, 0, 0, 0, 0, 0, 0, v.tap_hash };
+        int need = K0 - 1;
+        x.first_sep = 1;
+        x.through_decim(v.soff[0], D);
+        if (v.fused_front) {
+            const int D2 = v.d.stage_decim[1];
+            mem.fused = 1;
+            mem.K2 = v.d.stage_ntaps[1];
+            mem.lgD2 = ilog2(D2);
+            mem.off2 = v.soff[1];
+            mem.nout2 = decim_nout(nout, v.soff[1], D2);
+            need = K0 - 1 + D * (mem.K2 - 1);
+            x.first_sep = 2;
+            x.through_decim(v.soff[1], D2);
+        }
+        mem.min_idx = (v.seen >= need) ? -need : -(int)v.seen;  // older samples predate this VFO: zero
+        if (!x.split) { s1.push_back(mem); }
+        else { front_split(x, need); }
+        retune_job(x);
+        v.soff[0] = v.soff[0] + nout * D - n_in;
+        cur->n = nout;
+        if (mem.fused) {
+            Stream* nxt = &v.st[(size_t)v.i_first + 1];
+            v.soff[1] = v.soff[1] + mem.nout2 * v.d.stage_decim[1] - nout;
+            cur->n = 0;  // the stage-1 stream is never materialised
+            nxt->n = mem.nout2;
+            nxt->wlevel = x.at.lvl;
+            x.at.cur = nxt;
+        }
+    }
+    // A launch group: ONE front-end job per push, with the offsets, the NCO phase and the history bound block-by-block processing would
+    // have given that push (the closed-form NCO is anchored at the start of a job: tile phasor x in-tile table — one job over the whole
+    // group would round the same samples differently), reading its samples where they lie in the group's block and writing its outputs
+    // behind those of the pushes in front.  Everything behind the front end is a plain FIR over the stream, indifferent to the cuts.
+    void front_split(ChainCtx& x, int need) {
+        Vfo& v = x.v;
+        const S1Member& mem = x.mem;
+        const int D = v.d.stage_decim[0];
+        int so0 = v.soff[0], so1 = v.soff[1], prev_e = 0, oshift = 0;
+        long long seen = v.seen;
+        double ph = v.phi;
+        for (size_t j = 0; j < c->grp_ends.size(); j++) {
+            const int nj = c->grp_ends[j] - prev_e;
+            S1Member m = mem;
+            m.off0 = so0;
+            m.nout = decim_nout(nj, so0, D);
+            m.phi0 = ph;
+            int outs = m.nout;
             if (mem.fused) {
-                Stream* nxt = &v.st[(size_t)v.i_first + 1];
-                v.soff[1] = v.soff[1] + mem.nout2 * v.d.stage_decim[1] - nout;
-                cur->n = 0;  // the stage-1 stream is never materialised
-                nxt->n = mem.nout2;
-                nxt->wlevel = lvl;
-                cur = nxt;
+                m.off2 = so1;
+                m.nout2 = decim_nout(m.nout, so1, v.d.stage_decim[1]);
+                outs = m.nout2;
+            }
+            m.min_idx = ((seen >= need) ? -need : -(int)seen) + prev_e;
+            m.shift = prev_e;
+            m.oshift = oshift;
+            if (outs > 0) { s1.push_back(m); }
+            so0 = so0 + m.nout * D - nj;
+            if (mem.fused) { so1 = so1 + m.nout2 * v.d.stage_decim[1] - m.nout; }
+            const double pj = ph + (double)nj * v.theta;
+            ph = pj - std::floor(pj);
+            seen += nj;
+            oshift += outs;
+            prev_e = c->grp_ends[j];
+        }
+        x.phi_end = ph;
+        x.have_phi_end = true;
+    }
+    // setOffset hand-over: outputs whose window still reaches in front of the latest retune point are recomputed with the
+    // piecewise phase (vfo_retune_fix_kernel); retune points no window can reach any more are forgotten
+    void retune_job(ChainCtx& x) {
+        Vfo& v = x.v;
+        const S1Member& mem = x.mem;
+        const int D1 = v.d.stage_decim[0], K0 = mem.K, Kc = v.h12_K;
+        const int off = mem.fused ? mem.off0 + (mem.off2 - (mem.K2 - 1)) * D1 - (K0 - 1) : mem.off0 - (K0 - 1);
+        const int nout_f = mem.fused ? mem.nout2 : mem.nout;
+        while (!v.recs.empty() && v.recs.front().pos - v.seen <= (long long)off) { v.recs.erase(v.recs.begin()); }
+        while (v.recs.size() > SDRPP_RETUNE_MAX_SEG - 1) { v.recs.erase(v.recs.begin()); }
+        if (v.recs.empty() || nout_f <= 0) { return; }
+        const long long r_last = v.recs.back().pos - v.seen;  // push-relative, <= 0
+        const long long Dc = 1ll << v.h12_lgD;
+        const int nfix = (int)std::min<long long>((long long)nout_f, (r_last - off + Dc - 1) / Dc);  // outputs m with off + m * Dc < r_last
+        if (nfix <= 0) { return; }
+        RetuneJob rj{};
+        rj.out = (float2*)v.st[(size_t)v.i_first + (mem.fused ? 1 : 0)].data;
+        rj.taps = v.d_h12;
+        rj.K = Kc;
+        rj.log2_decim = v.h12_lgD;
+        rj.off = off;
+        rj.nfix = nfix;
+        rj.min_idx = mem.min_idx;
+        const int nr = (int)v.recs.size();
+        rj.nseg = nr + 1;
+        // segment q >= 1 starts at retune point q - 1 and runs with the increment that was in effect from there on (the
+        // newest with the current one); segment 0 = everything in front of the oldest remembered point, anchored there.
+        // Phases are continuous across the points, evaluated backwards from the current phase.
+        double P = v.phi + v.theta * (double)r_last;  // phase at the newest point
+        for (int q = nr; q >= 1; q--) {
+            const long long Sq = v.recs[(size_t)q - 1].pos - v.seen;
+            rj.start[q] = (int)std::max<long long>(Sq, -2000000000ll);
+            rj.theta[q] = (q == nr) ? v.theta : v.recs[(size_t)q].theta_before;
+            rj.phi[q] = P - std::floor(P);
+            if (q >= 2) {  // phase at the start of the segment in front: back along ITS increment
+                const long long Sp = v.recs[(size_t)q - 2].pos - v.seen;
+                P = P + v.recs[(size_t)q - 1].theta_before * (double)(Sp - Sq);
             }
         }
-        // the FM back end as one pipelined launch (ordinary passes): last decimator, resampler, channel filter, discriminator + audio low-pass all
-        // in their matrix form, and the pipeline's LDS layout fits
+        rj.start[0] = rj.start[1];
+        rj.theta[0] = v.recs[0].theta_before;
+        rj.phi[0] = rj.phi[1];
+        retune.push_back(rj);
+    }
+    // the FM back end as one pipelined launch (ordinary passes): last decimator, resampler, channel filter, discriminator + audio low-pass all
+    // in their matrix form, and the pipeline's LDS layout fits
+    void pipe_decide(ChainCtx& x) {
+        Vfo& v = x.v;
         const int last_dec = v.d.n_stages - 1;
-        bool piped_be = c->pipe_on && !ticking && !ifc_on && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= first_sep && v.tp_stage[last_dec].ok &&
-                        v.i_poly >= 0 && v.tp_poly.ok && v.i_chan >= 0 && v.chan_ntaps > 0 && v.tp_chan.ok && v.tp_audio.ok;
-        PipeJob pj{};
-        size_t pj_lds = 0;
-        if (piped_be) {
-            pj.st[0] = toep_job(v.tp_stage[last_dec], 0, StreamIn{}, nullptr, 0, 0, 0.0f);
-            pj.st[1] = toep_job(v.tp_poly, 0, StreamIn{}, nullptr, 0, 0, 0.0f);
-            pj.st[2] = toep_job(v.tp_chan, 0, StreamIn{}, nullptr, 0, 0, 0.0f);
-            pj.st[3] = toep_job(v.tp_audio, 0, StreamIn{}, nullptr, 0, 0, 0.0f);
-            pj.timeouts = c->hd_tick_flag ? (int*)(c->hd_tick_flag + 8) : nullptr;
-            piped_be = pipe_layout(pj, &pj_lds);
+        x.piped = c->pipe_on && !ticking && !x.ifc_on && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= x.first_sep && v.tp_stage[last_dec].ok &&
+                  v.i_poly >= 0 && v.tp_poly.ok && v.i_chan >= 0 && v.chan_ntaps > 0 && v.tp_chan.ok && v.tp_audio.ok;
+        if (!x.piped) { return; }
+        x.pj = PipeJob{};
+        const ToepTab* tabs[4] = { &v.tp_stage[last_dec], &v.tp_poly, &v.tp_chan, &v.tp_audio };
+        for (int s = 0; s < 4; s++) { x.pj.st[s] = toep_job(*tabs[s], 0, StreamIn{}, nullptr, 0, 0, 0.0f); }  // (the layout needs the tables' geometry only)
+        x.pj.timeouts = c->hd_tick_flag ? (int*)(c->hd_tick_flag + 8) : nullptr;
+        x.piped = pipe_layout(x.pj, &x.pj_lds);
+    }
+    // the radio's IF chain: one level of its own between the IF stream (which stays RxVFO::out) and whatever follows — the demodulator's
+    // levels below move down by one for this VFO, and read the chain's buffer in place of the IF
+    void if_chain(ChainCtx& x) {
+        Vfo& v = x.v;
+        if (!x.ifc_on) {
+            if (v.i_ifc >= 0) { v.st[(size_t)v.i_ifc].n = 0; }
+            return;
         }
-        for (int s = first_sep; s < v.d.n_stages; s++) {
-            Stream* nxt = &v.st[(size_t)v.i_first + s];
-            const int Ds = v.d.stage_decim[s];
-            const int no = decim_nout(cur->n, v.soff[s], Ds);
-            if (need_bnd) { bounds_decim(bnd, v.soff[s], Ds); }
-            if (split) { bounds_decim(tk, v.soff[s], Ds); }
-            lvl++;
-            cur->clevel = lvl;
-            if (piped_be && s == last_dec) {
-                pj.st[0] = toep_job(v.tp_stage[s], 0, stream_in(*cur), nxt->data, v.soff[s] - (v.d.stage_ntaps[s] - 1), no, 0.0f);
-                pj.keep[0] = std::max(0, no - nxt->hist_len);
-                pj.dec_stage = s;
-                pj.lvl = lvl;
-            }
-            else if (v.tp_stage[s].ok) { t_dec.add(lvl, toep_job(v.tp_stage[s], 0, stream_in(*cur), nxt->data, v.soff[s] - (v.d.stage_ntaps[s] - 1), no, 0.0f)); }
-            else { f_dec.add(lvl, FirBJob{ stream_in(*cur), nxt->data, v.d_staps[s], v.d.stage_ntaps[s], ilog2(Ds), v.soff[s], no, v.s_kp[s] }); }
-            v.soff[s] = v.soff[s] + no * Ds - cur->n;
-            nxt->n = no;
-            nxt->wlevel = lvl;
-            cur = nxt;
+        const Stream& in = *x.at.cur;
+        Stream& fs = v.st[(size_t)v.i_ifc];
+        const bool per_block = v.ifc.sq_on && blocks;
+        ifc.add(x.at.lvl + 1, IfcJob{ (const float2*)in.data, (float2*)fs.data, v.ifc.d_amp, in.n, v.ifc.nb_on, v.ifc.nb_rate, 1.0f - v.ifc.nb_rate, v.ifc.nb_level, v.ifc.sq_on, v.ifc.sq_level,
+                                      per_block ? x.d_bnd : nullptr, per_block ? x.nbnd : 0 });
+        x.at.step(fs, in.n);
+        v.lvl_ifc = x.at.lvl;
+        v.lvl_out = x.at.lvl;
+    }
+    void demod_fm(ChainCtx& x) {
+        Vfo& v = x.v;
+        fir_step(x, v.st[(size_t)v.i_out], v.tp_audio, v.d_audio, v.audio_ntaps, v.audio_kp, v.d.inv_deviation, t_audio_fm, audio_fm, x.pipe(3));
+        if (x.piped) {
+            pipes.push_back(x.pj);
+            pipe_lds = std::max(pipe_lds, x.pj_lds);
         }
-        if (v.i_poly >= 0) {
-            Stream* nxt = &v.st[(size_t)v.i_poly];
-            const int no = poly_nout(cur->n, v.poff, v.pphase, v.d.interp, v.d.decim);
-            if (need_bnd) { bounds_poly(bnd, v.poff, v.pphase, v.d.interp, v.d.decim); }
-            if (split) { bounds_poly(tk, v.poff, v.pphase, v.d.interp, v.d.decim); }
-            lvl++;
-            cur->clevel = lvl;
-            if (piped_be) {
-                pj.st[1] = toep_job(v.tp_poly, v.pphase, stream_in(*cur), nxt->data, v.poff - (v.tpp - 1), no, 0.0f);
-                pj.keep[1] = std::max(0, no - nxt->hist_len);
-            }
-            else if (v.tp_poly.ok) { t_poly.add(lvl, toep_job(v.tp_poly, v.pphase, stream_in(*cur), nxt->data, v.poff - (v.tpp - 1), no, 0.0f)); }
-            else if (v.d_cyc) {
-                polyb[(v.cyc_lmax == 4 ? 0 : 1) + ((v.d.decim & 1) ? 2 : 0)].add(lvl, PolyBJob{ stream_in(*cur), (float2*)nxt->data, v.d_cyc + (size_t)v.pphase * v.cyc_rows * v.cyc_lmax, v.d.interp, v.d.decim,
-                                                                  v.tpp, v.poff, no, v.cyc_rows });
-            }
-            else {
-                poly.add(lvl, PolyJob{ stream_in(*cur), (float2*)nxt->data, v.d_bank, v.d.interp, v.d.decim, v.tpp, v.pphase, v.poff, no });
-            }
-            const long long A = (long long)v.pphase + (long long)no * v.d.decim;
-            v.pphase = (int)(A % v.d.interp);
-            v.poff = v.poff + (int)(A / v.d.interp) - cur->n;
-            nxt->n = no;
-            nxt->wlevel = lvl;
-            cur = nxt;
-        }
-        if (v.i_chan >= 0 && v.chan_ntaps > 0) {
-            Stream* nxt = &v.st[(size_t)v.i_chan];
-            lvl++;
-            cur->clevel = lvl;
-            if (piped_be) {
-                pj.st[2] = toep_job(v.tp_chan, 0, stream_in(*cur), nxt->data, -(v.chan_ntaps - 1), cur->n, 0.0f);
-                pj.keep[2] = 0;  // the IF stream is the RxVFO's output: all of it
-            }
-            else if (v.tp_chan.ok) { t_chan.add(lvl, toep_job(v.tp_chan, 0, stream_in(*cur), nxt->data, -(v.chan_ntaps - 1), cur->n, 0.0f)); }
-            else { chan.add(lvl, FirBJob{ stream_in(*cur), nxt->data, v.d_chan, v.chan_ntaps, 0, 0, cur->n, v.chan_kp }); }
-            nxt->n = cur->n;
-            nxt->wlevel = lvl;
-            cur = nxt;
-        }
-        v.i_if = (int)(cur - &v.st[0]);
-        v.lvl_if = lvl;
-        v.lvl_out = lvl;
-        const int nif = cur->n;
+        v.lvl_out = x.at.lvl;
+    }
+    // envelope (one level), AGC / DC loop (the next), then the audio filter on the real stream `dem`: the IF stream's consumers have no memory
+    void demod_am(ChainCtx& x) {
+        Vfo& v = x.v;
+        const Stream& in = *x.at.cur;
+        const int nif = in.n, lvl = x.at.lvl;
+        Stream& dem = v.st[(size_t)v.i_dem];
         AgcState* agc = (AgcState*)v.d_state;
         float* dc = (float*)(v.d_state + 2 * sizeof(AgcState));
-        const int* d_bnd = nullptr;
-        if (need_bnd) {
-            d_bnd = arena_push(c, bnd);
-            if (!d_bnd) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
-        }
-        const int nbnd = need_bnd ? (int)bnd.size() : 0;
-        if (ifc_on) {
-            // the radio's IF chain: one level of its own between the IF stream (which stays RxVFO::out) and whatever follows — the demodulator's
-            // levels below move down by one for this VFO, and read the chain's buffer in place of the IF
-            Stream& fs = v.st[(size_t)v.i_ifc];
-            lvl++;
-            cur->clevel = lvl;
-            ifc.add(lvl, IfcJob{ (const float2*)cur->data, (float2*)fs.data, v.ifc.d_amp, nif, v.ifc.nb_on, v.ifc.nb_rate, 1.0f - v.ifc.nb_rate, v.ifc.nb_level, v.ifc.sq_on, v.ifc.sq_level,
-                                 (v.ifc.sq_on && blocks) ? d_bnd : nullptr, (v.ifc.sq_on && blocks) ? nbnd : 0 });
-            fs.n = nif;
-            fs.wlevel = lvl;
-            cur = &fs;
-            v.lvl_ifc = lvl;
-            v.lvl_out = lvl;
-        }
-        else if (v.i_ifc >= 0) { v.st[(size_t)v.i_ifc].n = 0; }
-        if (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) {
-            Stream& out = v.st[(size_t)v.i_out];
-            lvl++;
-            cur->clevel = lvl;
-            if (piped_be) {
-                pj.st[3] = toep_job(v.tp_audio, 0, stream_in(*cur), out.data, -(v.audio_ntaps - 1), nif, v.d.inv_deviation);
-                pipes.push_back(pj);
-                pipe_lds = std::max(pipe_lds, pj_lds);
-            }
-            else if (v.tp_audio.ok) { t_audio_fm.add(lvl, toep_job(v.tp_audio, 0, stream_in(*cur), out.data, -(v.audio_ntaps - 1), nif, v.d.inv_deviation)); }
-            else { audio_fm.add(lvl, FirBJob{ stream_in(*cur), out.data, v.d_audio, v.audio_ntaps, 0, 0, nif, v.audio_kp, v.d.inv_deviation }); }
-            out.n = nif;
-            out.wlevel = lvl;
-            v.lvl_out = lvl;
-        }
-        else if (v.d.demod == SDRPP_DEMOD_AM) {
-            Stream& dem = v.st[(size_t)v.i_dem];
-            Stream& out = v.st[(size_t)v.i_out];
-            if (!v.d.am_carrier_agc) { pre.add(lvl + 1, PreJob{ 2, nif, (const float2*)cur->data, dem.data, 0.0, 0.0 }); }
-            seq.add(lvl + 2, SeqJob{ 2, nif, (const float2*)cur->data, dem.data, nullptr, agc, agc + 1, dc, v.d.dc_block_rate, v.d.am_carrier_agc, d_bnd, nbnd });
-            dem.n = nif;
-            dem.wlevel = lvl + 2;
-            lvl += 3;
-            dem.clevel = lvl;
-            if (v.tp_audio.ok) { t_audio.add(lvl, toep_job(v.tp_audio, 0, stream_in(dem), out.data, -(v.audio_ntaps - 1), nif, 0.0f)); }
-            else { audio.add(lvl, FirBJob{ stream_in(dem), out.data, v.d_audio, v.audio_ntaps, 0, 0, nif, v.audio_kp }); }
-            out.n = nif;
-            out.wlevel = lvl;
-            v.lvl_out = lvl;
-        }
-        else if (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_DSB) {
-            Stream& dem = v.st[(size_t)v.i_dem];
-            Stream& out = v.st[(size_t)v.i_out];
-            if (v.nco_exact) { ssbx_l.add(lvl + 1, SsbRotXJob{ (const float2*)cur->data, dem.data, v.d_rot + 1, v.d.ssb_phase_delta_re, v.d.ssb_phase_delta_im, d_bnd, nbnd }); }
-            else if (split) {  // a launch group: the second translation anchored push by push, like the first (its phase advances as block-by-block processing advances it)
-                int lo = 0;
-                for (size_t j = 0; j < tk.size(); j++) {
-                    const int nj = tk[j] - lo;
-                    if (nj > 0) { pre.add(lvl + 1, PreJob{ v.d.demod, nj, (const float2*)cur->data + lo, dem.data + (size_t)lo * (size_t)dem.width, v.theta2, v.phi2 }); }
-                    const double q2 = v.phi2 + (double)nj * v.theta2;
-                    v.phi2 = q2 - std::floor(q2);
-                    lo = tk[j];
-                }
-            }
-            else { pre.add(lvl + 1, PreJob{ v.d.demod, nif, (const float2*)cur->data, dem.data, v.theta2, v.phi2 }); }
-            seq.add(lvl + 2, SeqJob{ v.d.demod, nif, (const float2*)cur->data, dem.data, out.data, agc, agc + 1, dc, 0.0f, 0, d_bnd, nbnd });
-            lvl += 2;
-            dem.n = 0;  // scratch only
-            out.n = nif;
-            out.wlevel = lvl;
-            v.lvl_out = lvl;
-            if (!split || v.nco_exact) {
-                const double p2 = v.phi2 + (double)nif * v.theta2;
-                v.phi2 = p2 - std::floor(p2);
+        if (!v.d.am_carrier_agc) { pre.add(lvl + 1, PreJob{ 2, nif, (const float2*)in.data, dem.data, 0.0, 0.0 }); }
+        seq.add(lvl + 2, SeqJob{ 2, nif, (const float2*)in.data, dem.data, nullptr, agc, agc + 1, dc, v.d.dc_block_rate, v.d.am_carrier_agc, x.d_bnd, x.nbnd });
+        dem.n = nif;
+        dem.wlevel = lvl + 2;
+        x.at = ChainCursor{ &dem, lvl + 2 };
+        fir_step(x, v.st[(size_t)v.i_out], v.tp_audio, v.d_audio, v.audio_ntaps, v.audio_kp, 0.0f, t_audio, audio);
+        v.lvl_out = x.at.lvl;
+    }
+    // second translation (one level), AGC loop straight into the stereo output (the next); `dem` is scratch, no stream of the chain
+    void demod_ssb(ChainCtx& x) {
+        Vfo& v = x.v;
+        const Stream& in = *x.at.cur;
+        const int nif = in.n, lvl = x.at.lvl;
+        Stream& dem = v.st[(size_t)v.i_dem];
+        Stream& out = v.st[(size_t)v.i_out];
+        AgcState* agc = (AgcState*)v.d_state;
+        float* dc = (float*)(v.d_state + 2 * sizeof(AgcState));
+        if (v.nco_exact) { ssbx_l.add(lvl + 1, SsbRotXJob{ (const float2*)in.data, dem.data, v.d_rot + 1, v.d.ssb_phase_delta_re, v.d.ssb_phase_delta_im, x.d_bnd, x.nbnd }); }
+        else if (x.split) {  // a launch group: the second translation anchored push by push, like the first (its phase advances as block-by-block processing advances it)
+            int lo = 0;
+            for (size_t j = 0; j < v.tk_if.size(); j++) {
+                const int nj = v.tk_if[j] - lo;
+                if (nj > 0) { pre.add(lvl + 1, PreJob{ v.d.demod, nj, (const float2*)in.data + lo, dem.data + (size_t)lo * (size_t)dem.width, v.theta2, v.phi2 }); }
+                const double q2 = v.phi2 + (double)nj * v.theta2;
+                v.phi2 = q2 - std::floor(q2);
+                lo = v.tk_if[j];
             }
         }
-        if (v.af.on && v.i_out >= 0) {  // radio AF chain on the demodulator's stereo output
-            Vfo::Af& a = v.af;
-            Stream* acur = &v.st[(size_t)v.i_out];
-            if (split) { v.tk_af = tk; }
-            for (int s = 0; s < a.n_stages; s++) {
-                Stream* nxt = &v.st[(size_t)a.i_stage0 + s];
-                const int Ds = a.decim_s[s], K = (int)a.staps[s].size();
-                const int no = decim_nout(acur->n, a.soff[s], Ds);
-                if (split) { bounds_decim(v.tk_af, a.soff[s], Ds); }
-                lvl++;
-                acur->clevel = lvl;
-                if (a.tp_stage[s].ok) { t_af_dec.add(lvl, toep_job(a.tp_stage[s], 0, stream_in(*acur), nxt->data, a.soff[s] - (K - 1), no, 0.0f)); }
-                else { af_dec.add(lvl, FirBJob{ stream_in(*acur), nxt->data, a.d_staps[s], K, ilog2(Ds), a.soff[s], no, a.s_kp[s] }); }
-                a.soff[s] = a.soff[s] + no * Ds - acur->n;
-                nxt->n = no;
-                nxt->wlevel = lvl;
-                acur = nxt;
-            }
-            if (a.i_poly >= 0) {
-                Stream* nxt = &v.st[(size_t)a.i_poly];
-                const int no = poly_nout(acur->n, a.poff, a.pphase, a.interp, a.decim);
-                if (split) { bounds_poly(v.tk_af, a.poff, a.pphase, a.interp, a.decim); }
-                lvl++;
-                acur->clevel = lvl;
-                if (a.tp_poly.ok) { t_af_poly.add(lvl, toep_job(a.tp_poly, a.pphase, stream_in(*acur), nxt->data, a.poff - (a.tpp - 1), no, 0.0f)); }
-                else { af_poly.add(lvl, PolyJob{ stream_in(*acur), (float2*)nxt->data, a.d_bank, a.interp, a.decim, a.tpp, a.pphase, a.poff, no }); }
-                const long long A = (long long)a.pphase + (long long)no * a.decim;
-                a.pphase = (int)(A % a.interp);
-                a.poff = a.poff + (int)(A / a.interp) - acur->n;
-                nxt->n = no;
-                nxt->wlevel = lvl;
-                acur = nxt;
-            }
-            if (a.i_hpf >= 0) {
-                Stream* nxt = &v.st[(size_t)a.i_hpf];
-                const int K = (int)a.htaps.size();
-                lvl++;
-                acur->clevel = lvl;
-                if (a.tp_hpf.ok) { t_af_hpf.add(lvl, toep_job(a.tp_hpf, 0, stream_in(*acur), nxt->data, -(K - 1), acur->n, 0.0f)); }
-                else { af_hpf.add(lvl, FirBJob{ stream_in(*acur), nxt->data, a.d_hpf, K, 0, 0, acur->n, a.hpf_kp }); }
-                nxt->n = acur->n;
-                nxt->wlevel = lvl;
-                acur = nxt;
-            }
-            if (a.i_deemp >= 0) {
-                Stream* nxt = &v.st[(size_t)a.i_deemp];
-                lvl++;
-                const int nseg = std::min(a.seg_cap, (acur->n + SDRPP_DEEMP_SEG - 1) / SDRPP_DEEMP_SEG);
-                af_deemp.add(lvl, DeempJob{ (const float2*)acur->data, (float2*)nxt->data, acur->n, a.alpha, a.d_last + a.state_cur, a.d_last + (a.state_cur ^ 1),
-                                             a.d_seg + (size_t)a.state_cur * ((size_t)a.seg_cap + 1), nseg, 0 });
-                if (nseg > 0) { a.state_cur ^= 1; }  // (a block without audio leaves the state where it is)
-                nxt->n = acur->n;
-                lvl += 1;  // (the de-emphasis is two dependent launches: segment maps, then the outputs)
-                nxt->wlevel = lvl;
-                acur = nxt;
-            }
-            a.i_last = (int)(acur - &v.st[0]);
-            v.lvl_af = lvl;
+        else { pre.add(lvl + 1, PreJob{ v.d.demod, nif, (const float2*)in.data, dem.data, v.theta2, v.phi2 }); }
+        seq.add(lvl + 2, SeqJob{ v.d.demod, nif, (const float2*)in.data, dem.data, out.data, agc, agc + 1, dc, 0.0f, 0, x.d_bnd, x.nbnd });
+        x.at.lvl += 2;
+        dem.n = 0;  // scratch only
+        out.n = nif;
+        out.wlevel = x.at.lvl;
+        v.lvl_out = x.at.lvl;
+        if (!x.split || v.nco_exact) {
+            const double p2 = v.phi2 + (double)nif * v.theta2;
+            v.phi2 = p2 - std::floor(p2);
         }
-        if (have_phi_end) { v.phi = phi_end; }
+    }
+    // radio AF chain on the demodulator's stereo output
+    void af_chain(ChainCtx& x) {
+        Vfo& v = x.v;
+        Vfo::Af& a = v.af;
+        x.at.cur = &v.st[(size_t)v.i_out];
+        x.bnd.clear();  // (the reference's blocks end at the demodulator; the push ends go on, in a list of the AF chain's own)
+        if (x.split) { v.tk_af = v.tk_if; }
+        x.tk = &v.tk_af;
+        for (int s = 0; s < a.n_stages; s++) {
+            decim_step(x, v.st[(size_t)a.i_stage0 + s], a.tp_stage[s], a.d_staps[s], (int)a.staps[s].size(), a.decim_s[s], a.s_kp[s], a.soff[s], t_af_dec, af_dec);
+        }
+        if (a.i_poly >= 0) { poly_step(x, v.st[(size_t)a.i_poly], a.tp_poly, a.interp, a.decim, a.tpp, a.pphase, a.poff, a.d_bank, nullptr, 0, 0, t_af_poly, af_poly); }
+        if (a.i_hpf >= 0) { fir_step(x, v.st[(size_t)a.i_hpf], a.tp_hpf, a.d_hpf, (int)a.htaps.size(), a.hpf_kp, 0.0f, t_af_hpf, af_hpf); }
+        if (a.i_deemp >= 0) {
+            const Stream& in = *x.at.cur;
+            Stream& nxt = v.st[(size_t)a.i_deemp];
+            const int nseg = std::min(a.seg_cap, (in.n + SDRPP_DEEMP_SEG - 1) / SDRPP_DEEMP_SEG);
+            af_deemp.add(x.at.lvl + 1, DeempJob{ (const float2*)in.data, (float2*)nxt.data, in.n, a.alpha, a.d_last + a.state_cur, a.d_last + (a.state_cur ^ 1),
+                                                 a.d_seg + (size_t)a.state_cur * ((size_t)a.seg_cap + 1), nseg, 0 });
+            if (nseg > 0) { a.state_cur ^= 1; }  // (a block without audio leaves the state where it is)
+            nxt.n = in.n;
+            x.at.lvl += 2;  // (the de-emphasis is two dependent launches: segment maps, then the outputs; a recursion over the block, no window into the last one)
+            nxt.wlevel = x.at.lvl;
+            x.at.cur = &nxt;
+        }
+        a.i_last = (int)(x.at.cur - &v.st[0]);
+        v.lvl_af = x.at.lvl;
+    }
+    void phase_advance(ChainCtx& x) {
+        Vfo& v = x.v;
+        if (x.have_phi_end) { v.phi = x.phi_end; }
         else {
             const double p = v.phi + (double)n_in * v.theta;
             v.phi = p - std::floor(p);
         }
         v.seen += n_in;
-        // history carries for every stream that has a consumer with memory
+    }
+    // history carries for every stream that has a consumer with memory
+    void history_carries(ChainCtx& x) {
+        Vfo& v = x.v;
         const Stream* phantom = (v.fused_front && v.d.n_stages >= 2 && !v.nco_exact) ? &v.st[(size_t)v.i_first] : nullptr;  // stage-1 output of a fused front end: never written, never read
         for (auto& s : v.st) {
-            if (s.hist_len > 0 && s.data && &s != phantom && (ifc_on || v.i_ifc < 0 || &s != &v.st[(size_t)v.i_ifc])) {
+            if (s.hist_len > 0 && s.data && &s != phantom && (x.ifc_on || v.i_ifc < 0 || &s != &v.st[(size_t)v.i_ifc])) {
                 // pipelined: at the level of the consumer (its window of the NEXT block reads the new history one tick later, the carry of
                 // the next block overwrites the old one one tick later still); a stream nobody reads with memory (a consumer may be attached
                 // later: sdrpp_vfo_set_af, a taps change): one level behind the role that WRITES it — not behind the whole chain, which with
                 // an AF chain is up to a dozen levels later, when the stream's ring buffer (kRing = 4) already holds a later block
-                const int cl = !ticking ? carry_last : (s.clevel > 0 ? s.clevel : (s.wlevel > 0 ? s.wlevel + 1 : lvl + 1));
+                const int cl = !ticking ? carry_last : (s.clevel > 0 ? s.clevel : (s.wlevel > 0 ? s.wlevel + 1 : x.at.lvl + 1));
                 carry.add(cl, CarryJob{ s.data, s.hist[s.cur], s.hist[s.cur ^ 1], s.hist_len, s.n, s.width, s.hist_len });
             }
         }
-        c->plan_top = std::max(c->plan_top, lvl + 2);
+    }
+
+    // ---- front-end jobs: the tap operand on the device, the in-tile phasors, one function per path that builds a job and files it ----
+    static constexpr double kTwoPi = 2.0 * 3.14159265358979323846;
+    // NCO advance inside a tile: exp(j * 2 * pi * step * jj) for jj = 0 .. n - 1, written to out[jj * stride]
+    static void tile_phasors(float2* out, size_t stride, int n, double step) {
+        for (int jj = 0; jj < n; jj++) {
+            double tt = step * (double)jj;
+            tt -= std::rint(tt);
+            const double a = kTwoPi * tt;
+            out[(size_t)jj * stride] = make_float2((float)std::cos(a), (float)std::sin(a));
+        }
+    }
+    // Tap operand of a front-end job, cached on the device under its membership key: `fill` writes the n (zeroed) entries of a table that is
+    // not there yet.  The one place that owns the cache's policy, the upload and its synchronisation.
+    template <class Fill>
+    int front_taps(const std::string& key, size_t n, Fill&& fill, float2** d_taps) {
+        auto it = c->s1_tap_cache.find(key);
+        if (it != c->s1_tap_cache.end()) {
+            *d_taps = it->second;
+            return SDRPP_OK;
+        }
+        std::vector<float2> host(n, make_float2(0.0f, 0.0f));
+        fill(host);
+        if (c->s1_tap_cache.size() > 4096) {  // retune churn: drop everything (rare)
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            for (auto& e : c->s1_tap_cache) { (void)hipFree(e.second); }
+            c->s1_tap_cache.clear();
+        }
+        *d_taps = nullptr;
+        int rc = dev_alloc(c, d_taps, host.size());
+        if (rc) { return rc; }
+        HIPCHK(c, hipMemcpyAsync(*d_taps, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // `host` is pageable and goes out of scope
+        c->s1_tap_cache[key] = *d_taps;
+        return SDRPP_OK;
+    }
+    // composite matrix table of members m[0 .. vt) (h, K, NP4: add_matrix_job): [NP4][64] floats (= NP4 * 32 float2; rows >= NP are zero padding) followed by [32][TILE] float2
+    static void fill_composite(std::vector<float2>& host, const S1Member& h, bool m_long, int K, int NP4, const S1Member* m, int vt) {
+        const int D1 = 1 << h.lgD, NP = (K + 1) / 2;
+        float* at = reinterpret_cast<float*>(host.data());
+        std::vector<double> h12((size_t)K);
+        const double kc = 0.5 * (double)(K - 1);
+        for (int i = 0; i < vt; i++) {
+            const Vfo& vv = *m[i].v;
+            // composite taps h12 = h1 (*) upsample(h2, D1) in double precision (both are linear phase, so is h12)
+            std::fill(h12.begin(), h12.end(), 0.0);
+            for (int k2 = 0; k2 < h.K2; k2++) {
+                const double w2 = m_long ? 1.0 : (double)vv.staps[1][(size_t)k2];
+                for (int k1 = 0; k1 < h.K; k1++) { h12[(size_t)k2 * D1 + k1] += w2 * (double)vv.staps[0][(size_t)k1]; }
+            }
+            for (int pz = 0; pz < NP; pz++) {
+                double t = ((double)pz - kc) * vv.theta;  // modulation centred on the filter: g[K-1-k] = conj(g[k])
+                t -= std::rint(t);
+                const double a = kTwoPi * t;
+                double gr = h12[(size_t)pz] * std::cos(a), gi = h12[(size_t)pz] * std::sin(a);
+                if ((K & 1) && pz == NP - 1) { gr = h12[(size_t)pz]; gi = 0.0; }
+                at[(size_t)pz * 64 + i] = (float)gr;
+                at[(size_t)pz * 64 + 32 + i] = (float)-gi;
+            }
+        }
+        for (int i = 0; i < SDRPP_FCM_VT; i++) {
+            tile_phasors(&host[(size_t)NP4 * 32 + (size_t)i * SDRPP_FCM_TILE], 1, SDRPP_FCM_TILE, i < vt ? m[i].v->theta * (double)(1 << (h.lgD + h.lgD2)) : 0.0);
+        }
+    }
+    // VALU pair table of members m[0 .. vt): [tap pairs][vt] modulated taps followed by [256][vt] phasors
+    static void fill_pairs(std::vector<float2>& host, const S1Member* m, int vt) {
+        const int K = (m[0].K + 1) / 2;  // tap pairs
+        for (int k = 0; k < K; k++) {
+            for (int i = 0; i < vt; i++) { host[(size_t)k * vt + i] = m[i].v->modtaps[(size_t)k]; }
+        }
+        // NCO advance inside a 256-output tile: exp(j*2*pi*theta*D1*j) (fused front kernel)
+        for (int i = 0; i < vt; i++) { tile_phasors(&host[(size_t)K * vt + i], (size_t)vt, 256, m[i].v->theta * (double)(1 << m[0].lgD)); }
+    }
+    // what every front-end job says about its members m[0 .. vt), in n entries (the matrix kernels read all of theirs: the last member again)
+    template <class Job>
+    static void job_members(Job& job, const S1Member* m, int vt, int n, int stream) {
+        job.nv = vt;
+        job.min_idx = m[0].min_idx;
+        job.anchor = m[0].shift;
+        for (int i = 0; i < n; i++) {
+            const S1Member& mi = m[std::min(i, vt - 1)];
+            job.theta[i] = mi.v->theta;
+            job.phi0[i] = mi.phi0;  // phase (turns) of push-relative sample 0
+            job.out[i] = (float2*)mi.v->st[(size_t)mi.v->i_first + stream].data + m[0].oshift;
+        }
+    }
+    // One job of the matrix-core path for members m[0 .. vt): its FrontCMJob, built and filed in its launch.  The job's filter is the composite
+    // of stages 1 + 2, or a long first stage alone (m_pf: the prefetch depth frontcm_ok picked for a composite).
+    int add_matrix_job(const S1Member* m, int vt, bool m_long, int m_pf) {
+        S1Member h = m[0];  // the job's geometry (that of its first member)
+        if (m_long) { h.K2 = 1; h.lgD2 = 0; h.off2 = 0; h.nout2 = h.nout; }  // the "composite" is the first stage alone
+        const int D1 = 1 << h.lgD, K = h.K + (h.K2 - 1) * D1, lgD = h.lgD + h.lgD2;
+        const int NP4 = ((K + 1) / 2 + 31) / 32 * 32;  // rows of the tap operand table, zero padded (the kernels read whole rings: up to 32 rows — eight steps of four pairs — at a time)
+        float2* d_taps = nullptr;
+        int rc = front_taps(member_key(m_long ? 'L' : 'M', m, vt), (size_t)NP4 * 32 + (size_t)SDRPP_FCM_VT * SDRPP_FCM_TILE, [&](std::vector<float2>& host) { fill_composite(host, h, m_long, K, NP4, m, vt); }, &d_taps);
+        if (rc) { return rc; }
+        FrontCMJob job{};
+        job_members(job, m, vt, SDRPP_FCM_VT, m_long ? 0 : 1);
+        job.ntaps = K;
+        job.log2_decim = lgD;
+        job.off = h.off0 + (h.off2 - (h.K2 - 1)) * D1 - (h.K - 1) + h.shift;
+        job.nout = h.nout2;
+        // (a long first stage with at most 16 VFOs runs in the 16 x 16 x 4 shape: 16 outputs per tile, vfo_frontcl_impl<PF, true>)
+        const int tile_n = (m_long && vt <= 16) ? 16 : SDRPP_FCM_TILE;
+        const int ntiles = (h.nout2 + tile_n - 1) / tile_n;
+        // one resident round: 256 CUs x 3 blocks x 4 wavefronts (a second, partly filled round would cost as much as the first);
+        // the long-stage kernel runs 2 wavefronts per block, its LDS footprint decides how many blocks fit
+        const int long_blocks = m_long ? std::max(1, (int)((size_t)(160 * 1024) / ((size_t)frontcl_lds_floats(K, lgD, fcl_nw) * 4))) : 0;
+        // (a launch group brings one job per push: together they get the wavefronts one job of the whole block would)
+        const int nsub = std::max<int>(1, (int)c->grp_ends.size());
+        const int resident = std::max(64, (m_long ? 256 * long_blocks * fcl_nw : (ticking ? std::min(3072, c->tick_fcm_waves) : 3072)) / nsub);
+        job.tiles_per_wave = std::max(1, (ntiles + resident - 1) / resident);
+        if (c->front_walk_waves > 0) { job.tiles_per_wave = std::max(1, (ntiles + c->front_walk_waves - 1) / c->front_walk_waves); }
+        job.atab = reinterpret_cast<const float*>(d_taps);
+        job.ptab = d_taps + (size_t)NP4 * 32;
+        FCMLaunch& L = m_long ? fcl : fcm[m_pf == 6 ? 0 : (m_pf == 10 ? 1 : 2)];
+        const int waves = (m_long ? fcl_nw : 4) * job.tiles_per_wave;  // tiles a workgroup walks
+        L.jobs.push_back(job);
+        L.max_blocks = std::max(L.max_blocks, (ntiles + waves - 1) / waves);
+        L.lds = std::max(L.lds, m_long ? (size_t)frontcl_lds_floats(K, lgD, fcl_nw) * 4 : (size_t)frontcm_layout(K, lgD).total * 4);
+        return SDRPP_OK;
+    }
+    // One job of the VALU path for members m[0 .. vts[li]), built and filed in launch class li: a Front2Job (stages 1 + 2 fused) or a Stage1Job
+    int add_valu_job(const S1Member* m, int li) {
+        const int vt = vts[li];
+        const S1Member& h = m[0];
+        float2* d_taps = nullptr;  // tap array for this membership (cached on the device)
+        int rc = front_taps(member_key('V', m, vt), (size_t)((h.K + 1) / 2) * vt + (size_t)256 * vt, [&](std::vector<float2>& host) { fill_pairs(host, m, vt); }, &d_taps);
+        if (rc) { return rc; }
+        const int D1 = 1 << h.lgD;
+        if (h.fused) {
+            Front2Job job{};
+            job_members(job, m, vt, vt, 1);
+            job.ntaps1 = h.K;
+            job.log2_decim1 = h.lgD;
+            job.off1 = h.off0 + h.shift;
+            job.ntaps2 = h.K2;
+            job.log2_decim2 = h.lgD2;
+            job.off2 = h.off2;
+            job.nout2 = h.nout2;
+            job.t2 = front2_t2(h.K, D1, h.K2, 1 << h.lgD2, 8);
+            job.ctaps = d_taps;
+            job.ptab = d_taps + (size_t)((h.K + 1) / 2) * vt;
+            job.taps2 = h.v->d_staps_nat[1];
+            f2l[li].jobs.push_back(job);
+            f2l[li].max_blocks = std::max(f2l[li].max_blocks, (job.nout2 + job.t2 - 1) / job.t2);
+            f2l[li].lds = std::max(f2l[li].lds, (std::max((size_t)D1 * (256 + (h.K - 1 + D1 - 1) / D1 + 1), (size_t)vt * 272) + (size_t)vt) * sizeof(float2));
+            return SDRPP_OK;
+        }
+        Stage1Job job{};
+        job_members(job, m, vt, vt, 0);
+        job.ntaps = h.K;
+        job.log2_decim = h.lgD;
+        job.off0 = h.off0 + h.shift;
+        job.nout = h.nout;
+        job.ctaps = d_taps;
+        s1l[li].jobs.push_back(job);
+        s1l[li].max_nout = std::max(s1l[li].max_nout, job.nout);
+        const int tile = pick_tile(D1, h.K, 8);
+        if (tile == 0 && h.lgD < 5) { return fail(c, SDRPP_ERR_UNSUPPORTED, "stage-1 filter (decim %d, %d taps) does not fit in LDS", D1, h.K); }
+        if (tile > 0) { s1l[li].tile = std::min(s1l[li].tile, tile); }
         return SDRPP_OK;
     }
 
@@ -741,193 +935,17 @@ struct BankPlan {
             const size_t m_min = m_long ? 2 : 17;
             while (m_ok && j - g >= m_min) {
                 const int vt = (int)std::min<size_t>(j - g, SDRPP_FCM_VT);
-                S1Member h = s1[g];
-                if (m_long) {  // the "composite" is the first stage alone
-                    h.K2 = 1;
-                    h.lgD2 = 0;
-                    h.off2 = 0;
-                    h.nout2 = h.nout;
-                }
-                const int D1 = 1 << h.lgD;
-                const int K = h.K + (h.K2 - 1) * D1, lgD = h.lgD + h.lgD2;
-                const int NP = (K + 1) / 2, NP4 = (NP + 31) / 32 * 32;  // rows of the tap operand table, zero padded (the kernels read whole rings: up to 32 rows — eight steps of four pairs — at a time)
-                const std::string key = member_key(m_long ? 'L' : 'M', &s1[g], vt);
-                float2* d_taps = nullptr;
-                auto it = c->s1_tap_cache.find(key);
-                if (it != c->s1_tap_cache.end()) { d_taps = it->second; }
-                else {
-                    // [NP4][64] floats (= NP4 * 32 float2; rows >= NP are zero padding) followed by [32][TILE] float2
-                    std::vector<float2> host((size_t)NP4 * 32 + (size_t)SDRPP_FCM_VT * SDRPP_FCM_TILE, make_float2(0.0f, 0.0f));
-                    float* at = reinterpret_cast<float*>(host.data());
-                    std::vector<double> h12((size_t)K);
-                    const double kc = 0.5 * (double)(K - 1);
-                    for (int m = 0; m < vt; m++) {
-                        const Vfo& vv = *s1[g + m].v;
-                        // composite taps h12 = h1 (*) upsample(h2, D1) in double precision (both are linear phase, so is h12)
-                        std::fill(h12.begin(), h12.end(), 0.0);
-                        for (int k2 = 0; k2 < h.K2; k2++) {
-                            const double w2 = m_long ? 1.0 : (double)vv.staps[1][(size_t)k2];
-                            for (int k1 = 0; k1 < h.K; k1++) { h12[(size_t)k2 * D1 + k1] += w2 * (double)vv.staps[0][(size_t)k1]; }
-                        }
-                        for (int pz = 0; pz < NP; pz++) {
-                            double t = ((double)pz - kc) * vv.theta;  // modulation centred on the filter: g[K-1-k] = conj(g[k])
-                            t -= std::rint(t);
-                            const double a = 2.0 * 3.14159265358979323846 * t;
-                            double gr = h12[(size_t)pz] * std::cos(a), gi = h12[(size_t)pz] * std::sin(a);
-                            if ((K & 1) && pz == NP - 1) { gr = h12[(size_t)pz]; gi = 0.0; }
-                            at[(size_t)pz * 64 + m] = (float)gr;
-                            at[(size_t)pz * 64 + 32 + m] = (float)-gi;
-                        }
-                    }
-                    for (int m = 0; m < SDRPP_FCM_VT; m++) {
-                        const double step = m < vt ? s1[g + m].v->theta * (double)(1 << lgD) : 0.0;
-                        for (int jj = 0; jj < SDRPP_FCM_TILE; jj++) {
-                            double tt = step * (double)jj;
-                            tt -= std::rint(tt);
-                            const double a = 2.0 * 3.14159265358979323846 * tt;
-                            host[(size_t)NP4 * 32 + (size_t)m * SDRPP_FCM_TILE + jj] = make_float2((float)std::cos(a), (float)std::sin(a));
-                        }
-                    }
-                    if (c->s1_tap_cache.size() > 4096) {
-                        HIPCHK(c, hipStreamSynchronize(c->stream));
-                        for (auto& e : c->s1_tap_cache) { (void)hipFree(e.second); }
-                        c->s1_tap_cache.clear();
-                    }
-                    int rc = dev_alloc(c, &d_taps, host.size());
-                    if (rc) { return rc; }
-                    HIPCHK(c, hipMemcpyAsync(d_taps, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    c->s1_tap_cache[key] = d_taps;
-                }
-                FrontCMJob job{};
-                job.nv = vt;
-                job.ntaps = K;
-                job.log2_decim = lgD;
-                job.off = h.off0 + (h.off2 - (h.K2 - 1)) * D1 - (h.K - 1) + h.shift;
-                job.nout = h.nout2;
-                job.min_idx = h.min_idx;
-                job.anchor = h.shift;
-                // (a long first stage with at most 16 VFOs runs in the 16 x 16 x 4 shape: 16 outputs per tile, vfo_frontcl_impl<PF, true>)
-                const int tile_n = (m_long && vt <= 16) ? 16 : SDRPP_FCM_TILE;
-                const int ntiles = (h.nout2 + tile_n - 1) / tile_n;
-                // one resident round: 256 CUs x 3 blocks x 4 wavefronts (a second, partly filled round would cost as much as the first);
-                // the long-stage kernel runs 2 wavefronts per block, its LDS footprint decides how many blocks fit
-                const int long_blocks = m_long ? std::max(1, (int)((size_t)(160 * 1024) / ((size_t)frontcl_lds_floats(K, lgD, fcl_nw) * 4))) : 0;
-                // (a launch group brings one job per push: together they get the wavefronts one job of the whole block would)
-                const int nsub = std::max<int>(1, (int)c->grp_ends.size());
-                const int resident = std::max(64, (m_long ? 256 * long_blocks * fcl_nw : (c->tick_planning ? std::min(3072, c->tick_fcm_waves) : 3072)) / nsub);
-                job.tiles_per_wave = std::max(1, (ntiles + resident - 1) / resident);
-                if (c->front_walk_waves > 0) { job.tiles_per_wave = std::max(1, (ntiles + c->front_walk_waves - 1) / c->front_walk_waves); }
-                job.atab = reinterpret_cast<const float*>(d_taps);
-                job.ptab = d_taps + (size_t)NP4 * 32;
-                for (int m = 0; m < SDRPP_FCM_VT; m++) {
-                    Vfo* v = s1[g + std::min(m, vt - 1)].v;
-                    job.theta[m] = v->theta;
-                    job.phi0[m] = s1[g + std::min(m, vt - 1)].phi0;
-                    job.out[m] = (float2*)v->st[(size_t)v->i_first + (m_long ? 0 : 1)].data + h.oshift;
-                }
-                if (m_long) {
-                    fcl.jobs.push_back(job);
-                    fcl.max_blocks = std::max(fcl.max_blocks, (ntiles + fcl_nw * job.tiles_per_wave - 1) / (fcl_nw * job.tiles_per_wave));
-                    fcl.lds = std::max(fcl.lds, (size_t)frontcl_lds_floats(K, lgD, fcl_nw) * 4);
-                }
-                else {
-                    FCMLaunch& L = fcm[m_pf == 6 ? 0 : (m_pf == 10 ? 1 : 2)];
-                    L.jobs.push_back(job);
-                    L.max_blocks = std::max(L.max_blocks, (ntiles + 4 * job.tiles_per_wave - 1) / (4 * job.tiles_per_wave));
-                    L.lds = std::max(L.lds, (size_t)frontcm_layout(K, lgD).total * 4);
-                }
+                int rc = add_matrix_job(&s1[g], vt, m_long, m_pf);
+                if (rc) { return rc; }
                 g += (size_t)vt;
             }
             while (g < j) {
                 const size_t left = j - g;
                 int li = left >= 8 ? 0 : (left >= 4 ? 1 : (left >= 2 ? 2 : 3));
                 if (ticking) { li = 3; }  // (pipelined: one VFO per job — the forms that are roles of the tick kernel, TR_S1_1 / TR_S1D_1 / TR_F2_1; same sums per VFO)
-                const int vt = vts[li];
-                // tap array for this membership (cached on the device)
-                const std::string key = member_key('V', &s1[g], vt);
-                float2* d_taps = nullptr;
-                auto it = c->s1_tap_cache.find(key);
-                if (it != c->s1_tap_cache.end()) { d_taps = it->second; }
-                else {
-                    const int K = (s1[g].K + 1) / 2;  // tap pairs
-                    std::vector<float2> host((size_t)K * vt + (size_t)256 * vt);
-                    for (int k = 0; k < K; k++) {
-                        for (int m = 0; m < vt; m++) { host[(size_t)k * vt + m] = s1[g + m].v->modtaps[(size_t)k]; }
-                    }
-                    // NCO advance inside a 256-output tile: exp(j*2*pi*theta*D1*j) (fused front kernel)
-                    for (int m = 0; m < vt; m++) {
-                        const double step = s1[g + m].v->theta * (double)(1 << s1[g].lgD);
-                        for (int jj = 0; jj < 256; jj++) {
-                            double tt = step * (double)jj;
-                            tt -= std::rint(tt);
-                            const double a = 2.0 * 3.14159265358979323846 * tt;
-                            host[(size_t)K * vt + (size_t)jj * vt + m] = make_float2((float)std::cos(a), (float)std::sin(a));
-                        }
-                    }
-                    if (c->s1_tap_cache.size() > 4096) {  // retune churn: drop everything (rare)
-                        HIPCHK(c, hipStreamSynchronize(c->stream));
-                        for (auto& e : c->s1_tap_cache) { (void)hipFree(e.second); }
-                        c->s1_tap_cache.clear();
-                    }
-                    int rc = dev_alloc(c, &d_taps, host.size());
-                    if (rc) { return rc; }
-                    HIPCHK(c, hipMemcpyAsync(d_taps, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));  // `host` is pageable and goes out of scope
-                    c->s1_tap_cache[key] = d_taps;
-                }
-                const S1Member& h = s1[g];
-                if (h.fused) {
-                    Front2Job job{};
-                    job.nv = vt;
-                    job.ntaps1 = h.K;
-                    job.log2_decim1 = h.lgD;
-                    job.off1 = h.off0 + h.shift;
-                    job.ntaps2 = h.K2;
-                    job.log2_decim2 = h.lgD2;
-                    job.off2 = h.off2;
-                    job.nout2 = h.nout2;
-                    job.t2 = front2_t2(h.K, 1 << h.lgD, h.K2, 1 << h.lgD2, 8);
-                    job.min_idx = h.min_idx;
-                    job.anchor = h.shift;
-                    job.ctaps = d_taps;
-                    job.ptab = d_taps + (size_t)((h.K + 1) / 2) * vt;
-                    job.taps2 = h.v->d_staps_nat[1];
-                    for (int m = 0; m < vt; m++) {
-                        Vfo* v = s1[g + m].v;
-                        job.theta[m] = v->theta;
-                        job.phi0[m] = s1[g + m].phi0;
-                        job.out[m] = (float2*)v->st[(size_t)v->i_first + 1].data + h.oshift;
-                    }
-                    f2l[li].jobs.push_back(job);
-                    f2l[li].max_blocks = std::max(f2l[li].max_blocks, (job.nout2 + job.t2 - 1) / job.t2);
-                    const int D1 = 1 << h.lgD;
-                    f2l[li].lds = std::max(f2l[li].lds, (std::max((size_t)D1 * (256 + (h.K - 1 + D1 - 1) / D1 + 1), (size_t)vt * 272) + (size_t)vt) * sizeof(float2));
-                }
-                else {
-                    Stage1Job job{};
-                    job.nv = vt;
-                    job.ntaps = h.K;
-                    job.log2_decim = h.lgD;
-                    job.off0 = h.off0 + h.shift;
-                    job.nout = h.nout;
-                    job.min_idx = h.min_idx;
-                    job.anchor = h.shift;
-                    job.ctaps = d_taps;
-                    for (int m = 0; m < vt; m++) {
-                        Vfo* v = s1[g + m].v;
-                        job.theta[m] = v->theta;
-                        job.phi0[m] = s1[g + m].phi0;  // phase (turns) of push-relative sample 0
-                        job.out[m] = (float2*)v->st[(size_t)v->i_first].data + h.oshift;
-                    }
-                    s1l[li].jobs.push_back(job);
-                    s1l[li].max_nout = std::max(s1l[li].max_nout, job.nout);
-                    const int D = 1 << job.log2_decim;
-                    const int tile = pick_tile(D, job.ntaps, 8);
-                    if (tile == 0 && job.log2_decim < 5) { return fail(c, SDRPP_ERR_UNSUPPORTED, "stage-1 filter (decim %d, %d taps) does not fit in LDS", D, job.ntaps); }
-                    if (tile > 0) { s1l[li].tile = std::min(s1l[li].tile, tile); }
-                }
-                g += (size_t)vt;
+                int rc = add_valu_job(&s1[g], li);
+                if (rc) { return rc; }
+                g += (size_t)vts[li];
             }
             i = j;
         }
@@ -935,19 +953,19 @@ struct BankPlan {
     }
 
     // ---- job tables into the arena (one upload for the whole block) ----
+    // a table that is not a Lev<> list: false = it has jobs and they did not fit
+    template <class T>
+    bool push_table(const std::vector<T>& jobs, T*& dev) {
+        dev = arena_push(c, jobs);
+        return jobs.empty() || dev;
+    }
     int upload() {
         for (int k = 0; k < 4; k++) {
-            if (!s1l[k].jobs.empty()) {
-                for (auto& jb : s1l[k].jobs) { s1l[k].lds = std::max(s1l[k].lds, fir_lds(s1l[k].tile, 1 << jb.log2_decim, jb.ntaps, 8)); }
-                d_s1[k] = arena_push(c, s1l[k].jobs);
-                if (!d_s1[k]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
-            }
+            for (auto& jb : s1l[k].jobs) { s1l[k].lds = std::max(s1l[k].lds, fir_lds(s1l[k].tile, 1 << jb.log2_decim, jb.ntaps, 8)); }
+            if (!push_table(s1l[k].jobs, d_s1[k])) { return arena_fail(c); }
         }
         for (int k = 0; k < 4; k++) {
-            if (!f2l[k].jobs.empty()) {
-                d_f2[k] = arena_push(c, f2l[k].jobs);
-                if (!d_f2[k]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
-            }
+            if (!push_table(f2l[k].jobs, d_f2[k])) { return arena_fail(c); }
         }
         if (!fcl.jobs.empty()) {
             // Tiles per wavefront of the long first stages, chosen over ALL their jobs (round 5, profiles/r05h_fcl_tiles_per_wave*.log): a tile is
@@ -986,25 +1004,18 @@ struct BankPlan {
                 fcl.max_blocks = std::max(fcl.max_blocks, (ntiles + fcl_nw * tpw - 1) / (fcl_nw * tpw));
             }
         }
-        d_fcl = arena_push(c, fcl.jobs);
-        if (!fcl.jobs.empty() && !d_fcl) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
+        if (!push_table(fcl.jobs, d_fcl)) { return arena_fail(c); }
         for (int k = 0; k < 3; k++) {
-            if (!fcm[k].jobs.empty()) {
-                d_fcm[k] = arena_push(c, fcm[k].jobs);
-                if (!d_fcm[k]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
-            }
+            if (!push_table(fcm[k].jobs, d_fcm[k])) { return arena_fail(c); }
         }
-        d_rotx = arena_push(c, rotx);
-        d_retune = arena_push(c, retune);
-        d_rot = arena_push(c, rot);
+        if (!push_table(rotx, d_rotx) || !push_table(retune, d_retune) || !push_table(rot, d_rot)) { return arena_fail(c); }
         d_fb = (!rotx.empty()) ? arena_push(c, fb) : nullptr;
         d_rotx_head = nullptr;
-        if (!rotx.empty() && d_rotx && d_fb && c->tick_planning) {
+        if (!rotx.empty() && !d_fb) { return arena_fail(c); }
+        if (!rotx.empty() && ticking) {
             std::vector<RotXHead> head{ RotXHead{ d_rotx, d_fb, (int)rotx.size(), (int)fb.size(), c->rot_exact_vpw, 0 } };
-            d_rotx_head = arena_push(c, head);
-            if (!d_rotx_head) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
+            if (!push_table(head, d_rotx_head)) { return arena_fail(c); }
         }
-        if ((!rotx.empty() && (!d_rotx || !d_fb)) || (!retune.empty() && !d_retune) || (!rot.empty() && !d_rot)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
         // Pipelined back ends: ONE launch — or none, when this push is better served by the separate launches
         pipe_seg = pipe_segments(pipes, c->pipe_on, pipe_lds);
         if (!pipes.empty() && pipe_seg == 0) {  // not this push: the same four jobs go to the separate launches
@@ -1019,33 +1030,38 @@ struct BankPlan {
         if (!pipes.empty()) {
             for (auto& pj : pipes) { pipe_lvl = std::max(pipe_lvl, pj.lvl); }
             d_pipes = arena_push(c, pipes);
-            if (!d_pipes) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
+            if (!d_pipes) { return arena_fail(c); }
         }
-        for (int i = 0; i < kToepLists; i++) {
-            Lev<ToepJob>& L = *tlists[i].L;
-            for (int l = 0; l < L.top; l++) {
-                if (L.at[l].empty()) { continue; }
-                tplan[i][l] = toep_plan(L.at[l], tlists[i].npl, c->tick_planning ? std::min(2048, c->tick_toep_blocks) : 2048);
-                if (tplan[i][l].lds > (size_t)kMaxLds) { return fail(c, SDRPP_ERR_UNSUPPORTED, "matrix-core FIR window does not fit in LDS"); }
+        int rc = SDRPP_OK, i = 0;
+        for_each_list([&](auto& L) {
+            if constexpr (std::is_same_v<decltype(L), Lev<ToepJob>&>) {  // the registry's first kToepLists, in tlists[]' order: list i
+                // (the plan of a list sets its jobs' macro tiles per wavefront: before the jobs are copied into the arena)
+                for (int l = 0; l < L.top && !rc; l++) {
+                    if (L.at[l].empty()) { continue; }
+                    tplan[i][l] = toep_plan(L.at[l], tlists[i].npl, ticking ? std::min(2048, c->tick_toep_blocks) : 2048);
+                    if (tplan[i][l].lds > (size_t)kMaxLds) { rc = fail(c, SDRPP_ERR_UNSUPPORTED, "matrix-core FIR window does not fit in LDS"); }
+                }
+                i++;
             }
-            if (!arena_push_lev(c, L)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
-        }
-        if (!arena_push_lev(c, f_dec) || !arena_push_lev(c, poly) || !arena_push_lev(c, polyb[0]) || !arena_push_lev(c, polyb[1]) || !arena_push_lev(c, polyb[2]) ||
-            !arena_push_lev(c, polyb[3]) || !arena_push_lev(c, chan) || !arena_push_lev(c, seq) || !arena_push_lev(c, ifc) || !arena_push_lev(c, pre) || !arena_push_lev(c, audio) ||
-            !arena_push_lev(c, audio_fm) || !arena_push_lev(c, af_dec) || !arena_push_lev(c, af_hpf) || !arena_push_lev(c, af_poly) || !arena_push_lev(c, af_deemp) ||
-            !arena_push_lev(c, ssbx_l) || !arena_push_lev(c, carry)) {
-            return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted");
-        }
-        int rc;
-        {
-            HostScope hs("arena_commit (H2D)");
-            rc = arena_commit(c);
-        }
+            if (!rc && !arena_push_lev(c, L)) { rc = arena_fail(c); }
+        });
         if (rc) { return rc; }
-        return SDRPP_OK;
+        if (i != kToepLists) { return fail(c, SDRPP_ERR_INVALID, "for_each_list: %d matrix-core lists, tlists[] has %d rows", i, kToepLists); }
+        HostScope hs("arena_commit (H2D)");
+        return arena_commit(c);
     }
 
     // ---- level 1: the front end ----
+    // f(std::integral_constant<int, VT>) for the VFOs per work-item of a VALU launch class (vts[]): its kernels take them as a template argument
+    template <class F>
+    static void with_vt(int vt, F&& f) {
+        switch (vt) {
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 1>{}); break;
+        }
+    }
     int emit_front() {
         {
             FamilyTimer t(c, F_S1);
@@ -1054,7 +1070,7 @@ struct BankPlan {
                     count_form(c, PF_ROTX_1);
                     launch(c, vfo_rotate_exact_kernel, dim3(((unsigned)rotx.size() + 63) / 64), dim3(64), (size_t)64 * 65 * sizeof(float2), src, (const RotXJob*)d_rotx, (int)rotx.size(), d_fb, (int)fb.size());
                 }
-                else if (c->tick_planning) {  // pipelined: the chain as a role of the tick (level 1: its VFOs' first stages follow at level 2)
+                else if (ticking) {  // pipelined: the chain as a role of the tick (level 1: its VFOs' first stages follow at level 2)
                     emit(c, L0 + 1, F_S1, TR_ROTX16, ((int)rotx.size() + c->rot_exact_vpw - 1) / c->rot_exact_vpw, 1, SDRPP_ROTX4_LDS_BYTES, d_rotx_head, &src);
                 }
                 else {
@@ -1069,37 +1085,27 @@ struct BankPlan {
                 bool direct = true;  // every job of the class decimates by >= 32: stream from global memory, no LDS tile
                 for (auto& jb : s1l[k].jobs) { direct = direct && jb.log2_decim >= 5; }
                 if (direct) {
-                    if (c->tick_planning && s1l[k].vt == 1) {
+                    if (ticking && s1l[k].vt == 1) {
                         emit(c, L0 + 1, F_S1, TR_S1D_1, (s1l[k].max_nout + 255) / 256, (int)s1l[k].jobs.size(), 0, d_s1[k], &src);
                         continue;
                     }
                     const dim3 grid((s1l[k].max_nout + 255) / 256, (unsigned)s1l[k].jobs.size());
                     count_form(c, s1l[k].vt == 8 ? (int)PF_S1D_8 : (s1l[k].vt == 4 ? (int)PF_S1D_4 : (s1l[k].vt == 2 ? (int)PF_S1D_2 : (int)TR_S1D_1)));
-                    switch (s1l[k].vt) {
-                    case 8: launch(c, vfo_stage1_direct_kernel<8>, grid, dim3(256), 0, src, (const Stage1Job*)d_s1[k]); break;
-                    case 4: launch(c, vfo_stage1_direct_kernel<4>, grid, dim3(256), 0, src, (const Stage1Job*)d_s1[k]); break;
-                    case 2: launch(c, vfo_stage1_direct_kernel<2>, grid, dim3(256), 0, src, (const Stage1Job*)d_s1[k]); break;
-                    default: launch(c, vfo_stage1_direct_kernel<1>, grid, dim3(256), 0, src, (const Stage1Job*)d_s1[k]); break;
-                    }
+                    with_vt(s1l[k].vt, [&](auto vt) { launch(c, vfo_stage1_direct_kernel<decltype(vt)::value>, grid, dim3(256), 0, src, (const Stage1Job*)d_s1[k]); });
                     continue;
                 }
-                if (c->tick_planning && s1l[k].vt == 1) {
+                if (ticking && s1l[k].vt == 1) {
                     emit(c, L0 + 1, F_S1, TR_S1_1, (s1l[k].max_nout + s1l[k].tile - 1) / s1l[k].tile, (int)s1l[k].jobs.size(), s1l[k].lds, d_s1[k], &src, s1l[k].tile);
                     continue;
                 }
                 const dim3 grid((s1l[k].max_nout + s1l[k].tile - 1) / s1l[k].tile, (unsigned)s1l[k].jobs.size());
                 const dim3 block(s1l[k].tile);
                 count_form(c, s1l[k].vt == 8 ? (int)PF_S1_8 : (s1l[k].vt == 4 ? (int)PF_S1_4 : (s1l[k].vt == 2 ? (int)PF_S1_2 : (int)TR_S1_1)));
-                switch (s1l[k].vt) {
-                case 8: launch(c, vfo_stage1_kernel<8>, grid, block, s1l[k].lds, src, (const Stage1Job*)d_s1[k]); break;
-                case 4: launch(c, vfo_stage1_kernel<4>, grid, block, s1l[k].lds, src, (const Stage1Job*)d_s1[k]); break;
-                case 2: launch(c, vfo_stage1_kernel<2>, grid, block, s1l[k].lds, src, (const Stage1Job*)d_s1[k]); break;
-                default: launch(c, vfo_stage1_kernel<1>, grid, block, s1l[k].lds, src, (const Stage1Job*)d_s1[k]); break;
-                }
+                with_vt(s1l[k].vt, [&](auto vt) { launch(c, vfo_stage1_kernel<decltype(vt)::value>, grid, block, s1l[k].lds, src, (const Stage1Job*)d_s1[k]); });
             }
             for (int k = 0; k < 4; k++) {
                 if (f2l[k].jobs.empty() || f2l[k].max_blocks == 0) { continue; }
-                if (c->tick_planning && f2l[k].vt == 1) {
+                if (ticking && f2l[k].vt == 1) {
                     emit(c, L0 + 1, F_S1, TR_F2_1, f2l[k].max_blocks, (int)f2l[k].jobs.size(), f2l[k].lds, d_f2[k], &src);
                     continue;
                 }
@@ -1110,15 +1116,8 @@ struct BankPlan {
                 bool all_44_3 = true;
                 for (auto& jb : f2l[k].jobs) { all_44_3 = all_44_3 && jb.ntaps1 == 44 && jb.log2_decim1 == 3; }
                 count_form(c, f2l[k].vt == 8 ? (int)(all_44_3 ? PF_F2_8_44_3 : PF_F2_8) : (f2l[k].vt == 4 ? (int)PF_F2_4 : (f2l[k].vt == 2 ? (int)PF_F2_2 : (int)TR_F2_1)));
-                switch (f2l[k].vt) {
-                case 8:
-                    if (all_44_3) { launch(c, vfo_front2_kernel<8, 44, 3>, grid, block, f2l[k].lds, src, (const Front2Job*)d_f2[k]); }
-                    else { launch(c, vfo_front2_kernel<8, 0, 0>, grid, block, f2l[k].lds, src, (const Front2Job*)d_f2[k]); }
-                    break;
-                case 4: launch(c, vfo_front2_kernel<4, 0, 0>, grid, block, f2l[k].lds, src, (const Front2Job*)d_f2[k]); break;
-                case 2: launch(c, vfo_front2_kernel<2, 0, 0>, grid, block, f2l[k].lds, src, (const Front2Job*)d_f2[k]); break;
-                default: launch(c, vfo_front2_kernel<1, 0, 0>, grid, block, f2l[k].lds, src, (const Front2Job*)d_f2[k]); break;
-                }
+                if (f2l[k].vt == 8 && all_44_3) { launch(c, vfo_front2_kernel<8, 44, 3>, grid, block, f2l[k].lds, src, (const Front2Job*)d_f2[k]); }
+                else { with_vt(f2l[k].vt, [&](auto vt) { launch(c, vfo_front2_kernel<decltype(vt)::value, 0, 0>, grid, block, f2l[k].lds, src, (const Front2Job*)d_f2[k]); }); }
             }
             for (int k = 0; k < 3; k++) {
                 if (fcm[k].jobs.empty() || fcm[k].max_blocks == 0) { continue; }
@@ -1133,7 +1132,7 @@ struct BankPlan {
                     max_tiles = std::max(max_tiles, (jb.nout + SDRPP_FCM_TILE - 1) / SDRPP_FCM_TILE);
                     one_tile = one_tile && jb.tiles_per_wave == 1;
                 }
-                const int small_limit = c->fcm16_max_tiles >= 0 ? c->fcm16_max_tiles : ((c->tick_planning && c->plan_block_from_host) ? 0 : 256);
+                const int small_limit = c->fcm16_max_tiles >= 0 ? c->fcm16_max_tiles : ((ticking && c->plan_block_from_host) ? 0 : 256);
                 if (role == TR_FCM_132_4 && one_tile && max_tiles > 0 && max_tiles <= small_limit) {
                     if (getenv("SDRPP_TICK_DEBUG")) { fprintf(stderr, "[sdrpp] front end in its small-block shape: %d tiles x %zu jobs\n", max_tiles, fcm[k].jobs.size()); }
                     emit(c, L0 + 1, F_S1, TR_FCM16_132_4, max_tiles, (int)fcm[k].jobs.size(), (size_t)frontcm16_layout(132, 4).total * 4, d_fcm[k], &src);
@@ -1181,7 +1180,7 @@ struct BankPlan {
             if (threads == 0) {
                 for (auto& jb : jobs) { max_nout = std::max(max_nout, jb.nout); }
                 if (max_nout > 0) {
-                    if (c->tick_planning) { emit(c, level, fam, TR_FIRD, std::min((max_nout + 255) / 256, 1024), (int)jobs.size(), 0, d_jobs); }
+                    if (ticking) { emit(c, level, fam, TR_FIRD, std::min((max_nout + 255) / 256, 1024), (int)jobs.size(), 0, d_jobs); }
                     else {
                         count_form(c, TR_FIRD);
                         launch(c, vfo_fir_direct_kernel<false>, dim3((unsigned)std::min((max_nout + 255) / 256, 1024), (unsigned)jobs.size()), dim3(256), 0, (const FirBJob*)d_jobs);
@@ -1240,7 +1239,7 @@ struct BankPlan {
                 lds = std::max(lds, ns * sizeof(float2));
             }
             if (lds > (size_t)kMaxLds) { return fail(c, SDRPP_ERR_UNSUPPORTED, "polyphase tile does not fit in LDS"); }
-            if (c->tick_planning) { emit(c, level, fam, TR_POLY, (max_nout + tile - 1) / tile, (int)jobs.size(), lds, d_jobs); }
+            if (ticking) { emit(c, level, fam, TR_POLY, (max_nout + tile - 1) / tile, (int)jobs.size(), lds, d_jobs); }
             else {
                 count_form(c, TR_POLY);
                 launch(c, vfo_poly_kernel, dim3((max_nout + tile - 1) / tile, (unsigned)jobs.size()), dim3(tile), lds, (const PolyJob*)d_jobs);
@@ -1310,9 +1309,8 @@ struct BankPlan {
     // ---- levels 2 ...: everything behind the front end, level by level (within a level the launches are independent of each other) ----
     int emit_levels() {
         int rc = SDRPP_OK;
-        int top = std::max({ t_dec.top, t_poly.top, t_chan.top, t_audio.top, t_audio_fm.top, t_af_dec.top, t_af_poly.top, t_af_hpf.top, f_dec.top, poly.top,
-                             polyb[0].top, polyb[1].top, polyb[2].top, polyb[3].top, chan.top, seq.top, ifc.top, pre.top, audio.top, audio_fm.top, af_dec.top, af_hpf.top,
-                             af_poly.top, af_deemp.top, ssbx_l.top, carry.top, d_pipes ? pipe_lvl + 1 : 0 });
+        int top = d_pipes ? pipe_lvl + 1 : 0;
+        for_each_list([&](auto& L) { top = std::max(top, L.top); });
         for (int l = 1; l < top; l++) {
             {
                 FamilyTimer t(c, F_DECIM);
@@ -1358,7 +1356,7 @@ struct BankPlan {
                 FamilyTimer t(c, F_DEMOD);
                 if (l < ssbx_l.top && !ssbx_l.at[l].empty()) {
                     const int nj = (int)ssbx_l.at[l].size();
-                    if (c->tick_planning) { emit(c, l, F_DEMOD, TR_SSBX, (nj + 3) / 4, 1, 0, ssbx_l.dev[l], nullptr, nj); }
+                    if (ticking) { emit(c, l, F_DEMOD, TR_SSBX, (nj + 3) / 4, 1, 0, ssbx_l.dev[l], nullptr, nj); }
                     else {
                         count_form(c, TR_SSBX);
                         launch(c, vfo_ssb_rotate_exact_kernel, dim3((unsigned)nj), dim3(64), 0, (const SsbRotXJob*)ssbx_l.dev[l]);
