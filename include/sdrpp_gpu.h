@@ -209,7 +209,7 @@ int sdrpp_vfo_count(sdrpp_ctx* ctx);
  *   keep & 2: the demodulator behind it lives on (setInSamplerate: the radio's demodulator block is not touched): discriminator and audio low-pass
  *             history, AGC / DC-blocker state, SSB's second translation.  Only where the new description has the same demodulator; a demodulator
  *             SWITCH creates a new demodulator object in the reference too: leave the bit off.
- *   keep & 4: the IF chain (sdrpp_vfo_set_if) moves to the new handle with its parameters and the blanker's amplitude estimate: the radio module's
+ *   keep & 4: the IF chain (sdrpp_vfo_set_if, sdrpp_vfo_set_fmnr) moves to the new handle with its parameters, the blanker's amplitude estimate and FMIF's delay line: the radio module's
  *             IF-chain blocks are not the demodulator's and outlive a demodulator switch (radio_module.h:84-96).  Without the bit the new handle has no chain.
  * An AF chain (sdrpp_vfo_set_af) is not carried over: attach it to the new handle (it starts cleared, as afChain's blocks do after a restart). */
 int sdrpp_vfo_replace(sdrpp_ctx* ctx, int old_id, const sdrpp_vfo_desc* desc, int keep, int* new_id);
@@ -273,7 +273,8 @@ int sdrpp_abi_sizeof_af_desc(void);
  * Calling it on a VFO that has a chain changes the parameters and keeps amp (setRate / setLevel keep it); a blanker switched from off to
  * on starts at amp = 1.  desc == NULL detaches.  With both blocks disabled, or without a chain, nothing is planned for it: every path is
  * what it is without this call.  VFOs with an active chain do not take part in the one-launch FM back end (sdrpp_set_backend_pipeline).
- * Not covered: FMIF (the FFT-based IF noise reduction, third block of the reference's IF chain) and the AF-side CTCSS squelch. */
+ * FMIF, the third block of the reference's chain, has a call of its own (sdrpp_vfo_set_fmnr below); sdrpp_vfo_set_if leaves it alone.
+ * Not covered: the AF-side CTCSS squelch. */
 typedef struct sdrpp_if_desc {
     int nb_enabled;
     float nb_rate, nb_level;
@@ -285,6 +286,24 @@ int sdrpp_vfo_ifc_count(sdrpp_ctx* ctx, int id);
 int sdrpp_vfo_ifc_read(sdrpp_ctx* ctx, int id, float* dst_host, int max);
 int sdrpp_vfo_ifc_device_buffer(sdrpp_ctx* ctx, int id, const float** out, int* n_out);
 int sdrpp_abi_sizeof_if_desc(void);
+/* FMIF, the radio's "IF Noise Reduction" (dsp/noise_reduction/fm_if.h:45-77), the LAST block of the chain: blanker -> squelch -> FMIF ->
+ * demodulator.  For every IF sample i, with N = bins and the window w[n] = (float)nuttall(n, N - 1):
+ *     X_i[k] = sum_n w[n] * x[i - (N-1) + n] * e^{-j 2 pi k n / N},   idx = first k of maximal sqrtf(re^2 + im^2),
+ *     out[i] = X_i[idx] * e^{+j 2 pi idx (N / 2) / N}    (integer N / 2: what the un-normalised backward DFT of that single bin holds at index N / 2)
+ * The radio module's presets are 9, 15, 31 and 32 bins (radio_module.h:31-36); any bins in 2 .. 32 is taken (more: SDRPP_ERR_UNSUPPORTED).
+ * It reads the blanker / squelch output while one of them runs, else RxVFO::out, and writes the chain's output (which = 3, sdrpp_vfo_ifc_*, a
+ * RAW VFO's `out`; the demodulator reads it).  A chain that consists of FMIF alone is an active chain.
+ * State: the delay line of N - 1 samples, zero at the start.  Changing `bins` clears it (setBins); enabled = 0 only unplugs the block — the bin
+ * count is recorded, nothing runs, and switching it on again with the same bins continues from the delay line as it was left; sdrpp_vfo_reset
+ * clears it; sdrpp_vfo_replace with keep & 4 moves bins, the switch and the delay line to the new handle with the rest of the chain.
+ * Numerics: the reference links whatever libfftw3f is installed, so (as for the waterfall branch) "the reference" is its control flow around an
+ * EXACT DFT.  Here window, DFT and output twiddle are one matrix designed in double and rounded to float, applied on the FP32 matrix cores: an
+ * output is within 1e-5 * sum_n w[n] * |x[i - (N-1) + n]| of that definition (each part a sum of 2 N products of float-rounded factors:
+ * (2 N + 2) * 2^-24 * sqrt(2) = 5.6e-6 at N = 32; measured on an MI355X over the streams of tests/test_fmif.py: at most 4.2e-7).  Among bins of EQUAL float magnitude the lowest wins, as in the reference; where the two
+ * largest magnitudes differ by less than the rounding of either (a few samples per thousand on FM signals, and the first windows after a
+ * cleared delay line, where every bin is equal) the neighbouring bin may win, and the output then is that bin's value.
+ * The results do not depend on how the stream is cut into pushes, launch groups or pipelined blocks. */
+int sdrpp_vfo_set_fmnr(sdrpp_ctx* ctx, int id, int enabled, int bins);
 
 /* ---- sink-side sample packing: float -> int16 / int8 on the device, before the copy to the host -----------------
  * `which`: 0 = what sdrpp_vfo_read returns (demodulator output, or the IF in RAW mode), 1 = the complex IF (RxVFO::out), 2 = the AF

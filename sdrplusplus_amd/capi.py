@@ -175,6 +175,7 @@ def load():
     if L.sdrpp_abi_sizeof_if_desc() != C.sizeof(IfDesc):
         raise ImportError("sdrpp_if_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_if_desc(), C.sizeof(IfDesc)))
     L.sdrpp_vfo_set_if.argtypes = [vp, C.c_int, C.POINTER(IfDesc)]
+    L.sdrpp_vfo_set_fmnr.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.sdrpp_vfo_ifc_count.argtypes = [vp, C.c_int]
     L.sdrpp_vfo_ifc_read.argtypes = [vp, C.c_int, c_float_p, C.c_int]
     L.sdrpp_vfo_ifc_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), c_int_p]
@@ -267,7 +268,7 @@ EXPORTED_SYMBOLS = [
     "sdrpp_wf_configure", "sdrpp_wf_set_smoothing", "sdrpp_wf_set_hold", "sdrpp_wf_latest", "sdrpp_wf_raster", "sdrpp_wf_signal_info",
     "sdrpp_preproc_configure", "sdrpp_preproc_reconfigure", "sdrpp_preproc_set_reference_order", "sdrpp_preproc_out_count", "sdrpp_preproc_read", "sdrpp_preproc_device_buffer",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
-    "sdrpp_vfo_set_if", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
+    "sdrpp_vfo_set_if", "sdrpp_vfo_set_fmnr", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
     "sdrpp_fft_configure", "sdrpp_fft_disable", "sdrpp_fft_set_view", "sdrpp_fft_lines", "sdrpp_fft_read", "sdrpp_fft_copy_device", "sdrpp_fft_device_buffers",
     "sdrpp_vfo_add", "sdrpp_vfo_remove", "sdrpp_vfo_replace", "sdrpp_vfo_count", "sdrpp_vfo_set_phase_delta", "sdrpp_vfo_set_channel_taps", "sdrpp_vfo_reset",
     "sdrpp_vfo_out_count", "sdrpp_vfo_read", "sdrpp_vfo_device_buffers",
@@ -456,7 +457,7 @@ class Context:
 
     def vfo_replace(self, vid, desc, keep, keepalive=()):
         """sdrpp_vfo_replace: RxVFO::setInSamplerate / setOutSamplerate — a new description, the RxVFO's own state (keep & 1) and the demodulator's
-        (keep & 2) carried over as the reference's objects carry it; keep & 4 moves the IF chain (sdrpp_vfo_set_if) and its state along.  Returns the new handle."""
+        (keep & 2) carried over as the reference's objects carry it; keep & 4 moves the IF chain (sdrpp_vfo_set_if, sdrpp_vfo_set_fmnr) and its state along.  Returns the new handle."""
         nid = C.c_int()
         self._chk(self.L.sdrpp_vfo_replace(self.h, vid, C.byref(desc), int(keep), C.byref(nid)))
         del keepalive
@@ -589,6 +590,11 @@ class Context:
         """Attach (or, with None, detach) the radio IF chain: noise blanker -> power squelch in front of the demodulator (sdrpp_vfo_set_if).
         On a VFO that already has one the parameters change and the blanker's amplitude estimate is kept."""
         self._chk(self.L.sdrpp_vfo_set_if(self.h, vid, C.byref(if_desc) if if_desc is not None else None))
+
+    def vfo_set_fmnr(self, vid, enabled, bins=32):
+        """FMIF, the radio's "IF Noise Reduction", as the last block of the IF chain (sdrpp_vfo_set_fmnr): `bins` in 2 .. 32 (radio.IFNR_BINS).
+        A change of `bins` clears its delay line; enabled = False only unplugs it."""
+        self._chk(self.L.sdrpp_vfo_set_fmnr(self.h, vid, int(bool(enabled)), int(bins)))
 
     def vfo_ifc_count(self, vid):
         return self._chk(self.L.sdrpp_vfo_ifc_count(self.h, vid))

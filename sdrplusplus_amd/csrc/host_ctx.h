@@ -13,6 +13,8 @@ constexpr int kGroupMax = SDRPP_GROUP_MAX;          // pipelined mode: blocks on
 constexpr int kResMeta = kResSlots * kGroupMax;     // ... and what the host knows about every block of those groups (ring by ticket)
 constexpr int kStageSlots = 4;      // pipelined mode: page-locked staging buffers for pushes from pageable host memory
 constexpr int kChanHistCap = 4095;  // channel filter may be re-designed up to 4096 taps without reallocating (rx_vfo.h:60-70)
+constexpr int kFmifTile = SDRPP_FMIF_TILE;       // FMIF: outputs per matrix tile = the largest bin count (radio_module.h:31-36); its input stream remembers kFmifTile - 1 samples
+constexpr int kFmifSeg = SDRPP_FMIF_SEG;       // ... and samples per segment job (one wavefront each): the cut depends on the block alone, never on the launch shape
 constexpr size_t kScratchBytes = 64u << 20;
 constexpr int kMaxLds = 64 * 1024;
 
@@ -80,14 +82,20 @@ struct Vfo {
     std::vector<Stream> st;
     int i_first = 0, i_poly = -1, i_chan = -1, i_dem = -1, i_out = -1, i_if = 0;
     int i_ifc = -1;  // the IF chain's output stream: a slot of `st` from the start, its buffers allocated when a chain is first attached (sdrpp_vfo_set_if)
+    int i_fmi = -1;  // what FMIF reads while the blanker / squelch run in front of it (their output): a slot like i_ifc, allocated with the first such chain
     int lvl_if = 1, lvl_out = 1, lvl_af = 1, lvl_ifc = 1;  // levels (do_vfos_plan) at which the IF stream / the demodulator's output / the AF chain's output / the IF chain's output of the most recent block are written
-    // radio IF chain (sdrpp_vfo_set_if): NoiseBlanker -> PowerSquelch between st[i_if] and the demodulator
+    // radio IF chain between st[i_if] and the demodulator: NoiseBlanker -> PowerSquelch (sdrpp_vfo_set_if) -> FMIF (sdrpp_vfo_set_fmnr)
     struct Ifc {
         bool on = false;  // a chain is attached (both blocks may still be disabled: then nothing is planned for it)
         int nb_on = 0, sq_on = 0;
         float nb_rate = 0.0f, nb_level = 0.0f, sq_level = 0.0f;
         float* d_amp = nullptr;  // NoiseBlanker::amp (device, persistent)
-        bool active() const { return on && (nb_on || sq_on); }
+        // FMIF (noise_reduction/fm_if.h): the last block of the chain, switched by a call of its own
+        bool fm_on = false;
+        int fm_bins = 32;            // radio_module.h:91
+        std::vector<float> fm_line;  // FMIF's delay line (kFmifTile - 1 complex samples, newest last) while no stream's history holds it: see fmif_line_save
+        bool nbsq() const { return on && (nb_on || sq_on); }
+        bool active() const { return nbsq() || fm_on; }
     } ifc;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
     ToepTab tp_stage[SDRPP_MAX_DECIM_STAGES], tp_poly, tp_chan, tp_audio;
@@ -262,6 +270,7 @@ struct sdrpp_ctx {
     int next_id = 1;
     // cached stage-1 job tap arrays, keyed by membership signature
     std::map<std::string, float2*> s1_tap_cache;  // key = 16 raw bytes: two independent 64-bit hashes of (kind, member ids, increments)
+    std::map<int, float*> fmif_tabs;      // FMIF's matrix per bin count in use (sdrpp_host::fmifMatrix), uploaded once
 
     // ---- pipelined ("tick") execution: one launch per block, the stages of consecutive blocks skewed over consecutive launches
     //      (tick_kernels.h; sdrpp_set_pipelined) ----

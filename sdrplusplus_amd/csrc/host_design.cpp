@@ -188,4 +188,22 @@ void zoomTable(int offset, int width, int inSize, int outSize, std::vector<int32
 // arg(phaseDelta) each sample, where phaseDelta is the float pair the reference stores (frequency_xlator.h:17).
 double turnsPerSample(float re, float im) { return std::atan2((double)im, (double)re) / (2.0 * kPi); }
 
+// FMIF (noise_reduction/fm_if.h:45-77, :113) as one matrix: the window (nuttall(n, N - 1), stored as float like the reference's fftWin), the forward
+// DFT and the twiddle the un-normalised backward DFT of a single bin gives at index N / 2,
+//     A[k][n] = w[n] * e^{-j 2 pi k (n - N/2) / N},      N = bins, integer N / 2
+// designed in double and rounded to float.  tab: [2][32][32] floats, re then im, A[k][n] at [n][k], zero for k >= N or n >= N.
+void fmifMatrix(int bins, float* tab) {
+    const int N = bins, half = N / 2;
+    for (int i = 0; i < 2 * 32 * 32; i++) { tab[i] = 0.0f; }
+    for (int n = 0; n < N; n++) {
+        const double w = (double)(float)nuttall((double)n, (double)(N - 1));
+        for (int k = 0; k < N; k++) {
+            const int m = (((k * (n - half)) % N) + N) % N;  // the angle reduced exactly
+            const double a = -2.0 * kPi * (double)m / (double)N;
+            tab[n * 32 + k] = (float)(w * std::cos(a));
+            tab[1024 + n * 32 + k] = (float)(w * std::sin(a));
+        }
+    }
+}
+
 }  // namespace sdrpp_host

@@ -419,6 +419,7 @@ int vfo_reset_state(sdrpp_ctx* c, Vfo& v) {
         const float one = 1.0f;
         HIPCHK(c, hipMemcpy(v.ifc.d_amp, &one, sizeof(float), hipMemcpyHostToDevice));
     }
+    std::fill(v.ifc.fm_line.begin(), v.ifc.fm_line.end(), 0.0f);  // FMIF::reset (fm_if.h:36-43): the delay line, wherever it is kept (the streams' histories are cleared above)
     return SDRPP_OK;
 }
 
@@ -519,7 +520,7 @@ void launch_role(sdrpp_ctx* c, const sdrpp_ctx::RoleLaunch& r) {
     case TR_FIRB_Q: hipLaunchKernelGGL((vfo_firb_kernel<1, true, true>), grid, dim3((unsigned)e.aux), r.lds, st, (const FirBJob*)e.jobs); break;
     case TR_PRE: hipLaunchKernelGGL(vfo_demod_pre_kernel, grid, b256, 0, st, (const PreJob*)e.jobs); break;
     case TR_SEQ: hipLaunchKernelGGL(vfo_sequential_kernel, grid, dim3(64), 0, st, (const SeqJob*)e.jobs, e.aux); break;
-    case TR_IFC: hipLaunchKernelGGL(vfo_ifchain_kernel, grid, b256, 0, st, (const IfcJob*)e.jobs, e.aux); break;
+    case TR_IFC: hipLaunchKernelGGL(vfo_ifchain_kernel, grid, b256, r.lds, st, (const IfcJob*)e.jobs, e.aux); break;
     case TR_PIPE: hipLaunchKernelGGL(vfo_pipe_kernel<1>, grid, b256, r.lds, st, (const PipeJob*)e.jobs); break;
     case TR_POLYC: hipLaunchKernelGGL(vfo_polyc_kernel, grid, b256, r.lds, st, (const PolyJob*)e.jobs, e.aux); break;
     case TR_DEEMP_P0: hipLaunchKernelGGL((vfo_deemph_kernel<0, 0>), grid, b256, 0, st, (const DeempJob*)e.jobs); break;

@@ -213,7 +213,8 @@ struct BankPlan {
     Lev<PolyBJob> polyb[4];  // [0]: LMAX 4, [1]: LMAX 8 (de-interleaved tile); [2], [3]: same with odd decimation (linear tile)
     Lev<FirBJob> chan;
     Lev<SeqJob> seq;
-    Lev<IfcJob> ifc;        // radio IF chain (noise blanker, squelch): between the channel filter's level and the demodulator's, for the VFOs that carry one
+    Lev<IfcJob> ifc;        // radio IF chain (noise blanker / squelch jobs, FMIF segment jobs): between the channel filter's level and the demodulator's, for the VFOs that carry one
+    size_t ifc_lds = 0;     // ... and the LDS its launches need (FMIF segments only)
     Lev<PreJob> pre;
     Lev<FirBJob> audio;     // AM: real stream -> low-pass -> stereo
     Lev<FirBJob> audio_fm;  // WFM/NFM: IF -> discriminator -> low-pass -> stereo, one kernel
@@ -292,6 +293,7 @@ struct BankPlan {
         s1.clear(); rot.clear(); rotx.clear(); retune.clear(); pipes.clear();
         for_each_list([](auto& L) { lev_reset(L); });
         pipe_lds = 0;
+        ifc_lds = 0;
         d_pipes = nullptr;
         pipe_seg = 0;
         pipe_lvl = 0;
@@ -601,20 +603,45 @@ struct BankPlan {
         x.pj.timeouts = c->hd_tick_flag ? (int*)(c->hd_tick_flag + 8) : nullptr;
         x.piped = pipe_layout(x.pj, &x.pj_lds);
     }
-    // the radio's IF chain: one level of its own between the IF stream (which stays RxVFO::out) and whatever follows — the demodulator's
-    // levels below move down by one for this VFO, and read the chain's buffer in place of the IF
+    // the radio's IF chain: a level of its own per part (blanker / squelch, then FMIF) between the IF stream (which stays RxVFO::out) and whatever
+    // follows — the demodulator's levels below move down by as many for this VFO, and read the chain's buffer in place of the IF
     void if_chain(ChainCtx& x) {
         Vfo& v = x.v;
+        if (v.i_fmi >= 0) { v.st[(size_t)v.i_fmi].n = 0; }
         if (!x.ifc_on) {
             if (v.i_ifc >= 0) { v.st[(size_t)v.i_ifc].n = 0; }
             return;
         }
-        const Stream& in = *x.at.cur;
         Stream& fs = v.st[(size_t)v.i_ifc];
-        const bool per_block = v.ifc.sq_on && blocks;
-        ifc.add(x.at.lvl + 1, IfcJob{ (const float2*)in.data, (float2*)fs.data, v.ifc.d_amp, in.n, v.ifc.nb_on, v.ifc.nb_rate, 1.0f - v.ifc.nb_rate, v.ifc.nb_level, v.ifc.sq_on, v.ifc.sq_level,
-                                      per_block ? x.d_bnd : nullptr, per_block ? x.nbnd : 0 });
-        x.at.step(fs, in.n);
+        const bool fm = v.ifc.fm_on;
+        if (v.ifc.nbsq()) {
+            const Stream& in = *x.at.cur;
+            Stream& to = fm ? v.st[(size_t)v.i_fmi] : fs;  // in front of FMIF: the stream whose history is FMIF's delay line
+            const bool per_block = v.ifc.sq_on && blocks;
+            ifc.add(x.at.lvl + 1, IfcJob{ (const float2*)in.data, (float2*)to.data, v.ifc.d_amp, in.n, v.ifc.nb_on, v.ifc.nb_rate, 1.0f - v.ifc.nb_rate, v.ifc.nb_level, v.ifc.sq_on, v.ifc.sq_level,
+                                          per_block ? x.d_bnd : nullptr, per_block ? x.nbnd : 0 });
+            x.at.step(to, in.n);
+        }
+        if (fm) {
+            // FMIF: one level behind the blanker / squelch job (a closed block is zeroed only at that job's end), a job per segment of
+            // kFmifSeg samples — parallel over samples, the stream's history in front of the first
+            const Stream& in = *x.at.cur;
+            IfcJob j{};
+            j.in = (const float2*)in.data;
+            j.out = (float2*)fs.data;
+            j.n = in.n;
+            j.kind = 1;
+            j.fm_bins = v.ifc.fm_bins;
+            j.fm_hist = in.hist[in.cur];
+            j.fm_hist_len = in.hist_len;
+            j.fm_tab = c->fmif_tabs[v.ifc.fm_bins];
+            for (int lo = 0; lo < in.n; lo += kFmifSeg) {
+                j.fm_lo = lo;
+                ifc.add(x.at.lvl + 1, j);
+            }
+            ifc_lds = (size_t)4 * SDRPP_FMIF_LDS_WAVE * sizeof(float);
+            x.at.step(fs, in.n);
+        }
         v.lvl_ifc = x.at.lvl;
         v.lvl_out = x.at.lvl;
     }
@@ -717,7 +744,8 @@ struct BankPlan {
         Vfo& v = x.v;
         const Stream* phantom = (v.fused_front && v.d.n_stages >= 2 && !v.nco_exact) ? &v.st[(size_t)v.i_first] : nullptr;  // stage-1 output of a fused front end: never written, never read
         for (auto& s : v.st) {
-            if (s.hist_len > 0 && s.data && &s != phantom && (x.ifc_on || v.i_ifc < 0 || &s != &v.st[(size_t)v.i_ifc])) {
+            const bool idle_fmi = v.i_fmi >= 0 && &s == &v.st[(size_t)v.i_fmi] && !(x.ifc_on && v.ifc.fm_on && v.ifc.nbsq());  // (no chain writes it: nothing to carry)
+            if (s.hist_len > 0 && s.data && &s != phantom && !idle_fmi && (x.ifc_on || v.i_ifc < 0 || &s != &v.st[(size_t)v.i_ifc])) {
                 // pipelined: at the level of the consumer (its window of the NEXT block reads the new history one tick later, the carry of
                 // the next block overwrites the old one one tick later still); a stream nobody reads with memory (a consumer may be attached
                 // later: sdrpp_vfo_set_af, a taps change): one level behind the role that WRITES it — not behind the whole chain, which with
@@ -1350,7 +1378,7 @@ struct BankPlan {
             if (l < ifc.top && !ifc.at[l].empty()) {
                 FamilyTimer t(c, F_DEMOD);
                 const int nj = (int)ifc.at[l].size();
-                emit(c, l, F_DEMOD, TR_IFC, (nj + 3) / 4, 1, 0, ifc.dev[l], nullptr, nj);
+                emit(c, l, F_DEMOD, TR_IFC, (nj + 3) / 4, 1, ifc_lds, ifc.dev[l], nullptr, nj);
             }
             if ((l < pre.top && !pre.at[l].empty()) || (l < seq.top && !seq.at[l].empty()) || (l < ssbx_l.top && !ssbx_l.at[l].empty())) {
                 FamilyTimer t(c, F_DEMOD);

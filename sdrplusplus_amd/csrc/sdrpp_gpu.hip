@@ -383,6 +383,7 @@ int sdrpp_destroy(sdrpp_ctx* c) {
     for (auto& kv : c->vfos) { vfo_free(*kv.second); }
     c->vfos.clear();
     for (auto& e : c->s1_tap_cache) { (void)hipFree(e.second); }
+    for (auto& e : c->fmif_tabs) { (void)hipFree(e.second); }
     for (auto& p : c->tpairs) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->ev_pool) { (void)hipEventDestroy(e); }
     for (int i = 0; i < kArenaSlots; i++) {
@@ -860,6 +861,18 @@ int sdrpp_vfo_set_if(sdrpp_ctx* c, int id, const sdrpp_if_desc* d) {
     LOOKUP_VFO(v, c, id);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ifc_apply(c, *v, d);
+}
+
+// ... and its last block, FMIF (the FM IF noise reduction), switched by a call of its own
+int sdrpp_vfo_set_fmnr(sdrpp_ctx* c, int id, int enabled, int bins) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    if (bins > kFmifTile) { return fail(c, SDRPP_ERR_UNSUPPORTED, "FMIF with %d bins (the matrix tile holds %d)", bins, kFmifTile); }
+    if (bins < 2) { return fail(c, SDRPP_ERR_INVALID, "FMIF with %d bins", bins); }
+    LOOKUP_VFO(v, c, id);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return fmnr_apply(c, *v, enabled != 0, bins);
 }
 
 int sdrpp_vfo_ifc_count(sdrpp_ctx* c, int id) {

@@ -217,9 +217,12 @@ int vfo_build(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
         v->chan_ntaps = d->chan_ntaps;
     }
     v->d.chan_taps = nullptr;
-    // the IF chain's output (sdrpp_vfo_set_if): only the slot — its buffers come with the first chain, a VFO without one pays nothing
+    // the IF chain's output (sdrpp_vfo_set_if, sdrpp_vfo_set_fmnr) and the stream between its blanker / squelch and FMIF: only the slots — their
+    // buffers come with the first chain that needs them, a VFO without one pays nothing
     v->st.emplace_back();
     v->i_ifc = (int)v->st.size() - 1;
+    v->st.emplace_back();
+    v->i_fmi = (int)v->st.size() - 1;
     if (d->demod != SDRPP_DEMOD_RAW) {
         if (fm || d->demod == SDRPP_DEMOD_AM) {
             static const float unit = 1.0f;
@@ -262,6 +265,44 @@ int vfo_build(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
 }
 
 // ---- radio IF chain -----------------------------------------------------------------------------------------------------------------
+// FMIF's delay line (fm_if.h: `buffer`, bins - 1 samples; kept here as the newest kFmifTile - 1, the matrix has zero columns for the rest) is the
+// history of the stream FMIF reads: the blanker / squelch output st[i_fmi] while one of them runs, else RxVFO::out.  Which stream that is changes
+// with every switch of the chain, and an unplugged FMIF keeps what it held (the reference only takes the block out of the chain).  So every call
+// that changes the chain saves the line under the old configuration (fmif_line_save) and puts it back under the new one (fmif_line_restore);
+// in between, and while FMIF is off, Vfo::Ifc::fm_line holds it.
+Stream& fmif_feed(Vfo& v) { return (v.ifc.nbsq() && v.i_fmi >= 0) ? v.st[(size_t)v.i_fmi] : rx_out(v); }
+int fmif_line_save(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Ifc& f = v.ifc;
+    if (f.fm_line.empty()) { f.fm_line.assign((size_t)(kFmifTile - 1) * 2, 0.0f); }
+    if (!f.fm_on) { return SDRPP_OK; }
+    const Stream& s = fmif_feed(v);
+    const int H = std::min(s.hist_len, kFmifTile - 1);
+    std::fill(f.fm_line.begin(), f.fm_line.end(), 0.0f);
+    if (H > 0 && s.hist[s.cur] && s.width == 2) {
+        HIPCHK(c, hipMemcpy(f.fm_line.data() + (size_t)(kFmifTile - 1 - H) * 2, s.hist[s.cur] + (size_t)(s.hist_len - H) * 2, (size_t)H * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return SDRPP_OK;
+}
+int fmif_line_restore(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Ifc& f = v.ifc;
+    if (!f.fm_on) { return SDRPP_OK; }
+    if (f.fm_line.empty()) { f.fm_line.assign((size_t)(kFmifTile - 1) * 2, 0.0f); }
+    Stream& s = fmif_feed(v);
+    int rc;
+    if (!s.base) {  // (st[i_fmi], first use)
+        if ((rc = stream_alloc(c, s, 2, kFmifTile - 1, v.st[(size_t)v.i_chan].cap))) { return rc; }
+    }
+    if ((rc = stream_grow_hist(c, s, kFmifTile - 1))) { return rc; }
+    HIPCHK(c, hipMemcpy(s.hist[s.cur] + (size_t)(s.hist_len - (kFmifTile - 1)) * 2, f.fm_line.data(), f.fm_line.size() * sizeof(float), hipMemcpyHostToDevice));
+    return SDRPP_OK;
+}
+// the IF chain's output stream, allocated with the first chain
+int ifc_out_ensure(sdrpp_ctx* c, Vfo& v) {
+    Stream& fs = v.st[(size_t)v.i_ifc];
+    if (fs.base) { return SDRPP_OK; }
+    const Stream& like = v.st[(size_t)v.i_chan];  // what the demodulator reads today: same capacity, same history
+    return stream_alloc(c, fs, 2, like.hist_len, like.cap);
+}
 // sdrpp_vfo_set_if on a VFO the caller has looked up (the stream is idle).  What the demodulator remembers of its input (the discriminator's
 // previous sample, the audio low-pass's delay line) moves with the switch: it was fed the IF until a chain becomes active and the chain's
 // output from then on, or the other way round.
@@ -269,15 +310,14 @@ int ifc_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_if_desc* d) {
     Vfo::Ifc& f = v.ifc;
     if (v.i_ifc < 0) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no IF chain slot", v.id); }
     Stream& fs = v.st[(size_t)v.i_ifc];
-    const bool was_active = f.active() && fs.base, was_nb = f.on && f.nb_on;
-    if (d) {
+    if (d) {  // (checked before anything changes)
         if (d->nb_enabled && !(d->nb_rate > 0.0f && d->nb_rate <= 1.0f && d->nb_level == d->nb_level)) { return fail(c, SDRPP_ERR_INVALID, "noise blanker: rate %g (0 < rate <= 1), level %g", d->nb_rate, d->nb_level); }
         if (d->squelch_enabled && d->squelch_level != d->squelch_level) { return fail(c, SDRPP_ERR_INVALID, "squelch level is not a number"); }
-        if (!fs.base) {
-            const Stream& like = v.st[(size_t)v.i_chan];  // what the demodulator reads today: same capacity, same history
-            int rc = stream_alloc(c, fs, 2, like.hist_len, like.cap);
-            if (rc) { return rc; }
-        }
+    }
+    if (int rc = fmif_line_save(c, v)) { return rc; }  // FMIF is left alone: its delay line moves to whatever stream it reads from now on
+    const bool was_active = f.active() && fs.base, was_nb = f.on && f.nb_on;
+    if (d) {
+        if (int rc = ifc_out_ensure(c, v)) { return rc; }
         if (!f.d_amp) {
             int rc = dev_alloc(c, &f.d_amp, 1);
             if (rc) { return rc; }
@@ -306,7 +346,38 @@ int ifc_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_if_desc* d) {
         if (rc) { return rc; }
     }
     if (!now_active) { fs.n = 0; }
-    return SDRPP_OK;
+    return fmif_line_restore(c, v);
+}
+
+// sdrpp_vfo_set_fmnr on a VFO the caller has looked up (the stream is idle): FMIF::setBins clears the delay line (fm_if.h:26-34), unplugging the
+// block keeps it, and what the demodulator remembers of its input moves when the chain as a whole starts or stops, as in ifc_apply.
+int fmnr_apply(sdrpp_ctx* c, Vfo& v, bool enabled, int bins) {
+    Vfo::Ifc& f = v.ifc;
+    if (v.i_ifc < 0 || v.i_fmi < 0) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no IF chain slot", v.id); }
+    Stream& fs = v.st[(size_t)v.i_ifc];
+    int rc;
+    if ((rc = fmif_line_save(c, v))) { return rc; }
+    if (enabled) {
+        if ((rc = ifc_out_ensure(c, v))) { return rc; }
+        if (c->fmif_tabs.find(bins) == c->fmif_tabs.end()) {
+            std::vector<float> tab((size_t)2 * 32 * 32);
+            sdrpp_host::fmifMatrix(bins, tab.data());
+            float* d_tab = nullptr;
+            if ((rc = upload(c, &d_tab, tab.data(), tab.size()))) { return rc; }
+            c->fmif_tabs[bins] = d_tab;
+        }
+    }
+    const bool was_active = f.active() && fs.base;
+    if (bins != f.fm_bins) { std::fill(f.fm_line.begin(), f.fm_line.end(), 0.0f); }
+    f.fm_bins = bins;
+    f.fm_on = enabled;
+    const bool now_active = f.active();
+    if (was_active != now_active && fs.base) {
+        Stream& feed = rx_out(v);
+        if ((rc = now_active ? hist_tail_copy(c, fs, feed, demod_if_need(v)) : hist_tail_copy(c, feed, fs, demod_if_need(v)))) { return rc; }
+    }
+    if (!now_active) { fs.n = 0; }
+    return fmif_line_restore(c, v);
 }
 
 // ---- sdrpp_vfo_replace: what of the old VFO lives on in the new one -----------------------------------------------------------------
@@ -357,12 +428,19 @@ int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
         if (rc) { return rc; }
         if (o.ifc.nb_on && o.ifc.d_amp && n.ifc.d_amp) { HIPCHK(c, hipMemcpy(n.ifc.d_amp, o.ifc.d_amp, sizeof(float), hipMemcpyDeviceToDevice)); }
     }
+    if (keep & 4) {  // ... and FMIF with them: its bin count, whether it is plugged in, and its delay line
+        if ((rc = fmif_line_save(c, o))) { return rc; }
+        n.ifc.fm_bins = o.ifc.fm_bins;
+        n.ifc.fm_line = o.ifc.fm_line;
+        if ((rc = fmnr_apply(c, n, o.ifc.fm_on, o.ifc.fm_bins))) { return rc; }
+    }
     return SDRPP_OK;
 }
 
 // ---- sdrpp_vfo_set_channel_taps -----------------------------------------------------------------------------------------------------
 int vfo_set_chan_taps(sdrpp_ctx* c, Vfo& v, const float* taps, int n) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = fmif_line_save(c, v)) { return rc; }  // (FMIF reads RxVFO::out, which changes its identity with the filter's bypass)
     Stream& fs = chan_feed(v);  // must remember n - 1 samples
     const int old_n = v.chan_ntaps, w = fs.width;
     const bool was_on = old_n > 0, now_on = n > 0;
@@ -408,7 +486,7 @@ int vfo_set_chan_taps(sdrpp_ctx* c, Vfo& v, const float* taps, int n) {
         rc = toep_build_fir(c, v.tp_chan, v.ctaps_chan.data(), n, 1);
         if (rc) { return rc; }
     }
-    return SDRPP_OK;
+    return fmif_line_restore(c, v);
 }
 
 // ---- radio AF chain -----------------------------------------------------------------------------------------------------------------

@@ -625,9 +625,20 @@ struct IfcJob {
     // reference blocks inside this push at the IF rate (cumulative sample counts; nullptr: the push is one block)
     const int* bounds;
     int nb;
+    // kind 1: one segment of FMIF (vfo_fmif_kernels.h) — `in` / `n` are its input stream's data of this push, `out` the chain's output
+    int kind;
+    int fm_bins, fm_lo;     // bin count; first sample of the segment
+    const float* fm_hist;   // the input stream's history (StreamIn)
+    int fm_hist_len;
+    const float* fm_tab;    // [2][32][32]: re / im of A[k][n] at [n][k]
 };
-__device__ __forceinline__ void vfo_ifchain_body(int id, const IfcJob* __restrict__ jobs) {
+#include "vfo_fmif_kernels.h"
+__device__ __forceinline__ void vfo_ifchain_body(int id, const IfcJob* __restrict__ jobs, float* smem) {
     const IfcJob job = jobs[id];
+    if (job.kind == 1) {
+        vfo_fmif_body(job, smem);
+        return;
+    }
     const int lane = threadIdx.x & 63;
     const int nblk = job.bounds ? job.nb : 1;
     float amp = job.nb_on ? *job.amp : 1.0f;
@@ -694,10 +705,12 @@ __device__ __forceinline__ void vfo_ifchain_body(int id, const IfcJob* __restric
     }
     if (job.nb_on && lane == 0) { *job.amp = amp; }
 }
-// four jobs per workgroup, one per wavefront (gx = ceil(njobs / 4)): the shape the role has inside a tick
+// four jobs per workgroup, one per wavefront (gx = ceil(njobs / 4)): the shape the role has inside a tick.  LDS: 4 * SDRPP_FMIF_LDS_WAVE floats where
+// the table holds FMIF segments, none otherwise.
 __global__ __launch_bounds__(256) void vfo_ifchain_kernel(const IfcJob* __restrict__ jobs, int njobs) {
+    HIP_DYNAMIC_SHARED(float, smemi)
     const int j = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
-    if (j < njobs) { vfo_ifchain_body(j, jobs); }
+    if (j < njobs) { vfo_ifchain_body(j, jobs, smemi); }
 }
 
 // =====================================================================================================================

@@ -132,9 +132,13 @@ public:
     // The radio module's IF chain in front of the demodulator (radio_module.h:84-96), on the device: NoiseBlanker(500 / IF rate, level) ->
     // PowerSquelch(level in dB), either switchable while the stream runs (sdrpp_vfo_set_if: the blanker's amplitude estimate lives through
     // level changes, re-plans and demodulator switches, as the reference's `nb` object does).  `out` stays the stream in front of the chain;
-    // a channel without a demodulator delivers the chain's output on it.  Not on the device: FMIF and the CTCSS squelch.
+    // a channel without a demodulator delivers the chain's output on it.  FMIF, the chain's last block, is setFMIFNR below.  Not on the device: the CTCSS squelch.
     void setNoiseBlanker(bool enabled, double level = 10.0);
     void setSquelch(bool enabled, double level = -100.0);
+    // FMIF, the radio's "IF Noise Reduction" (radio_module.h:92, 95; presets 9 / 15 / 31 / 32 bins, :31-36), behind blanker and squelch (sdrpp_vfo_set_fmnr):
+    // switchable while the stream runs like the two above — the block in flight finishes, the next one runs with the new setting.  A change of `bins`
+    // clears its delay line (FMIF::setBins), switching it off keeps it; re-plans and demodulator switches carry it along.
+    void setFMIFNR(bool enabled, int bins = 32);
     // Parity switch for THIS channel (sdrpp_vfo_desc.nco_mode): true = the reference's float rotator recursion on the device (what an SSB
     // product detector or a raw-IF consumer needs to follow a CPU build's own rounding drift), false = closed-form NCO, the fast path
     void setReferenceRotator(bool enabled);
@@ -147,6 +151,8 @@ public:
     int ncoMode = 0;  // 0: the front end's mode (IQFrontEnd::setReferenceRotator), 1: closed form, 2: reference rotator
     bool afOn = false, afHighPass = false;
     bool nbOn = false, squelchOn = false;
+    bool fmnrOn = false;
+    int fmnrBins = 32;
     double nbLevel = 10.0, squelchLevel = -100.0;
     double afAudioRate = 48000.0, afDeempTau = 50e-6;
 
@@ -1176,6 +1182,7 @@ private:
         int rc = oldId >= 0 ? sdrpp_vfo_replace(ctx, oldId, &d, keep | 4, &v.id) : sdrpp_vfo_add(ctx, &d, &v.id);
         if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_add: ") + sdrpp_last_error(ctx)); }
         if (v.nbOn || v.squelchOn) { applyIF(v); }  // (the blanker's rate follows the IF rate: radio_module.h:526)
+        if (oldId < 0 && (v.fmnrOn || v.fmnrBins != 32)) { applyFMNR(v); }  // (a replaced handle has it already: keep | 4)
         if (v.afOn && v.demod != Demod::RAW) { applyAF(v); }
     }
 
@@ -1190,6 +1197,11 @@ private:
         f.squelch_level = (float)v.squelchLevel;
         int rc = sdrpp_vfo_set_if(ctx, v.id, &f);
         if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_if: ") + sdrpp_last_error(ctx)); }
+    }
+
+    void applyFMNR(RxVFO& v) {
+        int rc = sdrpp_vfo_set_fmnr(ctx, v.id, v.fmnrOn ? 1 : 0, v.fmnrBins);
+        if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_fmnr: ") + sdrpp_last_error(ctx)); }
     }
 
     // radio_module.h:98-110: resamp.init(NULL, afRate, audioRate); hpTaps = highPass(300, 100, audioRate); deemp.init(NULL, tau, audioRate)
@@ -1505,6 +1517,14 @@ inline void RxVFO::setNoiseBlanker(bool enabled, double level) {
     nbOn = enabled;
     nbLevel = level;
     if (id >= 0) { fe->applyIF(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::setFMIFNR(bool enabled, int bins) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    fe->tempStop();
+    fmnrOn = enabled;
+    fmnrBins = bins;
+    if (id >= 0) { fe->applyFMNR(*this); }
     fe->tempStart();
 }
 inline void RxVFO::setSquelch(bool enabled, double level) {

@@ -14,11 +14,12 @@
 //   ... demod = new GpuWFM(&sigpath::iqFrontEnd);  demod->init(name, &config, vfo->output, bw, audioSR);
 //
 // The radio module's IF chain (radio_module.h:84-96) sits between the VFO and the demodulator; a fused VFO has no place for CPU blocks
-// there, so its two cheap blocks run on the device: the noise blanker and the power squelch (setNBEnabled / setNBLevel /
-// setSquelchEnabled / setSquelchLevel below, with the radio module's clamps; sdrpp_vfo_set_if).  The radio module keeps its own
-// `nb` / `powerSquelch` blocks disabled and forwards its menu / interface commands to these setters.
-// Not covered: FMIF (the FFT-based FM IF noise reduction) and the AF-side CTCSS squelch — with one of them enabled the demodulator's
-// input is no longer a VFO's own stream and init() / setInput() throw, as before.
+// there, so its three blocks run on the device: the noise blanker and the power squelch (setNBEnabled / setNBLevel /
+// setSquelchEnabled / setSquelchLevel below, with the radio module's clamps; sdrpp_vfo_set_if) and, for the FM modes, FMIF, the
+// "IF Noise Reduction" (setFMIFNREnabled / setIFNRPreset; sdrpp_vfo_set_fmnr).  The radio module keeps its own `nb` / `powerSquelch` /
+// `fmnr` blocks disabled and forwards its menu / interface commands to these setters.
+// Not covered: the AF-side CTCSS squelch — with it enabled the demodulator's input is no longer a VFO's own stream and init() /
+// setInput() throw, as before.
 // showMenu() draws nothing (GUI is out of scope); the options it would toggle are setLowPass / setAGC* / setCarrierAgc below.
 #pragma once
 #include <stdexcept>
@@ -111,6 +112,9 @@ public:
     void setNBLevel(float level) { _nbLevel = level < 1.0f ? 1.0f : (level > 10.0f ? 10.0f : level); applyIF(); }
     void setSquelchEnabled(bool enabled) { _squelchEnabled = enabled; applyIF(); }
     void setSquelchLevel(float level) { _squelchLevel = level < -100.0f ? -100.0f : (level > 0.0f ? 0.0f : level); applyIF(); }
+    // radio_module.h:676-690: the checkbox and the preset (9 / 15 / 31 / 32 bins); WFM runs 32 bins whatever the preset (:531)
+    void setFMIFNREnabled(bool enabled) { _fmnrEnabled = enabled; applyIF(); }
+    void setIFNRPreset(int bins) { _fmnrBins = bins; applyIF(); }
     RxVFO* channel() { return vfo; }
 
 private:
@@ -118,12 +122,13 @@ private:
         RxVFO* v = fe ? fe->vfoOfStream(input) : nullptr;
         if (!v) {
             throw std::runtime_error("[sdrpp_gpu::FusedDemodulator] the input is not the output stream of a VFO of this front end "
-                                     "(noise blanker and squelch run on the device — setNBEnabled / setSquelchEnabled; FMIF and the CTCSS squelch must stay disabled: "
+                                     "(noise blanker, squelch and FMIF run on the device — setNBEnabled / setSquelchEnabled / setFMIFNREnabled; the CTCSS squelch must stay disabled: "
                                      "the demodulator is fused behind the channeliser)");
         }
         if (vfo && vfo != v) {  // the previous channel goes back to delivering its IF
             vfo->setNoiseBlanker(false, _nbLevel);
             vfo->setSquelch(false, _squelchLevel);
+            vfo->setFMIFNR(false, vfo->fmnrBins);
             vfo->attachDemod(Demod::RAW);
         }
         vfo = v;
@@ -140,6 +145,9 @@ private:
         if (!vfo) { return; }
         if (vfo->nbOn != _nbEnabled || vfo->nbLevel != (double)_nbLevel) { vfo->setNoiseBlanker(_nbEnabled, _nbLevel); }
         if (vfo->squelchOn != _squelchEnabled || vfo->squelchLevel != (double)_squelchLevel) { vfo->setSquelch(_squelchEnabled, _squelchLevel); }
+        const bool fmnr = _fmnrEnabled && getFMIFNRAllowed();
+        const int bins = (MODE == Demod::WFM) ? 32 : _fmnrBins;
+        if (vfo->fmnrOn != fmnr || vfo->fmnrBins != bins) { vfo->setFMIFNR(fmnr, bins); }
     }
 
     IQFrontEnd* fe;
@@ -148,7 +156,8 @@ private:
     double _bandwidth = 0.0;
     bool _lowPass = true, _carrierAgc = false;
     double _agcAttack = 50.0, _agcDecay = 5.0;  // am.h:98-99, usb.h:92-93
-    bool _nbEnabled = false, _squelchEnabled = false;
+    bool _nbEnabled = false, _squelchEnabled = false, _fmnrEnabled = false;
+    int _fmnrBins = 32;  // radio_module.h:91
     float _nbLevel = 10.0f, _squelchLevel = -100.0f;  // radio_module.h:906, :446
 };
 

@@ -186,7 +186,7 @@ def af_desc(af_rate, audio_rate=48000.0, deemp_tau=50e-6, high_pass=False):
 
 def if_desc(if_rate, nb=False, nb_level=10.0, squelch=None):
     """sdrpp_if_desc for the radio module's IF chain (radio_module.h:84-96): NoiseBlanker(rate = 500 / if_rate, level; :90, :526) ->
-    PowerSquelch(level in dB; None = off).  FMIF and the CTCSS squelch are not on the device."""
+    PowerSquelch(level in dB; None = off).  FMIF, the chain's last block, is switched by Context.vfo_set_fmnr (IFNR_BINS); the CTCSS squelch is not on the device."""
     f = capi.IfDesc()
     f.nb_enabled = int(bool(nb))
     f.nb_rate = 500.0 / float(if_rate)
@@ -194,3 +194,7 @@ def if_desc(if_rate, nb=False, nb_level=10.0, squelch=None):
     f.squelch_enabled = int(squelch is not None)
     f.squelch_level = float(squelch) if squelch is not None else 0.0
     return f
+
+
+# The radio module's "IF Noise Reduction" presets: FMIF's bin count (radio_module.h:31-36); WFM always runs 32 (radio_module.h:531)
+IFNR_BINS = {"NOAA_APT": 9, "VOICE": 15, "NARROW_BAND": 31, "BROADCAST": 32}

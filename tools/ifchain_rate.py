@@ -3,7 +3,9 @@
 device memory and left on the device, without a chain, with the squelch on every VFO, and with blanker + squelch on every VFO.  Prints one JSON object
 per block size: ingest rate (MS/s, best of three trials) and the time per block (us), plus the one-wavefront-per-VFO figure the tracker is bound by —
 IF samples per second and VFO through the chain's role — from a single 250 kS/s RAW VFO at 10^6-sample blocks.
-    python tools/ifchain_rate.py [block sizes ...]            (default: 307200 1000000)"""
+    python tools/ifchain_rate.py [block sizes ...]            (default: 307200 1000000)
+    python tools/ifchain_rate.py --fmif [block sizes ...]     FMIF (sdrpp_vfo_set_fmnr) instead: a 32-VFO WFM bank at 10 MS/s, as it is and with 32-bin FMIF on
+                                                              every VFO (default sizes: 1000000 50000 = sr / 200) -> profiles/fmif_rate.md"""
 import json
 import os
 import sys
@@ -29,7 +31,39 @@ def rate(ctx, bufs, B, n):
     return best
 
 
+def fmif_main(sizes):
+    import torch
+
+    from sdrplusplus_amd import capi, radio, workloads
+
+    dev = torch.device("cuda", 0)
+    sr, nv = workloads.CFG[3]["sr"], 32
+    for B in sizes or [1000000, int(sr / 200)]:
+        xs = [workloads.synth(3, B, seed=7 + i, nvfo=nv) for i in range(3)]
+        xd = [torch.from_numpy(x.view(np.float32)).to(dev) for x in xs]
+        out = {"cfg": 3, "push": B, "nvfo": nv}
+        npush = max(24, min(400, (1 << 27) // B))
+        for name, bins in (("no_fmif", 0), ("fmif_32", 32), ("fmif_9", 9)):
+            ctx = capi.Context(0, max_push=B)
+            vids = []
+            for mode, if_rate, bw, centre, _ in workloads.vfo_plan(3, nv):
+                d, keep = radio.vfo_desc(sr, if_rate, bw, centre, mode)
+                vids.append(ctx.vfo_add(d, keep))
+                if bins:
+                    ctx.vfo_set_fmnr(vids[-1], True, bins)
+            ctx.set_pipelined(True, 0)
+            dt = rate(ctx, xd, B, npush)
+            st = ctx.pipeline_stats()
+            assert st["pass_blocks"] == 0, st
+            assert (st["roles"].get("ifc", 0) > 0) == bool(bins), st["roles"]
+            out[name] = {"MS_per_s": round(B / dt / 1e6, 1), "us_per_block": round(dt * 1e6, 1)}
+            ctx.close()
+        print(json.dumps(out), flush=True)
+
+
 def main():
+    if "--fmif" in sys.argv[1:]:
+        return fmif_main([int(a) for a in sys.argv[1:] if a != "--fmif"])
     import torch
 
     from sdrplusplus_amd import capi, radio, workloads
