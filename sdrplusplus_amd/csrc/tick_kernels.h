@@ -12,7 +12,7 @@
 // a block costs the host one launch (2.6 us measured, tools/probe/tick_probe.hip) and the device max(stage) instead of sum(stages).
 // Results arrive `depth` ticks late; sdrpp_pipeline_flush / any observing call runs the remaining ticks without new input.
 //
-// The roles are the bodies of the ordinary kernels (fft_kernels.h, vfo_kernels.h): same code, same arithmetic, bit-identical results
+// The roles are the bodies of the ordinary kernels (fft_kernels.h, the vfo_*_kernels.h headers under vfo_kernels.h): same code, same arithmetic, bit-identical results
 // (tests/test_pipelined.py compares the two execution paths sample for sample).  Per-block buffers are rings (`ring depth` buffers per
 // stream) so that a producer working on block n+1 does not overwrite what a consumer still reads of block n.
 #pragma once

@@ -1,5 +1,11 @@
-// FM IF noise reduction on the matrix cores — part of vfo_kernels.h (included from there, inside namespace sdrpp_k, behind struct IfcJob).
+// FM IF noise reduction on the matrix cores, and the job record it shares with the rest of the radio's IF chain (vfo_ifchain_kernels.h).
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <sdrpp_gfx950.h>
+#include "vfo_stream.h"
+
+namespace sdrpp_k {
 
 // =====================================================================================================================
 // FMIF (noise_reduction/fm_if.h:45-77), the last block of the radio's IF chain.  For every IF sample i, with N = bins:
@@ -22,6 +28,27 @@
 #define SDRPP_FMIF_TILE 32
 #define SDRPP_FMIF_SEG 256
 #define SDRPP_FMIF_LDS_WAVE ((SDRPP_FMIF_SEG + SDRPP_FMIF_TILE) * 2 + 64 * 4)  // floats per wavefront: the window, then the exchange of the argmax
+
+// The job record of the IF chain's role (vfo_ifchain_kernels.h): the blanker and squelch of one VFO, or one segment of FMIF.
+struct IfcJob {
+    const float2* in;  // the IF stream of this push (RxVFO::out)
+    float2* out;       // the chain's own output
+    float* amp;        // NoiseBlanker::amp, persistent (device)
+    int n;
+    int nb_on;
+    float nb_rate, nb_inv_rate, nb_level;
+    int sq_on;
+    float sq_level;
+    // reference blocks inside this push at the IF rate (cumulative sample counts; nullptr: the push is one block)
+    const int* bounds;
+    int nb;
+    // kind 1: one segment of FMIF (vfo_fmif_kernels.h) — `in` / `n` are its input stream's data of this push, `out` the chain's output
+    int kind;
+    int fm_bins, fm_lo;     // bin count; first sample of the segment
+    const float* fm_hist;   // the input stream's history (StreamIn)
+    int fm_hist_len;
+    const float* fm_tab;    // [2][32][32]: re / im of A[k][n] at [n][k]
+};
 
 __device__ __forceinline__ void vfo_fmif_body(const IfcJob& job, float* smem) {
     const int lane = threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
@@ -89,3 +116,5 @@ __device__ __forceinline__ void vfo_fmif_body(const IfcJob& job, float* smem) {
         wave_sync();  // (the next tile overwrites the exchange)
     }
 }
+
+}  // namespace sdrpp_k

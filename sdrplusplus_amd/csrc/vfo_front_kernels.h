@@ -1,5 +1,14 @@
-// Front ends: the fused VALU form, the matrix-core composite front end in its 32 x 32 x 2 and 16 x 16 x 4 shapes, the long first stages — part of vfo_kernels.h (included from there, inside namespace sdrpp_k; split out in round 5: the file had grown to 2 700 lines).
+// Front ends: the fused VALU form, the matrix-core composite front end in its 32 x 32 x 2 and 16 x 16 x 4 shapes, the long first stages.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <sdrpp_gfx950.h>
+#include <type_traits>
+#include "fft_kernels.h"
+#include "vfo_math.h"
+#include "vfo_stage1_kernels.h"
+
+namespace sdrpp_k {
 
 // =====================================================================================================================
 // Fused front: stage 1 (translation folded into the first decimating FIR) + stage 2 (second decimating FIR) in ONE kernel.
@@ -63,11 +72,7 @@ __device__ __forceinline__ void vfo_front2_body(const KIdx bid, float2* smem2, c
     }
     if (threadIdx.x < VT && (int)threadIdx.x < job.nv) {
         const int v = threadIdx.x;
-        double ph = fma((double)(base - job.anchor) + 0.5 * (double)(K1 - 1), job.theta[v], job.phi0[v]);
-        ph -= rint(ph);
-        float sn, cs;
-        sincospif(2.0f * (float)ph, &sn, &cs);
-        ptile[v] = make_float2(cs, sn);
+        ptile[v] = turn_phasor(fma((double)(base - job.anchor) + 0.5 * (double)(K1 - 1), job.theta[v], job.phi0[v]));
     }
     __syncthreads();
     const int j = threadIdx.x;
@@ -252,22 +257,12 @@ __device__ __forceinline__ void vfo_frontcm_body(const KIdx bid, float* smemf, c
     };
     auto tile_phasor = [&](int tb) {
         if (lane < VT && lane < job.nv) {
-            double ph = fma((double)(tile_base(tb) - job.anchor) + 0.5 * (double)(K - 1), job.theta[lane], job.phi0[lane]);
-            ph -= rint(ph);
-            float sn, cs;
-            sincospif(2.0f * (float)ph, &sn, &cs);
-            ptile[lane] = make_float2(cs, sn);
+            ptile[lane] = turn_phasor(fma((double)(tile_base(tb) - job.anchor) + 0.5 * (double)(K - 1), job.theta[lane], job.phi0[lane]));
         }
     };
 
     // ---- wavefront prologue: this lane's slice of the in-tile NCO table, first IQ tile ----
     const float2* PT = reinterpret_cast<const float2*>(smemf + L.nco_off) + jl;  // [v * tile]: exp(j 2 pi theta_v D n) of this lane's output n
-    auto wave_prologue = [&]() { fetch(tile_base(tile0)); };
-#ifdef SDRPP_FCM_EARLY_IQ
-    // measurement build: the first IQ tile is requested BEFORE the tap table (at 10^6-sample blocks ~600 workgroups start together and the first
-    // tile arrived ~10 us into a front-end workgroup's life, behind everybody's table and window requests)
-    if (has_tiles) { wave_prologue(); }
-#endif
     // ---- block prologue: tap operand table and output pointers (the only workgroup barrier of the kernel) ----
     if constexpr (KS > 0) {
         // pair-per-half form (see the matrix loop): lane (jl, hi) wants (gr, -gi) of VFO jl and pair 2 q + hi as ONE 8-byte read — row p of the
@@ -319,9 +314,7 @@ __device__ __forceinline__ void vfo_frontcm_body(const KIdx bid, float* smemf, c
     __syncthreads();
     TICK_MARK(0);
     if (!has_tiles) { return; }
-#ifndef SDRPP_FCM_EARLY_IQ
-    wave_prologue();
-#endif
+    fetch(tile_base(tile0));
 
     const float sgn = hi ? -1.0f : 1.0f;
     const float* P1 = hi ? XI : XR;
@@ -520,11 +513,7 @@ __device__ __forceinline__ void vfo_frontcm16_body(const KIdx bid, float* smemf,
     if (tid < VT) {
         outp[tid] = job.out[tid];
         if (tid < job.nv) {  // the tile's phasor per VFO: exactly vfo_frontcm_body's tile_phasor
-            double ph = fma((double)(tbase - job.anchor) + 0.5 * (double)(K - 1), job.theta[tid], job.phi0[tid]);
-            ph -= rint(ph);
-            float sn, cs;
-            sincospif(2.0f * (float)ph, &sn, &cs);
-            ptile[tid] = make_float2(cs, sn);
+            ptile[tid] = turn_phasor(fma((double)(tbase - job.anchor) + 0.5 * (double)(K - 1), job.theta[tid], job.phi0[tid]));
         }
     }
 #pragma unroll
@@ -597,9 +586,6 @@ __host__ __device__ inline int frontcl_lds_floats(int K, int lgD, int nw = 2) {
 // PF: IQ samples prefetched per lane into registers (covers windows of nsamp <= 64 * PF samples: PF = 38 -> first stages up to 448
 // taps at /64); PF = 0: longer windows are loaded in place, unpipelined.
 #define SDRPP_FCL_PF 38
-#ifndef SDRPP_FCL_RING_NARROW
-#define SDRPP_FCL_RING_NARROW 4
-#endif
 // NARROW (round 5): jobs of at most 16 VFOs — cfg 4's 43 channels per mode are a job of 32 and a job of 11 — in the 16 x 16 x 4 shape: 16 VFO rows x 16
 // outputs per tile, the instruction's k = 0 .. 3 (lanes 16 kq .. 16 kq + 15) are FOUR consecutive tap pairs, each lane owning the pair 4 Q + kq of
 // output n = lane & 15.  Same pair-per-lane operands, same table, half the matrix cycles of a 32-row tile that would be two thirds empty.
@@ -692,11 +678,7 @@ __device__ __forceinline__ void vfo_frontcl_impl(const KIdx bid, float* smemf, c
         const long long base = tile_base(tb);
         planes_store(base);  // the previous tile's reads are complete (wave_sync at the end of the loop body)
         if (lane < VT && lane < job.nv) {
-            double ph = fma((double)(base - job.anchor) + 0.5 * (double)(K - 1), job.theta[lane], job.phi0[lane]);
-            ph -= rint(ph);
-            float sn, cs;
-            sincospif(2.0f * (float)ph, &sn, &cs);
-            ptile[lane] = make_float2(cs, sn);
+            ptile[lane] = turn_phasor(fma((double)(base - job.anchor) + 0.5 * (double)(K - 1), job.theta[lane], job.phi0[lane]));
         }
         pf_valid = false;
         if (it + 1 < ntl) { fetch(tile_base(tb + 1)); }  // in flight during the matrix loop (spreading these loads over the loop — vector memory
@@ -711,7 +693,7 @@ __device__ __forceinline__ void vfo_frontcl_impl(const KIdx bid, float* smemf, c
             // zero padded to a multiple of SIXTEEN rows (plan_vfo.h), a padded step multiplies VALID samples (index clamped) by zero taps — so
             // that every ring slot is a fixed register (a uniform branch per slot made the compiler rotate the ring through moves and wait for
             // every tap load where it was issued)
-            constexpr int RING = NARROW ? SDRPP_FCL_RING_NARROW : 4;
+            constexpr int RING = 4;
             const int NQr = ((NQ + RING - 1) / RING) * RING;
             float gq[RING], hq[RING];
 #pragma unroll
@@ -795,3 +777,4 @@ __global__ __launch_bounds__(128, 2) void vfo_frontcl_kernel(IqSrc src, const Fr
     vfo_frontcl_body<PF>(kidx(blockIdx), smemf, src, jobs);
 }
 
+}  // namespace sdrpp_k

@@ -1,5 +1,12 @@
-// The reference's float rotator recursion on the device (parity mode), SSB's second rotator, the retune hand-over — part of vfo_kernels.h (included from there, inside namespace sdrpp_k; split out in round 5: the file had grown to 2 700 lines).
+// The reference's float rotator recursion on the device (parity mode), SSB's second rotator, the retune hand-over.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <sdrpp_gfx950.h>
+#include "fft_kernels.h"
+#include "vfo_math.h"
+
+namespace sdrpp_k {
 
 // =====================================================================================================================
 // Reference-rotator mode (sdrpp_set_nco_mode(ctx, 1); parity runs against the reference's CPU path).
@@ -355,10 +362,8 @@ __global__ __launch_bounds__(64) void vfo_retune_fix_kernel(IqSrc src, const Ret
         for (int q = 1; q < job.nseg; q++) {
             if (n >= job.start[q]) { s = q; }
         }
-        double ph = fma((double)(n - job.start[s]), job.theta[s], job.phi[s]);
-        ph -= rint(ph);
         float sn, cs;
-        sincospif(2.0f * (float)ph, &sn, &cs);
+        turn_sincos(fma((double)(n - job.start[s]), job.theta[s], job.phi[s]), sn, cs);
         const float2 x = iq_load_clamped(src, n);
         const float h = job.taps[k];
         const float rr = (x.x * cs) - (x.y * sn), ri = (x.x * sn) + (x.y * cs);
@@ -370,3 +375,4 @@ __global__ __launch_bounds__(64) void vfo_retune_fix_kernel(IqSrc src, const Ret
     if (lane == 0) { job.out[m] = make_float2(ar, ai); }
 }
 
+}  // namespace sdrpp_k

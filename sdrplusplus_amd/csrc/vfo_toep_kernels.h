@@ -1,5 +1,13 @@
-// Per-stream FIR work on the matrix cores (banded-Toeplitz form) — part of vfo_kernels.h (included from there, inside namespace sdrpp_k; split out in round 5: the file had grown to 2 700 lines).
+// Per-stream FIR work on the matrix cores (banded-Toeplitz form).
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <sdrpp_gfx950.h>
+#include "fft_kernels.h"
+#include "vfo_stream.h"
+#include "vfo_fir_kernels.h"
+
+namespace sdrpp_k {
 
 // =====================================================================================================================
 // Per-stream FIR work on the matrix cores ("Toeplitz" form).  Any of the per-VFO filters behind the front end — a decimating
@@ -355,3 +363,4 @@ __global__ __launch_bounds__(256, 5) void vfo_toep_kernel(const ToepJob* __restr
     vfo_toep_body<WIDTH, G, QUAD>(kidx(blockIdx), kidx(gridDim), smemt, jobs);
 }
 
+}  // namespace sdrpp_k

@@ -1,5 +1,5 @@
 // TEST: device math helpers of the kernels, compiled for the host against the fiber emulator's headers (tests/emu) and swept against
-// double-precision libm.  fm_phase is the discriminator's atan2 (vfo_kernels.h); the audio parity bar (1e-5 RMS) needs it to stay
+// double-precision libm.  fm_phase is the discriminator's atan2 (vfo_fir_kernels.h); the audio parity bar (1e-5 RMS) needs it to stay
 // within a few 1e-7 rad of atan2f everywhere, including the axes, the octant seams and tiny / huge magnitudes.
 #include <hip/hip_runtime.h>
 #include <sdrpp_gfx950.h>
