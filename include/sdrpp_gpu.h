@@ -319,6 +319,52 @@ int sdrpp_vfo_read_pcm(sdrpp_ctx* ctx, int id, int which, int pcm_type, float sc
 int sdrpp_preproc_read_pcm(sdrpp_ctx* ctx, int pcm_type, float scale, void* dst_host, int max_samples);
 int sdrpp_vfo_read_compressed(sdrpp_ctx* ctx, int id, int which, int pcm_type, unsigned char* dst_host, int max_bytes);
 
+/* ---- recorder sink behind a demodulating VFO (misc_modules/recorder) ---------------------------------------------------
+ * What the recorder module does to a radio's audio stream, block by block, on the device:
+ *   dsp::audio::Volume (audio/volume.h:14,22,37)            v = x * g per value, g = powf(volume, 2) computed once on the host as a float
+ *   dsp::bench::PeakLevelMeter<stereo_t> (peak_level_meter.h:52-57)   peak |v.l|, |v.r| of the block (the host keeps the running maximum and resets it)
+ *   dsp::convert::StereoToMono (stereo_to_mono.h:13-15), optional      m = (v.l + v.r) / 2.0f
+ *   wav::Writer::write (utils/wav.cpp:158-180) in the file's sample type, wav::SampleType numbering (utils/wav.h:25-30):
+ *     1 INT16    VOLK generic volk_32f_s32f_convert_16i(.., 32767.0f): s * 32767.0f, clamped to [-32768, 32767], rintf, cast
+ *     0 UINT8    (uint8_t)((s * 127.0f) + 128.0f): the product, then the sum, then truncation toward zero.  The reference's cast is UNDEFINED where that
+ *                float lies outside [0, 256): OUR DEFINITION there is saturation — 255 from 255.0 up, 0 from 0.0 down
+ *     3 FLOAT32  the floats as they are
+ *     2 INT32    NOT IMPLEMENTED (SDRPP_ERR_UNSUPPORTED), on purpose: VOLK's generic volk_32f_s32f_convert_32i clamps at 2147483647.0f, which as a float
+ *                is 2^31, so the cast of a clipped sample overflows int32 and the reference's own value is undefined; there is nothing to be exact against
+ *   "ignore silence" (recorder/src/main.cpp:28, 533-561): a block whose absolute maximum over the values that would be written is below SILENCE_LVL
+ *     (the float compared with the double 10e-6) is not written at all.  `silent` only REPORTS that decision: the block's bytes are delivered all the
+ *     same, `frames` stays the block's frame count, and the host skips the block.
+ * Every product and sum is rounded on its own (nothing contracts into a fused multiply-add), so every byte and every figure of the record is a bit-exact
+ * function of the float frames the same block delivers (sdrpp_vfo_read / sdrpp_vfo_af_read, result flag 1).
+ * SOURCE: the end of the VFO's chain, i.e. what result flag 1 delivers for it — the AF chain's output where one is attached, else the demodulator's
+ * output; sdrpp_vfo_set_af attaching or detaching moves what the sink reads.  Only for VFOs with a demodulator (RAW: SDRPP_ERR_UNSUPPORTED).
+ * A BLOCK is one push; outside pipelined mode with deferred processing on it is the whole pass (the silence decision and the peaks then cover all the
+ * staged pushes together; a decision per staged push is not offered).  An empty block (0 frames) gives frames = 0, peaks and abs_max 0, silent = 0.
+ * The sink has NO streaming state: calling sdrpp_vfo_set_rec again only changes the parameters, from the next block on (blocks already pushed in
+ * pipelined mode keep the parameters they were pushed with); desc == NULL detaches.  sdrpp_vfo_replace does not carry the sink over — like the AF
+ * chain the host re-attaches it: the reference's recorder binds to the sink stream, not to the VFO. */
+#define SDRPP_REC_UINT8 0     /* wav::SAMP_TYPE_UINT8                                                                                   */
+#define SDRPP_REC_INT16 1     /* wav::SAMP_TYPE_INT16                                                                                   */
+#define SDRPP_REC_INT32 2     /* wav::SAMP_TYPE_INT32: refused                                                                          */
+#define SDRPP_REC_FLOAT32 3   /* wav::SAMP_TYPE_FLOAT32                                                                                 */
+typedef struct sdrpp_rec_desc {
+    float volume;         /* the slider value; the gain applied is powf(volume, 2)                                                 */
+    int mono;             /* 1: StereoToMono behind the volume                                                                      */
+    int sample_type;      /* SDRPP_REC_UINT8 / _INT16 / _FLOAT32; SDRPP_REC_INT32: SDRPP_ERR_UNSUPPORTED; anything else: SDRPP_ERR_INVALID */
+    int ignore_silence;
+} sdrpp_rec_desc;
+typedef struct sdrpp_rec_info {
+    int frames, channels, sample_type;   /* of the block as it was converted: frames * channels samples of sample_type                */
+    int silent;           /* 1: ignore_silence is on and (double)abs_max < 10e-6 — the reference writes nothing for this block     */
+    float peak_l, peak_r; /* PeakLevelMeter of THIS block: max fabsf of the volume's output per channel (in front of the mono fold)  */
+    float abs_max;        /* max fabsf over the values that would be written (both channels, or the mono stream), before conversion */
+} sdrpp_rec_info;
+int sdrpp_vfo_set_rec(sdrpp_ctx* ctx, int id, const sdrpp_rec_desc* desc);
+/* The most recent push (pass) through the sink: up to max_frames frames of packed samples to dst_host (may be NULL with max_frames = 0), the record
+ * of the WHOLE block to *info (may be NULL); returns the frames copied.  SDRPP_ERR_INVALID for a VFO without a sink. */
+int sdrpp_vfo_rec_read(sdrpp_ctx* ctx, int id, void* dst_host, int max_frames, sdrpp_rec_info* info);
+int sdrpp_abi_sizeof_rec_desc(void);
+
 /* ---- WaterFall display state around the raw-line history (core/src/gui/widgets/waterfall.cpp) ---------------
  * The last `height` raw dB lines stay resident in HBM in the reference's ring order (getFFTBuffer :875-886), so a zoom / pan /
  * level change re-renders the whole waterfall on the device (updateWaterfallFb :600-631) instead of re-reading host memory, and
@@ -436,7 +482,9 @@ int64_t sdrpp_pending(sdrpp_ctx* ctx);   /* samples staged and not yet processed
  * result_flags (sdrpp_set_pipelined): which results every block also delivers into page-locked host memory, ready for sdrpp_result_wait
  * without any copy call: 1 = every VFO's output block (the end of its chain: the AF chain's output where one is attached, else what
  * sdrpp_vfo_read returns), 2 = zoomed lines + palette indices, 4 = raw dB lines, 8 = the pre-processed IQ stream of the block (only with a
- * pre-processing chain configured: without one it is the input block itself).
+ * pre-processing chain configured: without one it is the input block itself), 16 = for every VFO with a recorder sink (sdrpp_vfo_set_rec) its block as the
+ * sink converts it and one sdrpp_rec_info per push (sdrpp_result_rec below).  16 is independent of 1: with 16 alone no float frames cross the bus — a mono
+ * int16 recording is 2 bytes per frame against 8.
  * At most SDRPP_RESULT_SLOTS (24) launches' results exist at a time (one block per launch unless sdrpp_set_pipeline_group says otherwise): release
  * them (a block whose slot is still held 24 launches later fails the push).
  * HOW FAR BEHIND TO ASK: a streaming host takes block t - lag when it has pushed block t.  With lag >= depth + 1 (sdrpp_pipeline_stats
@@ -472,6 +520,13 @@ typedef struct sdrpp_result {
     const float* iq;          /* [n_iq] complex: what streams bound with bindIQStream receive (iq_frontend.cpp:32-39 -> Splitter)    */
 } sdrpp_result;
 int sdrpp_set_pipelined(sdrpp_ctx* ctx, int on, int result_flags);
+/* Result flag 16: what VFO `id`'s recorder sink made of push `ticket` — *data: frames * channels packed samples in the block's result slot (page-locked
+ * memory of the library; element aligned: in a launch group the group's converted block lies there in one piece and this push's share starts at its
+ * own first frame), *info: the record of this push alone (either may be NULL).  Valid between sdrpp_result_wait and sdrpp_result_release of that
+ * ticket, like the pointers a sdrpp_result holds; outside of that: SDRPP_ERR_INVALID.  SDRPP_ERR_NOT_FOUND: the VFO has no sink, or the block was pushed before the
+ * sink was attached or without flag 16.  Blocks of a pipelined run that were processed as an ordinary pass deliver the same.  A call of its own, so
+ * that sdrpp_result's layout and SDRPP_ABI_VERSION stay what they are. */
+int sdrpp_result_rec(sdrpp_ctx* ctx, uint64_t ticket, int id, const void** data, sdrpp_rec_info* info);
 /* SEVERAL BLOCKS PER LAUNCH.  A launch costs the device a start ramp, a tail and the gap to the next one whatever the block holds, and the host one
  * plan: at the reference's block size (sample_rate / 200) that is most of a block's time, and a host that pushes faster than the device works
  * only makes the launch queue longer.  With max_blocks > 1 a push is HELD — nothing planned, nothing launched — until max_blocks pushes have come

@@ -89,6 +89,35 @@ class IfDesc(C.Structure):
     ]
 
 
+class RecDesc(C.Structure):
+    """struct sdrpp_rec_desc (include/sdrpp_gpu.h): the recorder sink behind a demodulating VFO — volume, mono fold, sample type, ignore silence."""
+
+    _fields_ = [
+        ("volume", C.c_float),
+        ("mono", C.c_int),
+        ("sample_type", C.c_int),
+        ("ignore_silence", C.c_int),
+    ]
+
+
+class RecInfo(C.Structure):
+    """struct sdrpp_rec_info (include/sdrpp_gpu.h): what the recorder sink says about one block."""
+
+    _fields_ = [
+        ("frames", C.c_int),
+        ("channels", C.c_int),
+        ("sample_type", C.c_int),
+        ("silent", C.c_int),
+        ("peak_l", C.c_float),
+        ("peak_r", C.c_float),
+        ("abs_max", C.c_float),
+    ]
+
+
+REC_UINT8, REC_INT16, REC_INT32, REC_FLOAT32 = 0, 1, 2, 3   # wav::SampleType (utils/wav.h:25-30)
+REC_DTYPES = {REC_UINT8: np.uint8, REC_INT16: np.int16, REC_FLOAT32: np.float32}
+
+
 class Result(C.Structure):
     """struct sdrpp_result (include/sdrpp_gpu.h): one block's results in the library's page-locked host memory (pipelined mode)."""
 
@@ -179,6 +208,12 @@ def load():
     L.sdrpp_vfo_ifc_count.argtypes = [vp, C.c_int]
     L.sdrpp_vfo_ifc_read.argtypes = [vp, C.c_int, c_float_p, C.c_int]
     L.sdrpp_vfo_ifc_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), c_int_p]
+    L.sdrpp_abi_sizeof_rec_desc.argtypes = []
+    if L.sdrpp_abi_sizeof_rec_desc() != C.sizeof(RecDesc):
+        raise ImportError("sdrpp_rec_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_rec_desc(), C.sizeof(RecDesc)))
+    L.sdrpp_vfo_set_rec.argtypes = [vp, C.c_int, C.POINTER(RecDesc)]
+    L.sdrpp_vfo_rec_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(RecInfo)]
+    L.sdrpp_result_rec.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(RecInfo)]
     L.sdrpp_vfo_set_af.argtypes = [vp, C.c_int, C.POINTER(AfDesc)]
     L.sdrpp_vfo_af_count.argtypes = [vp, C.c_int]
     L.sdrpp_vfo_af_read.argtypes = [vp, C.c_int, c_float_p, C.c_int]
@@ -267,6 +302,7 @@ EXPORTED_SYMBOLS = [
     "sdrpp_vfo_read_pcm", "sdrpp_vfo_read_compressed", "sdrpp_preproc_read_pcm",
     "sdrpp_wf_configure", "sdrpp_wf_set_smoothing", "sdrpp_wf_set_hold", "sdrpp_wf_latest", "sdrpp_wf_raster", "sdrpp_wf_signal_info",
     "sdrpp_preproc_configure", "sdrpp_preproc_reconfigure", "sdrpp_preproc_set_reference_order", "sdrpp_preproc_out_count", "sdrpp_preproc_read", "sdrpp_preproc_device_buffer",
+    "sdrpp_vfo_set_rec", "sdrpp_vfo_rec_read", "sdrpp_abi_sizeof_rec_desc", "sdrpp_result_rec",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
     "sdrpp_vfo_set_if", "sdrpp_vfo_set_fmnr", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
     "sdrpp_fft_configure", "sdrpp_fft_disable", "sdrpp_fft_set_view", "sdrpp_fft_lines", "sdrpp_fft_read", "sdrpp_fft_copy_device", "sdrpp_fft_device_buffers",
@@ -586,6 +622,38 @@ class Context:
         got = self._chk(self.L.sdrpp_vfo_af_read(self.h, vid, out.ctypes.data_as(c_float_p), n))
         return out[:got]
 
+    def vfo_set_rec(self, vid, volume=1.0, mono=False, sample_type=REC_INT16, ignore_silence=False, attach=True):
+        """Attach the recorder sink (sdrpp_vfo_set_rec) or change its parameters from the next block on; attach=False detaches."""
+        d = RecDesc(float(volume), int(bool(mono)), int(sample_type), int(bool(ignore_silence)))
+        self._chk(self.L.sdrpp_vfo_set_rec(self.h, vid, C.byref(d) if attach else None))
+
+    @staticmethod
+    def _rec_unpack(addr, info):
+        """(samples [frames, channels] in the sink's type, copied from host address `addr`; the record as a dict)"""
+        n = info.frames * info.channels
+        dt = np.dtype(REC_DTYPES[info.sample_type])
+        a = np.empty((info.frames, info.channels), dtype=dt)
+        if n > 0:
+            C.memmove(a.ctypes.data, addr, n * dt.itemsize)
+        return a, dict(frames=info.frames, channels=info.channels, sample_type=info.sample_type, silent=info.silent,
+                       peak_l=np.float32(info.peak_l), peak_r=np.float32(info.peak_r), abs_max=np.float32(info.abs_max))
+
+    def vfo_rec_read(self, vid):
+        """sdrpp_vfo_rec_read: the most recent push (pass) as the recorder sink converts it -> (samples [frames, channels], record)."""
+        info = RecInfo()
+        self._chk(self.L.sdrpp_vfo_rec_read(self.h, vid, None, 0, C.byref(info)))
+        buf = np.empty(max(info.frames, 1) * 8, dtype=np.uint8)
+        got = self._chk(self.L.sdrpp_vfo_rec_read(self.h, vid, buf.ctypes.data_as(C.c_void_p), info.frames, C.byref(info)))
+        assert got == info.frames, (got, info.frames)
+        return self._rec_unpack(buf.ctypes.data, info)
+
+    def result_rec(self, ticket, vid):
+        """sdrpp_result_rec (result flag 16), between result_wait and result_release of that ticket -> (samples [frames, channels], record)."""
+        info = RecInfo()
+        data = C.c_void_p()
+        self._chk(self.L.sdrpp_result_rec(self.h, int(ticket), vid, C.byref(data), C.byref(info)))
+        return self._rec_unpack(data.value, info)
+
     def vfo_set_if(self, vid, if_desc):
         """Attach (or, with None, detach) the radio IF chain: noise blanker -> power squelch in front of the demodulator (sdrpp_vfo_set_if).
         On a VFO that already has one the parameters change and the blanker's amplitude estimate is kept."""
@@ -653,7 +721,7 @@ class Context:
     # pipelined execution (one launch per block, results a few blocks late)
     def set_pipelined(self, on, result_flags=0):
         """result_flags: 1 = every VFO's output block (AF output where a chain is attached), 2 = zoomed lines + palette indices, 4 = raw dB lines,
-        8 = the pre-processed IQ stream (with a pre-processing chain) into page-locked result slots."""
+        8 = the pre-processed IQ stream (with a pre-processing chain), 16 = the recorder sinks' converted blocks (result_rec) into page-locked result slots."""
         self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags)))
 
     def set_pipeline_group(self, max_blocks, adaptive=False, stable_words=False):

@@ -97,6 +97,12 @@ struct Vfo {
         bool nbsq() const { return on && (nb_on || sq_on); }
         bool active() const { return nbsq() || fm_on; }
     } ifc;
+    // recorder sink (sdrpp_vfo_set_rec): parameters only, no streaming state; reads what result_stream() names
+    struct Rec {
+        bool on = false;
+        float volume = 1.0f, gain = 1.0f;  // gain = powf(volume, 2) (audio/volume.h:14,22)
+        int mono = 0, type = 1, ignore_silence = 0;
+    } rec;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
     ToepTab tp_stage[SDRPP_MAX_DECIM_STAGES], tp_poly, tp_chan, tp_audio;
     // front end as one filter (what the fused translate + filter kernels evaluate): stages 0 (+ 1) of the plan
@@ -288,9 +294,11 @@ struct sdrpp_ctx {
         int fft_size = 0, data_width = 0, flags = 0;        // what the block was PLANNED with (the view / FFT size / result flags may change before it is collected)
         size_t off_zoomed = 0, off_index = 0, off_raw = 0, off_iq = 0;  // byte offsets in the slot
         int n_iq = 0;                                        // pre-processed IQ samples delivered (result flag 8)
+        std::vector<int> rec_ids;                            // result flag 16: the VFOs that had a recorder sink when the block was planned,
+        std::vector<size_t> rec_off, rec_info_off;           // ... where this push's converted samples and its sdrpp_rec_info lie in the slot
     };
     bool pipelined = false;
-    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines
+    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks
     int num_cus = 256;
     int tick_l0_at = getenv("SDRPP_GPU_TICK_L0_AT") ? atoi(getenv("SDRPP_GPU_TICK_L0_AT")) : 0;  // (read when the context is created)
     // grid rules of the roles inside a tick (the stand-alone kernels size their grids for a GPU of their own; in a tick ~8 roles share it, and

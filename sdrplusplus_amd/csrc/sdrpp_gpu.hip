@@ -901,6 +901,25 @@ int sdrpp_vfo_ifc_device_buffer(sdrpp_ctx* c, int id, const float** out, int* n_
 
 int sdrpp_abi_sizeof_if_desc(void) { return (int)sizeof(sdrpp_if_desc); }
 
+// ---- recorder sink: volume -> peak meter -> optional mono fold -> the file's sample type (misc_modules/recorder) --------------------------
+int sdrpp_vfo_set_rec(sdrpp_ctx* c, int id, const sdrpp_rec_desc* d) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return rec_apply(c, *v, d);
+}
+
+int sdrpp_vfo_rec_read(sdrpp_ctx* c, int id, void* dst_host, int max_frames, sdrpp_rec_info* info) {
+    DeviceScope dev_scope_(c);
+    if (!c || max_frames < 0 || (max_frames > 0 && !dst_host)) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return rec_read(c, *v, dst_host, max_frames, info);
+}
+
+int sdrpp_abi_sizeof_rec_desc(void) { return (int)sizeof(sdrpp_rec_desc); }
+
 int sdrpp_vfo_read_pcm(sdrpp_ctx* c, int id, int which, int pcm_type, float scale, void* dst_host, int max_frames) {
     DeviceScope dev_scope_(c);
     if (!c || !dst_host || max_frames < 0 || (pcm_type != 0 && pcm_type != 1)) { return SDRPP_ERR_INVALID; }
@@ -1398,7 +1417,7 @@ int64_t sdrpp_pending(sdrpp_ctx* c) { return c ? c->pending : SDRPP_ERR_INVALID;
 // ---- pipelined execution ----------------------------------------------------------------------------------------------------------------
 int sdrpp_set_pipelined(sdrpp_ctx* c, int on, int result_flags) {
     DeviceScope dev_scope_(c);
-    if (!c || result_flags < 0 || result_flags > 15) { return SDRPP_ERR_INVALID; }
+    if (!c || result_flags < 0 || result_flags > 31) { return SDRPP_ERR_INVALID; }
     if (on && c->deferred) { return fail(c, SDRPP_ERR_INVALID, "deferred and pipelined processing exclude each other"); }
     int rc = flush_pending(c);  // (drains the queue when the mode is being left)
     if (rc) { return rc; }
@@ -1507,6 +1526,18 @@ int sdrpp_result_wait(sdrpp_ctx* c, uint64_t ticket, sdrpp_result* out) {
     out->n_iq = R->n_iq;
     out->iq = R->n_iq > 0 ? reinterpret_cast<const float*>(base + R->off_iq) : nullptr;
     return SDRPP_OK;
+}
+int sdrpp_result_rec(sdrpp_ctx* c, uint64_t ticket, int id, const void** data, sdrpp_rec_info* info) {
+    if (!c) { return SDRPP_ERR_INVALID; }
+    sdrpp_ctx::Result* R = result_of(c, ticket);
+    if (!R || !R->held) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_result_rec: block %llu is not held (between sdrpp_result_wait and sdrpp_result_release)", (unsigned long long)ticket); }
+    for (size_t i = 0; i < R->rec_ids.size(); i++) {
+        if (R->rec_ids[i] != id) { continue; }
+        if (data) { *data = R->base + R->rec_off[i]; }
+        if (info) { memcpy(info, R->base + R->rec_info_off[i], sizeof(sdrpp_rec_info)); }
+        return SDRPP_OK;
+    }
+    return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of a recorder sink of VFO %d", (unsigned long long)ticket, id);
 }
 int sdrpp_result_release(sdrpp_ctx* c, uint64_t ticket) {
     if (!c || ticket == 0 || ticket > c->pushes) { return c ? SDRPP_ERR_NOT_FOUND : SDRPP_ERR_INVALID; }

@@ -243,6 +243,13 @@ const Stream& result_stream(const Vfo& v, int* level = nullptr) {
     if (level) { *level = raw ? v.lvl_if : v.lvl_out; }
     return raw ? v.st[(size_t)v.i_if] : v.st[(size_t)v.i_out];
 }
+// the push ends of a launch group (Vfo::tk_if / tk_af) at the rate of the stream result_stream() names
+const std::vector<int>& result_ends(const Vfo& v, const Stream& s) {
+    return (&s == &v.st[(size_t)v.i_if] || (v.i_out >= 0 && &s == &v.st[(size_t)v.i_out]) || (v.i_ifc >= 0 && &s == &v.st[(size_t)v.i_ifc])) ? v.tk_if : v.tk_af;
+}
+constexpr size_t kRecInfoStride = 32;  // one sdrpp_rec_info per push in a result slot
+static_assert(sizeof(sdrpp_rec_info) <= kRecInfoStride && sizeof(sdrpp_rec_info) == sizeof(RecInfo), "sdrpp_rec_info is what the recorder kernel writes");
+inline size_t rec_frame_bytes(const Vfo::Rec& r) { return (size_t)(r.type == SDRPP_REC_UINT8 ? 1 : (r.type == SDRPP_REC_INT16 ? 2 : 4)) * (r.mono ? 1 : 2); }
 size_t tick_results_need(sdrpp_ctx* c) {
     size_t need = 0;
     if (c->res_flags & 1) {
@@ -251,6 +258,14 @@ size_t tick_results_need(sdrpp_ctx* c) {
             size_t cap = std::max(result_stream(v).cap, v.st[(size_t)v.i_if].cap);  // (which stream ends the chain can change with sdrpp_vfo_set_af: room for either)
             if (v.i_out >= 0) { cap = std::max(cap, v.st[(size_t)v.i_out].cap); }
             need += ((cap + 16) * 8 + 15) & ~(size_t)15;
+        }
+    }
+    if (c->res_flags & 16) {  // recorder sinks: the converted block (at most 8 bytes per frame, whatever type the sink has when the block comes) + one record per push of a launch group
+        for (auto& kv : c->vfos) {
+            const Vfo& v = *kv.second;
+            if (!v.rec.on || v.i_out < 0) { continue; }
+            const size_t cap = std::max(result_stream(v).cap, v.st[(size_t)v.i_out].cap);
+            need += (((cap + 16) * 8 + 15) & ~(size_t)15) + (size_t)kGroupMax * kRecInfoStride;
         }
     }
     if ((c->res_flags & 8) && c->pre.on) {
@@ -341,13 +356,16 @@ sdrpp_ctx::ResRegion* tick_results_region(sdrpp_ctx* c, uint64_t gid) {
 // Every VFO's output block of the group lies in the group's result slot in one piece; push j's share of it is the samples between the push ends
 // carried down the VFO's chain (Vfo::tk_if / tk_af, plan_vfo.h), its lines the frames whose last sample arrived with it.
 struct ResCopy { const void* src; size_t off; size_t bytes; int level; };
+struct ResRec { const float* src; int n; size_t off, info_off; float gain; int mono, type, ignore_silence; int level; };  // a recorder sink's share of a push (result flag 16)
+inline RecJob rec_job(const ResRec& q, char* base) { return RecJob{ reinterpret_cast<const float2*>(q.src), base + q.off, base + q.info_off, q.n, q.gain, q.mono, q.type, q.ignore_silence, 0 }; }
 int64_t tick_frames_by(const sdrpp_ctx* c, int64_t e) {  // lines complete once the first `e` samples of the block just planned are in (do_fft's own count)
     const int64_t P = (int64_t)c->nz + c->skip;
     const int64_t a = c->plan_fft_pos0 + e - c->nz - c->plan_fft_next0 * P;
     return a >= 0 ? a / P + 1 : 0;
 }
-int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vector<ResCopy>& copies, size_t* region_off) {
+int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vector<ResCopy>& copies, std::vector<ResRec>& recs, size_t* region_off) {
     copies.clear();
+    recs.clear();
     *region_off = 0;
     if (!c->res_flags) {
         for (int j = 0; j < k; j++) {
@@ -377,7 +395,7 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
             const Vfo& v = *kv.second;
             int lvl = 1;
             const Stream& s = result_stream(v, &lvl);
-            const std::vector<int>& tk = (&s == &v.st[(size_t)v.i_if] || (v.i_out >= 0 && &s == &v.st[(size_t)v.i_out]) || (v.i_ifc >= 0 && &s == &v.st[(size_t)v.i_ifc])) ? v.tk_if : v.tk_af;
+            const std::vector<int>& tk = result_ends(v, s);
             if (split && ((int)tk.size() != k || tk[(size_t)k - 1] != s.n)) { return fail(c, SDRPP_ERR_INVALID, "internal: push ends of VFO %d do not add up (%zu ends, %d samples)", v.id, tk.size(), s.n); }
             for (int j = 0; j < k; j++) {
                 const int lo = (split && j > 0) ? tk[(size_t)j - 1] : 0, hi = split ? tk[(size_t)j] : s.n;
@@ -420,6 +438,26 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
             off += (bytes + 15) & ~(size_t)15;
         }
     }
+    if (c->res_flags & 16) {
+        // every recorder sink: the group's converted block in one piece (push j's share: frames [tk[j - 1], tk[j]) of it), then one record per push
+        for (auto& kv : c->vfos) {
+            const Vfo& v = *kv.second;
+            if (!v.rec.on || v.i_out < 0) { continue; }
+            int lvl = 1;
+            const Stream& s = result_stream(v, &lvl);
+            const std::vector<int>& tk = result_ends(v, s);
+            if (split && ((int)tk.size() != k || tk[(size_t)k - 1] != s.n)) { return fail(c, SDRPP_ERR_INVALID, "internal: push ends of VFO %d do not add up (%zu ends, %d samples)", v.id, tk.size(), s.n); }
+            const size_t bpf = rec_frame_bytes(v.rec), info0 = off + (((size_t)s.n * bpf + 15) & ~(size_t)15);
+            for (int j = 0; j < k; j++) {
+                const int lo = (split && j > 0) ? tk[(size_t)j - 1] : 0, hi = split ? tk[(size_t)j] : s.n;
+                R[j]->rec_ids.push_back(v.id);
+                R[j]->rec_off.push_back(off + (size_t)lo * bpf);
+                R[j]->rec_info_off.push_back(info0 + (size_t)j * kRecInfoStride);
+                recs.push_back(ResRec{ s.data + (size_t)lo * 2, hi - lo, off + (size_t)lo * bpf, info0 + (size_t)j * kRecInfoStride, v.rec.gain, v.rec.mono, v.rec.type, v.rec.ignore_silence, lvl + 1 });
+            }
+            off = info0 + (size_t)k * kRecInfoStride;
+        }
+    }
     if (off > c->res_cap) { return fail(c, SDRPP_ERR_INVALID, "internal: results of %zu bytes exceed what a launch may deliver (%zu)", off, c->res_cap); }
     int rc = tick_results_alloc(c, c->groups, off, region_off);
     if (rc) {
@@ -435,11 +473,29 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
 // gather roles of the block just planned -> c->emits (one level behind the producers); fills the result entries of its pushes
 int tick_results_plan(sdrpp_ctx* c, uint64_t first_ticket, int k) {
     static thread_local std::vector<ResCopy> copies;
+    static thread_local std::vector<ResRec> recs;
     size_t region = 0;
-    int rc = tick_results_describe(c, first_ticket, k, copies, &region);
-    if (rc || copies.empty()) { return rc; }
-    Lev<CopyJob> jobs;
+    int rc = tick_results_describe(c, first_ticket, k, copies, recs, &region);
+    if (rc || (copies.empty() && recs.empty())) { return rc; }
     char* base = c->res_ring_dev + region;
+    if (!recs.empty()) {  // the recorder sinks: jobs of the copy role (kind 3), one workgroup each, at the level the float gather of the same stream stands at
+        Lev<RecJob> rj;
+        Lev<CopyJob> cj;
+        for (auto& q : recs) { rj.add(q.level, rec_job(q, base)); }
+        if (!arena_push_lev(c, rj)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
+        for (int l = 0; l < rj.top; l++) {
+            for (size_t i = 0; i < rj.at[l].size(); i++) { cj.add(l, CopyJob{ rj.dev[l] + i, nullptr, 0, 3 | 0x100, 0 }); }
+        }
+        if (!arena_push_lev(c, cj)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
+        for (int l = 0; l < cj.top; l++) {
+            if (cj.at[l].empty()) { continue; }
+            emit(c, l, F_MISC, TR_COPY, 1, (int)cj.at[l].size(), 12 * sizeof(float), cj.dev[l]);
+            if (!c->emits.empty()) { c->emits.back().to_host = true; }
+            c->plan_top = std::max(c->plan_top, l + 1);
+        }
+    }
+    if (copies.empty()) { return SDRPP_OK; }
+    Lev<CopyJob> jobs;
     for (auto& q : copies) { jobs.add(q.level, CopyJob{ q.src, base + q.off, (long long)q.bytes, 0x100, 0 }); }
     if (!arena_push_lev(c, jobs)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
     for (int l = 0; l < jobs.top; l++) {
@@ -460,11 +516,16 @@ int tick_results_direct(sdrpp_ctx* c, uint64_t first_ticket, int k) {
     int rc = tick_results_ensure(c);
     if (rc) { return rc; }
     static thread_local std::vector<ResCopy> copies;
+    static thread_local std::vector<ResRec> recs;
     size_t region = 0;
-    rc = tick_results_describe(c, first_ticket, k, copies, &region);
+    rc = tick_results_describe(c, first_ticket, k, copies, recs, &region);
     if (rc) { return rc; }
     char* base = c->res_ring + region;
     for (auto& q : copies) { HIPCHK(c, hipMemcpyAsync(base + q.off, q.src, q.bytes, hipMemcpyDeviceToHost, c->stream)); }
+    for (auto& q : recs) {
+        hipLaunchKernelGGL(vfo_rec_kernel, dim3(1), dim3(256), 0, c->stream, rec_job(q, c->res_ring_dev + region));
+        HIPCHK(c, hipGetLastError());
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int j = 0; j < k; j++) {
         sdrpp_ctx::Result& R = c->res[(first_ticket + (uint64_t)j) % kResMeta];

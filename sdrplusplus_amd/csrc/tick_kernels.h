@@ -27,6 +27,7 @@ struct CopyJob {
     void* dst;
     long long bytes;  // multiple of 4 (kind 1: SOURCE bytes, multiple of 2)
     int kind;         // 0: verbatim; 1: interleaved int16 -> float (x / 32768: file_source/src/main.cpp:162); 2: complex conjugate (dsp/math/conjugate.h:12-15, bytes a multiple of 8); bit 8: dst is host memory
+                      // 3 (copy_body only, one workgroup per job): the recorder sink — src is a RecJob (vfo_rec_kernels.h) that names source, destination and record itself
     int pad;
 };
 __device__ __forceinline__ void copy_one(const CopyJob& job, int bx, int gx) {
@@ -75,8 +76,22 @@ __device__ __forceinline__ void copy_one(const CopyJob& job, int bx, int gx) {
     // (results for the host: page-locked memory is not cached on the device, the stores are complete — tick_finish waits for them — before
     // this wavefront counts itself done)
 }
-__device__ __forceinline__ void copy_body(const KIdx bid, const KIdx gdim, const CopyJob* __restrict__ jobs) { copy_one(jobs[bid.y], bid.x, gdim.x); }
-__global__ __launch_bounds__(256) void copy_kernel(const CopyJob* __restrict__ jobs) { copy_body(kidx(blockIdx), kidx(gridDim), jobs); }
+// (a call, not inlined: the recorder's six conversion loops inside the tick kernel moved its register allocation — 168 instead of 167 VGPRs in the
+// SET = 0 build, the step DESIGN.md 4c measured at 2 % of cfg 3's tick — and the job is one workgroup of a few microseconds per VFO and push)
+__device__ __attribute__((noinline)) void rec_body_call(const RecJob* j, float* sm) { rec_body(*j, sm); }
+// sm: 12 floats of LDS (the recorder's maxima)
+__device__ __forceinline__ void copy_body(const KIdx bid, const KIdx gdim, const CopyJob* __restrict__ jobs, float* sm) {
+    const CopyJob& job = jobs[bid.y];
+    if ((job.kind & 0xff) == 3) {  // (uniform over the workgroup)
+        if (bid.x == 0) { rec_body_call(reinterpret_cast<const RecJob*>(job.src), sm); }
+        return;
+    }
+    copy_one(job, bid.x, gdim.x);
+}
+__global__ __launch_bounds__(256) void copy_kernel(const CopyJob* __restrict__ jobs) {
+    __shared__ float sm[12];
+    copy_body(kidx(blockIdx), kidx(gridDim), jobs, sm);
+}
 
 // ---- roles ----
 enum TickRole : int {
@@ -268,7 +283,7 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : 3) void tick_kernel(TickL0 l0, 
             const int lb = b - first, gx = hdr[1];
             const KIdx bid{ lb % gx, lb / gx }, gdim{ gx, e_gy };
             switch (e_role) {
-            case TR_COPY: copy_body(bid, gdim, reinterpret_cast<const CopyJob*>(e_jobs)); break;
+            case TR_COPY: copy_body(bid, gdim, reinterpret_cast<const CopyJob*>(e_jobs), smem); break;
             case TR_CARRY: carry_body(bid, gdim, reinterpret_cast<const CarryJob*>(e_jobs), e_aux); break;
             case TR_ROTX16: {
                 const IqSrc src = e.p.src;

@@ -668,4 +668,39 @@ int pcm_read(sdrpp_ctx* c, const float* src, int count, int pcm_type, float scal
     return n;
 }
 
+// ---- recorder sink (misc_modules/recorder) ------------------------------------------------------------------------------------------
+// sdrpp_vfo_set_rec on a VFO the caller has looked up: parameters only — the sink has no state and plans nothing by itself
+int rec_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_rec_desc* d) {
+    if (!d) {
+        v.rec = Vfo::Rec{};
+        return SDRPP_OK;
+    }
+    if (v.d.demod == SDRPP_DEMOD_RAW || v.i_out < 0) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the recorder sink needs a demodulating VFO"); }
+    if (d->sample_type == SDRPP_REC_INT32) { return fail(c, SDRPP_ERR_UNSUPPORTED, "recorder sample type INT32: the reference's own conversion overflows where it clips"); }
+    if (d->sample_type != SDRPP_REC_UINT8 && d->sample_type != SDRPP_REC_INT16 && d->sample_type != SDRPP_REC_FLOAT32) { return fail(c, SDRPP_ERR_INVALID, "recorder sample type %d", d->sample_type); }
+    v.rec.on = true;
+    v.rec.volume = d->volume;
+    v.rec.gain = powf(d->volume, 2);  // audio/volume.h:14,22
+    v.rec.mono = d->mono != 0;
+    v.rec.type = d->sample_type;
+    v.rec.ignore_silence = d->ignore_silence != 0;
+    return SDRPP_OK;
+}
+// sdrpp_vfo_rec_read: the stream's most recent block through the sink, converted on the device so that the copy carries the file's bytes
+int rec_read(sdrpp_ctx* c, Vfo& v, void* dst_host, int max_frames, sdrpp_rec_info* info) {
+    if (!v.rec.on) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no recorder sink", v.id); }
+    const Stream& s = result_stream(v);
+    const size_t bpf = rec_frame_bytes(v.rec), info_off = ((size_t)s.n * bpf + 15) & ~(size_t)15;
+    if (int rc = pack_scratch(c, info_off + kRecInfoStride)) { return rc; }
+    const ResRec q{ s.data, s.n, 0, info_off, v.rec.gain, v.rec.mono, v.rec.type, v.rec.ignore_silence, 0 };
+    hipLaunchKernelGGL(vfo_rec_kernel, dim3(1), dim3(256), 0, c->stream, rec_job(q, c->d_pack));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = pipe_timeouts_check(c)) { return rc; }
+    const int n = std::min(max_frames, s.n);
+    if (n > 0) { HIPCHK(c, hipMemcpy(dst_host, c->d_pack, (size_t)n * bpf, hipMemcpyDeviceToHost)); }
+    if (info) { HIPCHK(c, hipMemcpy(info, c->d_pack + info_off, sizeof(sdrpp_rec_info), hipMemcpyDeviceToHost)); }
+    return n;
+}
+
 }  // namespace

@@ -22,6 +22,7 @@
 #include "vfo_ifchain_kernels.h"
 #include "vfo_carry_kernels.h"
 #include "vfo_af_kernels.h"
+#include "vfo_rec_kernels.h"
 #include "vfo_front_kernels.h"
 #include "vfo_toep_kernels.h"
 #include "vfo_polyc_kernels.h"  // (last, where vfo_polyc_kernel was defined before the split: the order of the kernels in the code object; it has no other meaning)

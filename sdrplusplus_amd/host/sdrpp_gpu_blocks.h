@@ -112,6 +112,7 @@ class RxVFO {
 public:
     dsp::stream<dsp::complex_t> out;   // RxVFO::out (IF); delivered when no demodulator is attached
     dsp::stream<dsp::stereo_t> audio;  // demodulator output (radio's Demodulator::getOutput()) when attached
+    dsp::stream<uint8_t> recorded;     // attachRecorder: one swap per block the recorder would write, the packed bytes of the file's sample type (silent blocks: no swap)
 
     void setInSamplerate(double inSamplerate);                // rx_vfo.h:38-43
     void setOffset(double offset);                            // rx_vfo.h:72-77
@@ -129,6 +130,14 @@ public:
     // every analog demodulator of the radio module).  detachAF() puts the demodulator output back on `audio`.
     void attachAF(double audioSamplerate = 48000.0, double deempTau = 50e-6, bool highPass = false);
     void detachAF();
+    // The recorder module behind the audio stream (misc_modules/recorder/src/main.cpp: volume -> PeakLevelMeter -> optional StereoToMono -> wav::Writer::write
+    // in `sampleType` = wav::SampleType: SDRPP_REC_UINT8 / _INT16 / _FLOAT32; "ignore silence"), on the device (sdrpp_vfo_set_rec): it reads what `audio` carries and
+    // delivers on `recorded` exactly the bytes stereoHandler / monoHandler would hand to the file, block by block — `audio` itself is delivered as always.
+    // Calling it again changes the parameters from the next block on; re-plans (setInSamplerate, a new demodulator) keep it.
+    void attachRecorder(double volume, bool mono, int sampleType, bool ignoreSilence);
+    void detachRecorder();
+    dsp::stereo_t getRecorderLevel();  // PeakLevelMeter::getLevel / resetLevel: the running maximum over the blocks since the last reset
+    void resetRecorderLevel();
     // The radio module's IF chain in front of the demodulator (radio_module.h:84-96), on the device: NoiseBlanker(500 / IF rate, level) ->
     // PowerSquelch(level in dB), either switchable while the stream runs (sdrpp_vfo_set_if: the blanker's amplitude estimate lives through
     // level changes, re-plans and demodulator switches, as the reference's `nb` object does).  `out` stays the stream in front of the chain;
@@ -155,6 +164,9 @@ public:
     int fmnrBins = 32;
     double nbLevel = 10.0, squelchLevel = -100.0;
     double afAudioRate = 48000.0, afDeempTau = 50e-6;
+    bool recOn = false, recMono = false, recIgnoreSilence = false;
+    double recVolume = 1.0;
+    int recType = SDRPP_REC_INT16;
 
 private:
     friend class IQFrontEnd;
@@ -162,6 +174,13 @@ private:
     int id = -1;
     std::vector<int> prevIds;  // handles this VFO had before its last re-plans (setInSamplerate / setOutSamplerate / a new demodulator): blocks pushed under them are still delivered
     std::string name;
+    std::mutex recLevelMtx;
+    dsp::stereo_t recLevel = { 0.0f, 0.0f };
+    void meter(const sdrpp_rec_info& info) {  // peak_level_meter.h:52-57 with the block's own peaks
+        std::lock_guard<std::mutex> lck(recLevelMtx);
+        if (info.peak_l > recLevel.l) { recLevel.l = info.peak_l; }
+        if (info.peak_r > recLevel.r) { recLevel.r = info.peak_r; }
+    }
 };
 
 class IQFrontEnd : public dsp::block {
@@ -325,6 +344,7 @@ public:
         rebuild(*v);
         registerOutput(&v->out);
         registerOutput(&v->audio);
+        registerOutput(&v->recorded);
         tempStart();
         return v;
     }
@@ -339,6 +359,7 @@ public:
         if (it->second->id >= 0) { sdrpp_vfo_remove(ctx, it->second->id); }
         unregisterOutput(&it->second->out);
         unregisterOutput(&it->second->audio);
+        unregisterOutput(&it->second->recorded);
         delete it->second;
         vfos.erase(it);
         tempStart();
@@ -781,7 +802,9 @@ private:
     // with streams bound AND a pre-processing chain in front — the pre-processed IQ (without a chain the bound streams get the input block itself)
     int pipelineFlags() const {
         const bool pre = _decimRatio > 1 || _dcBlocking || _invertIQ;
-        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0);
+        bool rec = false;
+        for (auto& kv : vfos) { rec = rec || (kv.second->recOn && kv.second->demod != Demod::RAW); }
+        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0);  // (a recorder adds its flag and drops nobody's: `audio` is delivered as before)
     }
     int enterPipelined() {
         if (sdrpp_sync(ctx)) { return -1; }  // (nothing is staged in bypass mode; a deferred pass left over from buffered mode runs here)
@@ -902,6 +925,29 @@ private:
                     }
                 }
             });
+        }
+        // the recorders: the block as the sink converted it (result flag 16), straight out of the slot; a silent block is metered and not handed on
+        if (pipeFlags & 16) {
+            for (auto& kv : vfos) {
+                RxVFO* v = kv.second;
+                if (!v->recOn) { continue; }
+                const void* data = nullptr;
+                sdrpp_rec_info info;
+                int rrc = sdrpp_result_rec(ctx, ticket, v->id, &data, &info);
+                for (size_t q = v->prevIds.size(); rrc == SDRPP_ERR_NOT_FOUND && q-- > 0;) { rrc = sdrpp_result_rec(ctx, ticket, v->prevIds[q], &data, &info); }
+                if (rrc) { continue; }  // (pushed before the recorder was attached)
+                v->meter(info);
+                const size_t bytes = (size_t)info.frames * recFrameBytes(info);
+                if (bytes > (size_t)STREAM_BUFFER_SIZE) {  // (nothing of this block has been handed to the helpers yet)
+                    sdrpp_result_release(ctx, ticket);
+                    return recTooLarge(*v, info);
+                }
+                if (info.silent || bytes == 0) { continue; }
+                jobs.emplace_back([this, v, data, bytes]() {
+                    memcpy(v->recorded.writeBuf, data, bytes);
+                    if (!v->recorded.swap((int)bytes)) { deliveryFailed = true; }
+                });
+            }
         }
         inflightTicket = ticket;
         helpers.begin(std::move(jobs));
@@ -1057,6 +1103,27 @@ private:
                 });
             }
         }
+        // the recorders: the pass through the sink, converted on the device, straight into the stream's buffer
+        for (auto& kv : vfos) {
+            RxVFO* v = kv.second;
+            if (!v->recOn || v->demod == Demod::RAW || v->id < 0) { continue; }
+            sdrpp_rec_info info;
+            sdrpp_rec_info cur;
+            cur.channels = v->recMono ? 1 : 2;
+            cur.sample_type = v->recType;
+            const int got = sdrpp_vfo_rec_read(ctx, v->id, v->recorded.writeBuf, STREAM_BUFFER_SIZE / (int)recFrameBytes(cur), &info);
+            if (got < 0) {
+                fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] reading the recorder sink failed: %s\n", sdrpp_last_error(ctx));
+                return -1;
+            }
+            if (got < info.frames) { return recTooLarge(*v, info); }
+            v->meter(info);
+            const int bytes = got * (int)recFrameBytes(info);
+            if (info.silent || bytes == 0) { continue; }
+            jobs.emplace_back([v, bytes, &failed]() {
+                if (!v->recorded.swap(bytes)) { failed = true; }
+            });
+        }
         helpers.run(std::move(jobs));
         if (failed) { return -1; }
         SDRPP_BLOCKS_TICK(6)
@@ -1184,6 +1251,26 @@ private:
         if (v.nbOn || v.squelchOn) { applyIF(v); }  // (the blanker's rate follows the IF rate: radio_module.h:526)
         if (oldId < 0 && (v.fmnrOn || v.fmnrBins != 32)) { applyFMNR(v); }  // (a replaced handle has it already: keep | 4)
         if (v.afOn && v.demod != Demod::RAW) { applyAF(v); }
+        if (v.recOn && v.demod != Demod::RAW) { applyRec(v); }  // (sdrpp_vfo_replace does not carry the sink: the recorder binds to the stream, and the stream lives on)
+    }
+
+    // `recorded` is a byte stream: its buffer holds STREAM_BUFFER_SIZE BYTES, an eighth of the frames `audio` holds as stereo floats.  A block is one swap
+    // (the silence decision is per block), so a block that does not fit is an error in either mode, never a truncation.
+    static size_t recFrameBytes(const sdrpp_rec_info& info) { return (size_t)info.channels * (info.sample_type == SDRPP_REC_UINT8 ? 1 : (info.sample_type == SDRPP_REC_INT16 ? 2 : 4)); }
+    int recTooLarge(const RxVFO& v, const sdrpp_rec_info& info) {
+        fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] recorder of VFO %s: a block of %d frames (%zu bytes) does not fit the stream buffer of %d bytes\n", v.name.c_str(), info.frames,
+                (size_t)info.frames * recFrameBytes(info), (int)STREAM_BUFFER_SIZE);
+        return -1;
+    }
+    void applyRec(RxVFO& v) {
+        sdrpp_rec_desc r;
+        memset(&r, 0, sizeof(r));
+        r.volume = (float)v.recVolume;
+        r.mono = v.recMono ? 1 : 0;
+        r.sample_type = v.recType;
+        r.ignore_silence = v.recIgnoreSilence ? 1 : 0;
+        int rc = sdrpp_vfo_set_rec(ctx, v.id, &r);
+        if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_rec: ") + sdrpp_last_error(ctx)); }
     }
 
     // radio_module.h:90-91: nb.init(NULL, 500.0 / ifRate, 10.0); powerSquelch.init(NULL, MIN_SQUELCH)
@@ -1510,6 +1597,33 @@ inline void RxVFO::detachAF() {
     afOn = false;
     if (id >= 0) { sdrpp_vfo_set_af(fe->ctx, id, nullptr); }
     fe->tempStart();
+}
+inline void RxVFO::attachRecorder(double volume, bool mono, int sampleType, bool ignoreSilence) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (sampleType != SDRPP_REC_UINT8 && sampleType != SDRPP_REC_INT16 && sampleType != SDRPP_REC_FLOAT32) { throw std::runtime_error("[sdrpp_gpu::RxVFO] recorder sample type must be UINT8 (0), INT16 (1) or FLOAT32 (3)"); }
+    fe->tempStop();  // recorder/src/main.cpp: the recorder's chain is stopped around every change of its settings
+    recOn = true;
+    recVolume = volume;
+    recMono = mono;
+    recType = sampleType;
+    recIgnoreSilence = ignoreSilence;
+    if (demod != Demod::RAW && id >= 0) { fe->applyRec(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::detachRecorder() {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    fe->tempStop();
+    recOn = false;
+    if (id >= 0) { sdrpp_vfo_set_rec(fe->ctx, id, nullptr); }
+    fe->tempStart();
+}
+inline dsp::stereo_t RxVFO::getRecorderLevel() {
+    std::lock_guard<std::mutex> lck(recLevelMtx);
+    return recLevel;
+}
+inline void RxVFO::resetRecorderLevel() {
+    std::lock_guard<std::mutex> lck(recLevelMtx);
+    recLevel = { 0.0f, 0.0f };
 }
 inline void RxVFO::setNoiseBlanker(bool enabled, double level) {
     std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
