@@ -378,6 +378,27 @@ int sdrpp_wf_latest(sdrpp_ctx* ctx, float* latest, float* hold);
 /* calculateVFOSignalInfo (:558-598) on the newest stored line: strength = max dB inside the VFO, snr = strength - mean of the two
  * half-bandwidth side bands.  Returns 1, or 0 while no line is stored. */
 int sdrpp_wf_signal_info(sdrpp_ctx* ctx, double center_offset, double bandwidth, double whole_bandwidth, float* strength, float* snr);
+/* ---- signal meters: calculateVFOSignalInfo for a TABLE of bands on EVERY raw line a push completes, inside the push's own launches ----
+ * sdrpp_wf_signal_info answers for one band on the newest stored line and has to drain a pipelined run to do so; a receiver that meters 32 to 128
+ * channels on every block sets a table instead.  Meter m is the band (descs[m].center_offset, descs[m].bandwidth) of a spectrum `whole_bandwidth`
+ * wide; for every line f of a push: out[f][m][0] = strength, out[f][m][1] = snr — the same arithmetic in the same summation order as
+ * sdrpp_wf_signal_info, so a line's values are bit-identical to what that call returns while the line is the newest of the history ring (which the
+ * meters do not need: they read the block's own lines).  Empty side bands (all four offsets in one bin, or a band at the lower edge whose side
+ * bands are clamped away on both sides) give snr = NaN, as the reference's 0.0 / 0.0 does.
+ * OUT-OF-BAND RULE (as for sdrpp_wf_signal_info): the four bin offsets are clamped to [0, fft_size]; for a band that reaches past
+ * +whole_bandwidth / 2 the reference reads one bin beyond the line (fftLine[rawFFTSize]), the device clamps that read to the last bin.
+ * Needs sdrpp_fft_configure (SDRPP_ERR_INVALID without).  n = 0 removes the table; n > SDRPP_MAX_METERS: SDRPP_ERR_UNSUPPORTED.  The table is kept
+ * as frequencies: sdrpp_fft_configure with another size keeps it and recomputes the offsets.  Setting a table is a configuration change (it
+ * flushes deferred pushes and sends a held launch group on its way) but does not drain a pipelined run: blocks already pushed keep the table they
+ * were pushed with — it travels with their job tables — and the new one applies from the next push. */
+#define SDRPP_MAX_METERS 1024
+typedef struct sdrpp_meter_desc { double center_offset, bandwidth; } sdrpp_meter_desc;
+int sdrpp_wf_set_meters(sdrpp_ctx* ctx, int n, const sdrpp_meter_desc* descs, double whole_bandwidth);
+/* Outside pipelined mode: the meters of the most recent push (pass), [n_lines][n_meters][2] floats, oldest line first.  *n_lines = 0 when the push
+ * completed no line or came before the table.  dst may be NULL to ask for the counts alone; more than max_lines lines: SDRPP_ERR_INVALID.  In
+ * pipelined mode the values come with the results (sdrpp_result_meters) and this call is SDRPP_ERR_INVALID. */
+int sdrpp_wf_meters_read(sdrpp_ctx* ctx, float* dst_host, int max_lines, int* n_lines, int* n_meters);
+int sdrpp_abi_sizeof_meter_desc(void);
 /* updateWaterfallFb: palette indices [height][data_width], newest line first, rows beyond the stored lines = -1 (opaque black). */
 int sdrpp_wf_raster(sdrpp_ctx* ctx, int draw_data_start, int draw_data_size, int data_width, float wf_min, float wf_max, int32_t* dst_host, int* n_lines);
 
@@ -527,6 +548,13 @@ int sdrpp_set_pipelined(sdrpp_ctx* ctx, int on, int result_flags);
  * sink was attached or without flag 16.  Blocks of a pipelined run that were processed as an ordinary pass deliver the same.  A call of its own, so
  * that sdrpp_result's layout and SDRPP_ABI_VERSION stay what they are. */
 int sdrpp_result_rec(sdrpp_ctx* ctx, uint64_t ticket, int id, const void** data, sdrpp_rec_info* info);
+/* Signal meters of push `ticket` (sdrpp_wf_set_meters): *data = [*n_lines][*n_meters][2] floats in the block's result slot, for the lines this push's
+ * own samples completed — the rows `zoomed` / `raw` give it — oldest first.  No result flag: while a table is set, EVERY pipelined block with the
+ * FFT on carries its meters (n_lines * n_meters * 8 bytes), result_flags = 0 included — sdrpp_result_wait / _release then work for such blocks.
+ * Valid between sdrpp_result_wait and sdrpp_result_release, else SDRPP_ERR_INVALID.  SDRPP_ERR_NOT_FOUND: the block was pushed before a table was
+ * set (or with the FFT off).  A block that completed no line: *n_lines = 0.  n_meters is the size of the table the block was pushed with.  Blocks
+ * of a pipelined run that were processed as an ordinary pass deliver the same.  Any of the three outputs may be NULL. */
+int sdrpp_result_meters(sdrpp_ctx* ctx, uint64_t ticket, const float** data, int* n_lines, int* n_meters);
 /* SEVERAL BLOCKS PER LAUNCH.  A launch costs the device a start ramp, a tail and the gap to the next one whatever the block holds, and the host one
  * plan: at the reference's block size (sample_rate / 200) that is most of a block's time, and a host that pushes faster than the device works
  * only makes the launch queue longer.  With max_blocks > 1 a push is HELD — nothing planned, nothing launched — until max_blocks pushes have come

@@ -114,6 +114,13 @@ class RecInfo(C.Structure):
     ]
 
 
+class MeterDesc(C.Structure):
+    """struct sdrpp_meter_desc (include/sdrpp_gpu.h): one band of the table of signal meters (sdrpp_wf_set_meters)."""
+
+    _fields_ = [("center_offset", C.c_double), ("bandwidth", C.c_double)]
+
+
+MAX_METERS = 1024   # SDRPP_MAX_METERS
 REC_UINT8, REC_INT16, REC_INT32, REC_FLOAT32 = 0, 1, 2, 3   # wav::SampleType (utils/wav.h:25-30)
 REC_DTYPES = {REC_UINT8: np.uint8, REC_INT16: np.int16, REC_FLOAT32: np.float32}
 
@@ -214,6 +221,12 @@ def load():
     L.sdrpp_vfo_set_rec.argtypes = [vp, C.c_int, C.POINTER(RecDesc)]
     L.sdrpp_vfo_rec_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(RecInfo)]
     L.sdrpp_result_rec.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(RecInfo)]
+    L.sdrpp_abi_sizeof_meter_desc.argtypes = []
+    if L.sdrpp_abi_sizeof_meter_desc() != C.sizeof(MeterDesc):
+        raise ImportError("sdrpp_meter_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_meter_desc(), C.sizeof(MeterDesc)))
+    L.sdrpp_wf_set_meters.argtypes = [vp, C.c_int, C.POINTER(MeterDesc), C.c_double]
+    L.sdrpp_wf_meters_read.argtypes = [vp, c_float_p, C.c_int, c_int_p, c_int_p]
+    L.sdrpp_result_meters.argtypes = [vp, C.c_uint64, C.POINTER(c_float_p), c_int_p, c_int_p]
     L.sdrpp_vfo_set_af.argtypes = [vp, C.c_int, C.POINTER(AfDesc)]
     L.sdrpp_vfo_af_count.argtypes = [vp, C.c_int]
     L.sdrpp_vfo_af_read.argtypes = [vp, C.c_int, c_float_p, C.c_int]
@@ -301,6 +314,7 @@ EXPORTED_SYMBOLS = [
     "sdrpp_design_phase_delta", "sdrpp_design_resampler", "sdrpp_design_waterfall_view", "sdrpp_design_deemphasis_alpha",
     "sdrpp_vfo_read_pcm", "sdrpp_vfo_read_compressed", "sdrpp_preproc_read_pcm",
     "sdrpp_wf_configure", "sdrpp_wf_set_smoothing", "sdrpp_wf_set_hold", "sdrpp_wf_latest", "sdrpp_wf_raster", "sdrpp_wf_signal_info",
+    "sdrpp_wf_set_meters", "sdrpp_wf_meters_read", "sdrpp_result_meters", "sdrpp_abi_sizeof_meter_desc",
     "sdrpp_preproc_configure", "sdrpp_preproc_reconfigure", "sdrpp_preproc_set_reference_order", "sdrpp_preproc_out_count", "sdrpp_preproc_read", "sdrpp_preproc_device_buffer",
     "sdrpp_vfo_set_rec", "sdrpp_vfo_rec_read", "sdrpp_abi_sizeof_rec_desc", "sdrpp_result_rec",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
@@ -567,6 +581,33 @@ class Context:
         a, b = C.c_float(), C.c_float()
         ok = self._chk(self.L.sdrpp_wf_signal_info(self.h, center_offset, bandwidth, whole_bandwidth, C.byref(a), C.byref(b)))
         return (a.value, b.value) if ok else None
+
+    def wf_set_meters(self, bands, whole_bandwidth):
+        """sdrpp_wf_set_meters: `bands` = (center_offset, bandwidth) pairs (radio.meter_table builds them from what vfo_desc takes); an empty list
+        removes the table.  From the next push on every line carries (strength, snr) of every band."""
+        bands = list(bands)
+        arr = (MeterDesc * max(len(bands), 1))()
+        for i, (off, bw) in enumerate(bands):
+            arr[i].center_offset, arr[i].bandwidth = float(off), float(bw)
+        self._chk(self.L.sdrpp_wf_set_meters(self.h, len(bands), arr, float(whole_bandwidth)))
+
+    def wf_meters(self):
+        """sdrpp_wf_meters_read (outside pipelined mode): the meters of the most recent push -> float32 [n_lines, n_meters, 2]."""
+        nl, nm = C.c_int(), C.c_int()
+        self._chk(self.L.sdrpp_wf_meters_read(self.h, None, 0, C.byref(nl), C.byref(nm)))
+        out = np.empty((nl.value, nm.value, 2), np.float32)
+        if out.size:
+            self._chk(self.L.sdrpp_wf_meters_read(self.h, out.ctypes.data_as(c_float_p), nl.value, C.byref(nl), C.byref(nm)))
+        return out
+
+    def result_meters(self, ticket):
+        """sdrpp_result_meters, between result_wait and result_release of that ticket -> a COPY, float32 [n_lines, n_meters, 2]."""
+        data = c_float_p()
+        nl, nm = C.c_int(), C.c_int()
+        self._chk(self.L.sdrpp_result_meters(self.h, int(ticket), C.byref(data), C.byref(nl), C.byref(nm)))
+        if nl.value == 0 or nm.value == 0:
+            return np.empty((nl.value, nm.value, 2), np.float32)
+        return np.ctypeslib.as_array(data, shape=(nl.value, nm.value, 2)).copy()
 
     def wf_raster(self, draw_start, draw_size, data_width, wf_min, wf_max):
         fb = np.empty((self.wf_height, data_width), np.int32)

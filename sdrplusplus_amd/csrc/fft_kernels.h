@@ -781,17 +781,33 @@ __global__ __launch_bounds__(256) void wf_trace_kernel(const float* __restrict__
 
 // calculateVFOSignalInfo (waterfall.cpp:558-598) on one raw line: out[0] = max over [o1, o2], out[1] = max - mean of [o0, o1) and (o2, o3)
 // (double accumulation; a tree instead of the reference's bin order: the double sums agree to ~1e-13 relative, the float snr to 1 ulp).
-__global__ __launch_bounds__(256) void wf_signal_info_kernel(const float* __restrict__ line, int o0, int o1, int o2, int o3, float* __restrict__ out) {
-    __shared__ double ssum[256];
-    __shared__ float smax[256];
+// One body for the single query and for the meter bank: 256 lanes stride over the bins, then the same tree in LDS — a band's value for a
+// line does not depend on which of the two asked.  Empty side bands (cnt == 0) stay 0.0 / 0.0: snr is NaN, as in the reference.
+// ssum: 256 doubles, smax: 256 floats of LDS.  The offsets are values in registers: no load depends on another one.
+#define SDRPP_WF_METER_LDS (256 * (sizeof(double) + sizeof(float)))
+// 256 lanes stride over the bins [lo, hi) of a line with up to U loads in flight per lane, consumed in index order: the order — and so every bit — of
+// the plain loop `for (i = lo + lane; i < hi; i += 256)`, at one trip to memory per U x 256 bins instead of one per 256 (a WFM channel on a 65536-point
+// line is 2 000 bins: eight dependent trips made a (meter, line) pair 6 us of pure latency)
+template <int U, class F>
+__device__ __forceinline__ void wf_stride_bins(const float* __restrict__ line, int lo, int hi, F&& use) {
+    for (int i = lo + (int)threadIdx.x; i < hi; i += 256 * U) {
+        float v[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) { v[u] = (i + 256 * u < hi) ? line[i + 256 * u] : 0.0f; }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (i + 256 * u < hi) { use(v[u]); }
+        }
+    }
+}
+__device__ __forceinline__ void wf_signal_info_body(const float* __restrict__ line, int o0, int o1, int o2, int o3, double* ssum, float* smax, float* __restrict__ out) {
     double acc = 0.0;
     float m = __uint_as_float(0xff800000u);
-    for (int i = o0 + threadIdx.x; i < o1; i += 256) { acc += (double)line[i]; }
-    for (int i = o2 + 1 + threadIdx.x; i < o3; i += 256) { acc += (double)line[i]; }
-    for (int i = o1 + threadIdx.x; i <= o2; i += 256) {
-        const float v = line[i];
+    wf_stride_bins<8>(line, o0, o1, [&](float v) { acc += (double)v; });
+    wf_stride_bins<8>(line, o2 + 1, o3, [&](float v) { acc += (double)v; });
+    wf_stride_bins<8>(line, o1, o2 + 1, [&](float v) {
         if (v > m) { m = v; }
-    }
+    });
     ssum[threadIdx.x] = acc;
     smax[threadIdx.x] = m;
     __syncthreads();
@@ -808,6 +824,31 @@ __global__ __launch_bounds__(256) void wf_signal_info_kernel(const float* __rest
         out[0] = smax[0];
         out[1] = (float)((double)smax[0] - avg);
     }
+}
+__global__ __launch_bounds__(256) void wf_signal_info_kernel(const float* __restrict__ line, int o0, int o1, int o2, int o3, float* __restrict__ out) {
+    __shared__ double ssum[256];
+    __shared__ float smax[256];
+    wf_signal_info_body(line, o0, o1, o2, o3, ssum, smax, out);
+}
+// The meter bank (sdrpp_wf_set_meters): `offs[m]` = the four clamped bin offsets of meter m (0 <= o0 <= o1 <= o2 < fft_size, o2 <= o3 <= fft_size:
+// wf_meter_offsets on the host), out[line][meter][2] = (strength, snr) for every raw line of the block.  Grid (ceil(n_meters / per_wg), n_lines):
+// a pair is a few microseconds of load latency and next to no arithmetic, so a workgroup WALKS `per_wg` meters of its line one after the other
+// (tick_kernels.h: tick_zoom) instead of holding a workgroup slot per pair.  sm: SDRPP_WF_METER_LDS bytes, 8-byte aligned.
+struct alignas(16) WfMeterOffs { int o0, o1, o2, o3; };
+__device__ __forceinline__ void wf_meter_body(const KIdx bid, float* sm, const float* __restrict__ lines, int fft_size, const WfMeterOffs* __restrict__ offs, int n_meters, int per_wg, float* __restrict__ out) {
+    double* ssum = reinterpret_cast<double*>(sm);
+    float* smax = reinterpret_cast<float*>(ssum + 256);
+    const float* line = lines + (size_t)bid.y * fft_size;
+    const int m0 = bid.x * per_wg, m1 = m0 + per_wg < n_meters ? m0 + per_wg : n_meters;
+    for (int m = m0; m < m1; m++) {
+        if (m > m0) { __syncthreads(); }  // the previous pair's totals have been read
+        const WfMeterOffs o = offs[m];
+        wf_signal_info_body(line, o.o0, o.o1, o.o2, o.o3, ssum, smax, out + ((size_t)bid.y * n_meters + m) * 2);
+    }
+}
+__global__ __launch_bounds__(256) void wf_meter_kernel(const float* __restrict__ lines, int fft_size, const WfMeterOffs* __restrict__ offs, int n_meters, int per_wg, float* __restrict__ out) {
+    __shared__ double sm[SDRPP_WF_METER_LDS / sizeof(double)];
+    wf_meter_body(kidx(blockIdx), reinterpret_cast<float*>(sm), lines, fft_size, offs, n_meters, per_wg, out);
 }
 
 // ---- sink-side sample packing: f32 -> int16 / int8 on the device, so the D2H copy carries 2 or 1 byte per value ----

@@ -215,6 +215,18 @@ struct sdrpp_ctx {
         float alpha = 0.0f, beta = 1.0f, hold_speed = 0.0f;
     } wf;
 
+    // signal meters (sdrpp_wf_set_meters): a table of bands, evaluated on every raw line a push completes (fft_kernels.h: wf_meter_body)
+    struct Meters {
+        std::vector<sdrpp_meter_desc> descs;  // the bands as frequencies: the table survives a change of the FFT size
+        double whole_bandwidth = 0.0;
+        std::vector<WfMeterOffs> offs;        // ... and as bin offsets at the current FFT size (wf_meter_offsets); pipelined blocks carry a copy among their job tables
+        WfMeterOffs* d_offs = nullptr;        // the same in device memory, for ordinary passes
+        float* d_out = nullptr;               // [lines][n][2] of the most recent ordinary pass
+        size_t out_cap = 0;                   // floats
+        int out_lines = 0, out_n = 0;         // what d_out holds
+        int n() const { return (int)descs.size(); }
+    } meters;
+
     char* d_pack = nullptr;  // scratch of the packed-sample reads (sdrpp_vfo_read_pcm / _compressed)
     size_t pack_cap = 0;
     float2* d_gather = nullptr;     // sdrpp_vfo_read_many: packed outputs + job table
@@ -296,6 +308,8 @@ struct sdrpp_ctx {
         int n_iq = 0;                                        // pre-processed IQ samples delivered (result flag 8)
         std::vector<int> rec_ids;                            // result flag 16: the VFOs that had a recorder sink when the block was planned,
         std::vector<size_t> rec_off, rec_info_off;           // ... where this push's converted samples and its sdrpp_rec_info lie in the slot
+        int n_meters = -1;                                   // signal meters the block was pushed with (-1: no table then); its n_lines x n_meters x 2 floats
+        size_t off_meters = 0;
     };
     bool pipelined = false;
     int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks

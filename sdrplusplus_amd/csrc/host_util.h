@@ -527,7 +527,10 @@ void launch_role(sdrpp_ctx* c, const sdrpp_ctx::RoleLaunch& r) {
     case TR_DEEMP_P1: hipLaunchKernelGGL((vfo_deemph_kernel<0, 1>), grid, b256, 0, st, (const DeempJob*)e.jobs); break;
     case TR_DC_P0: hipLaunchKernelGGL((vfo_deemph_kernel<1, 0>), grid, b256, 0, st, (const DeempJob*)e.jobs); break;
     case TR_DC_P1: hipLaunchKernelGGL((vfo_deemph_kernel<1, 1>), grid, b256, 0, st, (const DeempJob*)e.jobs); break;
-    case TR_WF_RING: hipLaunchKernelGGL(wf_ring_store_kernel, grid, b256, 0, st, e.p.wf.src, e.p.wf.n0, e.p.wf.n1, e.p.wf.a, e.p.wf.n2, e.p.wf.n3); break;
+    case TR_WF_RING:
+        if (e.aux > 0) { hipLaunchKernelGGL(wf_meter_kernel, grid, b256, 0, st, e.p.wf.src, e.p.wf.n1, (const WfMeterOffs*)e.jobs, e.p.wf.n2, e.aux, e.p.wf.a); }  // (its signal-meter form: emit_meter)
+        else { hipLaunchKernelGGL(wf_ring_store_kernel, grid, b256, 0, st, e.p.wf.src, e.p.wf.n0, e.p.wf.n1, e.p.wf.a, e.p.wf.n2, e.p.wf.n3); }
+        break;
     case TR_WF_TRACE: hipLaunchKernelGGL(wf_trace_kernel, grid, b256, 0, st, e.p.wf.src, e.p.wf.n0, e.p.wf.n1, e.p.wf.a, e.p.wf.b, e.p.wf.f0, e.p.wf.f1, e.p.wf.c, e.p.wf.f2); break;
     default: break;  // (the FFT branch launches its kernels itself outside pipelined mode: its pass-1 workgroups are wider there)
     }
@@ -565,6 +568,28 @@ void emit_wf(sdrpp_ctx* c, int level, int fam, int role, int gx, int gy, const T
     if (c->tick_planning) { c->emits.push_back(r); }
     else {
         count_form(c, role);
+        launch_role(c, r);
+    }
+}
+
+// ... and for the signal meters, the second form of TR_WF_RING (aux > 0; not a role of its own: the published role list stays what it is): `lines` = the
+// block's raw lines, `offs` = the table of n_meters bands in device memory, `per_wg` meters walked by one workgroup, out[n_lines][n_meters][2]
+void emit_meter(sdrpp_ctx* c, int level, int n_lines, const WfMeterOffs* offs, int per_wg, const float* lines, int fft_size, int n_meters, float* out, bool to_host) {
+    if (n_lines <= 0 || n_meters <= 0 || per_wg <= 0) { return; }
+    sdrpp_ctx::RoleLaunch r{};
+    r.e.role = TR_WF_RING;
+    r.e.gx = (n_meters + per_wg - 1) / per_wg;
+    r.e.gy = n_lines;
+    r.e.aux = per_wg;
+    r.e.jobs = offs;
+    r.e.p.wf = TickWf{ lines, out, nullptr, nullptr, n_lines, fft_size, n_meters, 0, 0.0f, 0.0f, 0.0f, 0.0f };
+    r.lds = SDRPP_WF_METER_LDS;
+    r.level = level;
+    r.fam = F_ZOOM;
+    r.to_host = to_host;
+    if (c->tick_planning) { c->emits.push_back(r); }
+    else {
+        count_form(c, TR_WF_RING);
         launch_role(c, r);
     }
 }

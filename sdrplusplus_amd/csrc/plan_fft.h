@@ -308,8 +308,63 @@ int plan_wf_state(sdrpp_ctx* c, int nframes, int level) {
     return SDRPP_OK;
 }
 
+// ---- signal meters (sdrpp_wf_set_meters; fft_kernels.h: wf_signal_info_body / wf_meter_body) -----------------------------------------
+// calculateVFOSignalInfo's four bin offsets (waterfall.cpp:566-577) of a band on a line of N bins, clamped to [0, N] as there; the reference then reads
+// fftLine[N] for a band that reaches past the upper edge: the device clamps that one to the last bin.  The one place the rule lives: the
+// single query and the table both come here.  Whatever the frequencies are, every bin the kernel touches lies in [0, N).
+inline WfMeterOffs wf_meter_offsets(double center_offset, double bandwidth, double whole_bandwidth, int N) {
+    const double f[4] = { center_offset - bandwidth, center_offset - (bandwidth / 2.0), center_offset + (bandwidth / 2.0), center_offset + bandwidth };
+    int off[4];
+    for (int i = 0; i < 4; i++) {
+        const double x = ((f[i] / (whole_bandwidth / 2.0)) * (double)(N / 2)) + (N / 2);
+        const int v = x >= (double)N ? N : (x > 0.0 ? (int)x : 0);  // (= the reference's (int) conversion followed by its clamp; a NaN ends at 0)
+        off[i] = std::min(std::max(v, 0), N);
+    }
+    if (off[2] >= N) { off[2] = N - 1; }
+    return WfMeterOffs{ off[0], off[1], off[2], off[3] };
+}
+// the table at the current FFT size, on the host and (for ordinary passes) in device memory
+int meters_rebuild(sdrpp_ctx* c) {
+    sdrpp_ctx::Meters& M = c->meters;
+    M.offs.clear();
+    M.out_lines = 0;
+    M.out_n = M.n();
+    if (M.n() == 0 || !c->fft_on) { return SDRPP_OK; }
+    for (auto& d : M.descs) { M.offs.push_back(wf_meter_offsets(d.center_offset, d.bandwidth, M.whole_bandwidth, c->fft_size)); }
+    if (!M.d_offs) {
+        int rc = dev_alloc(c, &M.d_offs, (size_t)SDRPP_MAX_METERS);
+        if (rc) { return rc; }
+    }
+    HIPCHK(c, hipMemcpy(M.d_offs, M.offs.data(), M.offs.size() * sizeof(WfMeterOffs), hipMemcpyHostToDevice));
+    return SDRPP_OK;
+}
+inline bool meters_active(const sdrpp_ctx* c) { return c->fft_on && !c->meters.offs.empty(); }
+// meters one workgroup walks: one while the block has few (meter, line) pairs, up to 4 once there are hundreds (a pair is a few microseconds of
+// latency: the walk keeps the role's workgroups few without making them the longest of their tick)
+inline int meters_per_wg(int n_lines, int n_meters) { return std::max(1, std::min(std::min(4, n_meters), (int)((long long)n_lines * n_meters / 128))); }
+// an ordinary pass: the meters of the block's lines behind the lines themselves, into the context's own output array
+int run_meters(sdrpp_ctx* c, int nframes) {
+    sdrpp_ctx::Meters& M = c->meters;
+    const int n = (int)M.offs.size();
+    const size_t need = (size_t)nframes * n * 2;
+    if (need > M.out_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        dev_free(M.d_out);
+        M.out_cap = 0;
+        int rc = dev_alloc(c, &M.d_out, need);
+        if (rc) { return rc; }
+        M.out_cap = need;
+    }
+    FamilyTimer t(c, F_ZOOM);
+    emit_meter(c, 1, nframes, M.d_offs, meters_per_wg(nframes, n), c->d_lines, c->fft_size, n, M.d_out, false);
+    M.out_lines = nframes;
+    M.out_n = n;
+    return SDRPP_OK;
+}
+
 int do_fft(sdrpp_ctx* c, const IqSrc& src, int64_t count) {
     c->n_lines = 0;
+    if (!c->tick_planning) { c->meters.out_lines = 0; }
     if (!c->fft_on) { return SDRPP_OK; }
     c->plan_fft_pos0 = c->fft_pos;
     c->plan_fft_next0 = c->fft_next;
@@ -383,6 +438,10 @@ int do_fft(sdrpp_ctx* c, const IqSrc& src, int64_t count) {
         }
         if (c->wf.height > 0) {
             int rc = plan_wf_state(c, (int)nframes, 1);
+            if (rc) { return rc; }
+        }
+        if (meters_active(c)) {
+            int rc = run_meters(c, (int)nframes);
             if (rc) { return rc; }
         }
         c->fft_next += nframes;

@@ -48,6 +48,7 @@ void plan_restore(sdrpp_ctx* c, const PlanSnapshot& S) {
     }
     c->fft_pos = S.fft_pos; c->fft_next = S.fft_next; c->n_lines = S.n_lines; c->iq_cur = S.iq_cur;
     c->wf.cur = S.wf_cur; c->wf.lines = S.wf_lines; c->wf.have_latest = S.wf_have;
+    c->meters.out_lines = 0;  // (the meters' output array may have been overwritten: it holds no push's lines now)
     for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { c->pre.soff[k] = S.pre_soff[k]; }
     c->pre.state_cur = S.pre_state;
     c->pre.raw.cur = S.pre_raw_cur;

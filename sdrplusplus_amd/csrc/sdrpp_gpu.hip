@@ -377,6 +377,8 @@ int sdrpp_destroy(sdrpp_ctx* c) {
 #endif
     preproc_free(c);
     wf_free(c);
+    dev_free(c->meters.d_offs);
+    dev_free(c->meters.d_out);
     dev_free(c->d_pack);
     dev_free(c->d_gather);
     dev_free(c->d_gather_jobs);
@@ -536,6 +538,8 @@ int sdrpp_fft_configure(sdrpp_ctx* c, int fft_size, int nz, int skip, const floa
     c->fft_next = 0;
     c->n_lines = 0;
     c->fft_on = true;
+    rc = meters_rebuild(c);  // the table of signal meters is kept as frequencies: its bin offsets follow the size
+    if (rc) { return rc; }
     if (c->data_width > 0) { return sdrpp_fft_set_view(c, c->view_start, c->view_size, c->data_width, c->wf_min, c->wf_max); }
     return SDRPP_OK;
 }
@@ -992,18 +996,12 @@ int sdrpp_wf_signal_info(sdrpp_ctx* c, double center_offset, double bandwidth, d
     if (W.height <= 0) { return fail(c, SDRPP_ERR_INVALID, "no waterfall history configured (sdrpp_wf_configure)"); }
     if (W.lines <= 0) { return 0; }  // the reference returns false: nothing to measure yet
     const int N = c->fft_size;
-    const double f[4] = { center_offset - bandwidth, center_offset - (bandwidth / 2.0), center_offset + (bandwidth / 2.0), center_offset + bandwidth };
-    int off[4];
-    for (int i = 0; i < 4; i++) {
-        const int v = (int)(((f[i] / (whole_bandwidth / 2.0)) * (double)(N / 2)) + (N / 2));
-        off[i] = std::min(std::max(v, 0), N);
-    }
-    if (off[2] >= N) { off[2] = N - 1; }  // the reference reads fftLine[rawFFTSize] here; clamp to the last bin
+    const WfMeterOffs o = wf_meter_offsets(center_offset, bandwidth, whole_bandwidth, N);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->fft_stream) { HIPCHK(c, hipStreamSynchronize(c->fft_stream)); }
     int rc = pack_scratch(c, 64);
     if (rc) { return rc; }
-    hipLaunchKernelGGL(wf_signal_info_kernel, dim3(1), dim3(256), 0, c->stream, (const float*)(W.d_ring + (size_t)W.cur * N), off[0], off[1], off[2], off[3], (float*)c->d_pack);
+    hipLaunchKernelGGL(wf_signal_info_kernel, dim3(1), dim3(256), 0, c->stream, (const float*)(W.d_ring + (size_t)W.cur * N), o.o0, o.o1, o.o2, o.o3, (float*)c->d_pack);
     float out[2];
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, c->d_pack, sizeof(out), hipMemcpyDeviceToHost));
@@ -1011,6 +1009,46 @@ int sdrpp_wf_signal_info(sdrpp_ctx* c, double center_offset, double bandwidth, d
     *snr = out[1];
     return 1;
 }
+
+// ---- signal meters: a table of bands on every line of every push (plan_fft.h: wf_meter_offsets / run_meters; tick_host.h: the result slots) ----
+int sdrpp_wf_set_meters(sdrpp_ctx* c, int n, const sdrpp_meter_desc* descs, double whole_bandwidth) {
+    DeviceScope dev_scope_(c);
+    if (!c || n < 0 || (n > 0 && !descs)) { return SDRPP_ERR_INVALID; }
+    if (!c->fft_on) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_wf_set_meters: no FFT configured (sdrpp_fft_configure)"); }
+    if (n > SDRPP_MAX_METERS) { return fail(c, SDRPP_ERR_UNSUPPORTED, "sdrpp_wf_set_meters: %d meters, at most %d", n, SDRPP_MAX_METERS); }
+    if (n > 0 && !(whole_bandwidth > 0.0 && std::isfinite(whole_bandwidth))) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_wf_set_meters: whole_bandwidth %g", whole_bandwidth); }
+    for (int i = 0; i < n; i++) {
+        if (!std::isfinite(descs[i].center_offset) || !std::isfinite(descs[i].bandwidth)) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_wf_set_meters: meter %d is not a finite band", i); }
+    }
+    // what has been pushed keeps the table it was pushed with: deferred pushes are processed, a held launch group goes out — the tick queue of a
+    // pipelined run is left alone (its blocks carry their own copy of the table)
+    int rc = flush_pending_opt(c, 0);
+    if (rc) { return rc; }
+    if (!c->pipelined) {  // an ordinary pass in flight reads the device copy
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->fft_stream) { HIPCHK(c, hipStreamSynchronize(c->fft_stream)); }
+    }
+    c->meters.descs.assign(descs, descs + n);
+    c->meters.whole_bandwidth = n > 0 ? whole_bandwidth : 0.0;
+    return meters_rebuild(c);
+}
+int sdrpp_wf_meters_read(sdrpp_ctx* c, float* dst, int max_lines, int* n_lines, int* n_meters) {
+    DeviceScope dev_scope_(c);
+    if (!c || max_lines < 0) { return SDRPP_ERR_INVALID; }
+    if (c->pipelined) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_wf_meters_read: in pipelined mode the meters come with the results (sdrpp_result_meters)"); }
+    FLUSH_PENDING(c);
+    const sdrpp_ctx::Meters& M = c->meters;
+    const int lines = (M.out_n > 0 && M.out_lines == c->n_lines) ? M.out_lines : 0;
+    if (n_lines) { *n_lines = lines; }
+    if (n_meters) { *n_meters = M.n(); }
+    if (!dst || lines == 0) { return SDRPP_OK; }
+    if (lines > max_lines) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_wf_meters_read: the push completed %d lines, room for %d", lines, max_lines); }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->fft_stream) { HIPCHK(c, hipStreamSynchronize(c->fft_stream)); }
+    HIPCHK(c, hipMemcpy(dst, M.d_out, (size_t)lines * M.out_n * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return SDRPP_OK;
+}
+int sdrpp_abi_sizeof_meter_desc(void) { return (int)sizeof(sdrpp_meter_desc); }
 
 int sdrpp_set_reference_block(sdrpp_ctx* c, int ref_block) {
     DeviceScope dev_scope_(c);
@@ -1538,6 +1576,16 @@ int sdrpp_result_rec(sdrpp_ctx* c, uint64_t ticket, int id, const void** data, s
         return SDRPP_OK;
     }
     return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of a recorder sink of VFO %d", (unsigned long long)ticket, id);
+}
+int sdrpp_result_meters(sdrpp_ctx* c, uint64_t ticket, const float** data, int* n_lines, int* n_meters) {
+    if (!c) { return SDRPP_ERR_INVALID; }
+    sdrpp_ctx::Result* R = result_of(c, ticket);
+    if (!R || !R->held) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_result_meters: block %llu is not held (between sdrpp_result_wait and sdrpp_result_release)", (unsigned long long)ticket); }
+    if (R->n_meters < 0) { return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu was pushed without a table of signal meters", (unsigned long long)ticket); }
+    if (data) { *data = R->n_lines > 0 ? reinterpret_cast<const float*>(R->base + R->off_meters) : nullptr; }
+    if (n_lines) { *n_lines = R->n_lines; }
+    if (n_meters) { *n_meters = R->n_meters; }
+    return SDRPP_OK;
 }
 int sdrpp_result_release(sdrpp_ctx* c, uint64_t ticket) {
     if (!c || ticket == 0 || ticket > c->pushes) { return c ? SDRPP_ERR_NOT_FOUND : SDRPP_ERR_INVALID; }

@@ -276,6 +276,7 @@ size_t tick_results_need(sdrpp_ctx* c) {
     if (c->fft_on) {
         if ((c->res_flags & 2) && c->data_width > 0) { need += 2 * ((c->lines_cap * (size_t)c->data_width * 4 + 15) & ~(size_t)15); }
         if (c->res_flags & 4) { need += (c->lines_cap * (size_t)c->fft_size * 4 + 15) & ~(size_t)15; }
+        need += (c->lines_cap * c->meters.offs.size() * 8 + 15) & ~(size_t)15;  // signal meters: no flag, every block carries them while a table is set
     }
     return need;
 }
@@ -356,6 +357,7 @@ sdrpp_ctx::ResRegion* tick_results_region(sdrpp_ctx* c, uint64_t gid) {
 // Every VFO's output block of the group lies in the group's result slot in one piece; push j's share of it is the samples between the push ends
 // carried down the VFO's chain (Vfo::tk_if / tk_af, plan_vfo.h), its lines the frames whose last sample arrived with it.
 struct ResCopy { const void* src; size_t off; size_t bytes; int level; };
+struct ResMeter { int n_lines = 0, n = 0; size_t off = 0; int level = 0; };  // the signal meters of the block's lines (n == 0: none)
 struct ResRec { const float* src; int n; size_t off, info_off; float gain; int mono, type, ignore_silence; int level; };  // a recorder sink's share of a push (result flag 16)
 inline RecJob rec_job(const ResRec& q, char* base) { return RecJob{ reinterpret_cast<const float2*>(q.src), base + q.off, base + q.info_off, q.n, q.gain, q.mono, q.type, q.ignore_silence, 0 }; }
 int64_t tick_frames_by(const sdrpp_ctx* c, int64_t e) {  // lines complete once the first `e` samples of the block just planned are in (do_fft's own count)
@@ -363,11 +365,12 @@ int64_t tick_frames_by(const sdrpp_ctx* c, int64_t e) {  // lines complete once 
     const int64_t a = c->plan_fft_pos0 + e - c->nz - c->plan_fft_next0 * P;
     return a >= 0 ? a / P + 1 : 0;
 }
-int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vector<ResCopy>& copies, std::vector<ResRec>& recs, size_t* region_off) {
+int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vector<ResCopy>& copies, std::vector<ResRec>& recs, ResMeter& meter, size_t* region_off) {
     copies.clear();
     recs.clear();
+    meter = ResMeter{};
     *region_off = 0;
-    if (!c->res_flags) {
+    if (!c->res_flags && !meters_active(c)) {
         for (int j = 0; j < k; j++) {
             sdrpp_ctx::Result& R0 = c->res[(first_ticket + (uint64_t)j) % kResMeta];
             if (!R0.held) { R0 = sdrpp_ctx::Result{}; }
@@ -438,6 +441,17 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
             off += (bytes + 15) & ~(size_t)15;
         }
     }
+    if (meters_active(c)) {  // one row of n (strength, snr) pairs per line, in line order: push j's share starts at its first line
+        const size_t n = c->meters.offs.size(), row = n * 8;
+        for (int j = 0; j < k; j++) {
+            R[j]->n_meters = (int)n;
+            R[j]->off_meters = off + (size_t)lo_lines[j] * row;
+        }
+        if (n_lines > 0) {
+            meter = ResMeter{ n_lines, (int)n, off, c->plan_lvl0 + (c->fft_lg <= 12 ? 1 : (c->fft_lg <= 16 ? 2 : 3)) + 1 };
+            off += ((size_t)n_lines * row + 15) & ~(size_t)15;
+        }
+    }
     if (c->res_flags & 16) {
         // every recorder sink: the group's converted block in one piece (push j's share: frames [tk[j - 1], tk[j]) of it), then one record per push
         for (auto& kv : c->vfos) {
@@ -474,10 +488,17 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
 int tick_results_plan(sdrpp_ctx* c, uint64_t first_ticket, int k) {
     static thread_local std::vector<ResCopy> copies;
     static thread_local std::vector<ResRec> recs;
+    ResMeter meter;
     size_t region = 0;
-    int rc = tick_results_describe(c, first_ticket, k, copies, recs, &region);
-    if (rc || (copies.empty() && recs.empty())) { return rc; }
+    int rc = tick_results_describe(c, first_ticket, k, copies, recs, meter, &region);
+    if (rc || (copies.empty() && recs.empty() && meter.n == 0)) { return rc; }
     char* base = c->res_ring_dev + region;
+    if (meter.n > 0) {  // the signal meters: TR_WF_RING's second form at the level that role reads the raw lines at (and the raw-line gather), straight into the slot; the table travels with the block
+        const WfMeterOffs* d_offs = arena_push(c, c->meters.offs);
+        if (!d_offs) { return fail(c, SDRPP_ERR_UNSUPPORTED, "job arena exhausted"); }
+        emit_meter(c, meter.level, meter.n_lines, d_offs, meters_per_wg(meter.n_lines, meter.n), c->d_lines, c->fft_size, meter.n, reinterpret_cast<float*>(base + meter.off), true);
+        c->plan_top = std::max(c->plan_top, meter.level + 1);
+    }
     if (!recs.empty()) {  // the recorder sinks: jobs of the copy role (kind 3), one workgroup each, at the level the float gather of the same stream stands at
         Lev<RecJob> rj;
         Lev<CopyJob> cj;
@@ -517,10 +538,15 @@ int tick_results_direct(sdrpp_ctx* c, uint64_t first_ticket, int k) {
     if (rc) { return rc; }
     static thread_local std::vector<ResCopy> copies;
     static thread_local std::vector<ResRec> recs;
+    ResMeter meter;
     size_t region = 0;
-    rc = tick_results_describe(c, first_ticket, k, copies, recs, &region);
+    rc = tick_results_describe(c, first_ticket, k, copies, recs, meter, &region);
     if (rc) { return rc; }
     char* base = c->res_ring + region;
+    if (meter.n > 0) {  // (the pass has left them in the context's own array: run_meters)
+        if (c->meters.out_lines != meter.n_lines || c->meters.out_n != meter.n) { return fail(c, SDRPP_ERR_INVALID, "internal: meters of %d lines x %d, results of %d x %d", c->meters.out_lines, c->meters.out_n, meter.n_lines, meter.n); }
+        HIPCHK(c, hipMemcpyAsync(base + meter.off, c->meters.d_out, (size_t)meter.n_lines * meter.n * 8, hipMemcpyDeviceToHost, c->stream));
+    }
     for (auto& q : copies) { HIPCHK(c, hipMemcpyAsync(base + q.off, q.src, q.bytes, hipMemcpyDeviceToHost, c->stream)); }
     for (auto& q : recs) {
         hipLaunchKernelGGL(vfo_rec_kernel, dim3(1), dim3(256), 0, c->stream, rec_job(q, c->res_ring_dev + region));
@@ -591,7 +617,7 @@ int tick_push(sdrpp_ctx* c, const float* d_iq, int64_t count, const CopyJob* lan
             }
         }
         int rc = fft_ring_ensure(c);
-        if (!rc && c->res_flags) { rc = tick_results_ensure(c); }
+        if (!rc && (c->res_flags || meters_active(c))) { rc = tick_results_ensure(c); }
         if (rc) { return rc; }
     }
     c->groups++;
@@ -685,7 +711,7 @@ int tick_push(sdrpp_ctx* c, const float* d_iq, int64_t count, const CopyJob* lan
         if (!rc) { rc = push_common(c, d_iq_raw, count_raw, k > 1 ? ends : nullptr); }
         // its results are where an ordinary pass leaves them (device buffers, readable after a synchronisation) and — with result flags —
         // also in the block's result slot like every other block's
-        if (!rc && c->res_flags) { rc = tick_results_direct(c, first_ticket, k); }
+        if (!rc && (c->res_flags || meters_active(c))) { rc = tick_results_direct(c, first_ticket, k); }
         else {
             for (int j = 0; j < k; j++) {
                 sdrpp_ctx::Result& R = c->res[(first_ticket + (uint64_t)j) % kResMeta];

@@ -124,6 +124,7 @@ enum TickRole : int {
     TR_DEEMP_P0, TR_DEEMP_P1,  // DeempJob[gy]: vfo_deemph_body<0, 0 / 1> (de-emphasis: segment maps, then the outputs one level later)
     TR_DC_P0, TR_DC_P1,        // DeempJob[gy]: vfo_deemph_body<1, 0 / 1> (the front end's DC blocker)
     TR_WF_RING, TR_WF_TRACE,   // p.wf: raw lines into the waterfall's ring; FFT trace smoothing / hold over the block's zoomed lines
+                               // TR_WF_RING with aux > 0: the other reader of the block's raw lines, the signal meters — jobs = WfMeterOffs[n2], aux = meters a workgroup walks (wf_meter_body)
     TR_PIPE,       // PipeJob[gy], gx = segments per VFO: vfo_pipe_kernel<1> — an FM back end (last decimator, resampler, channel filter, discriminator + audio low-pass) in ONE launch (ordinary passes only: the planner never puts it into a tick)
     // reference-rotator VFOs (sdrpp_vfo_desc.nco_mode = 2) inside a pipelined bank (round 5): the chain bounds the tick, every VFO's results stay pipelined
     TR_ROTX16,     // RotXHead (jobs), p.src, gx = workgroups of `vpw` VFOs: vfo_rotate_exact4_body<16> — the reference's float rotator recursion at the full rate
@@ -367,7 +368,11 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : 3) void tick_kernel(TickL0 l0, 
             case TR_DEEMP_P1: vfo_deemph_body<0, 1>(bid, smem, reinterpret_cast<const DeempJob*>(e_jobs)); break;
             case TR_DC_P0: vfo_deemph_body<1, 0>(bid, smem, reinterpret_cast<const DeempJob*>(e_jobs)); break;
             case TR_DC_P1: vfo_deemph_body<1, 1>(bid, smem, reinterpret_cast<const DeempJob*>(e_jobs)); break;
-            case TR_WF_RING: { const TickWf q = e.p.wf; wf_ring_store_body(bid, gdim, q.src, q.n0, q.n1, q.a, q.n2, q.n3); } break;
+            case TR_WF_RING: {
+                const TickWf q = e.p.wf;
+                if (e_aux > 0) { wf_meter_body(bid, smem, q.src, q.n1, reinterpret_cast<const WfMeterOffs*>(e_jobs), q.n2, e_aux, q.a); }  // (uniform over the workgroup)
+                else { wf_ring_store_body(bid, gdim, q.src, q.n0, q.n1, q.a, q.n2, q.n3); }
+            } break;
             case TR_WF_TRACE: { const TickWf q = e.p.wf; wf_trace_body(bid, q.src, q.n0, q.n1, q.a, q.b, q.f0, q.f1, q.c, q.f2); } break;
             // (the planner never puts TR_PIPE into a tick.  The case stays because the kernel's register allocation depends on it: without it
             // tick_kernel<0> took 168 registers instead of 167 and cfg 3's tick at 10^6-sample blocks 46.5 instead of 45.7 us)

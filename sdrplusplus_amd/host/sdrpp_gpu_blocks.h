@@ -138,6 +138,18 @@ public:
     void detachRecorder();
     dsp::stereo_t getRecorderLevel();  // PeakLevelMeter::getLevel / resetLevel: the running maximum over the blocks since the last reset
     void resetRecorderLevel();
+    // The waterfall's signal read-out for this VFO (calculateVFOSignalInfo, waterfall.cpp:558-598: what the reference shows for the selected VFO on every
+    // frame) while IQFrontEnd::setSignalMeters is on: strength and SNR of the band (offset, bandwidth) on the newest line that has been delivered.  false until
+    // a line has been delivered for this VFO (the reference returns false while there is no line).  A plain read of what the delivery stored: no call into
+    // the device, no lock the worker takes.
+    bool getSignalInfo(float& strength, float& snr) const {
+        if (!sigValid.load(std::memory_order_acquire)) { return false; }
+        const uint64_t b = sigBits.load(std::memory_order_relaxed);
+        const uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32);
+        memcpy(&strength, &lo, 4);
+        memcpy(&snr, &hi, 4);
+        return true;
+    }
     // The radio module's IF chain in front of the demodulator (radio_module.h:84-96), on the device: NoiseBlanker(500 / IF rate, level) ->
     // PowerSquelch(level in dB), either switchable while the stream runs (sdrpp_vfo_set_if: the blanker's amplitude estimate lives through
     // level changes, re-plans and demodulator switches, as the reference's `nb` object does).  `out` stays the stream in front of the chain;
@@ -174,6 +186,15 @@ private:
     int id = -1;
     std::vector<int> prevIds;  // handles this VFO had before its last re-plans (setInSamplerate / setOutSamplerate / a new demodulator): blocks pushed under them are still delivered
     std::string name;
+    std::atomic<uint64_t> sigBits{ 0 };  // (strength, snr) of the newest delivered line as one word: a reader never sees half a pair
+    std::atomic<bool> sigValid{ false };
+    void setSignal(float strength, float snr) {
+        uint32_t lo, hi;
+        memcpy(&lo, &strength, 4);
+        memcpy(&hi, &snr, 4);
+        sigBits.store(((uint64_t)hi << 32) | lo, std::memory_order_relaxed);
+        sigValid.store(true, std::memory_order_release);
+    }
     std::mutex recLevelMtx;
     dsp::stereo_t recLevel = { 0.0f, 0.0f };
     void meter(const sdrpp_rec_info& info) {  // peak_level_meter.h:52-57 with the block's own peaks
@@ -341,6 +362,7 @@ public:
         v->bandwidth = bandwidth;
         v->offset = offset;
         vfos[name] = v;
+        vfoOrder.push_back(v);
         rebuild(*v);
         registerOutput(&v->out);
         registerOutput(&v->audio);
@@ -360,8 +382,10 @@ public:
         unregisterOutput(&it->second->out);
         unregisterOutput(&it->second->audio);
         unregisterOutput(&it->second->recorded);
+        vfoOrder.erase(std::remove(vfoOrder.begin(), vfoOrder.end(), it->second), vfoOrder.end());
         delete it->second;
         vfos.erase(it);
+        sendMeters();
         tempStart();
     }
     // A several-GPU host gathers the waterfall lines of its streams on the display GPU over RCCL (sdrpp_gpu_rccl.h: BankLineGather): for that the
@@ -399,6 +423,16 @@ public:
             if (&kv.second->out == stream) { return kv.second; }
         }
         return nullptr;
+    }
+    // Addition (not in the reference, whose GUI computes the read-out of the selected VFO itself on every frame): signal meters for EVERY VFO on every
+    // line, on the device (sdrpp_wf_set_meters).  While on, the table is this front end's VFOs in addVFO order — band = (offset, bandwidth) of a spectrum
+    // one effective sample rate wide — re-sent whenever a VFO is added, removed, re-planned, retuned or its bandwidth / the sample rate changes; RxVFO::getSignalInfo
+    // returns the pair of the newest delivered line.  Blocks in flight across such a change keep the table they were pushed with, and their values go
+    // to the VFOs THAT table names.  Needs no history ring and costs a pipelined run no drain.
+    void setSignalMeters(bool enabled) {
+        std::lock_guard<std::recursive_mutex> lck(ctrlMtx);
+        _meters = enabled;
+        sendMeters(true);
     }
     // Control calls that do not restart the worker in the reference (RxVFO::setOffset, SSB's translation) reach the context through the
     // worker: the C-ABI context belongs to one thread at a time.  While the worker runs they are queued and applied in front of the next
@@ -949,9 +983,58 @@ private:
                 });
             }
         }
+        // the signal meters of the block's newest line, to the VFOs the table THIS block was pushed with names
+        if (!meterTables.empty()) {
+            const float* md = nullptr;
+            int ml = 0, mn = 0;
+            if (sdrpp_result_meters(ctx, ticket, &md, &ml, &mn) == 0 && ml > 0 && md) {
+                while (meterTables.size() > 1 && meterTables[1].fromTicket <= ticket) { meterTables.pop_front(); }  // (tickets are delivered in order)
+                if (meterTables.front().fromTicket <= ticket) { storeMeters(meterTables.front(), md + (size_t)(ml - 1) * (size_t)mn * 2, mn); }
+            }
+        }
         inflightTicket = ticket;
         helpers.begin(std::move(jobs));
         return 0;
+    }
+    // one row of meters -> the VFOs of `T` (by handle, as the block's VFO outputs are matched: a VFO re-planned since still owns its old handles)
+    struct MeterTable { uint64_t fromTicket; std::vector<int> ids; };
+    void storeMeters(const MeterTable& T, const float* row, int n) {
+        if ((int)T.ids.size() != n) { return; }
+        for (int m = 0; m < n; m++) {
+            for (RxVFO* v : vfoOrder) {
+                if (v->id == T.ids[(size_t)m] || std::find(v->prevIds.begin(), v->prevIds.end(), T.ids[(size_t)m]) != v->prevIds.end()) {
+                    v->setSignal(row[2 * m], row[2 * m + 1]);
+                    break;
+                }
+            }
+        }
+    }
+    // The table as it stands now -> the context, through the control path (in front of the worker's next block, or at once while it is stopped).  Call
+    // with ctrlMtx held.  Every table has a number: an operation that was queued while the worker ran and is overtaken by one applied during a stop
+    // (a setter that restarts the worker) does nothing when its turn comes.
+    void sendMeters(bool force = false) {
+        if (!_meters && !force) { return; }
+        std::vector<int> idsNow;
+        std::vector<sdrpp_meter_desc> descs;
+        if (_meters) {
+            for (RxVFO* v : vfoOrder) {
+                if (v->id < 0) { continue; }
+                idsNow.push_back(v->id);
+                descs.push_back(sdrpp_meter_desc{ v->offset, v->bandwidth });
+            }
+        }
+        const double whole = getEffectiveSamplerate();
+        const uint64_t seq = ++meterSeq;
+        control([this, idsNow, descs, whole, seq]() {
+            if (seq < meterSeqApplied) { return; }
+            meterSeqApplied = seq;
+            if (sdrpp_wf_set_meters(ctx, (int)descs.size(), descs.data(), whole)) {
+                fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] signal meters: %s\n", sdrpp_last_error(ctx));
+                return;
+            }
+            meterTables.push_back(MeterTable{ sdrpp_ticket(ctx) + 1, idsNow });  // (applies from the next push on)
+            if (!pipeOn) { while (meterTables.size() > 1) { meterTables.pop_front(); } }
+        });
     }
     int finishDelivery() {
         if (!inflightTicket) { return 0; }
@@ -1010,6 +1093,13 @@ private:
         }
         SDRPP_BLOCKS_TICK(2)
         if (_keepDevLine && nlines > 0) { refreshDeviceLine(nullptr, nlines - 1, _fftSize); }  // the newest line stays on the device as well (keepDeviceLine)
+        if (nlines > 0 && !meterTables.empty() && !meterTables.back().ids.empty()) {  // the signal meters of the pass, its newest line to the VFOs
+            int ml = 0, mn = 0;
+            if (sdrpp_wf_meters_read(ctx, nullptr, 0, &ml, &mn) == 0 && ml > 0 && mn > 0) {
+                meterRows.resize((size_t)ml * (size_t)mn * 2);
+                if (sdrpp_wf_meters_read(ctx, meterRows.data(), ml, &ml, &mn) == 0) { storeMeters(meterTables.back(), meterRows.data() + (size_t)(ml - 1) * (size_t)mn * 2, mn); }
+            }
+        }
         // all new lines with ONE device-to-host copy into page-locked staging; they are handed out below, next to the VFO blocks
         if (nlines > 0 && _acquire) {
             const size_t need = (size_t)nlines * (size_t)_fftSize;
@@ -1252,6 +1342,7 @@ private:
         if (oldId < 0 && (v.fmnrOn || v.fmnrBins != 32)) { applyFMNR(v); }  // (a replaced handle has it already: keep | 4)
         if (v.afOn && v.demod != Demod::RAW) { applyAF(v); }
         if (v.recOn && v.demod != Demod::RAW) { applyRec(v); }  // (sdrpp_vfo_replace does not carry the sink: the recorder binds to the stream, and the stream lives on)
+        sendMeters();  // (a new handle, perhaps a new bandwidth or input rate)
     }
 
     // `recorded` is a byte stream: its buffer holds STREAM_BUFFER_SIZE BYTES, an eighth of the frames `audio` holds as stereo floats.  A block is one swap
@@ -1332,6 +1423,12 @@ private:
     sdrpp_ctx* ctx = nullptr;
     DecimPlans _plans;
     std::map<std::string, RxVFO*> vfos;
+    std::vector<RxVFO*> vfoOrder;           // the same VFOs in addVFO order: the order of the table of signal meters
+    bool _meters = false;                   // setSignalMeters
+    uint64_t meterSeq = 0;                  // tables built so far (ctrlMtx)
+    uint64_t meterSeqApplied = 0;           // ... and the newest one the context has been given (worker / control path)
+    std::deque<MeterTable> meterTables;     // the tables blocks still in flight were pushed with, oldest first: from which ticket on, and which VFO handle each column is (worker / control path)
+    std::vector<float> meterRows;
     double _sampleRate = 0, _fftRate = 20.0;
     int _fftSize = 65536;
     int _decimRatio = 1;
@@ -1536,6 +1633,7 @@ inline void RxVFO::setOffset(double off) {
     IQFrontEnd* f = fe;
     RxVFO* self = this;
     fe->control([f, self, re, im]() { sdrpp_vfo_set_phase_delta(f->ctx, self->id, re, im); });  // phase stays continuous, no restart (rx_vfo.h:72-77)
+    fe->sendMeters();
 }
 inline void RxVFO::setBandwidth(double bw) {
     std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
@@ -1551,6 +1649,7 @@ inline void RxVFO::setBandwidth(double bw) {
     else {
         sdrpp_vfo_set_channel_taps(fe->ctx, id, nullptr, 0);
     }
+    fe->sendMeters();
     fe->tempStart();
 }
 inline void RxVFO::setOutSamplerate(double sr, double bw) {

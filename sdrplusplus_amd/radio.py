@@ -72,6 +72,13 @@ def _fp(a):
     return a.ctypes.data_as(capi.c_float_p)
 
 
+def meter_table(vfos):
+    """The table of signal meters (Context.wf_set_meters) for a list of VFOs given as (offset, bandwidth) pairs in the units and sign vfo_desc
+    takes them in: one band per VFO, in order — the band the waterfall measures for that VFO (calculateVFOSignalInfo, waterfall.cpp:558-598:
+    centre = the VFO's offset, width = its bandwidth)."""
+    return [(float(offset), float(bandwidth)) for offset, bandwidth in vfos]
+
+
 def vfo_desc(in_sr, out_sr, bandwidth, offset, mode="RAW", low_pass=True, agc_attack=50.0, agc_decay=5.0, carrier_agc=False, nco_mode=0):
     """Build a sdrpp_vfo_desc for RxVFO(in_sr -> out_sr, bandwidth, offset) followed by radio demodulator `mode`.
     Returns (desc, keepalive) — keepalive holds the numpy arrays the descriptor points into (sdrpp_vfo_add copies them)."""
