@@ -365,6 +365,58 @@ int sdrpp_vfo_set_rec(sdrpp_ctx* ctx, int id, const sdrpp_rec_desc* desc);
 int sdrpp_vfo_rec_read(sdrpp_ctx* ctx, int id, void* dst_host, int max_frames, sdrpp_rec_info* info);
 int sdrpp_abi_sizeof_rec_desc(void);
 
+/* ---- RDS branch of the WFM demodulator (dsp/demod/broadcast_fm.h:144-215 with _rdsOut on; decoder_modules/radio/src/demodulators/wfm.h:79) --------------
+ * The 5 kS/s complex baseband the radio's RDSDemod consumes, as dsp::demod::BroadcastFM makes it from the IF stream, feed-forward throughout:
+ *     d[i]   = Quadrature(x[i])                          the discriminator, the same values the audio low-pass reads (quadrature.h:39-46)
+ *     c[i]   = (d[i] + 0j) * phase;  phase *= delta      FrequencyXlator(-57000, IF rate) (channel/frequency_xlator.h:43-50)
+ *     rdsout = RationalResampler<complex_t>(IF rate -> 5000)(c)     (rational_resampler.h:120-165: at 250 kS/s the stored ratio-32 plan
+ *              {8 x 44 taps, 2 x 12, 2 x 69}, then the 5000 / 7813 polyphase stage, 593 750 taps, 119 per phase)
+ * Every filter is designed on the host (sdrpp_design_phase_delta, the stored decimation plan, sdrpp_design_resampler); the arrays are copied.
+ * What becomes of the baseband — RDSDemod's AGC, Costas loop and clock recovery, the group decoder — stays on the host: 5 kS/s and sequential.
+ * Only for SDRPP_DEMOD_WFM VFOs (anything else: SDRPP_ERR_UNSUPPORTED); bad stage or polyphase descriptions give the errors sdrpp_vfo_set_af gives;
+ * the first stage must decimate (n_stages >= 1) and its window must fit the kernel's tile (SDRPP_ERR_UNSUPPORTED otherwise: every plan of the
+ * reference up to ratio 32 with at most 128 taps does).
+ * SOURCE: what the demodulator reads — the IF chain's output where a chain is active, else RxVFO::out.  The discriminator values are recomputed from
+ * that stream and its history by the device routine the audio path uses; the branch never changes a bit of the VFO's audio, IF, AF, recorder or
+ * meter outputs.  DEVIATION from the reference: BroadcastFM::setRDSOut also clears the discriminator and the audio filter (one click in the
+ * audio); here switching the branch leaves the audio path alone.
+ * STATE, as the reference keeps it in `xlator` and `rdsResamp`: the rotator's phase, the delay lines, the decimators' offsets and the polyphase
+ * phase.  Attaching starts from a fresh BroadcastFM: phase (1, 0), cleared delay lines, offsets and phase 0.  enabled = 0 unplugs the branch and
+ * freezes all of it — nothing is planned, nothing delivered, nothing advances; enabled = 1 with the SAME description continues from there.  A call
+ * with another description starts cleared.  desc == NULL detaches.  sdrpp_vfo_reset leaves the branch's own state alone, as BroadcastFM::reset and
+ * RxVFO::reset do (the IF history it clears is the discriminator's "previous phase 0").  sdrpp_vfo_replace with keep & 2 and a WFM description
+ * moves the branch, parameters and state, to the new handle (it belongs to the demodulator object; where the new description runs the other NCO mode
+ * the parameters move and the branch starts cleared); otherwise the new handle has none.
+ * NCO: closed form, the phase arg(phase_delta) * n evaluated in float64 and anchored per push like SSB's second translation; a launch group is
+ * anchored push by push, so grouped results equal ungrouped ones bit for bit.  Against the reference's float recursion (renormalised every 512
+ * samples) the closed form differs by the recursion's own drift: 4.7e-6, 5.3e-6 and 9.5e-6 of the output RMS over the first 12 500, 50 000 and
+ * 200 000 IF samples (1.5e-5 over the last tenth of the longest; computed on the CPU between the two yardsticks of tests/test_rds.py, profiles/rds_rate.md)
+ * — the closed form stands for the reference within the project's 1e-5 for about the first 0.8 s of a stream, and for an exact NCO throughout.
+ * Where the VFO runs the reference rotator (nco_mode = 2, or the context's mode when the branch is attached) the branch runs the reference's float
+ * recursion at the IF rate — renormalised every 512 samples and at the reference-block ends (sdrpp_set_reference_block) carried down to the IF rate —
+ * writes the rotated stream, and its first decimator follows as a plain FIR: results then do not depend on the cut as long as the blocks are the same.
+ * The polyphase bank (2.4 MB at 5000 / 7813) exists ONCE per context for identical descriptions, however many VFOs carry the branch.
+ * Outside pipelined mode the accessors below name the most recent push, as the AF chain's do: SDRPP_ERR_INVALID for a VFO without a branch
+ * (count 0 while it is switched off).  Pipelined: sdrpp_pipeline_set_rds_results / sdrpp_result_rds. */
+typedef struct sdrpp_rds_desc {
+    float phase_delta_re, phase_delta_im;             /* sdrpp_design_phase_delta(-57000, if_rate)                              */
+    int n_stages;                                     /* PowerDecimator stages of the pre-decimation plan (>= 1)                */
+    int stage_decim[SDRPP_MAX_DECIM_STAGES];
+    int stage_ntaps[SDRPP_MAX_DECIM_STAGES];
+    const float* stage_taps[SDRPP_MAX_DECIM_STAGES];
+    int interp, decim;                                /* polyphase L/M; interp == decim -> stage absent                         */
+    int resamp_ntaps;
+    const float* resamp_taps;                         /* already scaled by interp (sdrpp_design_resampler(if_rate, 5000, ...))  */
+} sdrpp_rds_desc;
+int sdrpp_vfo_set_rds(sdrpp_ctx* ctx, int id, const sdrpp_rds_desc* desc, int enabled);
+/* The branch's output of the most recent push: complex samples at 5 kS/s (what BroadcastFM::rdsOut swap()s). */
+int sdrpp_vfo_rds_count(sdrpp_ctx* ctx, int id);
+int sdrpp_vfo_rds_read(sdrpp_ctx* ctx, int id, float* dst_host, int max);
+int sdrpp_vfo_rds_device_buffer(sdrpp_ctx* ctx, int id, const float** out, int* n_out);
+int sdrpp_abi_sizeof_rds_desc(void);
+/* Test and statistics hook: polyphase banks of RDS branches the context holds in device memory (identical descriptions share one). */
+int sdrpp_rds_bank_count(sdrpp_ctx* ctx);
+
 /* ---- WaterFall display state around the raw-line history (core/src/gui/widgets/waterfall.cpp) ---------------
  * The last `height` raw dB lines stay resident in HBM in the reference's ring order (getFFTBuffer :875-886), so a zoom / pan /
  * level change re-renders the whole waterfall on the device (updateWaterfallFb :600-631) instead of re-reading host memory, and
@@ -548,6 +600,17 @@ int sdrpp_set_pipelined(sdrpp_ctx* ctx, int on, int result_flags);
  * sink was attached or without flag 16.  Blocks of a pipelined run that were processed as an ordinary pass deliver the same.  A call of its own, so
  * that sdrpp_result's layout and SDRPP_ABI_VERSION stay what they are. */
 int sdrpp_result_rec(sdrpp_ctx* ctx, uint64_t ticket, int id, const void** data, sdrpp_rec_info* info);
+/* Result flag 32: the RDS branches' samples (sdrpp_vfo_set_rds) travel in every block's result slot, about 40 KB/s per channel.  The flag has a
+ * call of its own — sdrpp_set_pipelined keeps refusing values above 31, as it always has — to be made in pipelined mode, between blocks (what is
+ * queued runs first); leaving pipelined mode or calling sdrpp_set_pipelined again clears it.  32 is independent of 1.
+ * sdrpp_result_rds: *data = *count complex samples (2 floats each) VFO `id`'s branch made of push `ticket`, in the block's result slot (in a launch
+ * group the group's samples lie there in one piece and every push gets its own share).  Validity as for sdrpp_result_rec: between
+ * sdrpp_result_wait and sdrpp_result_release, else SDRPP_ERR_INVALID.  SDRPP_ERR_NOT_FOUND: the VFO has no branch or it was switched off, the
+ * block was pushed before the attach, or without flag 32.  Blocks of a pipelined run processed as an ordinary pass deliver the same.  Either
+ * output may be NULL. */
+#define SDRPP_RESULT_RDS 32
+int sdrpp_pipeline_set_rds_results(sdrpp_ctx* ctx, int on);
+int sdrpp_result_rds(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** data, int* count);
 /* Signal meters of push `ticket` (sdrpp_wf_set_meters): *data = [*n_lines][*n_meters][2] floats in the block's result slot, for the lines this push's
  * own samples completed — the rows `zoomed` / `raw` give it — oldest first.  No result flag: while a table is set, EVERY pipelined block with the
  * FFT on carries its meters (n_lines * n_meters * 8 bytes), result_flags = 0 included — sdrpp_result_wait / _release then work for such blocks.

@@ -77,6 +77,23 @@ class AfDesc(C.Structure):
     ]
 
 
+class RdsDesc(C.Structure):
+    """struct sdrpp_rds_desc (include/sdrpp_gpu.h): the WFM demodulator's RDS branch — translation by -57 kHz, resampler to 5 kS/s."""
+
+    _fields_ = [
+        ("phase_delta_re", C.c_float),
+        ("phase_delta_im", C.c_float),
+        ("n_stages", C.c_int),
+        ("stage_decim", C.c_int * MAX_DECIM_STAGES),
+        ("stage_ntaps", C.c_int * MAX_DECIM_STAGES),
+        ("stage_taps", c_float_p * MAX_DECIM_STAGES),
+        ("interp", C.c_int),
+        ("decim", C.c_int),
+        ("resamp_ntaps", C.c_int),
+        ("resamp_taps", c_float_p),
+    ]
+
+
 class IfDesc(C.Structure):
     """struct sdrpp_if_desc (include/sdrpp_gpu.h): the radio IF chain (noise blanker -> power squelch) in front of the demodulator."""
 
@@ -149,6 +166,7 @@ class Result(C.Structure):
 ABI_VERSION = 2    # SDRPP_ABI_VERSION (include/sdrpp_gpu.h)
 RESULT_SLOTS = 24  # SDRPP_RESULT_SLOTS: launches (one block each, or a group of up to GROUP_MAX: sdrpp_set_pipeline_group) whose pipelined results can exist at a time
 GROUP_MAX = 32     # SDRPP_GROUP_MAX
+RESULT_RDS = 32    # SDRPP_RESULT_RDS: the RDS branches' samples in every block's result slot (Context.set_pipelined, Context.result_rds)
 
 
 class SdrppError(RuntimeError):
@@ -221,6 +239,16 @@ def load():
     L.sdrpp_vfo_set_rec.argtypes = [vp, C.c_int, C.POINTER(RecDesc)]
     L.sdrpp_vfo_rec_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(RecInfo)]
     L.sdrpp_result_rec.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(RecInfo)]
+    L.sdrpp_abi_sizeof_rds_desc.argtypes = []
+    if L.sdrpp_abi_sizeof_rds_desc() != C.sizeof(RdsDesc):
+        raise ImportError("sdrpp_rds_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_rds_desc(), C.sizeof(RdsDesc)))
+    L.sdrpp_vfo_set_rds.argtypes = [vp, C.c_int, C.POINTER(RdsDesc), C.c_int]
+    L.sdrpp_vfo_rds_count.argtypes = [vp, C.c_int]
+    L.sdrpp_vfo_rds_read.argtypes = [vp, C.c_int, c_float_p, C.c_int]
+    L.sdrpp_vfo_rds_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), c_int_p]
+    L.sdrpp_rds_bank_count.argtypes = [vp]
+    L.sdrpp_pipeline_set_rds_results.argtypes = [vp, C.c_int]
+    L.sdrpp_result_rds.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(c_float_p), c_int_p]
     L.sdrpp_abi_sizeof_meter_desc.argtypes = []
     if L.sdrpp_abi_sizeof_meter_desc() != C.sizeof(MeterDesc):
         raise ImportError("sdrpp_meter_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_meter_desc(), C.sizeof(MeterDesc)))
@@ -317,6 +345,8 @@ EXPORTED_SYMBOLS = [
     "sdrpp_wf_set_meters", "sdrpp_wf_meters_read", "sdrpp_result_meters", "sdrpp_abi_sizeof_meter_desc",
     "sdrpp_preproc_configure", "sdrpp_preproc_reconfigure", "sdrpp_preproc_set_reference_order", "sdrpp_preproc_out_count", "sdrpp_preproc_read", "sdrpp_preproc_device_buffer",
     "sdrpp_vfo_set_rec", "sdrpp_vfo_rec_read", "sdrpp_abi_sizeof_rec_desc", "sdrpp_result_rec",
+    "sdrpp_vfo_set_rds", "sdrpp_vfo_rds_count", "sdrpp_vfo_rds_read", "sdrpp_vfo_rds_device_buffer", "sdrpp_abi_sizeof_rds_desc", "sdrpp_rds_bank_count",
+    "sdrpp_pipeline_set_rds_results", "sdrpp_result_rds",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
     "sdrpp_vfo_set_if", "sdrpp_vfo_set_fmnr", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
     "sdrpp_fft_configure", "sdrpp_fft_disable", "sdrpp_fft_set_view", "sdrpp_fft_lines", "sdrpp_fft_read", "sdrpp_fft_copy_device", "sdrpp_fft_device_buffers",
@@ -695,6 +725,35 @@ class Context:
         self._chk(self.L.sdrpp_result_rec(self.h, int(ticket), vid, C.byref(data), C.byref(info)))
         return self._rec_unpack(data.value, info)
 
+    def vfo_set_rds(self, vid, desc, enabled=True, keepalive=None):
+        """Attach the WFM demodulator's RDS branch (sdrpp_vfo_set_rds; radio.rds_desc), switch it (the same description: enabled = False freezes its
+        state, True continues from it) or, with None, detach it.  `keepalive` (the arrays the description points into) is only there so that a caller can
+        pass what radio.rds_desc returns: the library copies every array during the call, nothing is kept."""
+        self._chk(self.L.sdrpp_vfo_set_rds(self.h, vid, C.byref(desc) if desc is not None else None, int(bool(enabled))))
+
+    def vfo_rds_count(self, vid):
+        return self._chk(self.L.sdrpp_vfo_rds_count(self.h, vid))
+
+    def vfo_rds_read(self, vid):
+        """The RDS branch's output of the last push: complex64 at 5 kS/s (what BroadcastFM::rdsOut delivers)."""
+        n = self.vfo_rds_count(vid)
+        out = np.empty(max(n, 1), dtype=np.complex64)
+        got = self._chk(self.L.sdrpp_vfo_rds_read(self.h, vid, out.view(np.float32).ctypes.data_as(c_float_p), n))
+        return out[:got]
+
+    def rds_bank_count(self):
+        """Polyphase banks of RDS branches the context holds in device memory (identical descriptions share one)."""
+        return self._chk(self.L.sdrpp_rds_bank_count(self.h))
+
+    def result_rds(self, ticket, vid):
+        """sdrpp_result_rds (result flag RESULT_RDS), between result_wait and result_release of that ticket -> this push's complex64 samples (a copy)."""
+        data, n = c_float_p(), C.c_int()
+        self._chk(self.L.sdrpp_result_rds(self.h, int(ticket), vid, C.byref(data), C.byref(n)))
+        out = np.empty(n.value, dtype=np.complex64)
+        if n.value > 0:
+            C.memmove(out.ctypes.data, data, n.value * 8)
+        return out
+
     def vfo_set_if(self, vid, if_desc):
         """Attach (or, with None, detach) the radio IF chain: noise blanker -> power squelch in front of the demodulator (sdrpp_vfo_set_if).
         On a VFO that already has one the parameters change and the blanker's amplitude estimate is kept."""
@@ -762,8 +821,11 @@ class Context:
     # pipelined execution (one launch per block, results a few blocks late)
     def set_pipelined(self, on, result_flags=0):
         """result_flags: 1 = every VFO's output block (AF output where a chain is attached), 2 = zoomed lines + palette indices, 4 = raw dB lines,
-        8 = the pre-processed IQ stream (with a pre-processing chain), 16 = the recorder sinks' converted blocks (result_rec) into page-locked result slots."""
-        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags)))
+        8 = the pre-processed IQ stream (with a pre-processing chain), 16 = the recorder sinks' converted blocks (result_rec) into page-locked result slots,
+        32 (RESULT_RDS) = the RDS branches' samples (result_rds; the library switches that one by a call of its own, sdrpp_pipeline_set_rds_results)."""
+        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags) & ~RESULT_RDS))
+        if on and (int(result_flags) & RESULT_RDS):
+            self._chk(self.L.sdrpp_pipeline_set_rds_results(self.h, 1))
 
     def set_pipeline_group(self, max_blocks, adaptive=False, stable_words=False):
         """sdrpp_set_pipeline_group: up to `max_blocks` pushes per launch (every push keeps its own ticket and results); adaptive: the group follows

@@ -103,6 +103,39 @@ struct Vfo {
         float volume = 1.0f, gain = 1.0f;  // gain = powf(volume, 2) (audio/volume.h:14,22)
         int mono = 0, type = 1, ignore_silence = 0;
     } rec;
+    // RDS branch of the WFM demodulator (sdrpp_vfo_set_rds): fed by the stream the demodulator reads, beside the audio low-pass.  Its streams are its own
+    // (not in `st`: sdrpp_vfo_reset, which clears every history of `st`, leaves the branch alone, as BroadcastFM::reset leaves xlator and rdsResamp alone)
+    struct Rds {
+        bool attached = false, on = false;
+        bool exact = false;            // the reference's float recursion (the VFO's nco_exact when the branch was attached)
+        float pd_re = 1.0f, pd_im = 0.0f;
+        double theta = 0.0, phi = 0.0;  // closed-form NCO: turns per sample, phase of the next sample
+        float2* d_rot = nullptr;       // reference-rotator mode: FrequencyXlator::phase (device, persistent)
+        int n_stages = 0, decim_s[SDRPP_MAX_DECIM_STAGES] = { 1, 1, 1, 1 };
+        std::vector<float> staps[SDRPP_MAX_DECIM_STAGES], rtaps;
+        float* d_staps[SDRPP_MAX_DECIM_STAGES] = { nullptr, nullptr, nullptr, nullptr };  // phase-major, padded (FirBJob); stage 0 in closed form: natural order
+        int s_kp[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
+        ToepTab tp_stage[SDRPP_MAX_DECIM_STAGES];
+        int interp = 1, decim = 1, tpp = 0;
+        unsigned long long bank_key = 0;  // the context's shared polyphase bank this branch holds a reference to (0: none)
+        const float* d_bank = nullptr;
+        int tile = 0, pitch = 0;       // fused first stage: outputs per tile, LDS row pitch (rds_tile_geometry)
+        int soff[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
+        int pphase = 0, poff = 0;
+        std::vector<Stream> st;        // [exact: the rotated IF-rate stream,] the decimator stages' outputs, the polyphase stage's
+        int i_stage0 = 0, i_poly = -1, i_last = 0;
+        // the first decimator's delay line while the feed's history does not hold it (fresh attach: zeros; switched off, sdrpp_vfo_reset, moved: what the
+        // branch was fed last): the K0 newest DISCRIMINATOR values, newest last; `frozen`: the next block reads it in place of the feed's history.  It stays
+        // frozen until the branch has been fed K0 samples in a row since the last switch (`line_fed`): a block shorter than that is spliced onto the line
+        // (vfo_rds_line_body, from d_line[line_cur] into the other side) — the feed's own history would still hold samples the branch never saw.  A line of
+        // values, not of IF samples, has no seams: any number of switches may fall into that window
+        float* d_line[2] = { nullptr, nullptr };
+        int line_cur = 0, line_fed = 0;
+        bool frozen = false;
+        int lvl = 1;                   // level (do_vfos_plan) at which the branch's output of the most recent block is written
+        bool ran = false;              // the most recent block was planned with the branch on
+        std::vector<int> tk;           // a launch group: cumulative output counts at every push end
+    } rds;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
     ToepTab tp_stage[SDRPP_MAX_DECIM_STAGES], tp_poly, tp_chan, tp_audio;
     // front end as one filter (what the fused translate + filter kernels evaluate): stages 0 (+ 1) of the plan
@@ -289,6 +322,8 @@ struct sdrpp_ctx {
     // cached stage-1 job tap arrays, keyed by membership signature
     std::map<std::string, float2*> s1_tap_cache;  // key = 16 raw bytes: two independent 64-bit hashes of (kind, member ids, increments)
     std::map<int, float*> fmif_tabs;      // FMIF's matrix per bin count in use (sdrpp_host::fmifMatrix), uploaded once
+    struct RdsBank { float* d_bank = nullptr; int refs = 0; int interp = 0, tpp = 0; std::vector<float> taps; };
+    std::map<unsigned long long, RdsBank> rds_banks;  // polyphase banks of the RDS branches, ONE per distinct description (2.4 MB each), freed with their last user
 
     // ---- pipelined ("tick") execution: one launch per block, the stages of consecutive blocks skewed over consecutive launches
     //      (tick_kernels.h; sdrpp_set_pipelined) ----
@@ -306,13 +341,15 @@ struct sdrpp_ctx {
         int fft_size = 0, data_width = 0, flags = 0;        // what the block was PLANNED with (the view / FFT size / result flags may change before it is collected)
         size_t off_zoomed = 0, off_index = 0, off_raw = 0, off_iq = 0;  // byte offsets in the slot
         int n_iq = 0;                                        // pre-processed IQ samples delivered (result flag 8)
+        std::vector<int> rds_ids, rds_counts;                // result flag 32: the VFOs whose RDS branch ran in the block, this push's samples
+        std::vector<size_t> rds_off;                         // ... and where they lie in the slot
         std::vector<int> rec_ids;                            // result flag 16: the VFOs that had a recorder sink when the block was planned,
         std::vector<size_t> rec_off, rec_info_off;           // ... where this push's converted samples and its sdrpp_rec_info lie in the slot
         int n_meters = -1;                                   // signal meters the block was pushed with (-1: no table then); its n_lines x n_meters x 2 floats
         size_t off_meters = 0;
     };
     bool pipelined = false;
-    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks
+    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks, bit 5: RDS branches (sdrpp_pipeline_set_rds_results)
     int num_cus = 256;
     int tick_l0_at = getenv("SDRPP_GPU_TICK_L0_AT") ? atoi(getenv("SDRPP_GPU_TICK_L0_AT")) : 0;  // (read when the context is created)
     // grid rules of the roles inside a tick (the stand-alone kernels size their grids for a GPU of their own; in a tick ~8 roles share it, and

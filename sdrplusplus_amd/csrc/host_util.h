@@ -349,7 +349,42 @@ void build_modtaps(Vfo& v) {
     v.modtaps_dirty = false;
 }
 
+// what an RDS branch owns by itself (its share of the context's polyphase banks is given back by rds_detach, vfo_ctl.h)
+void rds_free_own(Vfo::Rds& r) {
+    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) {
+        dev_free(r.d_staps[i]);
+        toep_free(r.tp_stage[i]);
+    }
+    dev_free(r.d_rot);
+    dev_free(r.d_line[0]);
+    dev_free(r.d_line[1]);
+    for (auto& s : r.st) { stream_free(s); }
+    r.st.clear();
+}
+// Outputs per tile and LDS row pitch of the branch's fused first stage (vfo_rds_front_body) for K taps decimating by D: the window of a tile, de-interleaved
+// by decimation phase, and its phases must fit the wavefront's share of the role's LDS.  The pitch serves the window's STORES (8 bytes per lane, carried out 16
+// lanes at a time over 32 dword banks: 16 consecutive samples must land on 16 different 8-byte banks — consecutive samples lie `pitch` float2 apart, D of them
+// to a row position, so pitch = 16 / D modulo 32 / D, odd for D >= 16); the loads read consecutive addresses whatever the pitch.  false: no tile fits.
+bool rds_tile_geometry(int K, int D, int* tile, int* pitch) {
+    const int lgD = ilog2(D);
+    for (int t = 64; t >= 1; t--) {
+        int P = t + ((K - 1) >> lgD);
+        if (D >= 16) { P |= 1; }
+        else if (D >= 2) {
+            const int g = 16 / D;
+            while (P % (2 * g) != g) { P++; }
+        }
+        if (2 * D * P + (t - 1) * D + K + 1 <= SDRPP_RDS_LDS_WAVE) {  // the window, then one phase per sample and one in front
+            *tile = t;
+            *pitch = P;
+            return true;
+        }
+    }
+    return false;
+}
+
 void vfo_free(Vfo& v) {
+    rds_free_own(v.rds);
     for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { dev_free(v.d_staps[i]); dev_free(v.d_staps_nat[i]); }
     dev_free(v.d_bank);
     dev_free(v.d_cyc);

@@ -7,7 +7,8 @@ namespace {
 // ---- streaming state that planning a block changes, for roll-back: a block either happens completely or not at all ----------------------
 struct PlanSnapshot {
     struct V { int soff[SDRPP_MAX_DECIM_STAGES]; int pphase, poff; double phi, phi2; long long seen; int i_if, lvl_if, lvl_out, lvl_af, lvl_ifc; int n[24], cur[24]; size_t nrecs;
-               int af_soff[SDRPP_MAX_DECIM_STAGES], af_pphase, af_poff, af_last, af_state; };
+               int af_soff[SDRPP_MAX_DECIM_STAGES], af_pphase, af_poff, af_last, af_state;
+               int rds_soff[SDRPP_MAX_DECIM_STAGES], rds_pphase, rds_poff, rds_lvl, rds_n[SDRPP_MAX_DECIM_STAGES + 2], rds_cur[SDRPP_MAX_DECIM_STAGES + 2]; double rds_phi; bool rds_frozen, rds_ran; int rds_line_cur, rds_line_fed; };
     std::vector<V> v;
     int64_t fft_pos, fft_next;
     int n_lines, iq_cur, wf_cur, wf_lines;
@@ -25,8 +26,14 @@ void plan_snapshot(sdrpp_ctx* c, PlanSnapshot& S, bool rotate = false) {
         q.nrecs = v.recs.size();
         q.af_pphase = v.af.pphase; q.af_poff = v.af.poff; q.af_last = v.af.i_last; q.af_state = v.af.state_cur;
         for (size_t k = 0; k < v.st.size() && k < 24; k++) { q.n[k] = v.st[k].n; q.cur[k] = v.st[k].cur; }
+        if (v.rds.attached) {
+            for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { q.rds_soff[k] = v.rds.soff[k]; }
+            q.rds_pphase = v.rds.pphase; q.rds_poff = v.rds.poff; q.rds_lvl = v.rds.lvl; q.rds_phi = v.rds.phi; q.rds_frozen = v.rds.frozen; q.rds_ran = v.rds.ran; q.rds_line_cur = v.rds.line_cur; q.rds_line_fed = v.rds.line_fed;
+            for (size_t k = 0; k < v.rds.st.size(); k++) { q.rds_n[k] = v.rds.st[k].n; q.rds_cur[k] = v.rds.st[k].cur; }
+        }
         if (rotate) {
             for (auto& st : v.st) { stream_rotate(st); }
+            for (auto& st : v.rds.st) { stream_rotate(st); }
         }
     }
     S.fft_pos = c->fft_pos; S.fft_next = c->fft_next; S.n_lines = c->n_lines; S.iq_cur = c->iq_cur;
@@ -45,6 +52,11 @@ void plan_restore(sdrpp_ctx* c, const PlanSnapshot& S) {
         v.pphase = q.pphase; v.poff = q.poff; v.phi = q.phi; v.phi2 = q.phi2; v.seen = q.seen; v.i_if = q.i_if; v.lvl_if = q.lvl_if; v.lvl_out = q.lvl_out; v.lvl_af = q.lvl_af; v.lvl_ifc = q.lvl_ifc;
         v.af.pphase = q.af_pphase; v.af.poff = q.af_poff; v.af.i_last = q.af_last; v.af.state_cur = q.af_state;
         for (size_t k = 0; k < v.st.size() && k < 24; k++) { v.st[k].n = q.n[k]; v.st[k].cur = q.cur[k]; }
+        if (v.rds.attached) {
+            for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { v.rds.soff[k] = q.rds_soff[k]; }
+            v.rds.pphase = q.rds_pphase; v.rds.poff = q.rds_poff; v.rds.lvl = q.rds_lvl; v.rds.phi = q.rds_phi; v.rds.frozen = q.rds_frozen; v.rds.ran = q.rds_ran; v.rds.line_cur = q.rds_line_cur; v.rds.line_fed = q.rds_line_fed;
+            for (size_t k = 0; k < v.rds.st.size(); k++) { v.rds.st[k].n = q.rds_n[k]; v.rds.st[k].cur = q.rds_cur[k]; }
+        }
     }
     c->fft_pos = S.fft_pos; c->fft_next = S.fft_next; c->n_lines = S.n_lines; c->iq_cur = S.iq_cur;
     c->wf.cur = S.wf_cur; c->wf.lines = S.wf_lines; c->wf.have_latest = S.wf_have;
@@ -105,6 +117,7 @@ int push_common(sdrpp_ctx* c, const float* d_iq, int64_t count, const std::vecto
         c->n_lines = 0;
         for (auto& kv : c->vfos) {
             for (auto& s : kv.second->st) { s.n = 0; }
+            for (auto& s : kv.second->rds.st) { s.n = 0; }
         }
         return SDRPP_OK;
     }
@@ -128,6 +141,7 @@ int push_common(sdrpp_ctx* c, const float* d_iq, int64_t count, const std::vecto
             c->n_lines = 0;
             for (auto& kv : c->vfos) {
                 for (auto& s : kv.second->st) { s.n = 0; }
+                for (auto& s : kv.second->rds.st) { s.n = 0; }
             }
             return arena_end(c);
         }

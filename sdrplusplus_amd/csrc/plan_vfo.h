@@ -231,6 +231,11 @@ struct BankPlan {
     Lev<PolyJob> af_poly;
     Lev<DeempJob> af_deemp;
     Lev<SsbRotXJob> ssbx_l;
+    // RDS branch of the WFM demodulator (rds_branch): the fused first stage's jobs / the reference rotator's, filed as jobs of the IF chain's role once their
+    // own records have their place in the arena (upload); the later stages go into the AF chain's lists — complex_t and stereo_t are the same arithmetic there
+    Lev<RdsJob> rdsj;
+    Lev<RdsRotXJob> rdsx;
+    Lev<RdsLineJob> rdsl;
     Lev<CarryJob> carry;  // history carries at the level of the stream's consumer (a pass without pipelining: all at the last level)
     int max_rot = 0;
     // front-end jobs (group_front)
@@ -267,7 +272,7 @@ struct BankPlan {
         for (auto& t : tlists) { f(*t.L); }
         f(f_dec); f(poly);
         for (auto& q : polyb) { f(q); }
-        f(chan); f(seq); f(ifc); f(pre); f(audio); f(audio_fm);
+        f(chan); f(seq); f(rdsj); f(rdsx); f(rdsl); f(ifc); f(pre); f(audio); f(audio_fm);  // (rdsj / rdsx in front of ifc: upload files them there)
         f(af_dec); f(af_hpf); f(af_poly); f(af_deemp);
         f(ssbx_l); f(carry);
     }
@@ -402,10 +407,11 @@ struct BankPlan {
     int chain(Vfo& v) {
         ChainCtx x(v, L0 + 1);
         for (auto& s : v.st) { s.clevel = 0; s.wlevel = 0; }
+        for (auto& s : v.rds.st) { s.clevel = 0; s.wlevel = 0; }
         x.at.cur->wlevel = x.at.lvl;
         const bool agc_mode = v.d.demod == SDRPP_DEMOD_AM || (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_DSB);
         x.ifc_on = v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base;
-        const bool need_bnd = (agc_mode && (blocks || v.nco_exact)) || (x.ifc_on && v.ifc.sq_on && blocks);
+        const bool need_bnd = (agc_mode && (blocks || v.nco_exact)) || (x.ifc_on && v.ifc.sq_on && blocks) || (v.rds.on && v.rds.exact && blocks);
         if (need_bnd) { x.bnd = fb; }
         x.split = c->grp_ends.size() > 1;
         v.tk_if.clear();
@@ -442,11 +448,22 @@ struct BankPlan {
             x.nbnd = (int)x.bnd.size();
         }
         if_chain(x);
+        const ChainCursor feed = x.at;  // the stream the demodulator reads
         if (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) { demod_fm(x); }
         else if (v.d.demod == SDRPP_DEMOD_AM) { demod_am(x); }
         else if (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_DSB) { demod_ssb(x); }
         if (v.af.on && v.i_out >= 0) { af_chain(x); }
+        int last_lvl = x.at.lvl;
+        v.rds.ran = v.rds.on;
+        if (v.rds.on) {
+            rds_branch(x, feed);
+            last_lvl = std::max(last_lvl, x.at.lvl);
+        }
+        else {
+            for (auto& s : v.rds.st) { s.n = 0; }
+        }
         phase_advance(x);
+        x.at.lvl = last_lvl;
         history_carries(x);
         c->plan_top = std::max(c->plan_top, x.at.lvl + 2);
         return SDRPP_OK;
@@ -730,6 +747,77 @@ struct BankPlan {
         a.i_last = (int)(x.at.cur - &v.st[0]);
         v.lvl_af = x.at.lvl;
     }
+    // RDS branch of the WFM demodulator (broadcast_fm.h:144-215, _rdsOut): beside the audio low-pass, off the stream the demodulator reads (`feed`).
+    // Closed form: discriminator, translation and first decimator are ONE job list (vfo_rds_front_body) — a job per run of kRdsSegTiles tiles of every push,
+    // anchored at its push: a launch group is anchored push by push, so grouped samples equal ungrouped ones bit for bit.  Reference rotator: one job per VFO
+    // writes the rotated IF-rate stream, the first decimator follows as a plain FIR.  The later decimators and the polyphase stage are decim_step / poly_step.
+    static constexpr int kRdsSegTiles = 4;
+    void rds_branch(ChainCtx& x, const ChainCursor& feed) {
+        Vfo& v = x.v;
+        Vfo::Rds& r = v.rds;
+        const Stream& in = *feed.cur;
+        const int lvl = feed.lvl, nif = in.n;
+        x.bnd.clear();  // (what the rotator needs of them is in the arena already)
+        r.tk.clear();
+        if (x.split) { r.tk = v.tk_if; }
+        x.tk = &r.tk;
+        x.at = feed;
+        const float2* prev0 = reinterpret_cast<const float2*>(in.hist[in.cur]) + (in.hist_len - 1);  // the discriminator's previous sample
+        const int K0 = (int)r.staps[0].size(), D0 = r.decim_s[0];
+        if (r.exact) {
+            Stream& rot = r.st[0];
+            rdsx.add(lvl + 1, RdsRotXJob{ reinterpret_cast<const float2*>(in.data), prev0, reinterpret_cast<float2*>(rot.data), r.d_rot, r.pd_re, r.pd_im, v.d.inv_deviation, nif, x.d_bnd, x.nbnd });
+            x.at.step(rot, nif);
+            decim_step(x, r.st[(size_t)r.i_stage0], r.tp_stage[0], r.d_staps[0], K0, D0, r.s_kp[0], r.soff[0], t_af_dec, af_dec);
+        }
+        else {
+            Stream& nxt = r.st[(size_t)r.i_stage0];
+            StreamIn sin = stream_in(in);
+            if (r.frozen) { sin.hist_len = 0; }  // the delay line the branch was left with (RdsJob::dline), not what the stream has seen since: nothing in front of the block is read
+            RdsJob j{ sin, prev0, reinterpret_cast<float2*>(nxt.data), r.d_staps[0], r.frozen ? r.d_line[r.line_cur] : nullptr, K0, ilog2(D0), r.soff[0], 0, 0,
+                      r.tile, r.pitch, 0, v.d.inv_deviation, r.theta, r.phi };
+            const size_t npush = x.split ? v.tk_if.size() : 1;
+            int lo = 0, so = r.soff[0], m = 0;
+            for (size_t q = 0; q < npush; q++) {
+                const int hi = x.split ? v.tk_if[q] : nif, nq = hi - lo;
+                const int mq = decim_nout(nq, so, D0);
+                j.anchor = lo;
+                j.phi = r.phi;
+                for (int a = m; a < m + mq; a += kRdsSegTiles * r.tile) {
+                    j.m_lo = a;
+                    j.m_hi = std::min(a + kRdsSegTiles * r.tile, m + mq);
+                    rdsj.add(lvl + 1, j);
+                }
+                so = so + mq * D0 - nq;
+                m += mq;
+                const double p = r.phi + (double)nq * r.theta;
+                r.phi = p - std::floor(p);
+                lo = hi;
+            }
+            x.through_decim(r.soff[0], D0);
+            r.soff[0] = so;
+            x.at.step(nxt, m);
+            if (r.frozen && nif > 0) {
+                // the feed's history is the branch's delay line again only once the branch has seen K0 samples of it in a row; until then the block's
+                // discriminator values are spliced onto the line it was left with (a job beside the first stage's, which reads the other side)
+                r.line_fed += nif;
+                if (r.line_fed >= K0) { r.frozen = false; }
+                else {
+                    rdsl.add(lvl + 1, RdsLineJob{ reinterpret_cast<const float2*>(in.data), prev0, r.d_line[r.line_cur], r.d_line[r.line_cur ^ 1], nif, K0, v.d.inv_deviation });
+                    r.line_cur ^= 1;
+                }
+            }
+        }
+        for (int s = 1; s < r.n_stages; s++) {
+            decim_step(x, r.st[(size_t)r.i_stage0 + s], r.tp_stage[s], r.d_staps[s], (int)r.staps[s].size(), r.decim_s[s], r.s_kp[s], r.soff[s], t_af_dec, af_dec);
+        }
+        if (r.i_poly >= 0) {
+            static const ToepTab no_tab{};  // (5000 phases: no matrix form)
+            poly_step(x, r.st[(size_t)r.i_poly], no_tab, r.interp, r.decim, r.tpp, r.pphase, r.poff, r.d_bank, nullptr, 0, 0, t_af_poly, af_poly);
+        }
+        r.i_last = (int)(x.at.cur - &r.st[0]);
+        r.lvl = x.at.lvl;
+    }
     void phase_advance(ChainCtx& x) {
         Vfo& v = x.v;
         if (x.have_phi_end) { v.phi = x.phi_end; }
@@ -752,6 +840,14 @@ struct BankPlan {
                 // an AF chain is up to a dozen levels later, when the stream's ring buffer (kRing = 4) already holds a later block
                 const int cl = !ticking ? carry_last : (s.clevel > 0 ? s.clevel : (s.wlevel > 0 ? s.wlevel + 1 : x.at.lvl + 1));
                 carry.add(cl, CarryJob{ s.data, s.hist[s.cur], s.hist[s.cur ^ 1], s.hist_len, s.n, s.width, s.hist_len });
+            }
+        }
+        if (v.rds.ran) {  // the RDS branch's own streams (every one of them is written and read whenever the branch runs)
+            for (auto& s : v.rds.st) {
+                if (s.hist_len > 0 && s.data) {
+                    const int cl = !ticking ? carry_last : (s.clevel > 0 ? s.clevel : s.wlevel + 1);
+                    carry.add(cl, CarryJob{ s.data, s.hist[s.cur], s.hist[s.cur ^ 1], s.hist_len, s.n, s.width, s.hist_len });
+                }
             }
         }
     }
@@ -1070,6 +1166,33 @@ struct BankPlan {
                     if (tplan[i][l].lds > (size_t)kMaxLds) { rc = fail(c, SDRPP_ERR_UNSUPPORTED, "matrix-core FIR window does not fit in LDS"); }
                 }
                 i++;
+            }
+            if constexpr (std::is_same_v<decltype(L), Lev<IfcJob>&>) {  // the RDS branches' records have their addresses now: their jobs of the IF chain's role
+                for (int l = 0; l < rdsj.top && !rc; l++) {
+                    for (size_t k = 0; k < rdsj.at[l].size(); k++) {
+                        IfcJob j{};
+                        j.in = reinterpret_cast<const float2*>(rdsj.dev[l] + k);
+                        j.kind = 2;
+                        ifc.add(l, j);
+                        ifc_lds = std::max(ifc_lds, (size_t)4 * SDRPP_RDS_LDS_WAVE * sizeof(float));
+                    }
+                }
+                for (int l = 0; l < rdsl.top && !rc; l++) {
+                    for (size_t k = 0; k < rdsl.at[l].size(); k++) {
+                        IfcJob j{};
+                        j.in = reinterpret_cast<const float2*>(rdsl.dev[l] + k);
+                        j.kind = 4;
+                        ifc.add(l, j);
+                    }
+                }
+                for (int l = 0; l < rdsx.top && !rc; l++) {
+                    for (size_t k = 0; k < rdsx.at[l].size(); k++) {
+                        IfcJob j{};
+                        j.in = reinterpret_cast<const float2*>(rdsx.dev[l] + k);
+                        j.kind = 3;
+                        ifc.add(l, j);
+                    }
+                }
             }
             if (!rc && !arena_push_lev(c, L)) { rc = arena_fail(c); }
         });
@@ -1490,6 +1613,11 @@ int do_vfos_plan(sdrpp_ctx* c, const IqSrc& src, int64_t count, const CarryJob& 
     for (size_t i = 0; i < c->vfo_list.size(); i++) {
         for (auto& s : c->vfo_list[i]->st) {
             if (s.hist_len > 0 && s.data) { s.cur ^= 1; }
+        }
+        if (c->vfo_list[i]->rds.ran) {
+            for (auto& s : c->vfo_list[i]->rds.st) {
+                if (s.hist_len > 0 && s.data) { s.cur ^= 1; }
+            }
         }
     }
     return SDRPP_OK;

@@ -383,6 +383,8 @@ int sdrpp_destroy(sdrpp_ctx* c) {
     dev_free(c->d_gather);
     dev_free(c->d_gather_jobs);
     for (auto& kv : c->vfos) { vfo_free(*kv.second); }
+    for (auto& kv : c->rds_banks) { dev_free(kv.second.d_bank); }
+    c->rds_banks.clear();
     c->vfos.clear();
     for (auto& e : c->s1_tap_cache) { (void)hipFree(e.second); }
     for (auto& e : c->fmif_tabs) { (void)hipFree(e.second); }
@@ -773,6 +775,7 @@ int sdrpp_vfo_remove(sdrpp_ctx* c, int id) {
     FLUSH_PENDING(c);
     LOOKUP_VFO(v, c, id);
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    rds_detach(c, *v);
     vfo_free(*v);
     c->vfos.erase(id);
     vfo_list_rebuild(c);
@@ -923,6 +926,42 @@ int sdrpp_vfo_rec_read(sdrpp_ctx* c, int id, void* dst_host, int max_frames, sdr
 }
 
 int sdrpp_abi_sizeof_rec_desc(void) { return (int)sizeof(sdrpp_rec_desc); }
+
+// ---- RDS branch of the WFM demodulator: discriminator -> translation by -57 kHz -> resampler to 5 kS/s (broadcast_fm.h:144-215) -----------------
+int sdrpp_vfo_set_rds(sdrpp_ctx* c, int id, const sdrpp_rds_desc* d, int enabled) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return rds_apply(c, *v, d, enabled != 0);
+}
+
+int sdrpp_vfo_rds_count(sdrpp_ctx* c, int id) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return out_count(c, out_of_rds(*v), kNoRds, id);
+}
+
+int sdrpp_vfo_rds_read(sdrpp_ctx* c, int id, float* dst, int max) {
+    DeviceScope dev_scope_(c);
+    if (!c || !dst || max < 0) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return out_read(c, out_of_rds(*v), kNoRds, id, dst, max, false);
+}
+
+int sdrpp_vfo_rds_device_buffer(sdrpp_ctx* c, int id, const float** out, int* n_out) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return out_hand(c, out_of_rds(*v), kNoRds, id, out, n_out);
+}
+
+int sdrpp_abi_sizeof_rds_desc(void) { return (int)sizeof(sdrpp_rds_desc); }
+int sdrpp_rds_bank_count(sdrpp_ctx* c) { return c ? (int)c->rds_banks.size() : SDRPP_ERR_INVALID; }
 
 int sdrpp_vfo_read_pcm(sdrpp_ctx* c, int id, int which, int pcm_type, float scale, void* dst_host, int max_frames) {
     DeviceScope dev_scope_(c);
@@ -1090,6 +1129,7 @@ int sdrpp_vfo_reset(sdrpp_ctx* c, int id) {
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
     LOOKUP_VFO(v, c, id);
+    if (int rc = rds_freeze(c, *v)) { return rc; }  // (the RDS branch's delay line is not the demodulator's: it outlives the history cleared below)
     return vfo_reset_state(c, *v);
 }
 
@@ -1576,6 +1616,26 @@ int sdrpp_result_rec(sdrpp_ctx* c, uint64_t ticket, int id, const void** data, s
         return SDRPP_OK;
     }
     return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of a recorder sink of VFO %d", (unsigned long long)ticket, id);
+}
+int sdrpp_pipeline_set_rds_results(sdrpp_ctx* c, int on) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    if (!c->pipelined) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_pipeline_set_rds_results outside pipelined mode"); }
+    FLUSH_PENDING(c);
+    c->res_flags = on ? (c->res_flags | SDRPP_RESULT_RDS) : (c->res_flags & ~SDRPP_RESULT_RDS);
+    return SDRPP_OK;
+}
+int sdrpp_result_rds(sdrpp_ctx* c, uint64_t ticket, int id, const float** data, int* count) {
+    if (!c) { return SDRPP_ERR_INVALID; }
+    sdrpp_ctx::Result* R = result_of(c, ticket);
+    if (!R || !R->held) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_result_rds: block %llu is not held (between sdrpp_result_wait and sdrpp_result_release)", (unsigned long long)ticket); }
+    for (size_t i = 0; i < R->rds_ids.size(); i++) {
+        if (R->rds_ids[i] != id) { continue; }
+        if (data) { *data = reinterpret_cast<const float*>(R->base + R->rds_off[i]); }
+        if (count) { *count = R->rds_counts[i]; }
+        return SDRPP_OK;
+    }
+    return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of an RDS branch of VFO %d", (unsigned long long)ticket, id);
 }
 int sdrpp_result_meters(sdrpp_ctx* c, uint64_t ticket, const float** data, int* n_lines, int* n_meters) {
     if (!c) { return SDRPP_ERR_INVALID; }

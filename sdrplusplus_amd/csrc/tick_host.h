@@ -268,6 +268,12 @@ size_t tick_results_need(sdrpp_ctx* c) {
             need += (((cap + 16) * 8 + 15) & ~(size_t)15) + (size_t)kGroupMax * kRecInfoStride;
         }
     }
+    if (c->res_flags & 32) {  // RDS branches: the 5 kS/s baseband of the block
+        for (auto& kv : c->vfos) {
+            const Vfo::Rds& r = kv.second->rds;
+            if (r.attached && !r.st.empty()) { need += ((r.st.back().cap + 16) * 8 + 15) & ~(size_t)15; }
+        }
+    }
     if ((c->res_flags & 8) && c->pre.on) {
         size_t cap = c->pre.out.base ? c->pre.out.cap : 0;
         for (auto& st : c->pre.st) { cap = std::max(cap, st.cap); }
@@ -472,6 +478,25 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
             off = info0 + (size_t)k * kRecInfoStride;
         }
     }
+    if (c->res_flags & 32) {
+        // every RDS branch that ran in this block: the group's samples in one piece, push j's share between its push ends (Vfo::Rds::tk)
+        for (auto& kv : c->vfos) {
+            const Vfo& v = *kv.second;
+            const Vfo::Rds& r = v.rds;
+            if (!r.attached || !r.ran) { continue; }
+            const Stream& s = r.st[(size_t)r.i_last];
+            if (split && ((int)r.tk.size() != k || r.tk[(size_t)k - 1] != s.n)) { return fail(c, SDRPP_ERR_INVALID, "internal: push ends of VFO %d's RDS branch do not add up (%zu ends, %d samples)", v.id, r.tk.size(), s.n); }
+            for (int j = 0; j < k; j++) {
+                const int lo = (split && j > 0) ? r.tk[(size_t)j - 1] : 0, hi = split ? r.tk[(size_t)j] : s.n;
+                R[j]->rds_ids.push_back(v.id);
+                R[j]->rds_off.push_back(off + (size_t)lo * 8);
+                R[j]->rds_counts.push_back(hi - lo);
+            }
+            const size_t bytes = (size_t)s.n * 8;
+            if (bytes) { copies.push_back(ResCopy{ s.data, off, bytes, r.lvl + 1 }); }
+            off += (bytes + 15) & ~(size_t)15;
+        }
+    }
     if (off > c->res_cap) { return fail(c, SDRPP_ERR_INVALID, "internal: results of %zu bytes exceed what a launch may deliver (%zu)", off, c->res_cap); }
     int rc = tick_results_alloc(c, c->groups, off, region_off);
     if (rc) {
@@ -598,6 +623,12 @@ int tick_push(sdrpp_ctx* c, const float* d_iq, int64_t count, const CopyJob* lan
     if (as_tick) {  // rings of the per-block buffers, result slots (allocated on first use / after a change of the configuration)
         for (auto& kv : c->vfos) {
             for (auto& st : kv.second->st) {
+                if (st.n_extra < kRing - 1 && st.base) {
+                    int rc = stream_ring_ensure(c, st);
+                    if (rc) { return rc; }
+                }
+            }
+            for (auto& st : kv.second->rds.st) {
                 if (st.n_extra < kRing - 1 && st.base) {
                     int rc = stream_ring_ensure(c, st);
                     if (rc) { return rc; }

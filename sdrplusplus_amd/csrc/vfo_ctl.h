@@ -34,7 +34,11 @@ Stream* delivered(Vfo& v, int which) {
 // The stream the demodulator reads: the IF chain's output while a chain is active, else RxVFO::out.
 Stream& demod_feed(Vfo& v) { return delivered(v, 3) ? *delivered(v, 3) : rx_out(v); }
 // How much of its input the demodulator remembers: the fused discriminator + audio FIR re-reads the IF history.
-int demod_if_need(const Vfo& v) { return (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) ? std::max(v.audio_ntaps, 1) + 1 : 1; }
+// (and the RDS branch's fused first stage recomputes its delay line from it: the stage's K0 - 1 samples and the one in front of them)
+int demod_if_need(const Vfo& v) {
+    const int fm = (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) ? std::max(v.audio_ntaps, 1) + 1 : 1;
+    return (v.rds.attached && !v.rds.exact) ? std::max(fm, (int)v.rds.staps[0].size()) : fm;
+}
 
 // ---- delay-line hand-overs ----------------------------------------------------------------------------------------------------------
 // the newest min(both histories, max_samples) samples of `from`'s history become the newest of `to`'s
@@ -389,6 +393,7 @@ int fmnr_apply(sdrpp_ctx* c, Vfo& v, bool enabled, int bins) {
 //   * the demodulator behind it is a separate block that setInSamplerate leaves alone: discriminator / audio low-pass history, AGC and DC-blocker
 //     states, SSB's second translation                                                                                                     -> keep bit 1
 // (a demodulator SWITCH deletes and creates it, radio_module.h:419-563: bit 1 off).  The AF chain is re-attached by the caller and starts cleared.
+int rds_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n);  // (the RDS branch: below, with the rest of it)
 int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
     Stream& of = chan_feed(o);
     Stream& nf = chan_feed(n);
@@ -427,6 +432,9 @@ int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
         rc = ifc_apply(c, n, &fd);
         if (rc) { return rc; }
         if (o.ifc.nb_on && o.ifc.d_amp && n.ifc.d_amp) { HIPCHK(c, hipMemcpy(n.ifc.d_amp, o.ifc.d_amp, sizeof(float), hipMemcpyDeviceToDevice)); }
+    }
+    if ((keep & 2) && o.d.demod == n.d.demod && n.d.demod == SDRPP_DEMOD_WFM) {
+        if ((rc = rds_hand_over(c, o, n))) { return rc; }
     }
     if (keep & 4) {  // ... and FMIF with them: its bin count, whether it is plugged in, and its delay line
         if ((rc = fmif_line_save(c, o))) { return rc; }
@@ -594,6 +602,218 @@ int af_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_af_desc* af) {
     return SDRPP_OK;
 }
 
+// ---- RDS branch of the WFM demodulator ----------------------------------------------------------------------------------------------
+// FNV-1a over what makes a polyphase bank: identical descriptions share ONE device copy per context (5000 x 119 floats at 250 kS/s: 2.4 MB)
+unsigned long long rds_bank_hash(int interp, int decim, const float* taps, int n) {
+    unsigned long long h = 1469598103934665603ull;
+    auto mix = [&](unsigned u) { h = (h ^ u) * 1099511628211ull; };
+    mix((unsigned)interp);
+    mix((unsigned)decim);
+    mix((unsigned)n);
+    for (int i = 0; i < n; i++) {
+        unsigned u;
+        memcpy(&u, &taps[i], 4);
+        mix(u);
+    }
+    return h ? h : 1ull;
+}
+void rds_detach(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Rds& r = v.rds;
+    if (r.bank_key) {
+        auto it = c->rds_banks.find(r.bank_key);
+        if (it != c->rds_banks.end() && --it->second.refs <= 0) {
+            dev_free(it->second.d_bank);
+            c->rds_banks.erase(it);
+        }
+    }
+    rds_free_own(r);
+    r = Vfo::Rds{};
+}
+// The first decimator's delay line leaves the feed's history (the branch is switched off, or the history is about to be cleared or to move on without the
+// branch): the discriminator values of its newest K0 samples are set aside (the oldest of them, which would need a sample more, lies outside the filter's reach),
+// and the branch reads them in place of the history until it has been fed K0 samples in a row again.  A line that is in force already IS what the branch was
+// fed last (short blocks are spliced onto it as they come): it stays, and only the count of samples fed in a row starts over.
+int rds_freeze(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Rds& r = v.rds;
+    if (!r.attached || !r.on || r.exact) { return SDRPP_OK; }
+    r.line_fed = 0;
+    if (r.frozen) { return SDRPP_OK; }
+    const Stream& s = demod_feed(v);
+    const int K0 = (int)r.staps[0].size();
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float* line = r.d_line[r.line_cur];
+    if (s.hist_len >= K0 && s.hist[s.cur]) {
+        const float2* tail = reinterpret_cast<const float2*>(s.hist[s.cur]) + (s.hist_len - K0);
+        hipLaunchKernelGGL(vfo_rds_line_kernel, dim3(1), dim3(64), 0, c->stream, RdsLineJob{ tail, tail, line, line, K0, K0, v.d.inv_deviation });
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    else { HIPCHK(c, hipMemset(line, 0, (size_t)K0 * sizeof(float))); }  // (never: rds_apply grows every stream the demodulator may read)
+    r.frozen = true;
+    return SDRPP_OK;
+}
+bool rds_same_desc(const Vfo::Rds& r, const sdrpp_rds_desc* d) {
+    const bool has_poly = d->interp != d->decim;
+    if (r.pd_re != d->phase_delta_re || r.pd_im != d->phase_delta_im || r.n_stages != d->n_stages || (r.i_poly >= 0) != has_poly) { return false; }
+    for (int s = 0; s < d->n_stages; s++) {
+        if (r.decim_s[s] != d->stage_decim[s] || (int)r.staps[s].size() != d->stage_ntaps[s] || memcmp(r.staps[s].data(), d->stage_taps[s], r.staps[s].size() * sizeof(float)) != 0) { return false; }
+    }
+    if (has_poly && (r.interp != d->interp || r.decim != d->decim || (int)r.rtaps.size() != d->resamp_ntaps || memcmp(r.rtaps.data(), d->resamp_taps, r.rtaps.size() * sizeof(float)) != 0)) { return false; }
+    return true;
+}
+// sdrpp_vfo_set_rds on a VFO the caller has looked up (the stream is idle)
+int rds_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_rds_desc* d, bool enabled) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!d) {
+        rds_detach(c, v);
+        return SDRPP_OK;
+    }
+    if (v.d.demod != SDRPP_DEMOD_WFM) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the RDS branch needs a WFM VFO"); }
+    if (d->n_stages < 0 || d->n_stages > SDRPP_MAX_DECIM_STAGES) { return fail(c, SDRPP_ERR_INVALID, "rds n_stages %d", d->n_stages); }
+    for (int s = 0; s < d->n_stages; s++) {
+        if (!is_pow2(d->stage_decim[s]) || d->stage_ntaps[s] <= 0 || !d->stage_taps[s]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "rds stage %d: decimation must be a power of two with taps", s); }
+    }
+    const bool has_poly = d->interp != d->decim;
+    if (has_poly && (d->interp <= 0 || d->decim <= 0 || d->resamp_ntaps <= 0 || !d->resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad rds polyphase description"); }
+    if (d->n_stages < 1 || d->stage_decim[0] < 2) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the RDS branch's first stage must decimate"); }
+    int tile = 0, pitch = 0;
+    if (!v.nco_exact && !rds_tile_geometry(d->stage_ntaps[0], d->stage_decim[0], &tile, &pitch)) {
+        return fail(c, SDRPP_ERR_UNSUPPORTED, "rds first stage (decimation %d, %d taps): no tile of its window fits the kernel's LDS", d->stage_decim[0], d->stage_ntaps[0]);
+    }
+    Vfo::Rds& r = v.rds;
+    if (r.attached && r.exact == v.nco_exact && rds_same_desc(r, d)) {  // the same branch: only the switch
+        if (r.on && !enabled) {
+            if (int rc = rds_freeze(c, v)) { return rc; }
+            for (auto& s : r.st) { s.n = 0; }
+        }
+        r.on = enabled;
+        r.ran = r.ran && enabled;
+        return SDRPP_OK;
+    }
+    rds_detach(c, v);
+    // every early return below gives back what was built so far
+    struct Undo {
+        sdrpp_ctx* c; Vfo& v; bool armed = true;
+        ~Undo() { if (armed) { rds_detach(c, v); } }
+    } undo{ c, v };
+    int rc;
+    r.exact = v.nco_exact;
+    r.pd_re = d->phase_delta_re;
+    r.pd_im = d->phase_delta_im;
+    r.theta = sdrpp_host::turnsPerSample(d->phase_delta_re, d->phase_delta_im);
+    r.n_stages = d->n_stages;
+    r.interp = has_poly ? d->interp : 1;
+    r.decim = has_poly ? d->decim : 1;
+    r.tpp = has_poly ? (d->resamp_ntaps + d->interp - 1) / d->interp : 0;
+    r.tile = tile;
+    r.pitch = pitch;
+    const Stream& feed0 = v.st[(size_t)v.i_chan];
+    size_t cap = feed0.cap;
+    auto add_stream = [&](int hist, size_t capn) -> int {
+        r.st.emplace_back();
+        return stream_alloc(c, r.st.back(), 2, hist, capn) ? -1 : (int)r.st.size() - 1;
+    };
+    auto need_of = [&](int stage) -> int {  // history the input of `stage` keeps (n_stages: the polyphase stage)
+        if (stage < r.n_stages) { return d->stage_ntaps[stage] - 1; }
+        return has_poly ? r.tpp - 1 : 0;
+    };
+    r.st.reserve(SDRPP_MAX_DECIM_STAGES + 2);
+    if (r.exact) {
+        if (add_stream(need_of(0), cap) < 0) { return SDRPP_ERR_NOMEM; }
+        if ((rc = dev_alloc(c, &r.d_rot, 1))) { return rc; }
+        const float2 unit = make_float2(1.0f, 0.0f);  // frequency_xlator.h:21
+        HIPCHK(c, hipMemcpy(r.d_rot, &unit, sizeof(unit), hipMemcpyHostToDevice));
+    }
+    r.i_stage0 = (int)r.st.size();
+    for (int s = 0; s < r.n_stages; s++) {
+        r.decim_s[s] = d->stage_decim[s];
+        r.staps[s].assign(d->stage_taps[s], d->stage_taps[s] + d->stage_ntaps[s]);
+        if (s == 0 && !r.exact) { rc = upload(c, &r.d_staps[0], r.staps[0].data(), r.staps[0].size()); }  // (the fused stage reads them in natural order)
+        else {
+            rc = upload_blocked(c, &r.d_staps[s], r.staps[s].data(), (int)r.staps[s].size(), r.decim_s[s], &r.s_kp[s]);
+            if (!rc) { rc = toep_build_fir(c, r.tp_stage[s], r.staps[s].data(), (int)r.staps[s].size(), r.decim_s[s]); }
+        }
+        if (rc) { return rc; }
+        cap = cap / (size_t)r.decim_s[s] + 2;
+        if (add_stream(need_of(s + 1), cap) < 0) { return SDRPP_ERR_NOMEM; }
+    }
+    if (has_poly) {
+        r.rtaps.assign(d->resamp_taps, d->resamp_taps + d->resamp_ntaps);
+        const unsigned long long key = rds_bank_hash(d->interp, d->decim, d->resamp_taps, d->resamp_ntaps);
+        auto it = c->rds_banks.find(key);
+        if (it != c->rds_banks.end() && (it->second.interp != d->interp || it->second.tpp != r.tpp || it->second.taps != r.rtaps)) {
+            return fail(c, SDRPP_ERR_UNSUPPORTED, "rds polyphase bank: two different descriptions under one key");  // (a 64-bit collision: never seen)
+        }
+        if (it == c->rds_banks.end()) {
+            sdrpp_ctx::RdsBank B;
+            const std::vector<float> bank = polyphase_bank(r.rtaps.data(), d->resamp_ntaps, d->interp, r.tpp);
+            if ((rc = upload(c, &B.d_bank, bank.data(), bank.size()))) { return rc; }
+            B.interp = d->interp;
+            B.tpp = r.tpp;
+            B.taps = r.rtaps;
+            it = c->rds_banks.emplace(key, std::move(B)).first;
+        }
+        it->second.refs++;
+        r.bank_key = key;
+        r.d_bank = it->second.d_bank;
+        cap = cap * (size_t)r.interp / (size_t)r.decim + 4;
+        r.i_poly = add_stream(0, cap);
+        if (r.i_poly < 0) { return SDRPP_ERR_NOMEM; }
+    }
+    r.i_last = (int)r.st.size() - 1;
+    if (!r.exact) {
+        // the streams the demodulator may read must remember the first stage's reach; the branch starts from a cleared delay line
+        const int K0 = d->stage_ntaps[0];
+        if ((rc = stream_grow_hist(c, v.st[(size_t)v.i_chan], K0))) { return rc; }
+        if ((rc = stream_grow_hist(c, chan_feed(v), K0))) { return rc; }
+        if (v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base && (rc = stream_grow_hist(c, v.st[(size_t)v.i_ifc], K0))) { return rc; }
+        for (int i = 0; i < 2; i++) {
+            if ((rc = dev_alloc(c, &r.d_line[i], (size_t)K0))) { return rc; }
+            HIPCHK(c, hipMemset(r.d_line[i], 0, (size_t)K0 * sizeof(float)));
+        }
+        r.frozen = true;
+        r.line_cur = 0;
+        r.line_fed = 0;
+    }
+    r.attached = true;
+    r.on = enabled;
+    undo.armed = false;
+    return SDRPP_OK;
+}
+// sdrpp_vfo_replace with keep & 2 between two WFM VFOs: the branch — parameters, streams, state — belongs to the demodulator object and moves with it
+int rds_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n) {
+    if (!o.rds.attached) { return SDRPP_OK; }
+    if (o.rds.exact != n.nco_exact) {  // the other NCO mode keeps its state in another form: the same description, attached to the new handle from cleared state
+        const Vfo::Rds& q = o.rds;
+        sdrpp_rds_desc d{};
+        d.phase_delta_re = q.pd_re;
+        d.phase_delta_im = q.pd_im;
+        d.n_stages = q.n_stages;
+        for (int s = 0; s < q.n_stages; s++) {
+            d.stage_decim[s] = q.decim_s[s];
+            d.stage_ntaps[s] = (int)q.staps[s].size();
+            d.stage_taps[s] = q.staps[s].data();
+        }
+        d.interp = q.interp;
+        d.decim = q.decim;
+        d.resamp_ntaps = (int)q.rtaps.size();
+        d.resamp_taps = q.rtaps.empty() ? nullptr : q.rtaps.data();
+        return rds_apply(c, n, &d, q.on);
+    }
+    if (int rc = rds_freeze(c, o)) { return rc; }
+    n.rds = std::move(o.rds);
+    o.rds = Vfo::Rds{};
+    n.rds.ran = false;
+    for (auto& s : n.rds.st) { s.n = 0; }
+    if (!n.rds.exact) {
+        const int K0 = (int)n.rds.staps[0].size();
+        int rc;
+        if ((rc = stream_grow_hist(c, n.st[(size_t)n.i_chan], K0))) { return rc; }
+        if ((rc = stream_grow_hist(c, chan_feed(n), K0))) { return rc; }
+        if (n.i_ifc >= 0 && n.st[(size_t)n.i_ifc].base && (rc = stream_grow_hist(c, n.st[(size_t)n.i_ifc], K0))) { return rc; }
+    }
+    return SDRPP_OK;
+}
 // ---- read-out -----------------------------------------------------------------------------------------------------------------------
 // A pipelined back-end launch whose wavefronts gave up waiting for each other (never seen; a hang would be worse) counted that in THIS context's
 // page-locked word.  Called wherever the host has just synchronised with the stream and is about to hand out results.
@@ -614,6 +834,14 @@ int pipe_timeouts_check(sdrpp_ctx* c) {
 struct OutBuf { const float* data; int n; bool ok; };
 OutBuf out_of(const Stream* s) { return s ? OutBuf{ s->data, s->n, true } : OutBuf{ nullptr, 0, false }; }
 OutBuf out_of_preproc(const sdrpp_ctx* c) { return c->pre.on ? OutBuf{ c->pre.last, c->pre.last_n, true } : OutBuf{ nullptr, 0, false }; }
+// the RDS branch's output of the most recent push (nothing while it is switched off)
+const char* const kNoRds = "VFO %d has no RDS branch";
+OutBuf out_of_rds(const Vfo& v) {
+    const Vfo::Rds& r = v.rds;
+    if (!r.attached) { return OutBuf{ nullptr, 0, false }; }
+    const Stream& s = r.st[(size_t)r.i_last];
+    return OutBuf{ s.data, (r.on && r.ran) ? s.n : 0, true };
+}
 const char* const kNoAf = "VFO %d has no AF chain";
 const char* const kNoIfc = "VFO %d has no active IF chain";
 const char* const kNoPreproc = "no pre-processing chain configured";  // (takes no id)

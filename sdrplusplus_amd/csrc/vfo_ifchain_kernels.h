@@ -1,9 +1,10 @@
-// The radio's IF chain: noise blanker and power squelch; FMIF (vfo_fmif_kernels.h) runs under the same job record.
+// The radio's IF chain: noise blanker and power squelch; FMIF (vfo_fmif_kernels.h) and the RDS branch's jobs (vfo_rds_kernels.h) run under the same job record.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <sdrpp_gfx950.h>
 #include "vfo_fmif_kernels.h"
+#include "vfo_rds_kernels.h"
 
 namespace sdrpp_k {
 
@@ -23,6 +24,12 @@ __device__ __forceinline__ void vfo_ifchain_body(int id, const IfcJob* __restric
     const IfcJob job = jobs[id];
     if (job.kind == 1) {
         vfo_fmif_body(job, smem);
+        return;
+    }
+    if (job.kind >= 2) {  // the WFM demodulator's RDS branch (vfo_rds_kernels.h): `in` names the job's own record
+        if (job.kind == 2) { vfo_rds_front_call(reinterpret_cast<const RdsJob*>(job.in), smem); }
+        else if (job.kind == 4) { vfo_rds_line_call(reinterpret_cast<const RdsLineJob*>(job.in)); }
+        else { vfo_rds_rotate_exact_call(reinterpret_cast<const RdsRotXJob*>(job.in)); }
         return;
     }
     const int lane = threadIdx.x & 63;

@@ -112,6 +112,7 @@ class RxVFO {
 public:
     dsp::stream<dsp::complex_t> out;   // RxVFO::out (IF); delivered when no demodulator is attached
     dsp::stream<dsp::stereo_t> audio;  // demodulator output (radio's Demodulator::getOutput()) when attached
+    dsp::stream<dsp::complex_t> rdsOut;  // attachRDS: BroadcastFM::rdsOut — the 5 kS/s baseband RDSDemod consumes, one swap per block that produced samples
     dsp::stream<uint8_t> recorded;     // attachRecorder: one swap per block the recorder would write, the packed bytes of the file's sample type (silent blocks: no swap)
 
     void setInSamplerate(double inSamplerate);                // rx_vfo.h:38-43
@@ -136,6 +137,13 @@ public:
     // Calling it again changes the parameters from the next block on; re-plans (setInSamplerate, a new demodulator) keep it.
     void attachRecorder(double volume, bool mono, int sampleType, bool ignoreSilence);
     void detachRecorder();
+    // The WFM demodulator's RDS branch (dsp/demod/broadcast_fm.h:144-215, _rdsOut; sdrpp_vfo_set_rds) on the device: discriminator -> translation by -57 kHz ->
+    // RationalResampler to 5 kS/s, delivered on `rdsOut` block by block from the worker that delivers `audio`.  attachRDS starts the branch from cleared state;
+    // setRDSOut(false) unplugs it and freezes its state, setRDSOut(true) continues from it (BroadcastFM::setRDSOut); re-plans that keep the demodulator keep it.
+    // DEVIATION: the reference's setRDSOut also clears the discriminator and the audio filter (one click in the audio); here the audio path is left alone.
+    void attachRDS();
+    void detachRDS();
+    void setRDSOut(bool enabled);
     dsp::stereo_t getRecorderLevel();  // PeakLevelMeter::getLevel / resetLevel: the running maximum over the blocks since the last reset
     void resetRecorderLevel();
     // The waterfall's signal read-out for this VFO (calculateVFOSignalInfo, waterfall.cpp:558-598: what the reference shows for the selected VFO on every
@@ -177,6 +185,7 @@ public:
     double nbLevel = 10.0, squelchLevel = -100.0;
     double afAudioRate = 48000.0, afDeempTau = 50e-6;
     bool recOn = false, recMono = false, recIgnoreSilence = false;
+    bool rdsAttached = false, rdsOn = false;
     double recVolume = 1.0;
     int recType = SDRPP_REC_INT16;
 
@@ -367,6 +376,7 @@ public:
         registerOutput(&v->out);
         registerOutput(&v->audio);
         registerOutput(&v->recorded);
+        registerOutput(&v->rdsOut);
         tempStart();
         return v;
     }
@@ -382,6 +392,7 @@ public:
         unregisterOutput(&it->second->out);
         unregisterOutput(&it->second->audio);
         unregisterOutput(&it->second->recorded);
+        unregisterOutput(&it->second->rdsOut);
         vfoOrder.erase(std::remove(vfoOrder.begin(), vfoOrder.end(), it->second), vfoOrder.end());
         delete it->second;
         vfos.erase(it);
@@ -838,13 +849,15 @@ private:
         const bool pre = _decimRatio > 1 || _dcBlocking || _invertIQ;
         bool rec = false;
         for (auto& kv : vfos) { rec = rec || (kv.second->recOn && kv.second->demod != Demod::RAW); }
-        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0);  // (a recorder adds its flag and drops nobody's: `audio` is delivered as before)
+        bool rds = false;
+        for (auto& kv : vfos) { rds = rds || (kv.second->rdsAttached && kv.second->demod == Demod::WFM); }
+        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0) | (rds ? SDRPP_RESULT_RDS : 0);  // (a recorder or an RDS branch adds its flag and drops nobody's: `audio` is delivered as before)
     }
     int enterPipelined() {
         if (sdrpp_sync(ctx)) { return -1; }  // (nothing is staged in bypass mode; a deferred pass left over from buffered mode runs here)
         sdrpp_set_deferred(ctx, 0);
         pipeFlags = pipelineFlags();
-        if (sdrpp_set_pipelined(ctx, 1, pipeFlags)) {
+        if (sdrpp_set_pipelined(ctx, 1, pipeFlags & ~SDRPP_RESULT_RDS) || ((pipeFlags & SDRPP_RESULT_RDS) && sdrpp_pipeline_set_rds_results(ctx, 1))) {  // (flag 32 has a call of its own)
             fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] pipelined mode refused: %s\n", sdrpp_last_error(ctx));
             sdrpp_set_deferred(ctx, 1);
             _pipelining = false;
@@ -980,6 +993,22 @@ private:
                 jobs.emplace_back([this, v, data, bytes]() {
                     memcpy(v->recorded.writeBuf, data, bytes);
                     if (!v->recorded.swap((int)bytes)) { deliveryFailed = true; }
+                });
+            }
+        }
+        // the RDS branches: this push's 5 kS/s samples (result flag 32), straight out of the slot; a block that produced none is not handed on
+        if (pipeFlags & SDRPP_RESULT_RDS) {
+            for (auto& kv : vfos) {
+                RxVFO* v = kv.second;
+                if (!v->rdsAttached) { continue; }
+                const float* data = nullptr;
+                int cnt = 0;
+                int rrc = sdrpp_result_rds(ctx, ticket, v->id, &data, &cnt);
+                for (size_t q = v->prevIds.size(); rrc == SDRPP_ERR_NOT_FOUND && q-- > 0;) { rrc = sdrpp_result_rds(ctx, ticket, v->prevIds[q], &data, &cnt); }
+                if (rrc || cnt <= 0) { continue; }  // (pushed before the attach, or while the branch was switched off)
+                jobs.emplace_back([this, v, data, cnt]() {
+                    memcpy(v->rdsOut.writeBuf, data, (size_t)cnt * sizeof(dsp::complex_t));
+                    if (!v->rdsOut.swap(cnt)) { deliveryFailed = true; }
                 });
             }
         }
@@ -1214,6 +1243,20 @@ private:
                 if (!v->recorded.swap(bytes)) { failed = true; }
             });
         }
+        // the RDS branches: the pass's samples straight into the stream's buffer
+        for (auto& kv : vfos) {
+            RxVFO* v = kv.second;
+            if (!v->rdsAttached || !v->rdsOn || v->demod != Demod::WFM || v->id < 0) { continue; }
+            const int got = sdrpp_vfo_rds_read(ctx, v->id, reinterpret_cast<float*>(v->rdsOut.writeBuf), STREAM_BUFFER_SIZE);
+            if (got < 0) {
+                fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] reading the RDS branch failed: %s\n", sdrpp_last_error(ctx));
+                return -1;
+            }
+            if (got == 0) { continue; }
+            jobs.emplace_back([v, got, &failed]() {
+                if (!v->rdsOut.swap(got)) { failed = true; }
+            });
+        }
         helpers.run(std::move(jobs));
         if (failed) { return -1; }
         SDRPP_BLOCKS_TICK(6)
@@ -1342,6 +1385,7 @@ private:
         if (oldId < 0 && (v.fmnrOn || v.fmnrBins != 32)) { applyFMNR(v); }  // (a replaced handle has it already: keep | 4)
         if (v.afOn && v.demod != Demod::RAW) { applyAF(v); }
         if (v.recOn && v.demod != Demod::RAW) { applyRec(v); }  // (sdrpp_vfo_replace does not carry the sink: the recorder binds to the stream, and the stream lives on)
+        if (v.rdsAttached && v.demod == Demod::WFM) { applyRDS(v); }  // (a handle that kept its demodulator has the branch already, state and all: the same description only sets the switch)
         sendMeters();  // (a new handle, perhaps a new bandwidth or input rate)
     }
 
@@ -1362,6 +1406,35 @@ private:
         r.ignore_silence = v.recIgnoreSilence ? 1 : 0;
         int rc = sdrpp_vfo_set_rec(ctx, v.id, &r);
         if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_rec: ") + sdrpp_last_error(ctx)); }
+    }
+
+    // broadcast_fm.h:52-53: xlator.init(NULL, -57000.0, samplerate); rdsResamp.init(NULL, samplerate, 5000.0)
+    void applyRDS(RxVFO& v) {
+        sdrpp_rds_desc r;
+        memset(&r, 0, sizeof(r));
+        sdrpp_design_phase_delta(-57000.0, v.outSamplerate, &r.phase_delta_re, &r.phase_delta_im);
+        int mode = 0, predec = 1, interp = 1, decim = 1;
+        int nt = sdrpp_design_resampler(v.outSamplerate, 5000.0, _plans.maxRatio, &mode, &predec, &interp, &decim, nullptr, 0);
+        std::vector<float> rtaps((size_t)(nt > 0 ? nt : 1));
+        if (nt > 0) { sdrpp_design_resampler(v.outSamplerate, 5000.0, _plans.maxRatio, &mode, &predec, &interp, &decim, rtaps.data(), nt); }
+        const std::vector<DecimStage>* st = nullptr;
+        if ((mode == 0 || mode == 1) && predec > 1) {
+            auto it = _plans.plans.find(predec);
+            if (it == _plans.plans.end()) { throw std::runtime_error("[sdrpp_gpu::IQFrontEnd] no decimation plan for ratio " + std::to_string(predec)); }
+            st = &it->second;
+        }
+        r.n_stages = st ? (int)st->size() : 0;
+        for (int i = 0; i < r.n_stages; i++) {
+            r.stage_decim[i] = (*st)[(size_t)i].decimation;
+            r.stage_ntaps[i] = (int)(*st)[(size_t)i].taps.size();
+            r.stage_taps[i] = (*st)[(size_t)i].taps.data();
+        }
+        r.interp = (mode == 0 || mode == 2) ? interp : 1;
+        r.decim = (mode == 0 || mode == 2) ? decim : 1;
+        r.resamp_ntaps = (mode == 0 || mode == 2) ? nt : 0;
+        r.resamp_taps = rtaps.data();
+        int rc = sdrpp_vfo_set_rds(ctx, v.id, &r, v.rdsOn ? 1 : 0);
+        if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_rds: ") + sdrpp_last_error(ctx)); }
     }
 
     // radio_module.h:90-91: nb.init(NULL, 500.0 / ifRate, 10.0); powerSquelch.init(NULL, MIN_SQUELCH)
@@ -1714,6 +1787,35 @@ inline void RxVFO::detachRecorder() {
     fe->tempStop();
     recOn = false;
     if (id >= 0) { sdrpp_vfo_set_rec(fe->ctx, id, nullptr); }
+    fe->tempStart();
+}
+inline void RxVFO::attachRDS() {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (demod != Demod::WFM) { throw std::runtime_error("[sdrpp_gpu::RxVFO] the RDS branch belongs to the WFM demodulator"); }
+    fe->tempStop();
+    if (rdsAttached && id >= 0) { sdrpp_vfo_set_rds(fe->ctx, id, nullptr, 0); }  // (attaching again starts cleared)
+    rdsAttached = true;
+    rdsOn = true;
+    if (id >= 0) { fe->applyRDS(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::detachRDS() {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    fe->tempStop();
+    rdsAttached = false;
+    rdsOn = false;
+    if (id >= 0) { sdrpp_vfo_set_rds(fe->ctx, id, nullptr, 0); }
+    fe->tempStart();
+}
+inline void RxVFO::setRDSOut(bool enabled) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (!rdsAttached) {
+        if (enabled) { attachRDS(); }
+        return;
+    }
+    fe->tempStop();  // broadcast_fm.h:121-128
+    rdsOn = enabled;
+    if (id >= 0 && demod == Demod::WFM) { fe->applyRDS(*this); }
     fe->tempStart();
 }
 inline dsp::stereo_t RxVFO::getRecorderLevel() {

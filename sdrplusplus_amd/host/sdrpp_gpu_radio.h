@@ -115,6 +115,15 @@ public:
     // radio_module.h:676-690: the checkbox and the preset (9 / 15 / 31 / 32 bins); WFM runs 32 bins whatever the preset (:531)
     void setFMIFNREnabled(bool enabled) { _fmnrEnabled = enabled; applyIF(); }
     void setIFNRPreset(int bins) { _fmnrBins = bins; applyIF(); }
+    // WFM only (wfm.h:79, 118-126: `rdsDemod.init(&demod.rdsOut, ...)`, demod.setRDSOut(_rds)): the demodulator's RDS branch on the device.  A host writes
+    // rdsDemod.init(wfm.getRDSOutput(), 5000.0 / 2375, ...) where the reference passes &demod.rdsOut.  DEVIATION: the reference's setRDSOut also clears the
+    // discriminator and the audio filter (one click in the audio); here the audio path is left alone.
+    void setRDSOut(bool enabled) {
+        if (MODE != Demod::WFM) { throw std::runtime_error("[sdrpp_gpu::FusedDemodulator] RDS output belongs to the WFM demodulator"); }
+        _rdsOut = enabled;
+        if (vfo) { vfo->setRDSOut(enabled); }
+    }
+    dsp::stream<dsp::complex_t>* getRDSOutput() { return (MODE == Demod::WFM && vfo) ? &vfo->rdsOut : nullptr; }
     RxVFO* channel() { return vfo; }
 
 private:
@@ -129,11 +138,13 @@ private:
             vfo->setNoiseBlanker(false, _nbLevel);
             vfo->setSquelch(false, _squelchLevel);
             vfo->setFMIFNR(false, vfo->fmnrBins);
+            if (vfo->rdsAttached) { vfo->detachRDS(); }
             vfo->attachDemod(Demod::RAW);
         }
         vfo = v;
         apply();
         applyIF();
+        if (MODE == Demod::WFM && _rdsOut) { vfo->setRDSOut(true); }
     }
     void apply() {
         if (!vfo) { return; }
@@ -157,6 +168,7 @@ private:
     bool _lowPass = true, _carrierAgc = false;
     double _agcAttack = 50.0, _agcDecay = 5.0;  // am.h:98-99, usb.h:92-93
     bool _nbEnabled = false, _squelchEnabled = false, _fmnrEnabled = false;
+    bool _rdsOut = false;
     int _fmnrBins = 32;  // radio_module.h:91
     float _nbLevel = 10.0f, _squelchLevel = -100.0f;  // radio_module.h:906, :446
 };

@@ -191,6 +191,33 @@ def af_desc(af_rate, audio_rate=48000.0, deemp_tau=50e-6, high_pass=False):
     return a, keep
 
 
+def rds_desc(if_rate=250e3, out_rate=5000.0, offset=-57000.0):
+    """sdrpp_rds_desc for the WFM demodulator's RDS branch (broadcast_fm.h:60-62): FrequencyXlator(offset, if_rate) and
+    RationalResampler<complex_t>(if_rate -> out_rate) — at 250 kS/s the ratio-32 plan {8 x 44, 2 x 12, 2 x 69} and the 5000 / 7813 polyphase stage.
+    Returns (desc, keepalive)."""
+    r = capi.RdsDesc()
+    keep = []
+    r.phase_delta_re, r.phase_delta_im = capi.design_phase_delta(offset, if_rate)
+    rs = capi.design_resampler(if_rate, out_rate, plans().max_ratio)
+    stages = plans().stages(rs["predec"]) if rs["mode"] in (0, 1) else []
+    r.n_stages = len(stages)
+    for i, (dec, taps) in enumerate(stages):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        keep.append(t)
+        r.stage_decim[i] = dec
+        r.stage_ntaps[i] = len(t)
+        r.stage_taps[i] = _fp(t)
+    if rs["mode"] in (0, 2):
+        rt = np.ascontiguousarray(rs["taps"], dtype=np.float32)
+        keep.append(rt)
+        r.interp, r.decim = rs["interp"], rs["decim"]
+        r.resamp_ntaps = len(rt)
+        r.resamp_taps = _fp(rt)
+    else:
+        r.interp, r.decim, r.resamp_ntaps = 1, 1, 0
+    return r, keep
+
+
 def if_desc(if_rate, nb=False, nb_level=10.0, squelch=None):
     """sdrpp_if_desc for the radio module's IF chain (radio_module.h:84-96): NoiseBlanker(rate = 500 / if_rate, level; :90, :526) ->
     PowerSquelch(level in dB; None = off).  FMIF, the chain's last block, is switched by Context.vfo_set_fmnr (IFNR_BINS); the CTCSS squelch is not on the device."""
