@@ -55,6 +55,7 @@ int sdrpp_set_stream(sdrpp_ctx* ctx, void* hip_stream);
 int sdrpp_sync(sdrpp_ctx* ctx);
 /* ABI self-description for foreign-function bindings: returns the ABI version and, if non-NULL, sizeof(sdrpp_vfo_desc). */
 #define SDRPP_ABI_VERSION 2   /* 2: sdrpp_vfo_desc.nco_mode, sdrpp_pipeline_stats */
+/* (sdrpp_push_raw / sdrpp_push_frame / sdrpp_design_u8_table / sdrpp_iq_format are additions: no existing call or structure changed, the version stays 2) */
 int sdrpp_abi_version(int* sizeof_vfo_desc);
 /* Human-readable device name / arch into buf (for logs and bench records). */
 int sdrpp_device_info(sdrpp_ctx* ctx, char* buf, int buflen);
@@ -495,6 +496,46 @@ int sdrpp_push_device(sdrpp_ctx* ctx, const float* iq_dev, int64_t count);
 /* file_source path (source_modules/file_source/src/main.cpp:154-167): interleaved int16 IQ converted on the device
  * (x / 32768), halving the PCIe bytes.  Host pointer. */
 int sdrpp_push_int16(sdrpp_ctx* ctx, const int16_t* iq_host, int64_t count);
+/* The wire formats of the reference's sources, converted on the device: the bus carries the bytes the radio delivered (2 per complex sample for the
+ * 8-bit formats, 4 for int16) instead of 8.  Interleaved I / Q in host memory, `count` complex samples; the caller's buffer is free on return.
+ *   SDRPP_IQ_I8   (float)x * (1.0f / scalar)   volk_8i_s32f_convert_32f (generic)    hackrf_source / network_source / harogic_source: scalar 128;
+ *                                                                                     an SDR++ server frame: 128.0f / scaler
+ *   SDRPP_IQ_I16  (float)x * (1.0f / scalar)   volk_16i_s32f_convert_32f (generic)   file_source: 32768 (= sdrpp_push_int16, the same routine); kcsdr_source: 8192;
+ *                                                                                     spyserver 16-bit: 32768.0f * gain; a server frame: 32768.0f / scaler
+ *   SDRPP_IQ_U8   table[b]                     256 floats from sdrpp_design_u8_table  rtl_sdr_source, rtl_tcp_source, spyserver 8-bit
+ * 1.0f / scalar is ONE float division, done on the host; the int -> float conversion of an 8- or 16-bit integer is exact and the product one float multiply,
+ * so every value is exactly specified.  The U8 sources each subtract and scale in arithmetic of their own (double, float, mixed): the host computes the
+ * 256 possible results in that arithmetic and the device only looks them up.  The table is copied at the call, so it may change from one push to the next.
+ * scalar must be finite and non-zero (I8, I16), table non-NULL (U8), type one of the three: SDRPP_ERR_INVALID otherwise.
+ * Works in every mode a push has: at once, deferred, pipelined, in launch groups (sdrpp_set_pipeline_group).  In a group a push joins only if its format
+ * matches the held pushes' (type, the scalar's bits, for U8 the table's contents); otherwise what is held goes out first, as for any push of another kind.
+ * NOT offered, on purpose:
+ *   int32 (network_source): 8 bytes per sample like float — converting it on the device saves nothing;
+ *   a landing job per push of a group: server frames whose scaler changes from frame to frame therefore ride one launch each;
+ *   raw formats read in place from the caller's page-locked memory (what sdrpp_push_pinned_async does for floats): a raw push is always copied into the
+ *   library's staging slot first. */
+#define SDRPP_IQ_I8  0
+#define SDRPP_IQ_I16 1
+#define SDRPP_IQ_U8  2
+typedef struct sdrpp_iq_format {
+    int type;            /* SDRPP_IQ_*                                 */
+    float scalar;        /* I8 / I16; ignored for U8                   */
+    const float* table;  /* U8: 256 floats; ignored for I8 / I16       */
+} sdrpp_iq_format;
+int sdrpp_push_raw(sdrpp_ctx* ctx, const void* iq_host, int64_t count, const sdrpp_iq_format* fmt);
+/* One frame of the SDR++ server protocol as the client receives it — [u16 0][u16 type][f32 scaler][data], what SampleStreamDecompressor::process
+ * takes (core/src/dsp/compression/sample_stream_decompressor.h:13-34; the sink-side twin is sdrpp_vfo_read_compressed): type at byte 2, scaler at byte 4,
+ * data from byte 8.  PCM_TYPE_F32 is a plain sdrpp_push, _I16 sdrpp_push_raw with scalar 32768.0f / scaler, _I8 with 128.0f / scaler.  *samples (may be
+ * NULL) = the count the reference returns.  A frame shorter than 8 bytes: SDRPP_ERR_INVALID.  An unknown type gives 0 samples and SDRPP_OK as in the
+ * reference, and so does a frame whose data holds no whole sample: nothing is pushed. */
+int sdrpp_push_frame(sdrpp_ctx* ctx, const unsigned char* frame, int bytes, int* samples);
+/* The 256-entry table of a U8 source, in the types that source computes in:
+ *   source 0  rtl_sdr_source/src/main.cpp:535-536   ((float)b - 127.4) / 128.0f        the subtraction and the division in double (127.4 is a double), rounded to float
+ *   source 1  rtl_tcp_client.cpp:86-87              ((double)b - 128.0) / 128.0        all in double, rounded to float
+ *   source 2  spyserver_client.cpp:139-142          ((float)b - 128.0f) * (1.0f / (gain * 128.0f))   all in float
+ * gain: source 2 only.  SDRPP_ERR_INVALID for another source or a NULL table. */
+int sdrpp_design_u8_table(int source, float gain, float* table256);
+int sdrpp_abi_sizeof_iq_format(void);
 
 /* Page-locked host memory for buffers that are pushed from (the copy out of pageable memory is staged by the runtime and about three
  * times slower); NULL on failure.  The host blocks allocate their frame-buffer slots with it. */
@@ -541,7 +582,7 @@ int64_t sdrpp_pending(sdrpp_ctx* ctx);   /* samples staged and not yet processed
  * caller asks (sdrpp_pipeline_flush, sdrpp_result_wait, any observing call such as sdrpp_vfo_read / sdrpp_sync — these run the queued
  * stages without new input; sdrpp_fft_lines and sdrpp_vfo_out_count only report what the host already knows and do not).
  *   sdrpp_push_device        reads the caller's buffer IN PLACE one launch later at the earliest: it must stay valid until sdrpp_sync.
- *   sdrpp_push / _push_int16 copy into a page-locked staging slot (the caller's buffer is free on return), fetched by the next launch.
+ *   sdrpp_push / _push_int16 / _push_raw copy into a page-locked staging slot (the caller's buffer is free on return), fetched by the next launch.
  *   sdrpp_push_pinned_async  page-locked memory is fetched by the launch itself; sdrpp_push_wait returns when all such fetches have run.
  * The pre-processing chain (sdrpp_preproc_configure, default arithmetic), the radio's AF chain (sdrpp_vfo_set_af) and the waterfall display
  * state (sdrpp_wf_configure) run that way too — their stages are further levels of the block; so do VFOs on the reference-rotator NCO

@@ -137,6 +137,14 @@ class MeterDesc(C.Structure):
     _fields_ = [("center_offset", C.c_double), ("bandwidth", C.c_double)]
 
 
+class IqFormat(C.Structure):
+    """struct sdrpp_iq_format (include/sdrpp_gpu.h): the wire format of a raw push (sdrpp_push_raw)."""
+
+    _fields_ = [("type", C.c_int), ("scalar", C.c_float), ("table", C.POINTER(C.c_float))]
+
+
+IQ_I8, IQ_I16, IQ_U8 = 0, 1, 2                     # SDRPP_IQ_*
+U8_RTL_SDR, U8_RTL_TCP, U8_SPYSERVER = 0, 1, 2    # sdrpp_design_u8_table's sources
 MAX_METERS = 1024   # SDRPP_MAX_METERS
 REC_UINT8, REC_INT16, REC_INT32, REC_FLOAT32 = 0, 1, 2, 3   # wav::SampleType (utils/wav.h:25-30)
 REC_DTYPES = {REC_UINT8: np.uint8, REC_INT16: np.int16, REC_FLOAT32: np.float32}
@@ -312,6 +320,12 @@ def load():
     L.sdrpp_push.argtypes = [vp, c_float_p, C.c_int64]
     L.sdrpp_push_device.argtypes = [vp, vp, C.c_int64]
     L.sdrpp_push_int16.argtypes = [vp, C.POINTER(C.c_int16), C.c_int64]
+    L.sdrpp_abi_sizeof_iq_format.argtypes = []
+    if L.sdrpp_abi_sizeof_iq_format() != C.sizeof(IqFormat):
+        raise ImportError("sdrpp_iq_format layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_iq_format(), C.sizeof(IqFormat)))
+    L.sdrpp_push_raw.argtypes = [vp, vp, C.c_int64, C.POINTER(IqFormat)]
+    L.sdrpp_push_frame.argtypes = [vp, C.c_char_p, C.c_int, c_int_p]
+    L.sdrpp_design_u8_table.argtypes = [C.c_int, C.c_float, c_float_p]
     L.sdrpp_set_pipelined.argtypes = [vp, C.c_int, C.c_int]
     L.sdrpp_set_pipeline_group.argtypes = [vp, C.c_int, C.c_int]
     L.sdrpp_pipeline_group_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
@@ -353,6 +367,7 @@ EXPORTED_SYMBOLS = [
     "sdrpp_vfo_add", "sdrpp_vfo_remove", "sdrpp_vfo_replace", "sdrpp_vfo_count", "sdrpp_vfo_set_phase_delta", "sdrpp_vfo_set_channel_taps", "sdrpp_vfo_reset",
     "sdrpp_vfo_out_count", "sdrpp_vfo_read", "sdrpp_vfo_device_buffers",
     "sdrpp_set_reference_block", "sdrpp_set_nco_mode", "sdrpp_set_backend_pipeline", "sdrpp_vfo_set_ssb_phase_delta", "sdrpp_vfo_read_many", "sdrpp_set_deferred", "sdrpp_push_pinned_async", "sdrpp_push_wait", "sdrpp_pending", "sdrpp_host_alloc", "sdrpp_host_free", "sdrpp_device_alloc", "sdrpp_device_free", "sdrpp_device_copy", "sdrpp_device_count",
+    "sdrpp_push_raw", "sdrpp_push_frame", "sdrpp_design_u8_table", "sdrpp_abi_sizeof_iq_format",
     "sdrpp_push", "sdrpp_push_device", "sdrpp_push_int16", "sdrpp_push_stage", "sdrpp_push_staged", "sdrpp_push_staged_when",
     "sdrpp_set_pipelined", "sdrpp_set_pipeline_group", "sdrpp_pipeline_group_stats", "sdrpp_ticket", "sdrpp_pipeline_flush", "sdrpp_pipeline_launch_held", "sdrpp_result_ready", "sdrpp_result_wait", "sdrpp_result_release", "sdrpp_result_take_lines", "sdrpp_pipeline_stats", "sdrpp_pipeline_role_name", "sdrpp_pass_form_stats",
     "sdrpp_timing_enable", "sdrpp_timing_read", "sdrpp_kernel_family_name",
@@ -415,6 +430,15 @@ def design_resampler(in_sr, out_sr, max_ratio=8192):
 
 def design_deemphasis_alpha(tau, sample_rate):
     return float(load().sdrpp_design_deemphasis_alpha(tau, sample_rate))
+
+
+def design_u8_table(source, gain=1.0):
+    """sdrpp_design_u8_table: the 256 floats a U8 source converts its bytes to, in that source's own arithmetic (U8_RTL_SDR, U8_RTL_TCP, U8_SPYSERVER with gain)."""
+    t = np.empty(256, dtype=np.float32)
+    rc = load().sdrpp_design_u8_table(int(source), float(gain), t.ctypes.data_as(c_float_p))
+    if rc:
+        raise SdrppError(rc, "bad U8 table parameters")
+    return t
 
 
 def design_waterfall_view(view_offset, view_bandwidth, whole_bandwidth, raw_fft_size):
@@ -814,6 +838,23 @@ class Context:
     def push_int16(self, iq_i16):
         a = np.ascontiguousarray(iq_i16, dtype=np.int16)
         self._chk(self.L.sdrpp_push_int16(self.h, a.ctypes.data_as(C.POINTER(C.c_int16)), len(a) // 2))
+
+    def push_raw(self, iq, type, scalar=None, table=None):
+        """sdrpp_push_raw: interleaved I / Q pairs as int8 (IQ_I8), int16 (IQ_I16) or uint8 (IQ_U8) — converted on the device: (float)x * (1.0f / scalar), or table[b]."""
+        dt = {IQ_I8: np.int8, IQ_I16: np.int16, IQ_U8: np.uint8}.get(type, np.uint8)
+        a = np.ascontiguousarray(iq, dtype=dt).reshape(-1)
+        tab = None if table is None else np.ascontiguousarray(table, dtype=np.float32)
+        if tab is not None and tab.size != 256:
+            raise ValueError("a U8 table has 256 entries")
+        fmt = IqFormat(int(type), 0.0 if scalar is None else float(scalar), None if tab is None else tab.ctypes.data_as(c_float_p))
+        self._chk(self.L.sdrpp_push_raw(self.h, C.c_void_p(a.ctypes.data), len(a) // 2, C.byref(fmt)))
+
+    def push_frame(self, frame):
+        """sdrpp_push_frame: one SDR++-server frame ([u16 0][u16 type][f32 scaler][data]) -> the samples it held (0: nothing was pushed)."""
+        frame = bytes(frame)
+        n = C.c_int(0)
+        self._chk(self.L.sdrpp_push_frame(self.h, frame, len(frame), C.byref(n)))
+        return n.value
 
     def push_device(self, dev_ptr, count):
         self._chk(self.L.sdrpp_push_device(self.h, C.c_void_p(dev_ptr), int(count)))

@@ -883,10 +883,4 @@ __global__ __launch_bounds__(256) void pack_max_kernel(const float* __restrict__
     if (threadIdx.x == 0) { partial[blockIdx.x] = sm[0]; }
 }
 
-// int16 IQ -> float (file_source/main.cpp:162: volk_16i_s32f_convert_32f(out, in, 32768.0f, n))
-__global__ __launch_bounds__(256) void int16_to_float_kernel(const int16_t* __restrict__ in, float* __restrict__ out, long long n) {
-    const float inv = 1.0f / 32768.0f;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) { out[i] = ((float)in[i]) * inv; }
-}
-
 }  // namespace sdrpp_k

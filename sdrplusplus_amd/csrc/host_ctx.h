@@ -193,7 +193,9 @@ struct sdrpp_ctx {
     // next pass overlap the kernels of the current one; copies run on their own stream and are host-synchronised (the caller's
     // buffer is free again when sdrpp_push returns, like a dsp::stream read buffer after flush())
     float* iq_land[2] = { nullptr, nullptr };
-    int16_t* iq_land16[2] = { nullptr, nullptr };
+    int16_t* iq_land16[2] = { nullptr, nullptr };   // the raw bytes of sdrpp_push_raw / _push_int16 (4 bytes per sample at most), converted into iq_land by ingest_kernel
+    float* d_u8_tab = nullptr;                      // the SDRPP_IQ_U8 table of ordinary / deferred passes ...
+    std::vector<float> u8_tab;                      // ... and what it holds (uploaded when a push brings another one)
     hipEvent_t land_ev[2] = { nullptr, nullptr };   // recorded behind the pass that read the buffer
     bool land_used[2] = { false, false };
     int land_cur = 0;
@@ -404,7 +406,8 @@ struct sdrpp_ctx {
     unsigned* h_tick_flag = nullptr;      // page-locked: completed ticks (written by the last wavefront of each tick)
     unsigned* hd_tick_flag = nullptr;     // the same, device address
     uint64_t arena_tick[kArenaSlots] = {};  // pipelined: the tick that uploaded from this arena slot (+1; 0 = never)
-    float* tick_land[3] = {};             // landing ring of host pushes (max_push complex each; allocated on first use)
+    float* tick_land[3] = {};             // landing ring of host pushes (SDRPP_LAND_TABLE floats for a U8 table, then max_push complex each; allocated on first use)
+    std::vector<float> tick_land_tab[3];  // the U8 table in front of each (empty: none uploaded yet)
     float* stage_host[kStageSlots] = {};  // page-locked staging of pushes from pageable memory (max_push complex each; allocated on first use)
     uint64_t stage_tick[kStageSlots] = {};  // the tick whose landing copy reads the slot (+1)
     int stage_cur = 0;
@@ -430,7 +433,10 @@ struct sdrpp_ctx {
     int group_adaptive = 0;               // 1: a group goes out as soon as the device has fewer than two launches in flight (a host slower than the device: one block per launch)
     bool stage_pend_stable = false;       // sdrpp_set_pipeline_group flag 2: the words handed to sdrpp_push_staged_when stay valid until their block has been LAUNCHED — a held push does not wait for its copy
     struct Held {
-        int kind = -1;                    // -1: nothing held; 0: device memory read in place; 1 / 2: float / int16 samples in a page-locked staging slot; 3: the caller's page-locked memory
+        int kind = -1;                    // -1: nothing held; 0: device memory read in place; 1 / 2: float / raw (fmt_*: sdrpp_iq_format) samples in a page-locked staging slot; 3: the caller's page-locked memory
+        int fmt_type = 0;                 // kind 2: the wire format every held push has
+        float fmt_scalar = 0.0f;
+        std::vector<float> fmt_table;     // ... SDRPP_IQ_U8: its 256 floats
         const char* base = nullptr;       // kind 0 / 3: address of the first block (the following ones are contiguous with it)
         int stage_slot = -1;              // kind 1 / 2
         int64_t total = 0;                // samples held

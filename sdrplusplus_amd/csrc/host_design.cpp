@@ -86,6 +86,19 @@ void sdrpp_design_phase_delta(double offset_hz, double sample_rate, float* re, f
     *im = (float)std::sin(w);
 }
 
+// The 256 values a U8 source can produce, each in that source's own arithmetic (the types are the point: see include/sdrpp_gpu.h)
+int sdrpp_design_u8_table(int source, float gain, float* table256) {
+    if (!table256 || source < 0 || source > 2) { return SDRPP_ERR_INVALID; }
+    const float scale = 1.0f / (gain * 128.0f);  // spyserver_client.cpp:139
+    for (int i = 0; i < 256; i++) {
+        const unsigned char b = (unsigned char)i;
+        if (source == 0) { table256[i] = ((float)b - 127.4) / 128.0f; }          // rtl_sdr_source/src/main.cpp:535: double subtraction and division, rounded by the store
+        else if (source == 1) { table256[i] = ((double)b - 128.0) / 128.0; }      // rtl_tcp_client.cpp:86
+        else { table256[i] = ((float)b - 128.0f) * scale; }                       // spyserver_client.cpp:141
+    }
+    return SDRPP_OK;
+}
+
 float sdrpp_design_deemphasis_alpha(double tau, double sample_rate) {
     const float dt = 1.0f / sample_rate;  // deephasis.h:91-92: float dt = 1.0f / _samplerate; alpha = dt / (_tau + dt);
     return (float)(dt / (tau + dt));

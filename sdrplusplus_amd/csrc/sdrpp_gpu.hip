@@ -418,6 +418,7 @@ int sdrpp_destroy(sdrpp_ctx* c) {
         dev_free(c->iq_land16[i]);
         if (c->land_ev[i]) { (void)hipEventDestroy(c->land_ev[i]); }
     }
+    dev_free(c->d_u8_tab);
     if (c->ev_copy) { (void)hipEventDestroy(c->ev_copy); }
     if (c->copy_stream) { (void)hipStreamDestroy(c->copy_stream); }
     if (c->side_stream) { (void)hipStreamDestroy(c->side_stream); }
@@ -1418,23 +1419,40 @@ int sdrpp_push_device(sdrpp_ctx* c, const float* iq_dev, int64_t count) {
     return SDRPP_OK;
 }
 
-int sdrpp_push_int16(sdrpp_ctx* c, const int16_t* iq_host, int64_t count) {
-    DeviceScope dev_scope_(c);
+// ---- raw wire formats (ingest_kernels.h) ----
+// One routine behind sdrpp_push_raw, sdrpp_push_int16 and sdrpp_push_frame; `fmt` has been checked.
+static int push_raw_impl(sdrpp_ctx* c, const void* iq_host, int64_t count, const sdrpp_iq_format& fmt) {
     int rc = push_args_ok(c, iq_host, count);
     if (rc) { return rc; }
-    if (c->pipelined) { return tick_hold(c, 2, iq_host, count, nullptr); }
+    if (c->pipelined) { return tick_hold(c, 2, iq_host, count, nullptr, &fmt); }
     if (count == 0) { return c->deferred ? SDRPP_OK : push_common(c, nullptr, 0); }
     rc = landing_acquire(c, true);
     if (rc) { return rc; }
     const int b = c->land_cur;
-    int16_t* land16 = c->iq_land16[b] + 2 * c->pending;
-    HIPCHK(c, hipMemcpyAsync(land16, iq_host, (size_t)count * 2 * sizeof(int16_t), hipMemcpyHostToDevice, c->copy_stream));
+    // (4 bytes per staged sample whatever the format: the pushes of a deferred pass may differ in theirs, and the conversion of one must not find the
+    // raw bytes of the next where it still reads)
+    char* raw = reinterpret_cast<char*>(c->iq_land16[b]) + (size_t)4 * (size_t)c->pending;
+    const size_t bytes = (size_t)count * iq_format_bytes(fmt.type);
+    HIPCHK(c, hipMemcpyAsync(raw, iq_host, bytes, hipMemcpyHostToDevice, c->copy_stream));
     HIPCHK(c, hipEventRecord(c->ev_copy, c->copy_stream));
     HIPCHK(c, hipEventSynchronize(c->ev_copy));
+    if (fmt.type == SDRPP_IQ_U8 && (c->u8_tab.size() != 256 || memcmp(c->u8_tab.data(), fmt.table, 256 * sizeof(float)) != 0)) {
+        if (!c->d_u8_tab) {
+            rc = dev_alloc(c, &c->d_u8_tab, 256);
+            if (rc) { return rc; }
+        }
+        c->u8_tab.assign(fmt.table, fmt.table + 256);
+        // on the stream of the conversions: behind those that still read the previous table
+        if (hipMemcpyAsync(c->d_u8_tab, c->u8_tab.data(), 256 * sizeof(float), hipMemcpyHostToDevice, c->launch_stream) != hipSuccess) {
+            c->u8_tab.clear();
+            return fail(c, SDRPP_ERR_HIP, "upload of the U8 table failed");
+        }
+    }
     {
         FamilyTimer t(c, F_MISC);
-        const long long n = (long long)count * 2;
-        launch(c, int16_to_float_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)), dim3(256), 0, (const int16_t*)land16, c->iq_land[b] + 2 * c->pending, n);
+        const long long n16 = (long long)(bytes / 16);
+        launch(c, ingest_kernel, dim3((unsigned)std::max<long long>(1, std::min<long long>((n16 + 255) / 256, 2048))), dim3(256), 0, (const void*)raw, c->iq_land[b] + 2 * c->pending, (long long)bytes, fmt.type,
+               fmt.type == SDRPP_IQ_U8 ? 0.0f : 1.0f / fmt.scalar, (const float*)c->d_u8_tab);
     }
     if (c->deferred) {
         c->pending += count;
@@ -1443,6 +1461,54 @@ int sdrpp_push_int16(sdrpp_ctx* c, const int16_t* iq_host, int64_t count) {
     }
     return landing_process(c, count, nullptr);
 }
+int sdrpp_push_int16(sdrpp_ctx* c, const int16_t* iq_host, int64_t count) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    return push_raw_impl(c, iq_host, count, sdrpp_iq_format{ SDRPP_IQ_I16, 32768.0f, nullptr });  // (x * (1.0f / 32768.0f) is exact: what x / 32768 gave)
+}
+int sdrpp_push_raw(sdrpp_ctx* c, const void* iq_host, int64_t count, const sdrpp_iq_format* fmt) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    if (!fmt) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_push_raw: no format"); }
+    if (fmt->type == SDRPP_IQ_I8 || fmt->type == SDRPP_IQ_I16) {
+        if (!std::isfinite(fmt->scalar) || fmt->scalar == 0.0f) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_push_raw: scalar %g (need a finite number other than 0)", (double)fmt->scalar); }
+    }
+    else if (fmt->type == SDRPP_IQ_U8) {
+        if (!fmt->table) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_push_raw: SDRPP_IQ_U8 needs a table (sdrpp_design_u8_table)"); }
+    }
+    else { return fail(c, SDRPP_ERR_INVALID, "sdrpp_push_raw: unknown format %d", fmt->type); }
+    return push_raw_impl(c, iq_host, count, *fmt);
+}
+int sdrpp_push_frame(sdrpp_ctx* c, const unsigned char* frame, int bytes, int* samples) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    if (samples) { *samples = 0; }
+    if (!frame || bytes < 8) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_push_frame: %d bytes (a frame has an 8-byte header)", bytes); }
+    // SampleStreamDecompressor::process (sample_stream_decompressor.h:13-34); PCMType (pcm_type.h): 0 I8, 1 I16, 2 F32
+    uint16_t type;
+    float scaler;
+    memcpy(&type, frame + 2, sizeof(type));
+    memcpy(&scaler, frame + 4, sizeof(scaler));
+    const unsigned char* data = frame + 8;
+    int n = 0, rc = SDRPP_OK;
+    if (type == 2) {
+        n = (bytes - 8) / 8;
+        if (n > 0) {
+            // (the data start 8 bytes into the caller's frame: whatever alignment that has, the push copies bytes)
+            rc = sdrpp_push(c, reinterpret_cast<const float*>(data), n);
+        }
+    }
+    else if (type == 1 || type == 0) {
+        n = (bytes - 8) / (type == 1 ? 4 : 2);
+        if (n > 0) {
+            sdrpp_iq_format fmt{ type == 1 ? SDRPP_IQ_I16 : SDRPP_IQ_I8, (type == 1 ? 32768.0f : 128.0f) / scaler, nullptr };
+            rc = sdrpp_push_raw(c, data, n, &fmt);
+        }
+    }
+    if (!rc && samples) { *samples = n; }
+    return rc;
+}
+int sdrpp_abi_sizeof_iq_format(void) { return (int)sizeof(sdrpp_iq_format); }
 
 // page-locked host memory for buffers the caller pushes from (an H2D copy from pageable memory is staged by the runtime: ~3x slower)
 void* sdrpp_host_alloc(size_t bytes) {

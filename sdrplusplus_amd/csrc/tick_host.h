@@ -133,6 +133,9 @@ int tick_launch(sdrpp_ctx* c, const CopyJob* land) {
     if (land && land->bytes > 0) {
         l0.job[0] = *land;
         l0.blocks[0] = (int)std::max<long long>(1, std::min<long long>((land->bytes + 8191) / 8192, c->tick_land_blocks));
+        // (a converting copy: a workgroup per 32 KB of SOURCE, rounded down — eight 16-byte loads per work-item, the unrolled loop's trip, from the first
+        // block that has that much; the source is a quarter or half of what the verbatim copy fetches for the same samples)
+        if ((land->kind & 0xff) == 4) { l0.blocks[0] = (int)std::max<long long>(1, std::min<long long>(land->bytes / 32768, c->tick_land_blocks)); }
     }
     if (c->arena_off > 0) {
         l0.job[1] = CopyJob{ c->arena_host_dev[c->arena_slot], c->arena_dev, (long long)((c->arena_off + 15) & ~(size_t)15), 0, 0 };
@@ -775,6 +778,9 @@ int tick_push(sdrpp_ctx* c, const float* d_iq, int64_t count, const CopyJob* lan
     return rc;
 }
 
+// bytes per complex sample of a wire format (sdrpp_iq_format::type)
+inline size_t iq_format_bytes(int type) { return type == SDRPP_IQ_I16 ? 4 : 2; }
+
 // ---- several blocks per launch (sdrpp_set_pipeline_group) ---------------------------------------------------------------------------------
 // May pushes share a launch at all right now?  Not behind a pre-processing chain (its decimator changes the rate the push ends live at), not while a
 // block cannot run as a tick, and not with a VFO that only rotates (no decimation plan: its NCO is anchored at the start of a launch, the results
@@ -798,12 +804,25 @@ int tick_group_launch(sdrpp_ctx* c) {
     if (H.kind == 0) { rc = tick_push(c, reinterpret_cast<const float*>(H.base), H.total, nullptr, &H.ends, first_ticket); }  // read in place, one tick from now at the earliest
     else {
         const int li = (int)((c->groups + 1) % 3);
-        if (!c->tick_land[li]) { rc = dev_alloc(c, &c->tick_land[li], (size_t)c->max_push * 2 + 32); }
+        if (!c->tick_land[li]) { rc = dev_alloc(c, &c->tick_land[li], (size_t)SDRPP_LAND_TABLE + (size_t)c->max_push * 2 + 32); }
         void* d = nullptr;
         if (!rc && (hipHostGetDevicePointer(&d, H.kind == 3 ? (void*)H.base : (void*)c->stage_host[H.stage_slot], 0) != hipSuccess || !d)) { rc = fail(c, SDRPP_ERR_HIP, "hipHostGetDevicePointer(staging) failed"); }
+        float* const land_iq = c->tick_land[li] ? c->tick_land[li] + SDRPP_LAND_TABLE : nullptr;
+        if (!rc && H.kind == 2 && H.fmt_type == SDRPP_IQ_U8 && c->tick_land_tab[li] != H.fmt_table) {
+            // The landing copy runs in the very tick that uploads the block's job tables, so the table cannot travel in the arena: it goes in front of
+            // the landing buffer, on the stream, ahead of the launch that reads it (1 KB, and only when this buffer last saw another table).
+            if (hipMemcpyAsync(c->tick_land[li], H.fmt_table.data(), (size_t)SDRPP_LAND_TABLE * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = fail(c, SDRPP_ERR_HIP, "upload of the U8 table failed"); }
+            else { c->tick_land_tab[li] = H.fmt_table; }
+        }
         if (!rc) {
-            const CopyJob land{ d, c->tick_land[li], (long long)((size_t)H.total * (H.kind == 2 ? 4 : 8)), H.kind == 2 ? 1 : 0, 0 };
-            rc = tick_push(c, c->tick_land[li], H.total, &land, &H.ends, first_ticket);
+            CopyJob land{ d, land_iq, (long long)((size_t)H.total * 8), 0, 0 };
+            if (H.kind == 2) {
+                const float inv = H.fmt_type == SDRPP_IQ_U8 ? 0.0f : 1.0f / H.fmt_scalar;
+                int inv_bits;
+                memcpy(&inv_bits, &inv, sizeof(inv_bits));
+                land = CopyJob{ d, land_iq, (long long)((size_t)H.total * iq_format_bytes(H.fmt_type)), 4 | (H.fmt_type << 16), inv_bits };
+            }
+            rc = tick_push(c, land_iq, H.total, &land, &H.ends, first_ticket);
             if (H.kind != 3) { c->stage_tick[H.stage_slot] = c->ticks; }
         }
     }
@@ -817,17 +836,22 @@ int tick_group_launch(sdrpp_ctx* c) {
     return rc;
 }
 // One push of a pipelined run: joins the held group, or — the group full, the push of another kind or not contiguous with it, grouping off — sends
-// what is held on its way first.  kind 0: `p` = device address (read in place); 1 / 2: float / int16 samples in host memory, copied into the
+// what is held on its way first.  kind 0: `p` = device address (read in place); 1 / 2: float / raw (`fmt`) samples in host memory, copied into the
 // group's page-locked staging slot (p == nullptr: the host has filled the slot itself, sdrpp_push_stage); 3: the caller's page-locked memory.
-int tick_hold(sdrpp_ctx* c, int kind, const void* p, int64_t count, const volatile uint32_t* pending) {
+// A raw push is "of another kind" than the held ones unless its format is theirs: type, the scalar's bits, for U8 the table's contents — the landing
+// copy of a launch converts with ONE format.
+int tick_hold(sdrpp_ctx* c, int kind, const void* p, int64_t count, const volatile uint32_t* pending, const sdrpp_iq_format* fmt = nullptr) {
     if (count == 0) { return SDRPP_OK; }
     sdrpp_ctx::Held& H = c->held;
     const bool groupable = group_eligible(c);
-    const size_t bps = kind == 2 ? 4 : 8;
+    const size_t bps = kind == 2 ? iq_format_bytes(fmt->type) : 8;
     if (H.kind >= 0) {
         bool fits = groupable && H.kind == kind && (int)H.ends.size() < c->group_max && H.total + count <= c->max_push;
+        if (fits && kind == 2) {
+            fits = H.fmt_type == fmt->type && (fmt->type == SDRPP_IQ_U8 ? memcmp(H.fmt_table.data(), fmt->table, 256 * sizeof(float)) == 0 : memcmp(&H.fmt_scalar, &fmt->scalar, sizeof(float)) == 0);
+        }
         if (fits && (kind == 0 || kind == 3)) { fits = reinterpret_cast<const char*>(p) == H.base + (size_t)8 * (size_t)H.total; }
-        if (H.ends.empty() && H.kind == kind && (kind == 1 || kind == 2) && H.total == 0) { fits = true; }  // (a slot opened by sdrpp_push_stage, nothing in it yet)
+        if (H.ends.empty() && H.kind == kind && kind == 1 && H.total == 0) { fits = true; }  // (a slot opened by sdrpp_push_stage, nothing in it yet)
         if (!fits) {
             if ((kind == 1 || kind == 2) && !p) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_push_staged: %lld samples do not fit the open staging slot", (long long)count); }
             int rc = tick_group_launch(c);
@@ -841,6 +865,11 @@ int tick_hold(sdrpp_ctx* c, int kind, const void* p, int64_t count, const volati
         H.base = reinterpret_cast<const char*>(p);
         H.total = 0;
         H.ends.clear();
+        if (kind == 2) {
+            H.fmt_type = fmt->type;
+            H.fmt_scalar = fmt->scalar;
+            if (fmt->type == SDRPP_IQ_U8) { H.fmt_table.assign(fmt->table, fmt->table + 256); }
+        }
         if (kind == 1 || kind == 2) {
             const int si = c->stage_cur;
             c->stage_cur = (c->stage_cur + 1) % kStageSlots;

@@ -17,6 +17,7 @@
 // stream) so that a producer working on block n+1 does not overwrite what a consumer still reads of block n.
 #pragma once
 #include <cstddef>
+#include "ingest_kernels.h"
 
 namespace sdrpp_k {
 
@@ -25,21 +26,17 @@ namespace sdrpp_k {
 struct CopyJob {
     const void* src;
     void* dst;
-    long long bytes;  // multiple of 4 (kind 1: SOURCE bytes, multiple of 2)
-    int kind;         // 0: verbatim; 1: interleaved int16 -> float (x / 32768: file_source/src/main.cpp:162); 2: complex conjugate (dsp/math/conjugate.h:12-15, bytes a multiple of 8); bit 8: dst is host memory
+    long long bytes;  // multiple of 4 (kind 4: SOURCE bytes, whole samples)
+    int kind;         // 0: verbatim; 2: complex conjugate (dsp/math/conjugate.h:12-15, bytes a multiple of 8); bit 8: dst is host memory
                       // 3 (copy_body only, one workgroup per job): the recorder sink — src is a RecJob (vfo_rec_kernels.h) that names source, destination and record itself
+                      // 4 (the tick's landing copy only, land_one): converting copy (ingest_kernels.h), bits 16-23 the wire format (IngestType); `pad` holds the bits of the float 1 / scalar, the
+                      //    U8 format's table is the SDRPP_LAND_TABLE floats in front of dst (the landing buffers are allocated with that room)
     int pad;
 };
+#define SDRPP_LAND_TABLE 256
 __device__ __forceinline__ void copy_one(const CopyJob& job, int bx, int gx) {
     const long long tid = (long long)bx * 256 + threadIdx.x, nth = (long long)gx * 256;
-    if ((job.kind & 0xff) == 1) {
-        const short* in = reinterpret_cast<const short*>(job.src);
-        float* out = reinterpret_cast<float*>(job.dst);
-        const float inv = 1.0f / 32768.0f;
-        const long long n = job.bytes / 2;
-        for (long long i = tid; i < n; i += nth) { out[i] = ((float)in[i]) * inv; }
-    }
-    else if ((job.kind & 0xff) == 2) {
+    if ((job.kind & 0xff) == 2) {
         const float2* in = reinterpret_cast<const float2*>(job.src);
         float2* out = reinterpret_cast<float2*>(job.dst);
         const long long n = job.bytes / 8;
@@ -75,6 +72,15 @@ __device__ __forceinline__ void copy_one(const CopyJob& job, int bx, int gx) {
     }
     // (results for the host: page-locked memory is not cached on the device, the stores are complete — tick_finish waits for them — before
     // this wavefront counts itself done)
+}
+// the landing copy of a tick: verbatim, or converting (kind 4 exists here only — copy_kernel and the copy role never see one)
+__device__ __forceinline__ void land_one(const CopyJob& job, int bx, int gx) {
+    if ((job.kind & 0xff) == 4) {  // (uniform over the launch)
+        float* out = reinterpret_cast<float*>(job.dst);
+        ingest_body_call(job.src, out, job.bytes, (job.kind >> 16) & 0xff, __int_as_float(job.pad), out - SDRPP_LAND_TABLE, bx, gx);
+        return;
+    }
+    copy_one(job, bx, gx);
 }
 // (a call, not inlined: the recorder's six conversion loops inside the tick kernel moved its register allocation — 168 instead of 167 VGPRs in the
 // SET = 0 build, the step DESIGN.md 4c measured at 2 % of cfg 3's tick — and the job is one workgroup of a few microseconds per VFO and push)
@@ -262,7 +268,7 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : 3) void tick_kernel(TickL0 l0, 
     int tr_role = -1, tr_entry = -1;
 #endif
     if (is_l0) {
-        if (b < l0.blocks[0]) { copy_one(l0.job[0], b, l0.blocks[0]); }
+        if (b < l0.blocks[0]) { land_one(l0.job[0], b, l0.blocks[0]); }
         else { copy_one(l0.job[1], b - l0.blocks[0], l0.blocks[1]); }
     }
     else {

@@ -708,6 +708,58 @@ public:
         }
         return deliver((const dsp::complex_t*)nullptr, count);
     }
+    // The wire formats of the other sources (sdrpp_push_raw: int8 and int16 scaled by 1.0f / scalar, uint8 through the source's table) and one frame of the
+    // server protocol (sdrpp_push_frame), under ingestInt16's contract: the worker is not running, the block is processed and delivered before the call
+    // returns, -1 otherwise.  Streams bound with bindIQStream receive floats computed here by the same expressions, table included.
+    int ingestRaw(const void* iq, int count, const sdrpp_iq_format& fmt) {
+        std::lock_guard<std::recursive_mutex> lck(ctrlMtx);
+        if (running || count <= 0 || count > SDRPP_GPU_MAX_BLOCK) { return -1; }
+        if (pipeOn && leavePipelined() < 0) { return -1; }
+        if (sdrpp_push_raw(ctx, iq, count, &fmt)) {
+            fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] push failed: %s\n", sdrpp_last_error(ctx));
+            return -1;
+        }
+        if (!iqStreams.empty()) {
+            tapCopy.resize((size_t)count);
+            float* o = (float*)tapCopy.data();
+            const float inv = 1.0f / fmt.scalar;  // (volk_8i / 16i_s32f_convert_32f: the reciprocal once, a multiply per value)
+            if (fmt.type == SDRPP_IQ_I16) {
+                for (int i = 0; i < 2 * count; i++) {  // (a server frame's data start 8 bytes into the caller's buffer: no alignment is assumed)
+                    int16_t v;
+                    memcpy(&v, (const char*)iq + 2 * (size_t)i, sizeof(v));
+                    o[i] = (float)v * inv;
+                }
+            }
+            else if (fmt.type == SDRPP_IQ_I8) {
+                for (int i = 0; i < 2 * count; i++) { o[i] = (float)((const int8_t*)iq)[i] * inv; }
+            }
+            else {
+                for (int i = 0; i < 2 * count; i++) { o[i] = fmt.table[((const uint8_t*)iq)[i]]; }
+            }
+        }
+        return deliver((const dsp::complex_t*)nullptr, count);
+    }
+    // -> the samples the frame held (0: an unknown type or no whole sample — nothing was processed), -1 as above or for less than a header
+    int ingestServerFrame(const uint8_t* frame, int bytes) {
+        std::lock_guard<std::recursive_mutex> lck(ctrlMtx);
+        if (running || !frame || bytes < 8) { return -1; }
+        uint16_t type;
+        float scaler;
+        memcpy(&type, frame + 2, sizeof(type));
+        memcpy(&scaler, frame + 4, sizeof(scaler));
+        if (type == 2) {  // PCM_TYPE_F32
+            const int n = (bytes - 8) / 8;
+            if (n <= 0) { return 0; }
+            serverFrameFloats.resize((size_t)n);
+            memcpy(serverFrameFloats.data(), frame + 8, (size_t)n * 8);
+            return ingestFloat(serverFrameFloats.data(), n) < 0 ? -1 : n;
+        }
+        if (type != 0 && type != 1) { return 0; }
+        const int n = (bytes - 8) / (type == 1 ? 4 : 2);
+        if (n <= 0) { return 0; }
+        const sdrpp_iq_format fmt{ type == 1 ? SDRPP_IQ_I16 : SDRPP_IQ_I8, (type == 1 ? 32768.0f : 128.0f) / scaler, nullptr };
+        return ingestRaw(frame + 8, n, fmt) < 0 ? -1 : n;
+    }
     int ingestFloat(const dsp::complex_t* iq, int count) {
         std::lock_guard<std::recursive_mutex> lck(ctrlMtx);
         if (running || count <= 0 || count > SDRPP_GPU_MAX_BLOCK) { return -1; }
@@ -1535,6 +1587,7 @@ private:
     int frameSizes[FRAME_SLOTS] = {};
     int frameWrite = 0, frameRead = 0;
     std::vector<dsp::complex_t> tapCopy;  // the block the bound IQ consumers are about to receive
+    std::vector<dsp::complex_t> serverFrameFloats;  // ingestServerFrame: the data of a float frame, copied out of the frame (its floats start at byte 8 of a buffer of any alignment)
     std::deque<std::pair<uint64_t, std::vector<dsp::complex_t>>> tapPending;  // pipelined: (ticket, input block) kept for the bound streams until the block's turn
     std::vector<dsp::complex_t> inflightTap;
     int pipeFlags = 0;                      // result flags the context was put into pipelined mode with
