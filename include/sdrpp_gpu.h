@@ -249,12 +249,14 @@ typedef struct sdrpp_af_desc {
     int interp, decim;                                /* polyphase L/M; interp == decim -> stage absent                         */
     int resamp_ntaps;
     const float* resamp_taps;                         /* already scaled by interp (sdrpp_design_resampler)                      */
-    int hpf_ntaps;                                    /* 0 = high-pass block disabled                                           */
+    int hpf_ntaps;                                    /* 0 = high-pass block disabled; at most 65 536 taps (SDRPP_ERR_UNSUPPORTED) */
     const float* hpf_taps;
     float deemph_alpha;                               /* 0 = de-emphasis block disabled (sdrpp_design_deemphasis_alpha)         */
 } sdrpp_af_desc;
 /* afChain.enableBlock / setAudioSampleRate (radio_module.h:540-547, 585-600).  af == NULL detaches.  Arrays are copied; the chain
- * starts from cleared state.  Only for VFOs with a demodulator (demod != RAW). */
+ * starts from cleared state.  Only for VFOs with a demodulator (demod != RAW).  The high-pass is not bound by the channel filter's 4 096 taps
+ * (highPass(300, 100, rate) has 7 296 at 192 kHz): its delay line is sized from hpf_ntaps; more than 65 536 taps are refused with
+ * SDRPP_ERR_UNSUPPORTED and the tap count in the message. */
 int sdrpp_vfo_set_af(sdrpp_ctx* ctx, int id, const sdrpp_af_desc* af);
 /* AF output of the most recent push: stereo frames at the audio rate (what afChain.out swap()s to the sink stream). */
 int sdrpp_vfo_af_count(sdrpp_ctx* ctx, int id);

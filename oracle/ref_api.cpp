@@ -201,6 +201,39 @@ void ref_resampler_destroy(void* h) { delete (dsp::multirate::RationalResampler<
 int ref_resampler_process(void* h, int count, const float* in, float* out) {
     return ((dsp::multirate::RationalResampler<complex_t>*)h)->process(count, (const complex_t*)in, (complex_t*)out);
 }
+// The plan a RationalResampler settled on (its mode, the pre-decimation ratio, L / M, the prototype's tap count, taps per phase): protected there and in its
+// member blocks, read here through pointers to members that a deriving class may name — the reference is compiled as it lies.
+namespace {
+using RefRR = dsp::multirate::RationalResampler<complex_t>;
+using RefPD = dsp::multirate::PowerDecimator<complex_t>;
+using RefPR = dsp::multirate::PolyphaseResampler<complex_t>;
+struct PeekPD : RefPD {
+    static int ratio(const RefPD& d) { return (int)(d.*(&PeekPD::_ratio)); }
+};
+struct PeekPR : RefPR {
+    static int interp(const RefPR& r) { return r.*(&PeekPR::_interp); }
+    static int decim(const RefPR& r) { return r.*(&PeekPR::_decim); }
+    static int tpp(const RefPR& r) { return (r.*(&PeekPR::phases)).tapsPerPhase; }
+};
+struct PeekRR : RefRR {
+    static void info(const RefRR& r, int* out) {
+        const RefPD& d = r.*(&PeekRR::decim);
+        const RefPR& p = r.*(&PeekRR::resamp);
+        out[0] = (int)(r.*(&PeekRR::mode));
+        out[1] = PeekPD::ratio(d);
+        out[2] = PeekPR::interp(p);
+        out[3] = PeekPR::decim(p);
+        out[4] = (r.*(&PeekRR::rtaps)).size;
+        out[5] = PeekPR::tpp(p);
+    }
+};
+}
+// mode: 0 both, 1 pre-decimation only, 2 polyphase only, 3 nothing (RationalResampler::Mode); predec means something in modes 0 and 1, the rest in 0 and 2
+void ref_resampler_info(void* h, int* mode, int* predec, int* interp, int* decim, int* ntaps, int* tapsPerPhase) {
+    int v[6];
+    PeekRR::info(*(RefRR*)h, v);
+    *mode = v[0]; *predec = v[1]; *interp = v[2]; *decim = v[3]; *ntaps = v[4]; *tapsPerPhase = v[5];
+}
 void* ref_deemp_create(double tau, double sr) {
     auto* d = new dsp::filter::Deemphasis<stereo_t>;
     d->init(NULL, tau, sr);

@@ -529,7 +529,10 @@ int af_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_af_desc* af) {
     }
     const bool has_poly = af->interp != af->decim;
     if (has_poly && (af->interp <= 0 || af->decim <= 0 || af->resamp_ntaps <= 0 || !af->resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af polyphase description"); }
-    if (af->hpf_ntaps < 0 || af->hpf_ntaps > kChanHistCap + 1 || (af->hpf_ntaps > 0 && !af->hpf_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af high-pass description"); }
+    if (af->hpf_ntaps < 0 || (af->hpf_ntaps > 0 && !af->hpf_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af high-pass description"); }
+    // (no kChanHistCap here: that is the channel filter's pre-allocated history; the high-pass's input stream gets its history from the tap count below, and a
+    // filter too long for the matrix form and for an LDS tile of the register-blocked one runs untiled — highPass(300, 100) has 7 296 taps at 192 kHz)
+    if (af->hpf_ntaps > kAfHpfMaxTaps) { return fail(c, SDRPP_ERR_UNSUPPORTED, "af high-pass of %d taps (max %d)", af->hpf_ntaps, kAfHpfMaxTaps); }
     Vfo::Af& a = v.af;
     a.base = (int)v.st.size();
     a.n_stages = af->n_stages;

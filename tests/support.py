@@ -153,6 +153,8 @@ def ref(fast=False):
         L.ref_resampler_create.argtypes = [C.c_double, C.c_double]
         L.ref_resampler_destroy.argtypes = [C.c_void_p]
         L.ref_resampler_process.argtypes = [C.c_void_p, C.c_int, c_float_p, c_float_p]
+        if hasattr(L, "ref_resampler_info"):  # (a prebuilt oracle/_ref from before this entry point: the test that needs it says so)
+            L.ref_resampler_info.argtypes = [C.c_void_p] + [c_int_p] * 6
         L.ref_deemp_create.restype = C.c_void_p
         L.ref_deemp_create.argtypes = [C.c_double, C.c_double]
         L.ref_deemp_destroy.argtypes = [C.c_void_p]

@@ -160,6 +160,74 @@ def test_af_resampler_and_deemphasis_bit_exact():
     r.ref_deemp_destroy(rd)
 
 
+# every (AF input rate, audio rate) pair tests/test_af_chain.py takes the oracle's AF chain to: (mode, pre-decimation, L, M) as RationalResampler::reconfigure settles them
+AF_RATE_PAIRS = [
+    (24000.0, 24000.0, 3, 1, 1, 1), (24000.0, 12000.0, 1, 2, 1, 1), (24000.0, 48000.0, 2, 1, 2, 1), (24000.0, 96000.0, 2, 1, 4, 1), (24000.0, 192000.0, 2, 1, 8, 1),
+    (24000.0, 16000.0, 2, 1, 2, 3), (15000.0, 24000.0, 2, 1, 8, 5), (15000.0, 12000.0, 2, 1, 4, 5), (15000.0, 8000.0, 2, 1, 8, 15), (15000.0, 48000.0, 2, 1, 16, 5),
+    (15000.0, 44100.0, 2, 1, 147, 50), (15000.0, 176400.0, 2, 1, 294, 25), (50000.0, 50000.0, 3, 1, 1, 1), (50000.0, 44100.0, 2, 1, 441, 500),
+    (50000.0, 192000.0, 2, 1, 96, 25), (50000.0, 11025.0, 0, 4, 441, 500), (50000.0, 96000.0, 2, 1, 48, 25), (50000.0, 176400.0, 2, 1, 441, 125),
+    (250000.0, 44100.0, 0, 4, 441, 625), (250000.0, 8000.0, 0, 16, 64, 125), (250000.0, 50000.0, 0, 4, 4, 5), (250000.0, 96000.0, 0, 2, 96, 125),
+    (250000.0, 192000.0, 2, 1, 96, 125),
+]
+
+
+@pytest.mark.parametrize("in_sr,out_sr,mode,predec,interp,decim", AF_RATE_PAIRS, ids=["%d_%d" % (a, b) for a, b, *_ in AF_RATE_PAIRS])
+def test_af_resampler_every_rate_pair_bit_exact(in_sr, out_sr, mode, predec, interp, decim):
+    """RationalResampler at every AF rate pair of tests/test_af_chain.py, two uneven blocks: the plan figures (mode, pre-decimation, L / M, prototype taps, taps per
+    phase) and every output sample, oracle restatement against the compiled reference."""
+    o, r = S.oracle(), S.ref()
+    if not hasattr(r, "ref_resampler_info"):
+        pytest.skip("oracle/_ref was built before ref_resampler_info existed (rebuild it where /root/reference is)")
+    x = _noise(6007, 31)
+    oh = o.orc_resampler_create(S.plans_handle(), in_sr, out_sr, 2)
+    rh = r.ref_resampler_create(in_sr, out_sr)
+    oi, ri = [C.c_int() for _ in range(6)], [C.c_int() for _ in range(6)]
+    o.orc_resampler_info(oh, *[C.byref(v) for v in oi])
+    r.ref_resampler_info(rh, *[C.byref(v) for v in ri])
+    oi, ri = [v.value for v in oi], [v.value for v in ri]
+    assert oi[0] == ri[0] == mode, (oi, ri)
+    if mode in (0, 1):
+        assert oi[1] == ri[1] == predec, (oi, ri)
+    if mode in (0, 2):
+        assert oi[2:4] == ri[2:4] == [interp, decim] and oi[4:] == ri[4:] and oi[4] > 0, (oi, ri)
+    grow = int(np.ceil(max(1.0, out_sr / in_sr)))
+    for blk in (x[:2503], x[2503:]):
+        blk = np.ascontiguousarray(blk)
+        oo = np.empty(len(blk) * grow + 64, np.complex64)
+        ro = np.empty(len(blk) * grow + 64, np.complex64)
+        no = o.orc_resampler_process(oh, len(blk), S._fp(blk.view(np.float32)), S._fp(oo.view(np.float32)))
+        nr = r.ref_resampler_process(rh, len(blk), S._fp(blk.view(np.float32)), S._fp(ro.view(np.float32)))
+        assert no == nr > 0 and np.array_equal(oo[:no].view(np.uint32), ro[:nr].view(np.uint32))
+    o.orc_resampler_destroy(oh)
+    r.ref_resampler_destroy(rh)
+
+
+@pytest.mark.parametrize("rate,ntaps", [(44100.0, 1675), (96000.0, 3648), (176400.0, 6703), (192000.0, 7296)])
+def test_af_high_pass_taps_every_rate_bit_exact(rate, ntaps):
+    """highPass(300, 100, audio rate) (radio_module.h:597) where the AF rows take it: tap count and taps."""
+    o, r = S.oracle(), S.ref()
+    a, b = np.zeros(8192, np.float32), np.zeros(8192, np.float32)
+    na = o.orc_high_pass(300.0, 100.0, rate, 0, S._fp(a), len(a))
+    nb = r.ref_high_pass(300.0, 100.0, rate, 0, S._fp(b), len(b))
+    assert na == nb == ntaps and np.array_equal(a[:na].view(np.uint32), b[:nb].view(np.uint32))
+
+
+@pytest.mark.parametrize("tau,rate", [(22e-6, 48000.0), (75e-6, 48000.0), (22e-6, 192000.0), (75e-6, 44100.0), (50e-6, 44100.0), (50e-6, 192000.0), (75e-6, 50000.0), (50e-6, 50000.0), (22e-6, 96000.0)])
+def test_af_deemphasis_every_setting_bit_exact(tau, rate):
+    """Deemphasis (filter/deephasis.h) at the 22 us and 75 us modes, at 44 100 and 192 000 Hz and at every other setting tests/test_af_chain.py uses, over two blocks (the state carries)."""
+    o, r = S.oracle(), S.ref()
+    a = np.ascontiguousarray(_noise(4800, 3).view(np.float32).reshape(-1, 2))
+    od, rd = o.orc_deemp_create(tau, rate), r.ref_deemp_create(tau, rate)
+    for blk in (a[:1777], a[1777:]):
+        blk = np.ascontiguousarray(blk)
+        oa, ra = np.empty_like(blk), np.empty_like(blk)
+        o.orc_deemp_process(od, len(blk), S._fp(blk), S._fp(oa))
+        r.ref_deemp_process(rd, len(blk), S._fp(blk), S._fp(ra))
+        assert np.array_equal(oa.view(np.uint32), ra.view(np.uint32))
+    o.orc_deemp_destroy(od)
+    r.ref_deemp_destroy(rd)
+
+
 @pytest.mark.parametrize("ratio,dc,conj", [(1, True, False), (2, True, True), (8, False, True), (64, True, False)])
 def test_preproc_chain_bit_exact(ratio, dc, conj):
     """'next' row 2: IQFrontEnd's pre-processing chain (iq_frontend.cpp:32-39) = PowerDecimator<complex_t> -> DCBlocker<complex_t>
