@@ -49,25 +49,52 @@ struct ToepTab {
     bool ok = false;
 };
 
+// A description of a rate chain as all four entry points can fill it (rate_desc, host_util.h): the fields the public structs share under these names.
+struct RateDesc {
+    int n_stages = 0, stage_decim[SDRPP_MAX_DECIM_STAGES] = {}, stage_ntaps[SDRPP_MAX_DECIM_STAGES] = {};
+    const float* stage_taps[SDRPP_MAX_DECIM_STAGES] = {};
+    int interp = 1, decim = 1, resamp_ntaps = 0;
+    const float* resamp_taps = nullptr;
+};
+// A rate chain: the reference's PowerDecimator (power-of-two decimator stages) and, where interp != decim, its PolyphaseResampler behind them — the RxVFO
+// front end, the radio's AF chain, the WFM RDS branch and the IQ pre-processing chain each hold one (checked, built and freed by rate_* in host_util.h,
+// planned by decim_step / poly_step).  Its streams live with its owner.
+struct RateChain {
+    // the description (a chain without a polyphase stage: interp = decim = 1, tpp = 0, no rtaps)
+    int n_stages = 0, decim_s[SDRPP_MAX_DECIM_STAGES] = { 1, 1, 1, 1 };
+    std::vector<float> staps[SDRPP_MAX_DECIM_STAGES], rtaps;
+    int interp = 1, decim = 1, tpp = 0;
+    // device constants
+    float* d_staps[SDRPP_MAX_DECIM_STAGES] = { nullptr, nullptr, nullptr, nullptr };  // phase-major, padded (FirBJob); natural order where the owner asked for that (RateForm)
+    int s_kp[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
+    ToepTab tp_stage[SDRPP_MAX_DECIM_STAGES], tp_poly;
+    float* d_bank = nullptr;
+    bool bank_borrowed = false;  // d_bank is somebody else's allocation: rate_free leaves it alone
+    // integer streaming state
+    struct Pos { int soff[SDRPP_MAX_DECIM_STAGES]; int pphase, poff; } pos{};
+    int ntaps(int s) const { return (int)staps[s].size(); }
+    bool has_poly() const { return tpp > 0; }
+    // History the input of block `stage` keeps (0 .. n_stages - 1: the decimators, n_stages: the polyphase stage): its consumer's taps - 1; behind the last
+    // block of the chain whatever the owner's next consumer needs (`tail`).
+    int need(int stage, int tail) const {
+        if (stage < n_stages) { return ntaps(stage) - 1; }
+        return (stage == n_stages && has_poly()) ? tpp - 1 : tail;
+    }
+};
+
 struct Vfo {
     bool nco_exact = false;        // this VFO runs the reference's float rotator recursion (desc.nco_mode, else the context's mode)
     int id = 0;
-    sdrpp_vfo_desc d{};
-    std::vector<float> staps[SDRPP_MAX_DECIM_STAGES];
-    std::vector<float> rtaps, ctaps_chan, ataps;
+    sdrpp_vfo_desc d{};  // demodulator, AGC, deviation, NCO mode; its rate-chain fields are not read once the VFO is built (`rate` holds them)
+    RateChain rate;  // power-of-two decimators + resampler of the RxVFO (stage 0, or stages 0 and 1, inside the front-end kernels)
+    std::vector<float> ctaps_chan, ataps;
     // NCO
     double theta = 0.0, phi = 0.0;
     std::vector<float2> modtaps;  // stage-1 modulated taps
     bool modtaps_dirty = true;
-    // integer streaming state
-    int soff[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
-    int tpp = 0, pphase = 0, poff = 0;
     long long seen = 0;  // input samples this VFO has consumed since it was added / reset (bounds its view of the IQ history)
     // device constants
-    float* d_staps[SDRPP_MAX_DECIM_STAGES] = { nullptr, nullptr, nullptr, nullptr };  // phase-major, padded (FirBJob)
     float* d_staps_nat[SDRPP_MAX_DECIM_STAGES] = { nullptr, nullptr, nullptr, nullptr };  // natural order (fused front kernel)
-    int s_kp[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
-    float* d_bank = nullptr;
     float* d_cyc = nullptr;  // blocked polyphase: [interp][rows][lmax] cycle tap tables (one per carried phase)
     int cyc_rows = 0, cyc_lmax = 0;
     int chan_kp = 0, audio_kp = 0;
@@ -112,17 +139,9 @@ struct Vfo {
         float pd_re = 1.0f, pd_im = 0.0f;
         double theta = 0.0, phi = 0.0;  // closed-form NCO: turns per sample, phase of the next sample
         float2* d_rot = nullptr;       // reference-rotator mode: FrequencyXlator::phase (device, persistent)
-        int n_stages = 0, decim_s[SDRPP_MAX_DECIM_STAGES] = { 1, 1, 1, 1 };
-        std::vector<float> staps[SDRPP_MAX_DECIM_STAGES], rtaps;
-        float* d_staps[SDRPP_MAX_DECIM_STAGES] = { nullptr, nullptr, nullptr, nullptr };  // phase-major, padded (FirBJob); stage 0 in closed form: natural order
-        int s_kp[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
-        ToepTab tp_stage[SDRPP_MAX_DECIM_STAGES];
-        int interp = 1, decim = 1, tpp = 0;
+        RateChain rate;                  // stage 0 in closed form: natural-order taps, no matrix table; the polyphase bank is borrowed and has no table (5000 phases)
         unsigned long long bank_key = 0;  // the context's shared polyphase bank this branch holds a reference to (0: none)
-        const float* d_bank = nullptr;
         int tile = 0, pitch = 0;       // fused first stage: outputs per tile, LDS row pitch (rds_tile_geometry)
-        int soff[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
-        int pphase = 0, poff = 0;
         std::vector<Stream> st;        // [exact: the rotated IF-rate stream,] the decimator stages' outputs, the polyphase stage's
         int i_stage0 = 0, i_poly = -1, i_last = 0;
         // the first decimator's delay line while the feed's history does not hold it (fresh attach: zeros; switched off, sdrpp_vfo_reset, moved: what the
@@ -138,7 +157,7 @@ struct Vfo {
         std::vector<int> tk;           // a launch group: cumulative output counts at every push end
     } rds;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
-    ToepTab tp_stage[SDRPP_MAX_DECIM_STAGES], tp_poly, tp_chan, tp_audio;
+    ToepTab tp_chan, tp_audio;
     // front end as one filter (what the fused translate + filter kernels evaluate): stages 0 (+ 1) of the plan
     bool fused_front = false;      // stages 0 and 1 run as one composite filter (front2_t2 > 0)
     bool no_fuse = false;          // stage-1 taps are not linear phase: the composite forms do not apply
@@ -154,13 +173,9 @@ struct Vfo {
     // radio AF chain (sdrpp_vfo_set_af): RationalResampler<stereo_t> -> high-pass -> de-emphasis, fed by st[i_out]
     struct Af {
         bool on = false;
-        int n_stages = 0, decim_s[SDRPP_MAX_DECIM_STAGES] = { 1, 1, 1, 1 };
-        std::vector<float> staps[SDRPP_MAX_DECIM_STAGES], rtaps, htaps;
-        float* d_staps[SDRPP_MAX_DECIM_STAGES] = { nullptr, nullptr, nullptr, nullptr };
-        int s_kp[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
-        ToepTab tp_stage[SDRPP_MAX_DECIM_STAGES], tp_poly, tp_hpf;
-        int interp = 1, decim = 1, tpp = 0;
-        float* d_bank = nullptr;
+        RateChain rate;
+        std::vector<float> htaps;
+        ToepTab tp_hpf;
         float* d_hpf = nullptr;
         int hpf_kp = 0;
         float alpha = 0.0f;
@@ -168,8 +183,6 @@ struct Vfo {
         int state_cur = 0;
         float4* d_seg = nullptr;   // per-segment affine maps of the de-emphasis scan
         int seg_cap = 0;
-        int soff[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
-        int pphase = 0, poff = 0;
         int i_stage0 = -1, i_poly = -1, i_hpf = -1, i_deemp = -1, i_last = -1;  // indices into st (i_last: where the AF output is)
         int base = -1;  // first AF stream in st (they are appended behind the VFO's own streams)
     } af;
@@ -219,12 +232,7 @@ struct sdrpp_ctx {
     struct Pre {
         bool ref_order = false;            // sdrpp_preproc_set_reference_order: the reference's own summation order / sequential DC blocker
         bool on = false;
-        int n_stages = 0, decim_s[SDRPP_MAX_DECIM_STAGES] = { 1, 1, 1, 1 };
-        std::vector<float> staps[SDRPP_MAX_DECIM_STAGES];
-        ToepTab tp[SDRPP_MAX_DECIM_STAGES];
-        float* d_staps[SDRPP_MAX_DECIM_STAGES] = { nullptr, nullptr, nullptr, nullptr };
-        int s_kp[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
-        int soff[SDRPP_MAX_DECIM_STAGES] = { 0, 0, 0, 0 };
+        RateChain rate;  // decimator stages only
         float dc_rate = 0.0f;
         int conj = 0;
         Stream raw;               // history of the caller's buffer (data stays the caller's)

@@ -331,10 +331,129 @@ int toep_build_poly(sdrpp_ctx* c, ToepTab& T, const std::vector<float>& bank, in
     return toep_upload(c, T, tl, lb);
 }
 
+// ---- rate chains (RateChain, host_ctx.h): the one copy of what the RxVFO front end, the AF chain, the RDS branch and the pre-processing chain do alike -----
+// bank[(L-1) - (i mod L)][i div L] = taps[i], zero-padded to L x tpp (polyphase_bank.h:31-34), laid out [phase][tpp]
+std::vector<float> polyphase_bank(const float* taps, int n, int interp, int tpp) {
+    std::vector<float> bank((size_t)interp * tpp, 0.0f);
+    for (int i = 0; i < std::min(n, interp * tpp); i++) { bank[(size_t)((interp - 1) - (i % interp)) * tpp + (size_t)(i / interp)] = taps[i]; }
+    return bank;
+}
+// A caller's description as a view: the arrays of sdrpp_preproc_configure (an array left out reads as stages without decimation or taps, which
+// rate_check_stages refuses), or the fields sdrpp_vfo_desc, sdrpp_af_desc and sdrpp_rds_desc share.
+RateDesc rate_desc(int n_stages, const int* stage_decim, const int* stage_ntaps, const float* const* stage_taps, int interp = 1, int decim = 1, int resamp_ntaps = 0, const float* resamp_taps = nullptr) {
+    RateDesc q;
+    q.n_stages = n_stages;
+    for (int s = 0; s < std::min(n_stages, SDRPP_MAX_DECIM_STAGES); s++) {
+        q.stage_decim[s] = stage_decim ? stage_decim[s] : 0;
+        q.stage_ntaps[s] = stage_ntaps ? stage_ntaps[s] : 0;
+        q.stage_taps[s] = stage_taps ? stage_taps[s] : nullptr;
+    }
+    q.interp = interp;
+    q.decim = decim;
+    q.resamp_ntaps = resamp_ntaps;
+    q.resamp_taps = resamp_taps;
+    return q;
+}
+template <class D>
+RateDesc rate_desc(const D& d) { return rate_desc(d.n_stages, d.stage_decim, d.stage_ntaps, d.stage_taps, d.interp, d.decim, d.resamp_ntaps, d.resamp_taps); }
+// ... and a built chain's description as one (valid while the chain lives)
+RateDesc rate_desc(const RateChain& R) {
+    RateDesc q = rate_desc(R.n_stages, R.decim_s, nullptr, nullptr, R.interp, R.decim, (int)R.rtaps.size(), R.rtaps.empty() ? nullptr : R.rtaps.data());
+    for (int s = 0; s < R.n_stages; s++) {
+        q.stage_ntaps[s] = R.ntaps(s);
+        q.stage_taps[s] = R.staps[s].data();
+    }
+    return q;
+}
+// The validation, in two halves (sdrpp_vfo_add has a check of its own between them).  `who`: the chain's prefix in the messages ("", "af ", "rds ", "pre-processing ").
+int rate_check_stages(sdrpp_ctx* c, const RateDesc& d, const char* who) {
+    if (d.n_stages < 0 || d.n_stages > SDRPP_MAX_DECIM_STAGES) { return fail(c, SDRPP_ERR_INVALID, "%sn_stages %d", who, d.n_stages); }
+    for (int s = 0; s < d.n_stages; s++) {
+        if (!is_pow2(d.stage_decim[s]) || d.stage_ntaps[s] <= 0 || !d.stage_taps[s]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "%sstage %d: decimation must be a power of two with taps", who, s); }
+    }
+    return SDRPP_OK;
+}
+int rate_check_poly(sdrpp_ctx* c, const RateDesc& d, const char* who) {
+    if (d.interp != d.decim && (d.interp <= 0 || d.decim <= 0 || d.resamp_ntaps <= 0 || !d.resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad %spolyphase description", who); }
+    return SDRPP_OK;
+}
+// A checked description becomes that of a fresh chain: host side only — RateChain::need and the owner's own sizing read it before anything is built.
+void rate_describe(RateChain& R, const RateDesc& d) {
+    R.n_stages = d.n_stages;
+    for (int s = 0; s < d.n_stages; s++) {
+        R.decim_s[s] = d.stage_decim[s];
+        R.staps[s].assign(d.stage_taps[s], d.stage_taps[s] + d.stage_ntaps[s]);
+    }
+    if (d.interp != d.decim) {
+        R.interp = d.interp;
+        R.decim = d.decim;
+        R.tpp = (d.resamp_ntaps + d.interp - 1) / d.interp;
+        R.rtaps.assign(d.resamp_taps, d.resamp_taps + d.resamp_ntaps);
+    }
+}
+// What the owner of a chain chooses; everything else is the same for all four.
+struct RateForm {
+    unsigned natural = 0;     // bit s: d_staps[s] holds the taps of stage s in natural order, not in phase-major blocks
+    unsigned matrix = ~0u;    // bit s: stage s gets a matrix table (tp_stage[s])
+    float* bank = nullptr;    // the polyphase bank the chain borrows; nullptr: it uploads its own
+    bool poly_matrix = true;  // the polyphase stage gets a matrix table (tp_poly)
+};
+// Uploads the tap tables of a described chain and appends its output streams to `st`: one per decimator stage, then the polyphase stage's, each with the
+// history its consumer needs (RateChain::need).  `cap`: the samples the chain's input may hold; on return, what its output may.  `bank_out`: receives
+// the polyphase bank as uploaded, for an owner that derives tables of its own from it.
+int rate_build(sdrpp_ctx* c, RateChain& R, const RateForm& f, std::vector<Stream>& st, size_t& cap, int tail, std::vector<float>* bank_out = nullptr) {
+    int rc;
+    auto add_stream = [&](int hist) {
+        st.emplace_back();
+        return stream_alloc(c, st.back(), 2, hist, cap) ? SDRPP_ERR_NOMEM : SDRPP_OK;
+    };
+    for (int s = 0; s < R.n_stages; s++) {
+        const float* h = R.staps[s].data();
+        const int K = R.ntaps(s), D = R.decim_s[s];
+        rc = ((f.natural >> s) & 1) ? upload(c, &R.d_staps[s], h, (size_t)K) : upload_blocked(c, &R.d_staps[s], h, K, D, &R.s_kp[s]);
+        if (!rc && ((f.matrix >> s) & 1)) { rc = toep_build_fir(c, R.tp_stage[s], h, K, D); }
+        if (rc) { return rc; }
+        cap = cap / (size_t)D + 2;
+        if ((rc = add_stream(R.need(s + 1, tail)))) { return rc; }
+    }
+    if (R.has_poly()) {
+        R.d_bank = f.bank;
+        R.bank_borrowed = f.bank != nullptr;
+        if (!f.bank || f.poly_matrix) {
+            const std::vector<float> bank = polyphase_bank(R.rtaps.data(), (int)R.rtaps.size(), R.interp, R.tpp);
+            if (!f.bank && (rc = upload(c, &R.d_bank, bank.data(), bank.size()))) { return rc; }
+            if (f.poly_matrix && (rc = toep_build_poly(c, R.tp_poly, bank, R.interp, R.decim, R.tpp))) { return rc; }
+            if (bank_out) { *bank_out = bank; }
+        }
+        cap = cap * (size_t)R.interp / (size_t)R.decim + 4;
+        if ((rc = add_stream(tail))) { return rc; }
+    }
+    return SDRPP_OK;
+}
+// gives back what rate_build made (never a borrowed bank; the streams are the owner's)
+void rate_free(RateChain& R) {
+    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) {
+        dev_free(R.d_staps[i]);
+        toep_free(R.tp_stage[i]);
+    }
+    toep_free(R.tp_poly);
+    if (!R.bank_borrowed) { dev_free(R.d_bank); }
+    R = RateChain{};
+}
+// "is this the chain I already have?"
+bool rate_same(const RateChain& R, const RateDesc& d) {
+    const bool has_poly = d.interp != d.decim;
+    if (R.n_stages != d.n_stages || R.has_poly() != has_poly) { return false; }
+    for (int s = 0; s < R.n_stages; s++) {
+        if (R.decim_s[s] != d.stage_decim[s] || R.ntaps(s) != d.stage_ntaps[s] || !d.stage_taps[s] || memcmp(R.staps[s].data(), d.stage_taps[s], R.staps[s].size() * sizeof(float)) != 0) { return false; }
+    }
+    return !has_poly || (R.interp == d.interp && R.decim == d.decim && (int)R.rtaps.size() == d.resamp_ntaps && d.resamp_taps && memcmp(R.rtaps.data(), d.resamp_taps, R.rtaps.size() * sizeof(float)) == 0);
+}
+
 void build_modtaps(Vfo& v) {
     // g[k] = h[k] * exp(j*2*pi*(k - kc)*theta), kc = (K-1)/2, for the first (K+1)/2 taps; the other half is the conjugate
     // mirror (stage1_accumulate).  An odd K has a real centre tap.
-    const int K = v.d.stage_ntaps[0];
+    const int K = v.rate.ntaps(0);
     const int npairs = (K + 1) / 2;
     v.modtaps.resize((size_t)npairs);
     const double kc = 0.5 * (double)(K - 1);
@@ -342,19 +461,16 @@ void build_modtaps(Vfo& v) {
         double t = ((double)k - kc) * v.theta;
         t -= std::rint(t);
         const double a = 2.0 * 3.14159265358979323846 * t;
-        const double h = (double)v.staps[0][(size_t)k];
+        const double h = (double)v.rate.staps[0][(size_t)k];
         v.modtaps[(size_t)k] = make_float2((float)(h * std::cos(a)), (float)(h * std::sin(a)));
     }
-    if (K & 1) { v.modtaps[(size_t)npairs - 1] = make_float2(v.staps[0][(size_t)npairs - 1], 0.0f); }
+    if (K & 1) { v.modtaps[(size_t)npairs - 1] = make_float2(v.rate.staps[0][(size_t)npairs - 1], 0.0f); }
     v.modtaps_dirty = false;
 }
 
 // what an RDS branch owns by itself (its share of the context's polyphase banks is given back by rds_detach, vfo_ctl.h)
 void rds_free_own(Vfo::Rds& r) {
-    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) {
-        dev_free(r.d_staps[i]);
-        toep_free(r.tp_stage[i]);
-    }
+    rate_free(r.rate);
     dev_free(r.d_rot);
     dev_free(r.d_line[0]);
     dev_free(r.d_line[1]);
@@ -383,10 +499,25 @@ bool rds_tile_geometry(int K, int D, int* tile, int* pitch) {
     return false;
 }
 
+// the radio AF chain goes: what it built and its streams, which lie behind the VFO's own
+void af_detach(Vfo& v) {
+    Vfo::Af& a = v.af;
+    rate_free(a.rate);
+    toep_free(a.tp_hpf);
+    dev_free(a.d_hpf);
+    dev_free(a.d_last);
+    dev_free(a.d_seg);
+    if (a.base >= 0) {
+        for (size_t i = (size_t)a.base; i < v.st.size(); i++) { stream_free(v.st[i]); }
+        v.st.resize((size_t)a.base);
+    }
+    a = Vfo::Af{};
+}
 void vfo_free(Vfo& v) {
     rds_free_own(v.rds);
-    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { dev_free(v.d_staps[i]); dev_free(v.d_staps_nat[i]); }
-    dev_free(v.d_bank);
+    af_detach(v);
+    rate_free(v.rate);
+    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { dev_free(v.d_staps_nat[i]); }
     dev_free(v.d_cyc);
     dev_free(v.d_chan);
     dev_free(v.d_audio);
@@ -394,20 +525,8 @@ void vfo_free(Vfo& v) {
     dev_free(v.d_h12);
     dev_free(v.d_rot);
     dev_free(v.ifc.d_amp);
-    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { toep_free(v.tp_stage[i]); }
-    toep_free(v.tp_poly);
     toep_free(v.tp_chan);
     toep_free(v.tp_audio);
-    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) {
-        dev_free(v.af.d_staps[i]);
-        toep_free(v.af.tp_stage[i]);
-    }
-    toep_free(v.af.tp_poly);
-    toep_free(v.af.tp_hpf);
-    dev_free(v.af.d_bank);
-    dev_free(v.af.d_hpf);
-    dev_free(v.af.d_last);
-    dev_free(v.af.d_seg);
     for (auto& s : v.st) { stream_free(s); }
     v.st.clear();
 }
@@ -418,12 +537,8 @@ int vfo_reset_state(sdrpp_ctx* c, Vfo& v) {
     v.seen = 0;
     v.recs.clear();
     std::fill(v.chan_stale.begin(), v.chan_stale.end(), 0.0f);  // RxVFO::reset clears the channel filter's delay line whether it is bypassed or not (rx_vfo.h:79-87)
-    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { v.soff[i] = 0; }
-    v.pphase = 0;
-    v.poff = 0;
-    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { v.af.soff[i] = 0; }
-    v.af.pphase = 0;
-    v.af.poff = 0;
+    v.rate.pos = RateChain::Pos{};
+    v.af.rate.pos = RateChain::Pos{};
     if (v.af.d_last) { HIPCHK(c, hipMemsetAsync(v.af.d_last, 0, 2 * sizeof(float2), c->stream)); }
     for (auto& s : v.st) {
         for (int i = 0; i < 2; i++) {

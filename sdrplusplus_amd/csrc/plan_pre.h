@@ -13,6 +13,7 @@ namespace {
 // VFO bank start `plan_lvl0` levels later (reference-order arithmetic has no roles: such a block runs as an ordinary pass).
 int run_preproc(sdrpp_ctx* c, const float** d_iq, int64_t* count) {
     sdrpp_ctx::Pre& P = c->pre;
+    RateChain& R = P.rate;
     const bool ticking = c->tick_planning;
     const int n_in = (int)*count;
     std::vector<ToepJob> tj[SDRPP_MAX_DECIM_STAGES];
@@ -23,16 +24,17 @@ int run_preproc(sdrpp_ctx* c, const float** d_iq, int64_t* count) {
     P.raw.data = const_cast<float*>(*d_iq);
     P.raw.n = n_in;
     Stream* cur = &P.raw;
-    const int last_level = P.n_stages + (P.dc_rate != 0.0f ? 2 : (P.conj ? 1 : 0));
-    for (int s = 0; s < P.n_stages; s++) {
+    const int last_level = R.n_stages + (P.dc_rate != 0.0f ? 2 : (P.conj ? 1 : 0));
+    for (int s = 0; s < R.n_stages; s++) {
         Stream* nxt = &P.st[(size_t)s];
-        const int D = P.decim_s[s], K = (int)P.staps[s].size();
-        const int no = decim_nout(cur->n, P.soff[s], D);
+        const int D = R.decim_s[s], K = R.ntaps(s);
+        int& off = R.pos.soff[s];
+        const int no = decim_nout(cur->n, off, D);
         if ((size_t)no > nxt->cap) { return fail(c, SDRPP_ERR_INVALID, "pre-processing stage %d: %d outputs exceed the capacity", s, no); }
-        bounds_decim(c->vfo_bounds, P.soff[s], D);  // the reference's blocks behind this stage
-        if (P.tp[s].ok && !P.ref_order) { tj[s].push_back(toep_job(P.tp[s], 0, stream_in(*cur), nxt->data, P.soff[s] - (K - 1), no, 0.0f)); }
-        else { fj[s].push_back(FirBJob{ stream_in(*cur), nxt->data, P.d_staps[s], K, ilog2(D), P.soff[s], no, P.s_kp[s] }); }
-        P.soff[s] = P.soff[s] + no * D - cur->n;
+        bounds_decim(c->vfo_bounds, off, D);  // the reference's blocks behind this stage
+        if (R.tp_stage[s].ok && !P.ref_order) { tj[s].push_back(toep_job(R.tp_stage[s], 0, stream_in(*cur), nxt->data, off - (K - 1), no, 0.0f)); }
+        else { fj[s].push_back(FirBJob{ stream_in(*cur), nxt->data, R.d_staps[s], K, ilog2(D), off, no, R.s_kp[s] }); }
+        off = off + no * D - cur->n;
         nxt->n = no;
         if (cur->hist_len > 0) { carry.add(ticking ? 1 + s : std::max(1, last_level), CarryJob{ cur->data, cur->hist[cur->cur], cur->hist[cur->cur ^ 1], cur->hist_len, cur->n, 2, cur->hist_len }); }
         cur = nxt;
@@ -54,7 +56,7 @@ int run_preproc(sdrpp_ctx* c, const float** d_iq, int64_t* count) {
     ToepPlan tp[SDRPP_MAX_DECIM_STAGES];
     ToepJob* d_tj[SDRPP_MAX_DECIM_STAGES] = {};
     FirBJob* d_fj[SDRPP_MAX_DECIM_STAGES] = {};
-    for (int s = 0; s < P.n_stages; s++) {
+    for (int s = 0; s < R.n_stages; s++) {
         tp[s] = toep_plan(tj[s], 2, ticking ? c->tick_toep_blocks : 2048);
         d_tj[s] = arena_push(c, tj[s]);
         d_fj[s] = arena_push(c, fj[s]);
@@ -73,7 +75,7 @@ int run_preproc(sdrpp_ctx* c, const float** d_iq, int64_t* count) {
     };
     {
         FamilyTimer t(c, F_MISC);
-        for (int s = 0; s < P.n_stages; s++) {
+        for (int s = 0; s < R.n_stages; s++) {
             const int level = 1 + s;
             if (!tj[s].empty() && tp[s].grid_x > 0) { emit(c, level, F_MISC, TR_TOEP_C, tp[s].grid_x, (int)tj[s].size(), tp[s].lds, d_tj[s]); }
             for (auto& jb : fj[s]) {  // register-blocked fallback (one job): largest work-group whose window fits
@@ -95,14 +97,14 @@ int run_preproc(sdrpp_ctx* c, const float** d_iq, int64_t* count) {
             if (n_out > 0) { launch(c, iq_dc_block_exact_kernel, dim3(1), dim3(64), 0, dc[0].in, dc[0].out, n_out, P.dc_rate, dc[0].state_out, P.conj); }
         }
         else if (!dc.empty() && dc[0].nseg > 0) {
-            emit(c, P.n_stages + 1, F_MISC, TR_DC_P0, dc[0].nseg, 1, 3 * 256 * sizeof(float), d_dc);
-            emit(c, P.n_stages + 2, F_MISC, TR_DC_P1, dc[0].nseg, 1, 3 * 256 * sizeof(float), d_dc);
+            emit(c, R.n_stages + 1, F_MISC, TR_DC_P0, dc[0].nseg, 1, 3 * 256 * sizeof(float), d_dc);
+            emit(c, R.n_stages + 2, F_MISC, TR_DC_P1, dc[0].nseg, 1, 3 * 256 * sizeof(float), d_dc);
         }
-        else if (!conj.empty()) { emit(c, P.n_stages + 1, F_MISC, TR_COPY, std::max(1, std::min((n_out + 2047) / 2048, 256)), 1, 0, d_conj); }
+        else if (!conj.empty()) { emit(c, R.n_stages + 1, F_MISC, TR_COPY, std::max(1, std::min((n_out + 2047) / 2048, 256)), 1, 0, d_conj); }
         if (!ticking) { emit_carries(std::max(1, last_level)); }
     }
     if (P.raw.hist_len > 0) { P.raw.cur ^= 1; }
-    for (int s = 0; s + 1 < P.n_stages; s++) {
+    for (int s = 0; s + 1 < R.n_stages; s++) {
         if (P.st[(size_t)s].hist_len > 0) { P.st[(size_t)s].cur ^= 1; }
     }
     P.last = result;

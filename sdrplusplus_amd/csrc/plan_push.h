@@ -6,62 +6,65 @@ namespace {
 
 // ---- streaming state that planning a block changes, for roll-back: a block either happens completely or not at all ----------------------
 struct PlanSnapshot {
-    struct V { int soff[SDRPP_MAX_DECIM_STAGES]; int pphase, poff; double phi, phi2; long long seen; int i_if, lvl_if, lvl_out, lvl_af, lvl_ifc; int n[24], cur[24]; size_t nrecs;
-               int af_soff[SDRPP_MAX_DECIM_STAGES], af_pphase, af_poff, af_last, af_state;
-               int rds_soff[SDRPP_MAX_DECIM_STAGES], rds_pphase, rds_poff, rds_lvl, rds_n[SDRPP_MAX_DECIM_STAGES + 2], rds_cur[SDRPP_MAX_DECIM_STAGES + 2]; double rds_phi; bool rds_frozen, rds_ran; int rds_line_cur, rds_line_fed; };
+    struct V { RateChain::Pos pos, af_pos, rds_pos; double phi, phi2; long long seen; int i_if, lvl_if, lvl_out, lvl_af, lvl_ifc; size_t nrecs;
+               int af_last, af_state;
+               int rds_lvl; double rds_phi; bool rds_frozen, rds_ran; int rds_line_cur, rds_line_fed; };
     std::vector<V> v;
+    std::vector<int> nc;  // n and cur of every stream of every VFO (its own, then its RDS branch's), in the order of the walk
     int64_t fft_pos, fft_next;
     int n_lines, iq_cur, wf_cur, wf_lines;
     bool wf_have;
-    int pre_soff[SDRPP_MAX_DECIM_STAGES], pre_state, pre_raw_cur, pre_cur[SDRPP_MAX_DECIM_STAGES];
+    RateChain::Pos pre_pos;
+    int pre_state, pre_raw_cur, pre_cur[SDRPP_MAX_DECIM_STAGES];
 };
 // `rotate`: pipelined mode — every stream of the VFO moves on to its next ring buffer in the same walk (stream_rotate)
 void plan_snapshot(sdrpp_ctx* c, PlanSnapshot& S, bool rotate = false) {
     S.v.resize(c->vfo_list.size());
+    S.nc.clear();
     for (size_t i = 0; i < c->vfo_list.size(); i++) {
         Vfo& v = *c->vfo_list[i];
         PlanSnapshot::V& q = S.v[i];
-        for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { q.soff[k] = v.soff[k]; q.af_soff[k] = v.af.soff[k]; }
-        q.pphase = v.pphase; q.poff = v.poff; q.phi = v.phi; q.phi2 = v.phi2; q.seen = v.seen; q.i_if = v.i_if; q.lvl_if = v.lvl_if; q.lvl_out = v.lvl_out; q.lvl_af = v.lvl_af; q.lvl_ifc = v.lvl_ifc;
+        q.pos = v.rate.pos; q.af_pos = v.af.rate.pos; q.rds_pos = v.rds.rate.pos;
+        q.phi = v.phi; q.phi2 = v.phi2; q.seen = v.seen; q.i_if = v.i_if; q.lvl_if = v.lvl_if; q.lvl_out = v.lvl_out; q.lvl_af = v.lvl_af; q.lvl_ifc = v.lvl_ifc;
         q.nrecs = v.recs.size();
-        q.af_pphase = v.af.pphase; q.af_poff = v.af.poff; q.af_last = v.af.i_last; q.af_state = v.af.state_cur;
-        for (size_t k = 0; k < v.st.size() && k < 24; k++) { q.n[k] = v.st[k].n; q.cur[k] = v.st[k].cur; }
-        if (v.rds.attached) {
-            for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { q.rds_soff[k] = v.rds.soff[k]; }
-            q.rds_pphase = v.rds.pphase; q.rds_poff = v.rds.poff; q.rds_lvl = v.rds.lvl; q.rds_phi = v.rds.phi; q.rds_frozen = v.rds.frozen; q.rds_ran = v.rds.ran; q.rds_line_cur = v.rds.line_cur; q.rds_line_fed = v.rds.line_fed;
-            for (size_t k = 0; k < v.rds.st.size(); k++) { q.rds_n[k] = v.rds.st[k].n; q.rds_cur[k] = v.rds.st[k].cur; }
-        }
-        if (rotate) {
-            for (auto& st : v.st) { stream_rotate(st); }
-            for (auto& st : v.rds.st) { stream_rotate(st); }
+        q.af_last = v.af.i_last; q.af_state = v.af.state_cur;
+        q.rds_lvl = v.rds.lvl; q.rds_phi = v.rds.phi; q.rds_frozen = v.rds.frozen; q.rds_ran = v.rds.ran; q.rds_line_cur = v.rds.line_cur; q.rds_line_fed = v.rds.line_fed;
+        for (auto* list : { &v.st, &v.rds.st }) {
+            for (auto& st : *list) {
+                S.nc.push_back(st.n);
+                S.nc.push_back(st.cur);
+                if (rotate) { stream_rotate(st); }
+            }
         }
     }
     S.fft_pos = c->fft_pos; S.fft_next = c->fft_next; S.n_lines = c->n_lines; S.iq_cur = c->iq_cur;
     S.wf_cur = c->wf.cur; S.wf_lines = c->wf.lines; S.wf_have = c->wf.have_latest;
-    for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { S.pre_soff[k] = c->pre.soff[k]; }
+    S.pre_pos = c->pre.rate.pos;
     S.pre_state = c->pre.state_cur;
     S.pre_raw_cur = c->pre.raw.cur;
     for (size_t k = 0; k < c->pre.st.size() && k < SDRPP_MAX_DECIM_STAGES; k++) { S.pre_cur[k] = c->pre.st[k].cur; }
 }
 // (retune records a plan has dropped stay dropped: they were out of every window's reach)
 void plan_restore(sdrpp_ctx* c, const PlanSnapshot& S) {
+    const int* nc = S.nc.data();
     for (size_t i = 0; i < c->vfo_list.size(); i++) {
         Vfo& v = *c->vfo_list[i];
         const PlanSnapshot::V& q = S.v[i];
-        for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { v.soff[k] = q.soff[k]; v.af.soff[k] = q.af_soff[k]; }
-        v.pphase = q.pphase; v.poff = q.poff; v.phi = q.phi; v.phi2 = q.phi2; v.seen = q.seen; v.i_if = q.i_if; v.lvl_if = q.lvl_if; v.lvl_out = q.lvl_out; v.lvl_af = q.lvl_af; v.lvl_ifc = q.lvl_ifc;
-        v.af.pphase = q.af_pphase; v.af.poff = q.af_poff; v.af.i_last = q.af_last; v.af.state_cur = q.af_state;
-        for (size_t k = 0; k < v.st.size() && k < 24; k++) { v.st[k].n = q.n[k]; v.st[k].cur = q.cur[k]; }
-        if (v.rds.attached) {
-            for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { v.rds.soff[k] = q.rds_soff[k]; }
-            v.rds.pphase = q.rds_pphase; v.rds.poff = q.rds_poff; v.rds.lvl = q.rds_lvl; v.rds.phi = q.rds_phi; v.rds.frozen = q.rds_frozen; v.rds.ran = q.rds_ran; v.rds.line_cur = q.rds_line_cur; v.rds.line_fed = q.rds_line_fed;
-            for (size_t k = 0; k < v.rds.st.size(); k++) { v.rds.st[k].n = q.rds_n[k]; v.rds.st[k].cur = q.rds_cur[k]; }
+        v.rate.pos = q.pos; v.af.rate.pos = q.af_pos; v.rds.rate.pos = q.rds_pos;
+        v.phi = q.phi; v.phi2 = q.phi2; v.seen = q.seen; v.i_if = q.i_if; v.lvl_if = q.lvl_if; v.lvl_out = q.lvl_out; v.lvl_af = q.lvl_af; v.lvl_ifc = q.lvl_ifc;
+        v.af.i_last = q.af_last; v.af.state_cur = q.af_state;
+        v.rds.lvl = q.rds_lvl; v.rds.phi = q.rds_phi; v.rds.frozen = q.rds_frozen; v.rds.ran = q.rds_ran; v.rds.line_cur = q.rds_line_cur; v.rds.line_fed = q.rds_line_fed;
+        for (auto* list : { &v.st, &v.rds.st }) {
+            for (auto& st : *list) {
+                st.n = *nc++;
+                st.cur = *nc++;
+            }
         }
     }
     c->fft_pos = S.fft_pos; c->fft_next = S.fft_next; c->n_lines = S.n_lines; c->iq_cur = S.iq_cur;
     c->wf.cur = S.wf_cur; c->wf.lines = S.wf_lines; c->wf.have_latest = S.wf_have;
     c->meters.out_lines = 0;  // (the meters' output array may have been overwritten: it holds no push's lines now)
-    for (int k = 0; k < SDRPP_MAX_DECIM_STAGES; k++) { c->pre.soff[k] = S.pre_soff[k]; }
+    c->pre.rate.pos = S.pre_pos;
     c->pre.state_cur = S.pre_state;
     c->pre.raw.cur = S.pre_raw_cur;
     for (size_t k = 0; k < c->pre.st.size() && k < SDRPP_MAX_DECIM_STAGES; k++) { c->pre.st[k].cur = S.pre_cur[k]; }
@@ -88,9 +91,9 @@ int iq_hist_need(sdrpp_ctx* c) {
     int need_hist = 1;
     if (c->fft_on) { need_hist = std::max(need_hist, c->nz - 1); }
     for (auto& kv : c->vfos) {
-        const sdrpp_vfo_desc& d = kv.second->d;
-        if (d.n_stages > 0) { need_hist = std::max(need_hist, d.stage_ntaps[0] - 1); }
-        if (d.n_stages > 1) { need_hist = std::max(need_hist, d.stage_ntaps[0] - 1 + d.stage_decim[0] * (d.stage_ntaps[1] - 1)); }  // fused front
+        const RateChain& R = kv.second->rate;
+        if (R.n_stages > 0) { need_hist = std::max(need_hist, R.ntaps(0) - 1); }
+        if (R.n_stages > 1) { need_hist = std::max(need_hist, R.ntaps(0) - 1 + R.decim_s[0] * (R.ntaps(1) - 1)); }  // fused front
     }
     return need_hist;
 }
@@ -103,9 +106,9 @@ CarryJob iq_carry_job(sdrpp_ctx* c, const float* d_iq, int64_t count) {
         if (partial > 0) { need = std::max(need, (int)std::min<int64_t>(partial, c->nz - 1)); }
     }
     for (auto& kv : c->vfos) {
-        const sdrpp_vfo_desc& d = kv.second->d;
-        if (d.n_stages > 0) { need = std::max(need, d.stage_ntaps[0] - 1); }
-        if (d.n_stages > 1) { need = std::max(need, d.stage_ntaps[0] - 1 + d.stage_decim[0] * (d.stage_ntaps[1] - 1)); }
+        const RateChain& R = kv.second->rate;
+        if (R.n_stages > 0) { need = std::max(need, R.ntaps(0) - 1); }
+        if (R.n_stages > 1) { need = std::max(need, R.ntaps(0) - 1 + R.decim_s[0] * (R.ntaps(1) - 1)); }
     }
     need = std::min(need, c->iq_hist_cap);
     return CarryJob{ d_iq, c->iq_hist[c->iq_cur], c->iq_hist[c->iq_cur ^ 1], c->iq_hist_cap, (int)count, 2, need };
@@ -127,7 +130,7 @@ int push_common(sdrpp_ctx* c, const float* d_iq, int64_t count, const std::vecto
         rc0 = arena_begin(c);
     }
     if (rc0) { return rc0; }
-    static thread_local PlanSnapshot snap;  // (re-used: with 128 VFOs a fresh one is a 38 KB allocation per block; a nested pass starts only after the outer plan has been restored)
+    static thread_local PlanSnapshot snap;  // (re-used: a fresh one is two allocations per block, tens of KB with 128 VFOs; a nested pass starts only after the outer plan has been restored)
     plan_snapshot(c, snap);
     c->plan_lvl0 = 0;
     block_bounds(c, count, push_ends);

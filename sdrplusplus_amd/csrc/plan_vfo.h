@@ -370,18 +370,25 @@ struct BankPlan {
         if (pipe) { *pipe = j; }
         else { toep.add(l, j); }
     }
-    __attribute__((always_inline)) void decim_step(ChainCtx& x, Stream& nxt, const ToepTab& tp, const float* d_taps, int K, int D, int kp, int& off, Lev<ToepJob>& toep, Lev<FirBJob>& firb, ToepJob* pipe = nullptr) {
+    __attribute__((always_inline)) void decim_step(ChainCtx& x, Stream& nxt, RateChain& R, int s, Lev<ToepJob>& toep, Lev<FirBJob>& firb, ToepJob* pipe = nullptr) {
         const Stream& in = *x.at.cur;
+        const ToepTab& tp = R.tp_stage[s];
+        const int K = R.ntaps(s), D = R.decim_s[s];
+        int& off = R.pos.soff[s];
         const int l = x.at.lvl + 1;
         const int no = decim_nout(in.n, off, D);
         x.through_decim(off, D);
         if (tp.ok) { place(toep, pipe, l, toep_job(tp, 0, stream_in(in), nxt.data, off - (K - 1), no, 0.0f)); }
-        else { firb.add(l, FirBJob{ stream_in(in), nxt.data, d_taps, K, ilog2(D), off, no, kp }); }
+        else { firb.add(l, FirBJob{ stream_in(in), nxt.data, R.d_staps[s], K, ilog2(D), off, no, R.s_kp[s] }); }
         off = off + no * D - in.n;
         x.at.step(nxt, no);
     }
-    __attribute__((always_inline)) void poly_step(ChainCtx& x, Stream& nxt, const ToepTab& tp, int L, int M, int tpp, int& phase, int& off, const float* d_bank, const float* d_cyc, int cyc_rows, int cyc_lmax, Lev<ToepJob>& toep, Lev<PolyJob>& valu, ToepJob* pipe = nullptr) {
+    // (`d_cyc`: the cycle tables of the register-blocked form, which the RxVFO's resampler alone has)
+    __attribute__((always_inline)) void poly_step(ChainCtx& x, Stream& nxt, RateChain& R, const float* d_cyc, int cyc_rows, int cyc_lmax, Lev<ToepJob>& toep, Lev<PolyJob>& valu, ToepJob* pipe = nullptr) {
         const Stream& in = *x.at.cur;
+        const ToepTab& tp = R.tp_poly;
+        const int L = R.interp, M = R.decim, tpp = R.tpp;
+        int &phase = R.pos.pphase, &off = R.pos.poff;
         const int l = x.at.lvl + 1;
         const int no = poly_nout(in.n, off, phase, L, M);
         x.through_poly(off, phase, L, M);
@@ -390,7 +397,7 @@ struct BankPlan {
             polyb[(cyc_lmax == 4 ? 0 : 1) + ((M & 1) ? 2 : 0)].add(l, PolyBJob{ stream_in(in), (float2*)nxt.data, d_cyc + (size_t)phase * cyc_rows * cyc_lmax, L, M,
                                                                                       tpp, off, no, cyc_rows });
         }
-        else { valu.add(l, PolyJob{ stream_in(in), (float2*)nxt.data, d_bank, L, M, tpp, phase, off, no }); }
+        else { valu.add(l, PolyJob{ stream_in(in), (float2*)nxt.data, R.d_bank, L, M, tpp, phase, off, no }); }
         const long long A = (long long)phase + (long long)no * M;
         phase = (int)(A % L);
         off = off + (int)(A / L) - in.n;
@@ -419,11 +426,11 @@ struct BankPlan {
         if (x.split) { v.tk_if = c->grp_ends; }
         front_end(x);
         pipe_decide(x);
-        const int last_dec = v.d.n_stages - 1;
-        for (int s = x.first_sep; s < v.d.n_stages; s++) {
+        const int last_dec = v.rate.n_stages - 1;
+        for (int s = x.first_sep; s < v.rate.n_stages; s++) {
             Stream& nxt = v.st[(size_t)v.i_first + s];
             const bool to_pipe = x.piped && s == last_dec;
-            decim_step(x, nxt, v.tp_stage[s], v.d_staps[s], v.d.stage_ntaps[s], v.d.stage_decim[s], v.s_kp[s], v.soff[s], t_dec, f_dec, to_pipe ? x.pipe(0) : nullptr);
+            decim_step(x, nxt, v.rate, s, t_dec, f_dec, to_pipe ? x.pipe(0) : nullptr);
             if (to_pipe) {
                 x.pj.keep[0] = std::max(0, nxt.n - nxt.hist_len);
                 x.pj.dec_stage = s;
@@ -432,7 +439,7 @@ struct BankPlan {
         }
         if (v.i_poly >= 0) {
             Stream& nxt = v.st[(size_t)v.i_poly];
-            poly_step(x, nxt, v.tp_poly, v.d.interp, v.d.decim, v.tpp, v.pphase, v.poff, v.d_bank, v.d_cyc, v.cyc_rows, v.cyc_lmax, t_poly, poly, x.pipe(1));
+            poly_step(x, nxt, v.rate, v.d_cyc, v.cyc_rows, v.cyc_lmax, t_poly, poly, x.pipe(1));
             if (x.piped) { x.pj.keep[1] = std::max(0, nxt.n - nxt.hist_len); }
         }
         if (v.i_chan >= 0 && v.chan_ntaps > 0) {
@@ -476,48 +483,49 @@ struct BankPlan {
         Stream* cur = x.at.cur;
         if (v.nco_exact) {
             // the reference's own data flow: rotate at the full rate (float recursion), then every stage of the plan as a plain FIR
-            Stream* tgt = (v.d.n_stages == 0) ? cur : &v.st[(size_t)v.i_rot];
+            Stream* tgt = (v.rate.n_stages == 0) ? cur : &v.st[(size_t)v.i_rot];
             rotx.push_back(RotXJob{ (float2*)tgt->data, v.d_rot, v.d.phase_delta_re, v.d.phase_delta_im });
             tgt->n = n_in;
             tgt->wlevel = x.at.lvl;
             x.at.cur = tgt;
             return;
         }
-        if (v.d.n_stages == 0) {
+        if (v.rate.n_stages == 0) {
             rot.push_back(RotJob{ v.theta, v.phi, (float2*)cur->data, n_in });
             cur->n = n_in;
             max_rot = std::max(max_rot, n_in);
             return;
         }
-        const int D = v.d.stage_decim[0];
-        const int nout = decim_nout(n_in, v.soff[0], D);
+        int* so = v.rate.pos.soff;
+        const int D = v.rate.decim_s[0];
+        const int nout = decim_nout(n_in, so[0], D);
         if (v.modtaps_dirty) { build_modtaps(v); }
-        const int K0 = v.d.stage_ntaps[0];
+        const int K0 = v.rate.ntaps(0);
         S1Member& mem = x.mem;
-        mem = S1Member{ &v, K0, ilog2(D), v.soff[0], nout, v.phi, 0, 0, 0, 0, 0, 0, v.tap_hash };
+        mem = S1Member{ &v, K0, ilog2(D), so[0], nout, v.phi, 0, 0, 0, 0, 0, 0, v.tap_hash };
         int need = K0 - 1;
         x.first_sep = 1;
-        x.through_decim(v.soff[0], D);
+        x.through_decim(so[0], D);
         if (v.fused_front) {
-            const int D2 = v.d.stage_decim[1];
+            const int D2 = v.rate.decim_s[1];
             mem.fused = 1;
-            mem.K2 = v.d.stage_ntaps[1];
+            mem.K2 = v.rate.ntaps(1);
             mem.lgD2 = ilog2(D2);
-            mem.off2 = v.soff[1];
-            mem.nout2 = decim_nout(nout, v.soff[1], D2);
+            mem.off2 = so[1];
+            mem.nout2 = decim_nout(nout, so[1], D2);
             need = K0 - 1 + D * (mem.K2 - 1);
             x.first_sep = 2;
-            x.through_decim(v.soff[1], D2);
+            x.through_decim(so[1], D2);
         }
         mem.min_idx = (v.seen >= need) ? -need : -(int)v.seen;  // older samples predate this VFO: zero
         if (!x.split) { s1.push_back(mem); }
         else { front_split(x, need); }
         retune_job(x);
-        v.soff[0] = v.soff[0] + nout * D - n_in;
+        so[0] = so[0] + nout * D - n_in;
         cur->n = nout;
         if (mem.fused) {
             Stream* nxt = &v.st[(size_t)v.i_first + 1];
-            v.soff[1] = v.soff[1] + mem.nout2 * v.d.stage_decim[1] - nout;
+            so[1] = so[1] + mem.nout2 * v.rate.decim_s[1] - nout;
             cur->n = 0;  // the stage-1 stream is never materialised
             nxt->n = mem.nout2;
             nxt->wlevel = x.at.lvl;
@@ -531,8 +539,8 @@ struct BankPlan {
     void front_split(ChainCtx& x, int need) {
         Vfo& v = x.v;
         const S1Member& mem = x.mem;
-        const int D = v.d.stage_decim[0];
-        int so0 = v.soff[0], so1 = v.soff[1], prev_e = 0, oshift = 0;
+        const int D = v.rate.decim_s[0];
+        int so0 = v.rate.pos.soff[0], so1 = v.rate.pos.soff[1], prev_e = 0, oshift = 0;
         long long seen = v.seen;
         double ph = v.phi;
         for (size_t j = 0; j < c->grp_ends.size(); j++) {
@@ -544,7 +552,7 @@ struct BankPlan {
             int outs = m.nout;
             if (mem.fused) {
                 m.off2 = so1;
-                m.nout2 = decim_nout(m.nout, so1, v.d.stage_decim[1]);
+                m.nout2 = decim_nout(m.nout, so1, v.rate.decim_s[1]);
                 outs = m.nout2;
             }
             m.min_idx = ((seen >= need) ? -need : -(int)seen) + prev_e;
@@ -552,7 +560,7 @@ struct BankPlan {
             m.oshift = oshift;
             if (outs > 0) { s1.push_back(m); }
             so0 = so0 + m.nout * D - nj;
-            if (mem.fused) { so1 = so1 + m.nout2 * v.d.stage_decim[1] - m.nout; }
+            if (mem.fused) { so1 = so1 + m.nout2 * v.rate.decim_s[1] - m.nout; }
             const double pj = ph + (double)nj * v.theta;
             ph = pj - std::floor(pj);
             seen += nj;
@@ -567,7 +575,7 @@ struct BankPlan {
     void retune_job(ChainCtx& x) {
         Vfo& v = x.v;
         const S1Member& mem = x.mem;
-        const int D1 = v.d.stage_decim[0], K0 = mem.K, Kc = v.h12_K;
+        const int D1 = v.rate.decim_s[0], K0 = mem.K, Kc = v.h12_K;
         const int off = mem.fused ? mem.off0 + (mem.off2 - (mem.K2 - 1)) * D1 - (K0 - 1) : mem.off0 - (K0 - 1);
         const int nout_f = mem.fused ? mem.nout2 : mem.nout;
         while (!v.recs.empty() && v.recs.front().pos - v.seen <= (long long)off) { v.recs.erase(v.recs.begin()); }
@@ -610,12 +618,12 @@ struct BankPlan {
     // in their matrix form, and the pipeline's LDS layout fits
     void pipe_decide(ChainCtx& x) {
         Vfo& v = x.v;
-        const int last_dec = v.d.n_stages - 1;
-        x.piped = c->pipe_on && !ticking && !x.ifc_on && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= x.first_sep && v.tp_stage[last_dec].ok &&
-                  v.i_poly >= 0 && v.tp_poly.ok && v.i_chan >= 0 && v.chan_ntaps > 0 && v.tp_chan.ok && v.tp_audio.ok;
+        const int last_dec = v.rate.n_stages - 1;
+        x.piped = c->pipe_on && !ticking && !x.ifc_on && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= x.first_sep && v.rate.tp_stage[last_dec].ok &&
+                  v.i_poly >= 0 && v.rate.tp_poly.ok && v.i_chan >= 0 && v.chan_ntaps > 0 && v.tp_chan.ok && v.tp_audio.ok;
         if (!x.piped) { return; }
         x.pj = PipeJob{};
-        const ToepTab* tabs[4] = { &v.tp_stage[last_dec], &v.tp_poly, &v.tp_chan, &v.tp_audio };
+        const ToepTab* tabs[4] = { &v.rate.tp_stage[last_dec], &v.rate.tp_poly, &v.tp_chan, &v.tp_audio };
         for (int s = 0; s < 4; s++) { x.pj.st[s] = toep_job(*tabs[s], 0, StreamIn{}, nullptr, 0, 0, 0.0f); }  // (the layout needs the tables' geometry only)
         x.pj.timeouts = c->hd_tick_flag ? (int*)(c->hd_tick_flag + 8) : nullptr;
         x.piped = pipe_layout(x.pj, &x.pj_lds);
@@ -727,10 +735,8 @@ struct BankPlan {
         x.bnd.clear();  // (the reference's blocks end at the demodulator; the push ends go on, in a list of the AF chain's own)
         if (x.split) { v.tk_af = v.tk_if; }
         x.tk = &v.tk_af;
-        for (int s = 0; s < a.n_stages; s++) {
-            decim_step(x, v.st[(size_t)a.i_stage0 + s], a.tp_stage[s], a.d_staps[s], (int)a.staps[s].size(), a.decim_s[s], a.s_kp[s], a.soff[s], t_af_dec, af_dec);
-        }
-        if (a.i_poly >= 0) { poly_step(x, v.st[(size_t)a.i_poly], a.tp_poly, a.interp, a.decim, a.tpp, a.pphase, a.poff, a.d_bank, nullptr, 0, 0, t_af_poly, af_poly); }
+        for (int s = 0; s < a.rate.n_stages; s++) { decim_step(x, v.st[(size_t)a.i_stage0 + s], a.rate, s, t_af_dec, af_dec); }
+        if (a.i_poly >= 0) { poly_step(x, v.st[(size_t)a.i_poly], a.rate, nullptr, 0, 0, t_af_poly, af_poly); }
         if (a.i_hpf >= 0) { fir_step(x, v.st[(size_t)a.i_hpf], a.tp_hpf, a.d_hpf, (int)a.htaps.size(), a.hpf_kp, 0.0f, t_af_hpf, af_hpf); }
         if (a.i_deemp >= 0) {
             const Stream& in = *x.at.cur;
@@ -763,21 +769,22 @@ struct BankPlan {
         x.tk = &r.tk;
         x.at = feed;
         const float2* prev0 = reinterpret_cast<const float2*>(in.hist[in.cur]) + (in.hist_len - 1);  // the discriminator's previous sample
-        const int K0 = (int)r.staps[0].size(), D0 = r.decim_s[0];
+        RateChain& R = r.rate;
+        const int K0 = R.ntaps(0), D0 = R.decim_s[0];
         if (r.exact) {
             Stream& rot = r.st[0];
             rdsx.add(lvl + 1, RdsRotXJob{ reinterpret_cast<const float2*>(in.data), prev0, reinterpret_cast<float2*>(rot.data), r.d_rot, r.pd_re, r.pd_im, v.d.inv_deviation, nif, x.d_bnd, x.nbnd });
             x.at.step(rot, nif);
-            decim_step(x, r.st[(size_t)r.i_stage0], r.tp_stage[0], r.d_staps[0], K0, D0, r.s_kp[0], r.soff[0], t_af_dec, af_dec);
+            decim_step(x, r.st[(size_t)r.i_stage0], R, 0, t_af_dec, af_dec);
         }
         else {
             Stream& nxt = r.st[(size_t)r.i_stage0];
             StreamIn sin = stream_in(in);
             if (r.frozen) { sin.hist_len = 0; }  // the delay line the branch was left with (RdsJob::dline), not what the stream has seen since: nothing in front of the block is read
-            RdsJob j{ sin, prev0, reinterpret_cast<float2*>(nxt.data), r.d_staps[0], r.frozen ? r.d_line[r.line_cur] : nullptr, K0, ilog2(D0), r.soff[0], 0, 0,
+            RdsJob j{ sin, prev0, reinterpret_cast<float2*>(nxt.data), R.d_staps[0], r.frozen ? r.d_line[r.line_cur] : nullptr, K0, ilog2(D0), R.pos.soff[0], 0, 0,
                       r.tile, r.pitch, 0, v.d.inv_deviation, r.theta, r.phi };
             const size_t npush = x.split ? v.tk_if.size() : 1;
-            int lo = 0, so = r.soff[0], m = 0;
+            int lo = 0, so = R.pos.soff[0], m = 0;
             for (size_t q = 0; q < npush; q++) {
                 const int hi = x.split ? v.tk_if[q] : nif, nq = hi - lo;
                 const int mq = decim_nout(nq, so, D0);
@@ -794,8 +801,8 @@ struct BankPlan {
                 r.phi = p - std::floor(p);
                 lo = hi;
             }
-            x.through_decim(r.soff[0], D0);
-            r.soff[0] = so;
+            x.through_decim(R.pos.soff[0], D0);
+            R.pos.soff[0] = so;
             x.at.step(nxt, m);
             if (r.frozen && nif > 0) {
                 // the feed's history is the branch's delay line again only once the branch has seen K0 samples of it in a row; until then the block's
@@ -808,13 +815,8 @@ struct BankPlan {
                 }
             }
         }
-        for (int s = 1; s < r.n_stages; s++) {
-            decim_step(x, r.st[(size_t)r.i_stage0 + s], r.tp_stage[s], r.d_staps[s], (int)r.staps[s].size(), r.decim_s[s], r.s_kp[s], r.soff[s], t_af_dec, af_dec);
-        }
-        if (r.i_poly >= 0) {
-            static const ToepTab no_tab{};  // (5000 phases: no matrix form)
-            poly_step(x, r.st[(size_t)r.i_poly], no_tab, r.interp, r.decim, r.tpp, r.pphase, r.poff, r.d_bank, nullptr, 0, 0, t_af_poly, af_poly);
-        }
+        for (int s = 1; s < R.n_stages; s++) { decim_step(x, r.st[(size_t)r.i_stage0 + s], R, s, t_af_dec, af_dec); }
+        if (r.i_poly >= 0) { poly_step(x, r.st[(size_t)r.i_poly], R, nullptr, 0, 0, t_af_poly, af_poly); }  // (5000 phases: the branch keeps no matrix table)
         r.i_last = (int)(x.at.cur - &r.st[0]);
         r.lvl = x.at.lvl;
     }
@@ -830,7 +832,7 @@ struct BankPlan {
     // history carries for every stream that has a consumer with memory
     void history_carries(ChainCtx& x) {
         Vfo& v = x.v;
-        const Stream* phantom = (v.fused_front && v.d.n_stages >= 2 && !v.nco_exact) ? &v.st[(size_t)v.i_first] : nullptr;  // stage-1 output of a fused front end: never written, never read
+        const Stream* phantom = (v.fused_front && v.rate.n_stages >= 2 && !v.nco_exact) ? &v.st[(size_t)v.i_first] : nullptr;  // stage-1 output of a fused front end: never written, never read
         for (auto& s : v.st) {
             const bool idle_fmi = v.i_fmi >= 0 && &s == &v.st[(size_t)v.i_fmi] && !(x.ifc_on && v.ifc.fm_on && v.ifc.nbsq());  // (no chain writes it: nothing to carry)
             if (s.hist_len > 0 && s.data && &s != phantom && !idle_fmi && (x.ifc_on || v.i_ifc < 0 || &s != &v.st[(size_t)v.i_ifc])) {
@@ -898,8 +900,8 @@ struct BankPlan {
             // composite taps h12 = h1 (*) upsample(h2, D1) in double precision (both are linear phase, so is h12)
             std::fill(h12.begin(), h12.end(), 0.0);
             for (int k2 = 0; k2 < h.K2; k2++) {
-                const double w2 = m_long ? 1.0 : (double)vv.staps[1][(size_t)k2];
-                for (int k1 = 0; k1 < h.K; k1++) { h12[(size_t)k2 * D1 + k1] += w2 * (double)vv.staps[0][(size_t)k1]; }
+                const double w2 = m_long ? 1.0 : (double)vv.rate.staps[1][(size_t)k2];
+                for (int k1 = 0; k1 < h.K; k1++) { h12[(size_t)k2 * D1 + k1] += w2 * (double)vv.rate.staps[0][(size_t)k1]; }
             }
             for (int pz = 0; pz < NP; pz++) {
                 double t = ((double)pz - kc) * vv.theta;  // modulation centred on the filter: g[K-1-k] = conj(g[k])

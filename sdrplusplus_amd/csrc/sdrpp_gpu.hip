@@ -308,10 +308,7 @@ int sdrpp_wf_raster(sdrpp_ctx* c, int draw_start, int draw_size, int data_width,
 
 static void preproc_free(sdrpp_ctx* c) {
     sdrpp_ctx::Pre& P = c->pre;
-    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) {
-        dev_free(P.d_staps[i]);
-        toep_free(P.tp[i]);
-    }
+    rate_free(P.rate);
     P.raw.data = nullptr;  // the caller's buffer, never owned
     stream_free(P.raw);
     for (auto& s : P.st) { stream_free(s); }
@@ -640,42 +637,29 @@ int sdrpp_preproc_configure(sdrpp_ctx* c, int n_stages, const int* stage_decim, 
     DeviceScope dev_scope_(c);
     if (!c || n_stages < 0 || n_stages > SDRPP_MAX_DECIM_STAGES) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
-    for (int s = 0; s < n_stages; s++) {
-        if (!stage_decim || !stage_ntaps || !stage_taps || !is_pow2(stage_decim[s]) || stage_ntaps[s] <= 0 || !stage_taps[s]) {
-            return fail(c, SDRPP_ERR_UNSUPPORTED, "pre-processing stage %d: decimation must be a power of two with taps", s);
-        }
-    }
+    const RateDesc rd = rate_desc(n_stages, stage_decim, stage_ntaps, stage_taps);
+    if (int rc = rate_check_stages(c, rd, "pre-processing ")) { return rc; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     preproc_free(c);
     if (n_stages == 0 && dc_rate == 0.0f && !conjugate) { return SDRPP_OK; }  // chain fully disabled: pushes go straight through
     sdrpp_ctx::Pre& P = c->pre;
+    RateChain& R = P.rate;
+    rate_describe(R, rd);
     P.ref_order = c->pre_ref_order;
-    P.n_stages = n_stages;
     P.dc_rate = dc_rate;
     P.conj = conjugate ? 1 : 0;
     int rc;
     size_t cap = (size_t)c->max_push;
     if (n_stages > 0) {
         P.raw.width = 2;
-        P.raw.hist_len = stage_ntaps[0] - 1;
+        P.raw.hist_len = R.need(0, 0);
         for (int i = 0; i < 2; i++) {
             rc = dev_alloc(c, &P.raw.hist[i], (size_t)std::max(P.raw.hist_len, 1) * 2);
             if (rc) { return rc; }
             HIPCHK(c, hipMemset(P.raw.hist[i], 0, (size_t)std::max(P.raw.hist_len, 1) * 2 * sizeof(float)));
         }
     }
-    P.st.resize((size_t)n_stages);
-    for (int s = 0; s < n_stages; s++) {
-        P.decim_s[s] = stage_decim[s];
-        P.staps[s].assign(stage_taps[s], stage_taps[s] + stage_ntaps[s]);
-        rc = upload_blocked(c, &P.d_staps[s], P.staps[s].data(), (int)P.staps[s].size(), P.decim_s[s], &P.s_kp[s]);
-        if (rc) { return rc; }
-        rc = toep_build_fir(c, P.tp[s], P.staps[s].data(), (int)P.staps[s].size(), P.decim_s[s]);
-        if (rc) { return rc; }
-        cap = cap / (size_t)P.decim_s[s] + 2;
-        rc = stream_alloc(c, P.st[(size_t)s], 2, (s + 1 < n_stages) ? stage_ntaps[s + 1] - 1 : 0, cap);
-        if (rc) { return rc; }
-    }
+    if ((rc = rate_build(c, R, RateForm{}, P.st, cap, 0))) { return rc; }
     if (dc_rate != 0.0f || conjugate) {
         rc = stream_alloc(c, P.out, 2, 0, cap);
         if (rc) { return rc; }
@@ -705,22 +689,19 @@ int sdrpp_preproc_reconfigure(sdrpp_ctx* c, int n_stages, const int* stage_decim
     HIPCHK(c, hipStreamSynchronize(c->stream));
     sdrpp_ctx::Pre& P = c->pre;
     if (P.on && P.dc_rate != 0.0f && P.d_off) { HIPCHK(c, hipMemcpy(&c->pre_dc_last, P.d_off + P.state_cur, sizeof(float2), hipMemcpyDeviceToHost)); }
-    bool same = (keep & 1) && P.on && n_stages > 0 && P.n_stages == n_stages && stage_decim && stage_ntaps && stage_taps;
-    for (int s = 0; same && s < n_stages; s++) {
-        same = P.decim_s[s] == stage_decim[s] && (int)P.staps[s].size() == stage_ntaps[s] && stage_taps[s] && memcmp(P.staps[s].data(), stage_taps[s], sizeof(float) * (size_t)stage_ntaps[s]) == 0;
-    }
+    const bool same = (keep & 1) && P.on && n_stages > 0 && rate_same(P.rate, rate_desc(n_stages, stage_decim, stage_ntaps, stage_taps));
     sdrpp_ctx::Pre old;
     if (same) {  // set the decimator's streams (delay lines, ring buffers) and offsets aside; the rest of the old chain is freed by the configure below
         std::swap(old.raw, P.raw);
         std::swap(old.st, P.st);
-        for (int s = 0; s < SDRPP_MAX_DECIM_STAGES; s++) { old.soff[s] = P.soff[s]; }
+        old.rate.pos = P.rate.pos;
     }
     int rc = sdrpp_preproc_configure(c, n_stages, stage_decim, stage_ntaps, stage_taps, dc_rate, conjugate);
     if (same) {
         if (!rc && P.on) {
             std::swap(old.raw, P.raw);
             std::swap(old.st, P.st);
-            for (int s = 0; s < SDRPP_MAX_DECIM_STAGES; s++) { P.soff[s] = old.soff[s]; }
+            P.rate.pos = old.rate.pos;
         }
         old.raw.data = nullptr;
         stream_free(old.raw);
@@ -808,7 +789,7 @@ int sdrpp_vfo_set_phase_delta(sdrpp_ctx* c, int id, float re, float im) {
     const double th = sdrpp_host::turnsPerSample(re, im);
     // the samples already in the first decimator's delay line stay rotated with the old increment (rx_vfo.h:72-77 only swaps
     // phaseDelta): remember where it changed so the first outputs of the next pushes can be handed over exactly (do_vfos)
-    if (!v->nco_exact && v->d.n_stages > 0 && th != v->theta) {
+    if (!v->nco_exact && v->rate.n_stages > 0 && th != v->theta) {
         if (!v->recs.empty() && v->recs.back().pos == v->seen) { /* retuned twice between pushes: the older increment stays the one before */ }
         else { v->recs.push_back(Vfo::Retune{ v->seen, v->theta }); }
     }
@@ -934,7 +915,9 @@ int sdrpp_vfo_set_rds(sdrpp_ctx* c, int id, const sdrpp_rds_desc* d, int enabled
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
     LOOKUP_VFO(v, c, id);
-    return rds_apply(c, *v, d, enabled != 0);
+    if (!d) { return rds_apply(c, *v, nullptr, 0.0f, 0.0f, false); }
+    const RateDesc rd = rate_desc(*d);
+    return rds_apply(c, *v, &rd, d->phase_delta_re, d->phase_delta_im, enabled != 0);
 }
 
 int sdrpp_vfo_rds_count(sdrpp_ctx* c, int id) {

@@ -656,7 +656,7 @@ int tick_push(sdrpp_ctx* c, const float* d_iq, int64_t count, const CopyJob* lan
     }
     c->groups++;
     const bool have_slot = as_tick;
-    static thread_local PlanSnapshot snap;  // (re-used: with 128 VFOs a fresh one is a 38 KB allocation per block; a nested pass starts only after the outer plan has been restored)
+    static thread_local PlanSnapshot snap;  // (re-used: a fresh one is two allocations per block, tens of KB with 128 VFOs; a nested pass starts only after the outer plan has been restored)
     int rc = SDRPP_OK;
     if (as_tick) {
         HostScope hs("tick plan");
@@ -788,7 +788,7 @@ inline size_t iq_format_bytes(int type) { return type == SDRPP_IQ_I16 ? 4 : 2; }
 bool group_eligible(sdrpp_ctx* c) {
     if (c->group_max <= 1 || c->pre.on || !tick_eligible(c)) { return false; }
     for (Vfo* v : c->vfo_list) {
-        if (!v->nco_exact && v->d.n_stages == 0) { return false; }
+        if (!v->nco_exact && v->rate.n_stages == 0) { return false; }
     }
     return true;
 }

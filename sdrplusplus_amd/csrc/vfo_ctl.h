@@ -15,7 +15,7 @@ Vfo* vfo_lookup(sdrpp_ctx* c, int id) {
 
 // ---- which stream is what -----------------------------------------------------------------------------------------------------------
 // The stream the channel filter reads: the resampler's output, else the last decimator stage's (stream 0 of a VFO without stages).
-Stream& chan_feed(Vfo& v) { return v.st[(size_t)((v.i_poly >= 0) ? v.i_poly : v.i_first + std::max(v.d.n_stages, 1) - 1)]; }
+Stream& chan_feed(Vfo& v) { return v.st[(size_t)((v.i_poly >= 0) ? v.i_poly : v.i_first + std::max(v.rate.n_stages, 1) - 1)]; }
 // RxVFO::out as the VFO is configured NOW: the channel filter's output, or its input while the filter is bypassed (st[i_if]: where the last push's lies).
 Stream& rx_out(Vfo& v) { return (v.chan_ntaps > 0 && v.i_chan >= 0) ? v.st[(size_t)v.i_chan] : chan_feed(v); }
 // What a read-out call names with `which` (sdrpp_vfo_read_many / _read_pcm / _read_compressed); nullptr: the VFO has no such stream.
@@ -37,7 +37,7 @@ Stream& demod_feed(Vfo& v) { return delivered(v, 3) ? *delivered(v, 3) : rx_out(
 // (and the RDS branch's fused first stage recomputes its delay line from it: the stage's K0 - 1 samples and the one in front of them)
 int demod_if_need(const Vfo& v) {
     const int fm = (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) ? std::max(v.audio_ntaps, 1) + 1 : 1;
-    return (v.rds.attached && !v.rds.exact) ? std::max(fm, (int)v.rds.staps[0].size()) : fm;
+    return (v.rds.attached && !v.rds.exact) ? std::max(fm, v.rds.rate.ntaps(0)) : fm;
 }
 
 // ---- delay-line hand-overs ----------------------------------------------------------------------------------------------------------
@@ -72,27 +72,17 @@ int fir_line_restore(sdrpp_ctx* c, Stream& s, int ntaps, const std::vector<float
 }
 
 // ---- building a VFO -----------------------------------------------------------------------------------------------------------------
-// bank[(L-1) - (i mod L)][i div L] = taps[i], zero-padded to L x tpp (polyphase_bank.h:31-34), laid out [phase][tpp]
-std::vector<float> polyphase_bank(const float* taps, int n, int interp, int tpp) {
-    std::vector<float> bank((size_t)interp * tpp, 0.0f);
-    for (int i = 0; i < std::min(n, interp * tpp); i++) { bank[(size_t)((interp - 1) - (i % interp)) * tpp + (size_t)(i / interp)] = taps[i]; }
-    return bank;
-}
-
 // sdrpp_vfo_add behind its argument check and flush: validates the description, builds the VFO and hands it to the context
 int vfo_build(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
-    if (d->n_stages < 0 || d->n_stages > SDRPP_MAX_DECIM_STAGES) { return fail(c, SDRPP_ERR_INVALID, "n_stages %d", d->n_stages); }
-    for (int s = 0; s < d->n_stages; s++) {
-        if (!is_pow2(d->stage_decim[s]) || d->stage_ntaps[s] <= 0 || !d->stage_taps[s]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "stage %d: decimation must be a power of two with taps", s); }
-    }
+    const RateDesc rd = rate_desc(*d);
+    if (int rc = rate_check_stages(c, rd, "")) { return rc; }
     if (d->n_stages > 0) {  // the fused translation + FIR kernel uses the linear-phase pairing (all reference plans are symmetric)
         const float* h = d->stage_taps[0];
         for (int k = 0; k < d->stage_ntaps[0] / 2; k++) {
             if (h[k] != h[d->stage_ntaps[0] - 1 - k]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "first decimation stage must have symmetric (linear-phase) taps"); }
         }
     }
-    const bool has_poly = (d->interp != d->decim);
-    if (has_poly && (d->interp <= 0 || d->decim <= 0 || d->resamp_ntaps <= 0 || !d->resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad polyphase description"); }
+    if (int rc = rate_check_poly(c, rd, "")) { return rc; }
     if (d->chan_ntaps < 0 || d->chan_ntaps > kChanHistCap + 1) { return fail(c, SDRPP_ERR_UNSUPPORTED, "channel filter of %d taps (max %d)", d->chan_ntaps, kChanHistCap + 1); }
     if (d->demod < SDRPP_DEMOD_RAW || d->demod > SDRPP_DEMOD_DSB) { return fail(c, SDRPP_ERR_INVALID, "demod %d", d->demod); }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -108,6 +98,10 @@ int vfo_build(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
     std::unique_ptr<Vfo, VfoFreer> v(new Vfo);
     v->id = c->next_id++;
     v->d = *d;
+    for (int s = 0; s < SDRPP_MAX_DECIM_STAGES; s++) { v->d.stage_taps[s] = nullptr; }  // (the caller's arrays: `rate` has its own copies)
+    v->d.resamp_taps = nullptr;
+    RateChain& R = v->rate;
+    rate_describe(R, rd);
     if (d->nco_mode < 0 || d->nco_mode > 2) { return fail(c, SDRPP_ERR_INVALID, "nco_mode %d: 0 (context), 1 (closed form) or 2 (reference rotator)", d->nco_mode); }
     v->nco_exact = d->nco_mode == 0 ? (c->nco_exact != 0) : (d->nco_mode == 2);
     int rc;
@@ -118,95 +112,72 @@ int vfo_build(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
         int r = stream_alloc(c, v->st.back(), width, hist, capn);
         return r ? -1 : (int)v->st.size() - 1;
     };
-    // what consumes the decimator / rotator output
-    const int tpp = has_poly ? (d->resamp_ntaps + d->interp - 1) / d->interp : 0;
     const bool fm = (d->demod == SDRPP_DEMOD_WFM || d->demod == SDRPP_DEMOD_NFM);
     if (fm || d->demod == SDRPP_DEMOD_AM) { v->audio_ntaps = std::max(d->audio_ntaps, 1); }  // fm.h:165-168 loadDummyTaps: a single unit tap when the low-pass is off
     const int if_hist = demod_if_need(*v);
     const int chan_hist = ((std::max(std::max(d->chan_ntaps - 1, 1), if_hist) + 63) / 64) * 64;  // grown on demand by sdrpp_vfo_set_channel_taps
-    auto hist_after_decim = [&]() -> int {
-        if (has_poly) { return tpp - 1; }
-        return chan_hist;  // channel filter or the discriminator
-    };
-    for (int s = 0; s < d->n_stages; s++) {
-        v->staps[s].assign(d->stage_taps[s], d->stage_taps[s] + d->stage_ntaps[s]);
-        v->d.stage_taps[s] = nullptr;
-        rc = upload_blocked(c, &v->d_staps[s], v->staps[s].data(), (int)v->staps[s].size(), d->stage_decim[s], &v->s_kp[s]);
-        if (rc) { return rc; }
-        rc = upload(c, &v->d_staps_nat[s], v->staps[s].data(), v->staps[s].size());
-        if (rc) { return rc; }
-        if (s >= 1 || v->nco_exact) {  // stage 0 runs as a plain FIR only behind the reference rotator
-            rc = toep_build_fir(c, v->tp_stage[s], v->staps[s].data(), (int)v->staps[s].size(), d->stage_decim[s]);
-            if (rc) { return rc; }
-        }
-        cap = cap / (size_t)d->stage_decim[s] + 2;
-        const int hist = (s + 1 < d->n_stages) ? d->stage_ntaps[s + 1] - 1 : hist_after_decim();
-        if (add_stream(2, hist, cap) < 0) { return SDRPP_ERR_NOMEM; }
+    // what consumes the decimator / rotator output: the polyphase stage, else the channel filter or the discriminator
+    if (R.n_stages == 0) {
+        if (add_stream(2, R.need(0, chan_hist), cap) < 0) { return SDRPP_ERR_NOMEM; }
     }
-    if (d->n_stages == 0) {
-        if (add_stream(2, hist_after_decim(), cap) < 0) { return SDRPP_ERR_NOMEM; }
+    // every stage in blocks (and, below, in natural order for the fused front kernel); stage 0 runs as a plain FIR only behind the reference rotator
+    RateForm form;
+    form.matrix = v->nco_exact ? ~0u : ~1u;
+    std::vector<float> bank;
+    if ((rc = rate_build(c, R, form, v->st, cap, chan_hist, &bank))) { return rc; }
+    if (R.has_poly()) { v->i_poly = (int)v->st.size() - 1; }
+    for (int s = 0; s < R.n_stages; s++) {
+        if ((rc = upload(c, &v->d_staps_nat[s], R.staps[s].data(), R.staps[s].size()))) { return rc; }
     }
     v->i_first = 0;
     {   // the front end as one filter: fusion decision (geometry only), tap identity, composite taps for the retune hand-over
         unsigned long long hsh = 1469598103934665603ull;  // FNV-1a over the taps of stages 0 and 1
-        for (int s = 0; s < std::min(d->n_stages, 2); s++) {
-            for (float t : v->staps[s]) {
+        for (int s = 0; s < std::min(R.n_stages, 2); s++) {
+            for (float t : R.staps[s]) {
                 unsigned u;
                 memcpy(&u, &t, 4);
                 hsh = (hsh ^ u) * 1099511628211ull;
             }
         }
         v->tap_hash = hsh;
-        if (d->n_stages >= 2) {  // the composite forms pair taps k and K-1-k: stage 1 must be linear phase as well
-            const std::vector<float>& h2 = v->staps[1];
+        if (R.n_stages >= 2) {  // the composite forms pair taps k and K-1-k: stage 1 must be linear phase as well
+            const std::vector<float>& h2 = R.staps[1];
             for (size_t k = 0; k < h2.size() / 2; k++) { v->no_fuse = v->no_fuse || (h2[k] != h2[h2.size() - 1 - k]); }
         }
-        v->fused_front = !v->nco_exact && !v->no_fuse && d->n_stages >= 2 && front2_t2(d->stage_ntaps[0], d->stage_decim[0], d->stage_ntaps[1], d->stage_decim[1], 8) > 0;
-        if (d->n_stages >= 1 && !v->nco_exact) {
-            const int K0 = d->stage_ntaps[0], D1 = d->stage_decim[0], K2 = v->fused_front ? d->stage_ntaps[1] : 1;
+        v->fused_front = !v->nco_exact && !v->no_fuse && R.n_stages >= 2 && front2_t2(R.ntaps(0), R.decim_s[0], R.ntaps(1), R.decim_s[1], 8) > 0;
+        if (R.n_stages >= 1 && !v->nco_exact) {
+            const int K0 = R.ntaps(0), D1 = R.decim_s[0], K2 = v->fused_front ? R.ntaps(1) : 1;
             const int K = K0 + (K2 - 1) * D1;
             std::vector<double> h12((size_t)K, 0.0);
             for (int k2 = 0; k2 < K2; k2++) {
-                const double w2 = v->fused_front ? (double)v->staps[1][(size_t)k2] : 1.0;
-                for (int k1 = 0; k1 < K0; k1++) { h12[(size_t)k2 * D1 + k1] += w2 * (double)v->staps[0][(size_t)k1]; }
+                const double w2 = v->fused_front ? (double)R.staps[1][(size_t)k2] : 1.0;
+                for (int k1 = 0; k1 < K0; k1++) { h12[(size_t)k2 * D1 + k1] += w2 * (double)R.staps[0][(size_t)k1]; }
             }
             std::vector<float> hf(h12.begin(), h12.end());
             rc = upload(c, &v->d_h12, hf.data(), hf.size());
             if (rc) { return rc; }
             v->h12_K = K;
-            v->h12_lgD = ilog2(D1) + (v->fused_front ? ilog2(d->stage_decim[1]) : 0);
+            v->h12_lgD = ilog2(D1) + (v->fused_front ? ilog2(R.decim_s[1]) : 0);
         }
-        if (v->nco_exact && d->n_stages >= 1) {  // reference-rotator mode: the rotated full-rate stream feeds stage 0
-            v->i_rot = add_stream(2, d->stage_ntaps[0] - 1, (size_t)c->max_push);
+        if (v->nco_exact && R.n_stages >= 1) {  // reference-rotator mode: the rotated full-rate stream feeds stage 0
+            // (behind the chain's streams on purpose: rate_build appends the stages' and the resampler's in one go, and i_rot is only ever an index)
+            v->i_rot = add_stream(2, R.ntaps(0) - 1, (size_t)c->max_push);
             if (v->i_rot < 0) { return SDRPP_ERR_NOMEM; }
         }
     }
-    if (has_poly) {
-        v->rtaps.assign(d->resamp_taps, d->resamp_taps + d->resamp_ntaps);
-        v->d.resamp_taps = nullptr;
-        v->tpp = tpp;
-        const std::vector<float> bank = polyphase_bank(v->rtaps.data(), d->resamp_ntaps, d->interp, tpp);
-        rc = upload(c, &v->d_bank, bank.data(), bank.size());
-        if (rc) { return rc; }
-        rc = toep_build_poly(c, v->tp_poly, bank, d->interp, d->decim, tpp);
-        if (rc) { return rc; }
-        if (d->interp <= 8) {  // register-blocked kernel: per carried phase, taps of one full phase cycle
-            const int L = d->interp, M = d->decim, lmax = (L <= 4) ? 4 : 8, rows = tpp + M;
-            std::vector<float> cyc((size_t)L * rows * lmax, 0.0f);
-            for (int ph0 = 0; ph0 < L; ph0++) {
-                for (int r = 0; r < L; r++) {
-                    const int A = ph0 + r * M, ph = A % L, o = A / L;
-                    for (int k = 0; k < tpp; k++) { cyc[((size_t)ph0 * rows + (size_t)(k + o)) * lmax + r] = bank[(size_t)ph * tpp + k]; }
-                }
+    if (R.has_poly() && R.interp <= 8) {  // register-blocked kernel: per carried phase, taps of one full phase cycle
+        const int L = R.interp, M = R.decim, tpp = R.tpp, lmax = (L <= 4) ? 4 : 8, rows = tpp + M;
+        std::vector<float> cyc((size_t)L * rows * lmax, 0.0f);
+        for (int ph0 = 0; ph0 < L; ph0++) {
+            for (int r = 0; r < L; r++) {
+                const int A = ph0 + r * M, ph = A % L, o = A / L;
+                for (int k = 0; k < tpp; k++) { cyc[((size_t)ph0 * rows + (size_t)(k + o)) * lmax + r] = bank[(size_t)ph * tpp + k]; }
             }
-            rc = upload(c, &v->d_cyc, cyc.data(), cyc.size());
-            if (rc) { return rc; }
-            v->cyc_rows = rows;
-            v->cyc_lmax = lmax;
         }
-        cap = cap * (size_t)d->interp / (size_t)d->decim + 4;
-        v->i_poly = add_stream(2, chan_hist, cap);
-        if (v->i_poly < 0) { return SDRPP_ERR_NOMEM; }
+        rc = upload(c, &v->d_cyc, cyc.data(), cyc.size());
+        if (rc) { return rc; }
+        v->cyc_rows = rows;
+        v->cyc_lmax = lmax;
     }
     // channel-filter output stream always exists (taps may be enabled later); its consumer is the demodulator
     v->i_chan = add_stream(2, if_hist, cap);
@@ -498,58 +469,27 @@ int vfo_set_chan_taps(sdrpp_ctx* c, Vfo& v, const float* taps, int n) {
 }
 
 // ---- radio AF chain -----------------------------------------------------------------------------------------------------------------
-void af_detach(Vfo& v) {
-    Vfo::Af& a = v.af;
-    for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) {
-        dev_free(a.d_staps[i]);
-        toep_free(a.tp_stage[i]);
-    }
-    toep_free(a.tp_poly);
-    toep_free(a.tp_hpf);
-    dev_free(a.d_bank);
-    dev_free(a.d_hpf);
-    dev_free(a.d_last);
-    dev_free(a.d_seg);
-    if (a.base >= 0) {
-        for (size_t i = (size_t)a.base; i < v.st.size(); i++) { stream_free(v.st[i]); }
-        v.st.resize((size_t)a.base);
-    }
-    a = Vfo::Af{};
-}
-
 // sdrpp_vfo_set_af on a VFO the caller has looked up: the old chain goes, `af` (if any) is built behind st[i_out]
 int af_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_af_desc* af) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     af_detach(v);
     if (!af) { return SDRPP_OK; }
     if (v.d.demod == SDRPP_DEMOD_RAW || v.i_out < 0) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the AF chain needs a demodulating VFO"); }
-    if (af->n_stages < 0 || af->n_stages > SDRPP_MAX_DECIM_STAGES) { return fail(c, SDRPP_ERR_INVALID, "af n_stages %d", af->n_stages); }
-    for (int s = 0; s < af->n_stages; s++) {
-        if (!is_pow2(af->stage_decim[s]) || af->stage_ntaps[s] <= 0 || !af->stage_taps[s]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "af stage %d: decimation must be a power of two with taps", s); }
-    }
-    const bool has_poly = af->interp != af->decim;
-    if (has_poly && (af->interp <= 0 || af->decim <= 0 || af->resamp_ntaps <= 0 || !af->resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af polyphase description"); }
+    const RateDesc rd = rate_desc(*af);
+    if (int rc = rate_check_stages(c, rd, "af ")) { return rc; }
+    if (int rc = rate_check_poly(c, rd, "af ")) { return rc; }
     if (af->hpf_ntaps < 0 || (af->hpf_ntaps > 0 && !af->hpf_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af high-pass description"); }
     // (no kChanHistCap here: that is the channel filter's pre-allocated history; the high-pass's input stream gets its history from the tap count below, and a
     // filter too long for the matrix form and for an LDS tile of the register-blocked one runs untiled — highPass(300, 100) has 7 296 taps at 192 kHz)
     if (af->hpf_ntaps > kAfHpfMaxTaps) { return fail(c, SDRPP_ERR_UNSUPPORTED, "af high-pass of %d taps (max %d)", af->hpf_ntaps, kAfHpfMaxTaps); }
     Vfo::Af& a = v.af;
+    RateChain& R = a.rate;
+    rate_describe(R, rd);
     a.base = (int)v.st.size();
-    a.n_stages = af->n_stages;
-    a.interp = has_poly ? af->interp : 1;
-    a.decim = has_poly ? af->decim : 1;
-    a.tpp = has_poly ? (af->resamp_ntaps + af->interp - 1) / af->interp : 0;
     a.alpha = af->deemph_alpha;
     int rc;
-    // history a stream must keep = (taps - 1) of its consumer; `stage` = first block that can be the consumer
-    // (0..n_stages-1 decimators, n_stages polyphase, n_stages+1 high-pass; de-emphasis needs none)
-    auto need_of = [&](int stage) -> int {
-        if (stage < a.n_stages) { return af->stage_ntaps[stage] - 1; }
-        if (stage <= a.n_stages && has_poly) { return a.tpp - 1; }
-        if (stage <= a.n_stages + 1 && af->hpf_ntaps > 0) { return af->hpf_ntaps - 1; }
-        return 0;
-    };
-    rc = stream_grow_hist(c, v.st[(size_t)v.i_out], need_of(0));
+    const int tail = std::max(af->hpf_ntaps - 1, 0);  // behind the resampler: the high-pass (the de-emphasis needs no history)
+    rc = stream_grow_hist(c, v.st[(size_t)v.i_out], R.need(0, tail));
     if (rc) { return rc; }
     size_t cap = v.st[(size_t)v.i_out].cap;
     auto add_stream = [&](int hist, size_t capn) -> int {
@@ -557,29 +497,9 @@ int af_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_af_desc* af) {
         int r = stream_alloc(c, v.st.back(), 2, hist, capn);
         return r ? -1 : (int)v.st.size() - 1;
     };
-    for (int s = 0; s < a.n_stages; s++) {
-        a.decim_s[s] = af->stage_decim[s];
-        a.staps[s].assign(af->stage_taps[s], af->stage_taps[s] + af->stage_ntaps[s]);
-        rc = upload_blocked(c, &a.d_staps[s], a.staps[s].data(), (int)a.staps[s].size(), a.decim_s[s], &a.s_kp[s]);
-        if (rc) { return rc; }
-        rc = toep_build_fir(c, a.tp_stage[s], a.staps[s].data(), (int)a.staps[s].size(), a.decim_s[s]);
-        if (rc) { return rc; }
-        cap = cap / (size_t)a.decim_s[s] + 2;
-        const int idx = add_stream(need_of(s + 1), cap);
-        if (idx < 0) { return SDRPP_ERR_NOMEM; }
-        if (s == 0) { a.i_stage0 = idx; }
-    }
-    if (has_poly) {
-        a.rtaps.assign(af->resamp_taps, af->resamp_taps + af->resamp_ntaps);
-        const std::vector<float> bank = polyphase_bank(a.rtaps.data(), af->resamp_ntaps, a.interp, a.tpp);
-        rc = upload(c, &a.d_bank, bank.data(), bank.size());
-        if (rc) { return rc; }
-        rc = toep_build_poly(c, a.tp_poly, bank, a.interp, a.decim, a.tpp);
-        if (rc) { return rc; }
-        cap = cap * (size_t)a.interp / (size_t)a.decim + 4;
-        a.i_poly = add_stream(need_of(a.n_stages + 1), cap);
-        if (a.i_poly < 0) { return SDRPP_ERR_NOMEM; }
-    }
+    if ((rc = rate_build(c, R, RateForm{}, v.st, cap, tail))) { return rc; }
+    if (R.n_stages > 0) { a.i_stage0 = a.base; }
+    if (R.has_poly()) { a.i_poly = a.base + R.n_stages; }
     if (af->hpf_ntaps > 0) {
         a.htaps.assign(af->hpf_taps, af->hpf_taps + af->hpf_ntaps);
         rc = upload_blocked(c, &a.d_hpf, a.htaps.data(), (int)a.htaps.size(), 1, &a.hpf_kp);
@@ -642,7 +562,7 @@ int rds_freeze(sdrpp_ctx* c, Vfo& v) {
     r.line_fed = 0;
     if (r.frozen) { return SDRPP_OK; }
     const Stream& s = demod_feed(v);
-    const int K0 = (int)r.staps[0].size();
+    const int K0 = r.rate.ntaps(0);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     float* line = r.d_line[r.line_cur];
     if (s.hist_len >= K0 && s.hist[s.cur]) {
@@ -655,36 +575,45 @@ int rds_freeze(sdrpp_ctx* c, Vfo& v) {
     r.frozen = true;
     return SDRPP_OK;
 }
-bool rds_same_desc(const Vfo::Rds& r, const sdrpp_rds_desc* d) {
-    const bool has_poly = d->interp != d->decim;
-    if (r.pd_re != d->phase_delta_re || r.pd_im != d->phase_delta_im || r.n_stages != d->n_stages || (r.i_poly >= 0) != has_poly) { return false; }
-    for (int s = 0; s < d->n_stages; s++) {
-        if (r.decim_s[s] != d->stage_decim[s] || (int)r.staps[s].size() != d->stage_ntaps[s] || memcmp(r.staps[s].data(), d->stage_taps[s], r.staps[s].size() * sizeof(float)) != 0) { return false; }
+// The context's shared polyphase bank for a described chain (keyed by rds_bank_hash, one reference per branch): uploaded with its first user
+int rds_bank_acquire(sdrpp_ctx* c, Vfo::Rds& r) {
+    const RateChain& R = r.rate;
+    const unsigned long long key = rds_bank_hash(R.interp, R.decim, R.rtaps.data(), (int)R.rtaps.size());
+    auto it = c->rds_banks.find(key);
+    if (it != c->rds_banks.end() && (it->second.interp != R.interp || it->second.tpp != R.tpp || it->second.taps != R.rtaps)) {
+        return fail(c, SDRPP_ERR_UNSUPPORTED, "rds polyphase bank: two different descriptions under one key");  // (a 64-bit collision: never seen)
     }
-    if (has_poly && (r.interp != d->interp || r.decim != d->decim || (int)r.rtaps.size() != d->resamp_ntaps || memcmp(r.rtaps.data(), d->resamp_taps, r.rtaps.size() * sizeof(float)) != 0)) { return false; }
-    return true;
+    if (it == c->rds_banks.end()) {
+        sdrpp_ctx::RdsBank B;
+        const std::vector<float> bank = polyphase_bank(R.rtaps.data(), (int)R.rtaps.size(), R.interp, R.tpp);
+        if (int rc = upload(c, &B.d_bank, bank.data(), bank.size())) { return rc; }
+        B.interp = R.interp;
+        B.tpp = R.tpp;
+        B.taps = R.rtaps;
+        it = c->rds_banks.emplace(key, std::move(B)).first;
+    }
+    it->second.refs++;
+    r.bank_key = key;
+    return SDRPP_OK;
 }
-// sdrpp_vfo_set_rds on a VFO the caller has looked up (the stream is idle)
-int rds_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_rds_desc* d, bool enabled) {
+// sdrpp_vfo_set_rds on a VFO the caller has looked up (the stream is idle); d == nullptr: the branch goes.  The NCO increment (pd_re, pd_im) travels beside
+// the view and is part of the branch's identity: "the same branch" below means the same chain (rate_same) with the same increment in the same NCO mode.
+int rds_apply(sdrpp_ctx* c, Vfo& v, const RateDesc* d, float pd_re, float pd_im, bool enabled) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!d) {
         rds_detach(c, v);
         return SDRPP_OK;
     }
     if (v.d.demod != SDRPP_DEMOD_WFM) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the RDS branch needs a WFM VFO"); }
-    if (d->n_stages < 0 || d->n_stages > SDRPP_MAX_DECIM_STAGES) { return fail(c, SDRPP_ERR_INVALID, "rds n_stages %d", d->n_stages); }
-    for (int s = 0; s < d->n_stages; s++) {
-        if (!is_pow2(d->stage_decim[s]) || d->stage_ntaps[s] <= 0 || !d->stage_taps[s]) { return fail(c, SDRPP_ERR_UNSUPPORTED, "rds stage %d: decimation must be a power of two with taps", s); }
-    }
-    const bool has_poly = d->interp != d->decim;
-    if (has_poly && (d->interp <= 0 || d->decim <= 0 || d->resamp_ntaps <= 0 || !d->resamp_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad rds polyphase description"); }
+    if (int rc = rate_check_stages(c, *d, "rds ")) { return rc; }
+    if (int rc = rate_check_poly(c, *d, "rds ")) { return rc; }
     if (d->n_stages < 1 || d->stage_decim[0] < 2) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the RDS branch's first stage must decimate"); }
     int tile = 0, pitch = 0;
     if (!v.nco_exact && !rds_tile_geometry(d->stage_ntaps[0], d->stage_decim[0], &tile, &pitch)) {
         return fail(c, SDRPP_ERR_UNSUPPORTED, "rds first stage (decimation %d, %d taps): no tile of its window fits the kernel's LDS", d->stage_decim[0], d->stage_ntaps[0]);
     }
     Vfo::Rds& r = v.rds;
-    if (r.attached && r.exact == v.nco_exact && rds_same_desc(r, d)) {  // the same branch: only the switch
+    if (r.attached && r.exact == v.nco_exact && r.pd_re == pd_re && r.pd_im == pd_im && rate_same(r.rate, *d)) {  // the same branch: only the switch
         if (r.on && !enabled) {
             if (int rc = rds_freeze(c, v)) { return rc; }
             for (auto& s : r.st) { s.n = 0; }
@@ -700,73 +629,38 @@ int rds_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_rds_desc* d, bool enabled) {
         ~Undo() { if (armed) { rds_detach(c, v); } }
     } undo{ c, v };
     int rc;
+    RateChain& R = r.rate;
+    rate_describe(R, *d);
     r.exact = v.nco_exact;
-    r.pd_re = d->phase_delta_re;
-    r.pd_im = d->phase_delta_im;
-    r.theta = sdrpp_host::turnsPerSample(d->phase_delta_re, d->phase_delta_im);
-    r.n_stages = d->n_stages;
-    r.interp = has_poly ? d->interp : 1;
-    r.decim = has_poly ? d->decim : 1;
-    r.tpp = has_poly ? (d->resamp_ntaps + d->interp - 1) / d->interp : 0;
+    r.pd_re = pd_re;
+    r.pd_im = pd_im;
+    r.theta = sdrpp_host::turnsPerSample(pd_re, pd_im);
     r.tile = tile;
     r.pitch = pitch;
-    const Stream& feed0 = v.st[(size_t)v.i_chan];
-    size_t cap = feed0.cap;
-    auto add_stream = [&](int hist, size_t capn) -> int {
-        r.st.emplace_back();
-        return stream_alloc(c, r.st.back(), 2, hist, capn) ? -1 : (int)r.st.size() - 1;
-    };
-    auto need_of = [&](int stage) -> int {  // history the input of `stage` keeps (n_stages: the polyphase stage)
-        if (stage < r.n_stages) { return d->stage_ntaps[stage] - 1; }
-        return has_poly ? r.tpp - 1 : 0;
-    };
+    size_t cap = v.st[(size_t)v.i_chan].cap;
     r.st.reserve(SDRPP_MAX_DECIM_STAGES + 2);
     if (r.exact) {
-        if (add_stream(need_of(0), cap) < 0) { return SDRPP_ERR_NOMEM; }
+        r.st.emplace_back();
+        if (stream_alloc(c, r.st.back(), 2, R.need(0, 0), cap)) { return SDRPP_ERR_NOMEM; }
         if ((rc = dev_alloc(c, &r.d_rot, 1))) { return rc; }
         const float2 unit = make_float2(1.0f, 0.0f);  // frequency_xlator.h:21
         HIPCHK(c, hipMemcpy(r.d_rot, &unit, sizeof(unit), hipMemcpyHostToDevice));
     }
     r.i_stage0 = (int)r.st.size();
-    for (int s = 0; s < r.n_stages; s++) {
-        r.decim_s[s] = d->stage_decim[s];
-        r.staps[s].assign(d->stage_taps[s], d->stage_taps[s] + d->stage_ntaps[s]);
-        if (s == 0 && !r.exact) { rc = upload(c, &r.d_staps[0], r.staps[0].data(), r.staps[0].size()); }  // (the fused stage reads them in natural order)
-        else {
-            rc = upload_blocked(c, &r.d_staps[s], r.staps[s].data(), (int)r.staps[s].size(), r.decim_s[s], &r.s_kp[s]);
-            if (!rc) { rc = toep_build_fir(c, r.tp_stage[s], r.staps[s].data(), (int)r.staps[s].size(), r.decim_s[s]); }
-        }
-        if (rc) { return rc; }
-        cap = cap / (size_t)r.decim_s[s] + 2;
-        if (add_stream(need_of(s + 1), cap) < 0) { return SDRPP_ERR_NOMEM; }
+    RateForm form;  // stage 0 in closed form: the fused stage reads its taps in natural order; the bank is the context's, and 5000 phases have no matrix form
+    form.natural = r.exact ? 0u : 1u;
+    form.matrix = r.exact ? ~0u : ~1u;
+    form.poly_matrix = false;
+    if (R.has_poly()) {
+        if ((rc = rds_bank_acquire(c, r))) { return rc; }
+        form.bank = c->rds_banks[r.bank_key].d_bank;
     }
-    if (has_poly) {
-        r.rtaps.assign(d->resamp_taps, d->resamp_taps + d->resamp_ntaps);
-        const unsigned long long key = rds_bank_hash(d->interp, d->decim, d->resamp_taps, d->resamp_ntaps);
-        auto it = c->rds_banks.find(key);
-        if (it != c->rds_banks.end() && (it->second.interp != d->interp || it->second.tpp != r.tpp || it->second.taps != r.rtaps)) {
-            return fail(c, SDRPP_ERR_UNSUPPORTED, "rds polyphase bank: two different descriptions under one key");  // (a 64-bit collision: never seen)
-        }
-        if (it == c->rds_banks.end()) {
-            sdrpp_ctx::RdsBank B;
-            const std::vector<float> bank = polyphase_bank(r.rtaps.data(), d->resamp_ntaps, d->interp, r.tpp);
-            if ((rc = upload(c, &B.d_bank, bank.data(), bank.size()))) { return rc; }
-            B.interp = d->interp;
-            B.tpp = r.tpp;
-            B.taps = r.rtaps;
-            it = c->rds_banks.emplace(key, std::move(B)).first;
-        }
-        it->second.refs++;
-        r.bank_key = key;
-        r.d_bank = it->second.d_bank;
-        cap = cap * (size_t)r.interp / (size_t)r.decim + 4;
-        r.i_poly = add_stream(0, cap);
-        if (r.i_poly < 0) { return SDRPP_ERR_NOMEM; }
-    }
+    if ((rc = rate_build(c, R, form, r.st, cap, 0))) { return rc; }
+    if (R.has_poly()) { r.i_poly = (int)r.st.size() - 1; }
     r.i_last = (int)r.st.size() - 1;
     if (!r.exact) {
         // the streams the demodulator may read must remember the first stage's reach; the branch starts from a cleared delay line
-        const int K0 = d->stage_ntaps[0];
+        const int K0 = R.ntaps(0);
         if ((rc = stream_grow_hist(c, v.st[(size_t)v.i_chan], K0))) { return rc; }
         if ((rc = stream_grow_hist(c, chan_feed(v), K0))) { return rc; }
         if (v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base && (rc = stream_grow_hist(c, v.st[(size_t)v.i_ifc], K0))) { return rc; }
@@ -787,21 +681,8 @@ int rds_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_rds_desc* d, bool enabled) {
 int rds_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n) {
     if (!o.rds.attached) { return SDRPP_OK; }
     if (o.rds.exact != n.nco_exact) {  // the other NCO mode keeps its state in another form: the same description, attached to the new handle from cleared state
-        const Vfo::Rds& q = o.rds;
-        sdrpp_rds_desc d{};
-        d.phase_delta_re = q.pd_re;
-        d.phase_delta_im = q.pd_im;
-        d.n_stages = q.n_stages;
-        for (int s = 0; s < q.n_stages; s++) {
-            d.stage_decim[s] = q.decim_s[s];
-            d.stage_ntaps[s] = (int)q.staps[s].size();
-            d.stage_taps[s] = q.staps[s].data();
-        }
-        d.interp = q.interp;
-        d.decim = q.decim;
-        d.resamp_ntaps = (int)q.rtaps.size();
-        d.resamp_taps = q.rtaps.empty() ? nullptr : q.rtaps.data();
-        return rds_apply(c, n, &d, q.on);
+        const RateDesc d = rate_desc(o.rds.rate);
+        return rds_apply(c, n, &d, o.rds.pd_re, o.rds.pd_im, o.rds.on);
     }
     if (int rc = rds_freeze(c, o)) { return rc; }
     n.rds = std::move(o.rds);
@@ -809,7 +690,7 @@ int rds_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n) {
     n.rds.ran = false;
     for (auto& s : n.rds.st) { s.n = 0; }
     if (!n.rds.exact) {
-        const int K0 = (int)n.rds.staps[0].size();
+        const int K0 = n.rds.rate.ntaps(0);
         int rc;
         if ((rc = stream_grow_hist(c, n.st[(size_t)n.i_chan], K0))) { return rc; }
         if ((rc = stream_grow_hist(c, chan_feed(n), K0))) { return rc; }

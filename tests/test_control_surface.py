@@ -264,3 +264,140 @@ def test_preproc_packed_read_converts_what_the_float_read_returns(backend):
         assert got.dtype == dt and got.shape == want.shape and np.array_equal(got, want), (pcm_type, scale)
         assert np.array_equal(ctx.preproc_read_pcm(pcm_type, scale, 1000), want[:1000])
     ctx.close()
+
+
+ERR_UNSUPPORTED = -5      # SDRPP_ERR_UNSUPPORTED
+MAX_DECIM_STAGES = 4      # SDRPP_MAX_DECIM_STAGES
+B_SMALL = 4000            # 100 IF samples at 250 kS/s behind the resampler, 125 in front of it
+
+
+def _clone(d):
+    c = type(d)()
+    C.memmove(C.byref(c), C.byref(d), C.sizeof(d))
+    return c
+
+
+def _stage_faults(n_stages):
+    """(what, code, edit of a description's stage fields, the stage the message names or None): one fault each, in the last stage"""
+    s = n_stages - 1
+    return [
+        ("n_stages -1", ERR_INVALID, lambda d: setattr(d, "n_stages", -1), None),
+        ("n_stages max + 1", ERR_INVALID, lambda d: setattr(d, "n_stages", MAX_DECIM_STAGES + 1), None),
+        ("decimation 3", ERR_UNSUPPORTED, lambda d: d.stage_decim.__setitem__(s, 3), s),
+        ("no taps", ERR_UNSUPPORTED, lambda d: d.stage_ntaps.__setitem__(s, 0), s),
+        ("null taps", ERR_UNSUPPORTED, lambda d: d.stage_taps.__setitem__(s, fp()), s),
+    ]
+
+
+def _poly_faults():
+    return [
+        ("resamp_ntaps 0", lambda d: setattr(d, "resamp_ntaps", 0)),
+        ("resamp_taps null", lambda d: setattr(d, "resamp_taps", fp())),
+        ("interp 0", lambda d: setattr(d, "interp", 0)),
+    ]
+
+
+def _through(n, decims):
+    """outputs of power-of-two decimators that start at sample 0"""
+    for D in decims:
+        n = (n + D - 1) // D
+    return n
+
+
+def test_description_faults_name_their_chain(backend):
+    """A decimator + resampler description with exactly one fault, at each of the four entry points that take one: the code, the chain's prefix and the stage
+    in the message, and what the rejected call leaves behind — no VFO more, no AF chain (sdrpp_vfo_set_af detaches before it looks), the old RDS branch and the
+    old pre-processing chain as they were (compared bit for bit with a twin that saw no rejected call)."""
+    from sdrplusplus_amd import capi, radio
+
+    ctx = capi.Context(0, max_push=B_SMALL)
+    L, h = ctx.L, ctx.h
+    vd, vkeep = radio.vfo_desc(SR, 250e3, 150e3, 0.9e6, "WFM")
+    ad, akeep = radio.af_desc(250e3, 48000.0, 50e-6, False)
+    rd, rkeep = radio.rds_desc(250e3)
+    for d in (vd, ad, rd):
+        assert d.n_stages >= 2 and d.interp != d.decim and d.resamp_ntaps > 0
+    twins = [ctx.vfo_add(vd, vkeep) for _ in range(2)]  # the same VFO twice: every rejected call below goes to the first
+    a, b = twins
+    for v in twins:
+        ctx.vfo_set_af(v, ad, akeep)
+        ctx.vfo_set_rds(v, rd, True, rkeep)
+    nid = C.c_int()
+    entry = {
+        "": lambda d: L.sdrpp_vfo_add(h, C.byref(d), C.byref(nid)),
+        "af ": lambda d: L.sdrpp_vfo_set_af(h, a, C.byref(d)),
+        "rds ": lambda d: L.sdrpp_vfo_set_rds(h, a, C.byref(d), 1),
+    }
+    for prefix, good in (("", vd), ("af ", ad), ("rds ", rd)):
+        faults = [(w, code, e, (prefix + "n_stages %d" % (-1 if "-1" in w else MAX_DECIM_STAGES + 1)) if s is None else prefix + "stage %d:" % s)
+                  for w, code, e, s in _stage_faults(good.n_stages)]
+        faults += [(w, ERR_INVALID, e, "bad %spolyphase description" % prefix) for w, e in _poly_faults()]
+        for what, code, edit, text in faults:
+            bad = _clone(good)
+            edit(bad)
+            rc = entry[prefix](bad)
+            _fails(ctx, rc, code, text)
+            if not text.startswith("bad "):  # the message begins with the prefix (the front end's, which has none, with the text itself)
+                assert L.sdrpp_last_error(h).decode().startswith(text), (prefix, what, L.sdrpp_last_error(h).decode())
+            assert ctx.vfo_count() == 2, (prefix, what)
+            if prefix == "af ":  # the chain the VFO had is gone; the next fault meets a VFO with a chain again
+                assert L.sdrpp_vfo_af_count(h, a) == ERR_INVALID, what
+                ctx.vfo_set_af(a, ad, akeep)
+            if prefix == "rds ":
+                assert L.sdrpp_vfo_rds_count(h, a) >= 0, what
+    ctx.push(_signal(B_SMALL, (0.9e6,), 7))
+    ra, rb = ctx.vfo_rds_read(a), ctx.vfo_rds_read(b)
+    n_rds = -(-_through(100, list(rd.stage_decim)[:rd.n_stages]) * rd.interp // rd.decim)  # 100 IF samples through the decimators, then the resampler from phase 0
+    assert len(ra) == n_rds > 0 and _same(_pairs(ra), _pairs(rb)) and np.any(ra != 0)
+    assert ctx.vfo_af_count(a) == ctx.vfo_af_count(b) > 0 and _same(ctx.vfo_af_read(a), ctx.vfo_af_read(b))
+    ctx.close()
+
+    # the pre-processing chain: arrays, no polyphase part; its n_stages range check has no message
+    stages = radio.plans().stages(4)
+    assert len(stages) >= 2
+    arrs = [np.ascontiguousarray(t, np.float32) for _, t in stages]
+
+    class Pre:  # the call's three arrays under the descriptions' field names
+        def __init__(self):
+            self.n_stages = len(stages)
+            self.stage_decim = (C.c_int * (MAX_DECIM_STAGES + 1))(*[int(d) for d, _ in stages])
+            self.stage_ntaps = (C.c_int * (MAX_DECIM_STAGES + 1))(*[len(t) for t in arrs])
+            self.stage_taps = (fp * (MAX_DECIM_STAGES + 1))(*[t.ctypes.data_as(fp) for t in arrs])
+
+    pair = [capi.Context(0, max_push=B_SMALL) for _ in range(2)]
+    x = _signal(2 * B_SMALL, (0.9e6,), 8)
+    for p in pair:
+        p.preproc_configure(stages, 50.0 / (SR / 4), True)
+        p.push(x[:B_SMALL])
+    p0 = pair[0]
+    for what, code, edit, s in _stage_faults(len(stages)):
+        bad = Pre()
+        edit(bad)
+        rc = p0.L.sdrpp_preproc_configure(p0.h, bad.n_stages, bad.stage_decim, bad.stage_ntaps, bad.stage_taps, 0.0, 0)
+        if s is None:
+            assert rc == code, (what, rc)
+        else:
+            _fails(p0, rc, code, "pre-processing stage %d:" % s)
+    for p in pair:
+        p.push(x[B_SMALL:])
+    za, zb = pair[0].preproc_read(), pair[1].preproc_read()
+    assert len(za) == B_SMALL // 4 and _same(_pairs(za), _pairs(zb)) and np.any(za != 0)
+    for p in pair:
+        p.close()
+
+    # interp == decim and no resampler taps: accepted, and the chain ends behind its decimators
+    ctx = capi.Context(0, max_push=B_SMALL)
+    flat = []
+    for good in (vd, ad, rd):
+        d = _clone(good)
+        d.interp, d.decim, d.resamp_ntaps, d.resamp_taps = 5, 5, 0, fp()
+        flat.append(d)
+    v = ctx.vfo_add(flat[0], vkeep)
+    ctx.vfo_set_af(v, flat[1], akeep)
+    ctx.vfo_set_rds(v, flat[2], True, rkeep)
+    ctx.push(_signal(B_SMALL, (0.9e6,), 9))
+    n_if = _through(B_SMALL, list(vd.stage_decim)[:vd.n_stages])
+    assert n_if == 125 and ctx.vfo_out_count(v) == n_if
+    assert ctx.vfo_af_count(v) == _through(n_if, list(ad.stage_decim)[:ad.n_stages])
+    assert ctx.vfo_rds_count(v) == _through(n_if, list(rd.stage_decim)[:rd.n_stages])
+    ctx.close()
