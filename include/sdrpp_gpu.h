@@ -161,7 +161,10 @@ enum sdrpp_demod_mode {
     SDRPP_DEMOD_AM = 2,   /* dsp::demod::AM<stereo_t> (am.h:101-133)                                                 */
     SDRPP_DEMOD_USB = 3,  /* dsp::demod::SSB<stereo_t> (ssb.h:77-92)                                                 */
     SDRPP_DEMOD_LSB = 4,
-    SDRPP_DEMOD_DSB = 5
+    SDRPP_DEMOD_DSB = 5,
+    SDRPP_DEMOD_CW = 6    /* dsp::demod::CW<stereo_t> (cw.h:17-29, 57-68): statement for statement SSB(USB, bandwidth = 2 * tone) — one translation by
+                           * `tone`, ComplexToReal, loop::AGC, MonoToStereo (ssb.h:23-35, 77-92, 106-108).  The tone's increment travels in
+                           * ssb_phase_delta_re/im: sdrpp_design_phase_delta(tone, if_rate).  The radio module runs it at 3 kS/s (demodulators/cw.h:82). */
 };
 
 typedef struct sdrpp_vfo_desc {
@@ -184,11 +187,11 @@ typedef struct sdrpp_vfo_desc {
     float inv_deviation;      /* Quadrature::_invDeviation = 1/hzToRads(deviation, if_rate) (quadrature.h:19-26)         */
     int audio_ntaps;          /* WFM alFir / NFM fir / AM lpf real taps; 0 = filter bypassed (fm.h:88, broadcast_fm.h:205) */
     const float* audio_taps;
-    /* loop::AGC (agc.h:15-27), used by AM (audio or carrier AGC) and SSB */
+    /* loop::AGC (agc.h:15-27), used by AM (audio or carrier AGC), SSB and CW */
     float agc_set_point, agc_attack, agc_decay, agc_max_gain, agc_max_output_amp, agc_init_gain;
     int am_carrier_agc;       /* AM: 1 = AGCMode::CARRIER, 0 = AGCMode::AUDIO (am.h:14-17)                               */
     float dc_block_rate;      /* AM: DCBlocker rate (am.h:32 -> dc_blocker.h:54-60)                                       */
-    float ssb_phase_delta_re, ssb_phase_delta_im; /* SSB second xlator (ssb.h:24,106-117)                                */
+    float ssb_phase_delta_re, ssb_phase_delta_im; /* SSB second xlator (ssb.h:24,106-117); CW: the tone's (cw.h:20,28)     */
     /* NCO of THIS VFO: 0 = the context's mode (sdrpp_set_nco_mode), 1 = closed form, 2 = the reference's float rotator recursion.
      * FM and AM do not see the difference (no output depends on the absolute phase); a product detector (SSB) and the raw IF follow
      * the reference's own rounding drift only with the recursion, which costs a sequential pass over the full-rate stream — so a bank
@@ -208,8 +211,9 @@ int sdrpp_vfo_count(sdrpp_ctx* ctx);
  *             The decimator stages and the polyphase resampler start from cleared state, as the reference re-creates / resets them
  *             (power_decimator.h:91-108, polyphase_resampler.h:38-67).
  *   keep & 2: the demodulator behind it lives on (setInSamplerate: the radio's demodulator block is not touched): discriminator and audio low-pass
- *             history, AGC / DC-blocker state, SSB's second translation.  Only where the new description has the same demodulator; a demodulator
- *             SWITCH creates a new demodulator object in the reference too: leave the bit off.
+ *             history, AGC / DC-blocker state, SSB's second translation (CW -> CW: the tone translation's phase).  Only where the new description has
+ *             the same demodulator; a demodulator SWITCH creates a new demodulator object in the reference too: leave the bit off.  The AGC's amplitude
+ *             estimate lives on while its attack / decay follow the NEW description (AGC::setAttack / setDecay, agc.h:31-43, swap the coefficients only).
  *   keep & 4: the IF chain (sdrpp_vfo_set_if, sdrpp_vfo_set_fmnr) moves to the new handle with its parameters, the blanker's amplitude estimate and FMIF's delay line: the radio module's
  *             IF-chain blocks are not the demodulator's and outlive a demodulator switch (radio_module.h:84-96).  Without the bit the new handle has no chain.
  * An AF chain (sdrpp_vfo_set_af) is not carried over: attach it to the new handle (it starts cleared, as afChain's blocks do after a restart). */
@@ -217,9 +221,11 @@ int sdrpp_vfo_replace(sdrpp_ctx* ctx, int old_id, const sdrpp_vfo_desc* desc, in
 /* RxVFO::setOffset (rx_vfo.h:72-77): only phaseDelta changes, phase stays continuous; the samples already inside the first
  * decimator's delay line keep their old rotation (the first outputs after the change are handed over sample-exactly). */
 int sdrpp_vfo_set_phase_delta(sdrpp_ctx* ctx, int id, float re, float im);
-/* SSB::setBandwidth / setMode (ssb.h:44-62, 106-117): the second translation's increment follows bandwidth / 2; phase continuous. */
+/* SSB::setBandwidth / setMode (ssb.h:44-62, 106-117): the second translation's increment follows bandwidth / 2; phase continuous.
+ * CW::setTone (dsp/demod/cw.h:31-36) is the same call with sdrpp_design_phase_delta(tone, if_rate): FrequencyXlator::setOffset, phase continuous. */
 int sdrpp_vfo_set_ssb_phase_delta(sdrpp_ctx* ctx, int id, float re, float im);
-/* RxVFO::setBandwidth (rx_vfo.h:60-70): swap the channel-filter taps, history kept (fir.h:31-52). n = 0 bypasses. */
+/* RxVFO::setBandwidth (rx_vfo.h:60-70): swap the channel-filter taps, history kept (fir.h:31-52). n = 0 bypasses.  The delay line is sized from the
+ * tap count (CW's 50 Hz channel at 3 kS/s has 4 560 taps); more than 65 536 taps are refused (SDRPP_ERR_UNSUPPORTED), here and in sdrpp_vfo_add. */
 int sdrpp_vfo_set_channel_taps(sdrpp_ctx* ctx, int id, const float* taps, int n);
 /* RxVFO::reset + demod reset: clears histories, NCO phase and loop states. */
 int sdrpp_vfo_reset(sdrpp_ctx* ctx, int id);

@@ -18,7 +18,7 @@ DEFAULT_LIB = os.path.join(_HERE, "csrc", "libsdrpp_gpu.so")
 MAX_DECIM_STAGES = 4
 NUM_KERNEL_FAMILIES = 13  # SDRPP_NUM_KERNEL_FAMILIES (checked against the header in tests/test_capi_host.py)
 
-DEMOD_RAW, DEMOD_WFM, DEMOD_NFM, DEMOD_AM, DEMOD_USB, DEMOD_LSB, DEMOD_DSB = -1, 0, 1, 2, 3, 4, 5
+DEMOD_RAW, DEMOD_WFM, DEMOD_NFM, DEMOD_AM, DEMOD_USB, DEMOD_LSB, DEMOD_DSB, DEMOD_CW = -1, 0, 1, 2, 3, 4, 5, 6
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)

@@ -12,7 +12,7 @@ constexpr int kResSlots = SDRPP_RESULT_SLOTS;       // pipelined mode: page-lock
 constexpr int kGroupMax = SDRPP_GROUP_MAX;          // pipelined mode: blocks one launch may carry
 constexpr int kResMeta = kResSlots * kGroupMax;     // ... and what the host knows about every block of those groups (ring by ticket)
 constexpr int kStageSlots = 4;      // pipelined mode: page-locked staging buffers for pushes from pageable host memory
-constexpr int kChanHistCap = 4095;  // channel filter may be re-designed up to 4096 taps without reallocating (rx_vfo.h:60-70)
+constexpr int kChanMaxTaps = 65536;  // channel filter (rx_vfo.h:60-70): a sanity bound only — its delay line is sized from the tap count and grown by sdrpp_vfo_set_channel_taps (CW: lowPass(25, 2.5, 3000) has 4 560 taps)
 constexpr int kAfHpfMaxTaps = 65536;  // AF high-pass (sdrpp_vfo_set_af): a sanity bound only, its history is sized from the tap count (include/sdrpp_gpu.h)
 constexpr int kFmifTile = SDRPP_FMIF_TILE;       // FMIF: outputs per matrix tile = the largest bin count (radio_module.h:31-36); its input stream remembers kFmifTile - 1 samples
 constexpr int kFmifSeg = SDRPP_FMIF_SEG;       // ... and samples per segment job (one wavefront each): the cut depends on the block alone, never on the launch shape

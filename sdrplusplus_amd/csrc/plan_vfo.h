@@ -246,7 +246,7 @@ struct BankPlan {
     F2Launch f2l[4];
     FCMLaunch fcm[3];  // PF 6 / 10 / 16
     FCMLaunch fcl;     // long first stages (vfo_frontcl_kernel)
-    int fcl_nw = 2;    // tile engines per workgroup of that launch: 4 as a role of a tick when four wavefronts' planes fit half a CU's LDS
+    int fcl_nw = 2;    // tile engines per workgroup of that launch: 4 as a role of a tick when four wavefronts' planes fit half a CU's LDS, 1 where two engines' exceed a workgroup's
     const int vts[4] = { 8, 4, 2, 1 };
     // device addresses of the job tables (upload)
     Stage1Job* d_s1[4] = {};
@@ -416,7 +416,7 @@ struct BankPlan {
         for (auto& s : v.st) { s.clevel = 0; s.wlevel = 0; }
         for (auto& s : v.rds.st) { s.clevel = 0; s.wlevel = 0; }
         x.at.cur->wlevel = x.at.lvl;
-        const bool agc_mode = v.d.demod == SDRPP_DEMOD_AM || (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_DSB);
+        const bool agc_mode = v.d.demod == SDRPP_DEMOD_AM || (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_CW);
         x.ifc_on = v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base;
         const bool need_bnd = (agc_mode && (blocks || v.nco_exact)) || (x.ifc_on && v.ifc.sq_on && blocks) || (v.rds.on && v.rds.exact && blocks);
         if (need_bnd) { x.bnd = fb; }
@@ -458,7 +458,7 @@ struct BankPlan {
         const ChainCursor feed = x.at;  // the stream the demodulator reads
         if (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) { demod_fm(x); }
         else if (v.d.demod == SDRPP_DEMOD_AM) { demod_am(x); }
-        else if (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_DSB) { demod_ssb(x); }
+        else if (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_CW) { demod_ssb(x); }
         if (v.af.on && v.i_out >= 0) { af_chain(x); }
         int last_lvl = x.at.lvl;
         v.rds.ran = v.rds.on;
@@ -1045,6 +1045,18 @@ struct BankPlan {
                 if (!m.fused && m.lgD >= 5 && m.K >= 9 && (size_t)frontcl_lds_floats(m.K, m.lgD, 4) * 4 > (size_t)(160 * 1024 / 2)) { fcl_nw = 2; }
             }
         }
+        // A long first stage whose TWO engines' planes exceed a workgroup's LDS while one engine's fit (plan 8192's /128 stage of 726 taps: 77 056 B
+        // against 38 656 B) runs with one tile engine per workgroup, and the launch with it: a launch has one engine count (aux).  Only where
+        // such a stage has a job to fill (two VFOs of one geometry): a launch without one keeps the count it had.
+        auto one_engine_only = [](const S1Member& m) {
+            return !m.fused && m.lgD >= 5 && m.K >= 9 && (size_t)frontcl_lds_floats(m.K, m.lgD, 2) * 4 > (size_t)kMaxLds && (size_t)frontcl_lds_floats(m.K, m.lgD, 1) * 4 <= (size_t)kMaxLds;
+        };
+        for (size_t a = 0; a < s1.size();) {
+            size_t b = a;
+            while (b < s1.size() && same(s1[b], s1[a])) { b++; }
+            if (b - a >= 2 && one_engine_only(s1[a])) { fcl_nw = 1; }
+            a = b;
+        }
         size_t i = 0;
         while (i < s1.size()) {
             size_t j = i;
@@ -1054,7 +1066,7 @@ struct BankPlan {
             int m_pf = 0;
             const bool m_fused = s1[i].fused && frontcm_ok(s1[i].K, s1[i].lgD, s1[i].K2, s1[i].lgD2, &m_pf);
             // ... or a long first stage on its own (decimation >= 32: no fusion, vfo_frontcl_kernel)
-            const bool m_long = !m_fused && !s1[i].fused && s1[i].lgD >= 5 && s1[i].K >= 9 && (size_t)frontcl_lds_floats(s1[i].K, s1[i].lgD) * 4 <= (size_t)kMaxLds;
+            const bool m_long = !m_fused && !s1[i].fused && s1[i].lgD >= 5 && s1[i].K >= 9 && (size_t)frontcl_lds_floats(s1[i].K, s1[i].lgD, fcl_nw == 1 ? 1 : 2) * 4 <= (size_t)kMaxLds;
             const bool m_ok = m_fused || m_long;
             // worth it from 17 VFOs against the fused VALU kernel (8 VFOs per work-item); a long first stage has no good VALU form (its
             // per-VFO windows do not fit LDS), there the matrix kernel pays off from 2 VFOs on

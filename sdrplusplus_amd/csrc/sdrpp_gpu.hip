@@ -802,7 +802,8 @@ int sdrpp_vfo_set_phase_delta(sdrpp_ctx* c, int id, float re, float im) {
 
 int sdrpp_vfo_set_channel_taps(sdrpp_ctx* c, int id, const float* taps, int n) {
     DeviceScope dev_scope_(c);
-    if (!c || n < 0 || n > kChanHistCap + 1 || (n > 0 && !taps)) { return SDRPP_ERR_INVALID; }
+    if (!c || n < 0 || (n > 0 && !taps)) { return SDRPP_ERR_INVALID; }
+    if (n > kChanMaxTaps) { return fail(c, SDRPP_ERR_UNSUPPORTED, "channel filter of %d taps (max %d)", n, kChanMaxTaps); }
     FLUSH_PENDING(c);
     LOOKUP_VFO(v, c, id);
     return vfo_set_chan_taps(c, *v, taps, n);
@@ -1101,7 +1102,7 @@ int sdrpp_vfo_set_ssb_phase_delta(sdrpp_ctx* c, int id, float re, float im) {
     if (!c) { return SDRPP_ERR_INVALID; }
     FLUSH_PENDING(c);
     LOOKUP_VFO(v, c, id);
-    if (v->d.demod < SDRPP_DEMOD_USB) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no SSB demodulator", id); }
+    if (v->d.demod < SDRPP_DEMOD_USB) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no SSB demodulator", id); }  // (USB, LSB, DSB; CW: the tone)
     v->d.ssb_phase_delta_re = re;
     v->d.ssb_phase_delta_im = im;
     v->theta2 = sdrpp_host::turnsPerSample(re, im);  // the translation is sample-wise: nothing to hand over, the phase stays continuous

@@ -83,8 +83,8 @@ int vfo_build(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
         }
     }
     if (int rc = rate_check_poly(c, rd, "")) { return rc; }
-    if (d->chan_ntaps < 0 || d->chan_ntaps > kChanHistCap + 1) { return fail(c, SDRPP_ERR_UNSUPPORTED, "channel filter of %d taps (max %d)", d->chan_ntaps, kChanHistCap + 1); }
-    if (d->demod < SDRPP_DEMOD_RAW || d->demod > SDRPP_DEMOD_DSB) { return fail(c, SDRPP_ERR_INVALID, "demod %d", d->demod); }
+    if (d->chan_ntaps < 0 || d->chan_ntaps > kChanMaxTaps) { return fail(c, SDRPP_ERR_UNSUPPORTED, "channel filter of %d taps (max %d)", d->chan_ntaps, kChanMaxTaps); }
+    if (d->demod < SDRPP_DEMOD_RAW || d->demod > SDRPP_DEMOD_CW) { return fail(c, SDRPP_ERR_INVALID, "demod %d", d->demod); }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // every early return below gives the device allocations made so far back (vfo_free); only a fully built VFO is handed to the context
     struct VfoFreer {
@@ -214,7 +214,7 @@ int vfo_build(sdrpp_ctx* c, const sdrpp_vfo_desc* d, int* id) {
                 if (v->i_dem < 0) { return SDRPP_ERR_NOMEM; }
             }
         }
-        if (d->demod >= SDRPP_DEMOD_USB) {  // SSB: real scratch between the parallel translation and the sequential AGC
+        if (d->demod >= SDRPP_DEMOD_USB) {  // SSB family (CW is SSB with the tone as its translation): real scratch between the parallel translation and the sequential AGC
             v->i_dem = add_stream(1, 0, cap);
             if (v->i_dem < 0) { return SDRPP_ERR_NOMEM; }
         }
@@ -392,7 +392,21 @@ int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
             rc = hist_tail_copy(c, n.st[(size_t)n.i_dem], o.st[(size_t)o.i_dem], 1 << 30);
             if (rc) { return rc; }
         }
-        if (o.d_state && n.d_state) { HIPCHK(c, hipMemcpy(n.d_state, o.d_state, 2 * sizeof(AgcState) + sizeof(float), hipMemcpyDeviceToDevice)); }
+        if (o.d_state && n.d_state) {
+            // the loops' states live on; their attack / decay are the NEW description's (AGC::setAttack / setDecay swap the coefficients only, agc.h:31-43)
+            char blob[2 * sizeof(AgcState) + sizeof(float)];
+            HIPCHK(c, hipMemcpy(blob, o.d_state, sizeof(blob), hipMemcpyDeviceToHost));
+            AgcState st[2];
+            memcpy(st, blob, sizeof(st));
+            for (int i = 0; i < 2; i++) {
+                st[i].attack = n.d.agc_attack;
+                st[i].inv_attack = 1.0f - n.d.agc_attack;
+                st[i].decay = n.d.agc_decay;
+                st[i].inv_decay = 1.0f - n.d.agc_decay;
+            }
+            memcpy(blob, st, sizeof(st));
+            HIPCHK(c, hipMemcpy(n.d_state, blob, sizeof(blob), hipMemcpyHostToDevice));
+        }
         n.phi2 = o.phi2;
         if (o.d_rot && n.d_rot) { HIPCHK(c, hipMemcpy(n.d_rot + 1, o.d_rot + 1, sizeof(float2), hipMemcpyDeviceToDevice)); }
     }
@@ -479,7 +493,7 @@ int af_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_af_desc* af) {
     if (int rc = rate_check_stages(c, rd, "af ")) { return rc; }
     if (int rc = rate_check_poly(c, rd, "af ")) { return rc; }
     if (af->hpf_ntaps < 0 || (af->hpf_ntaps > 0 && !af->hpf_taps)) { return fail(c, SDRPP_ERR_INVALID, "bad af high-pass description"); }
-    // (no kChanHistCap here: that is the channel filter's pre-allocated history; the high-pass's input stream gets its history from the tap count below, and a
+    // (the high-pass's input stream gets its history from the tap count below, and a
     // filter too long for the matrix form and for an LDS tile of the register-blocked one runs untiled — highPass(300, 100) has 7 296 taps at 192 kHz)
     if (af->hpf_ntaps > kAfHpfMaxTaps) { return fail(c, SDRPP_ERR_UNSUPPORTED, "af high-pass of %d taps (max %d)", af->hpf_ntaps, kAfHpfMaxTaps); }
     Vfo::Af& a = v.af;

@@ -41,7 +41,7 @@ __device__ __forceinline__ void vfo_demod_pre_body(const KIdx bid, const KIdx gd
 __global__ __launch_bounds__(256) void vfo_demod_pre_kernel(const PreJob* __restrict__ jobs) { vfo_demod_pre_body(kidx(blockIdx), kidx(gridDim), jobs); }
 
 struct SeqJob {
-    int mode;  // 2 AM, 3/4/5 SSB family
+    int mode;  // 2 AM, 3/4/5 SSB family, 6 CW (the SSB arithmetic with the tone as its translation)
     int n;
     const float2* in;  // complex IF samples of this push (AM carrier-AGC mode only)
     float* pre;        // real samples from vfo_demod_pre_kernel; AM overwrites them in place with the low-pass input

@@ -579,6 +579,8 @@ __global__ __launch_bounds__(256) void vfo_frontcm16_kernel(IqSrc src, const Fro
 // shape: 2 wavefronts per block (a wavefront's two IQ planes are ~20 KB), the IQ window goes straight from global memory to the
 // planes (no register staging: it would need ~70 VGPRs), and the tap operand — up to 363 pairs x 64 lanes — streams from
 // global memory / L2 through a four-deep register ring instead of living in LDS.
+// Plan 8192's first stage (/128, 726 taps: CW's 3 kS/s in a 24.576 or 61.44 MS/s capture) has a window of 4 694 samples: two engines' planes are
+// 77 056 B, more than a workgroup gets, ONE engine's are 38 656 B — that stage runs with nw = 1 (plan_vfo.h: group_front), same tiles, same sums.
 __host__ __device__ inline int frontcl_lds_floats(int K, int lgD, int nw = 2) {
     const int nsamp = (SDRPP_FCM_TILE - 1) * (1 << lgD) + K;
     return nw * 2 * frontcm_plane(nsamp, lgD) + nw * SDRPP_FCM_VT * 2 + SDRPP_FCM_VT * 2;  // nw waves x 2 planes + tile phasors + pointers
@@ -590,7 +592,8 @@ __host__ __device__ inline int frontcl_lds_floats(int K, int lgD, int nw = 2) {
 // outputs per tile, the instruction's k = 0 .. 3 (lanes 16 kq .. 16 kq + 15) are FOUR consecutive tap pairs, each lane owning the pair 4 Q + kq of
 // output n = lane & 15.  Same pair-per-lane operands, same table, half the matrix cycles of a 32-row tile that would be two thirds empty.
 template <int PF, bool NARROW>
-// nw: tile engines (wavefronts) per workgroup — 2 for a launch of its own (128 work-items); as a role of the tick kernel, whose workgroups are
+// nw: tile engines (wavefronts) per workgroup — 2 for a launch of its own (128 work-items), 1 (64 work-items) where two engines' planes exceed a workgroup's
+// LDS; as a role of the tick kernel, whose workgroups are
 // 256 wide, 4 when four wavefronts' planes fit half a CU's LDS (the build of the tick kernel that holds this role runs two workgroups per CU:
 // with two engines each only ONE wavefront per SIMD was at work, and the long first stages were three quarters of cfg 4's tick).
 __device__ __forceinline__ void vfo_frontcl_impl(const KIdx bid, float* smemf, const IqSrc& src, const FrontCMJob* __restrict__ jobs, int nw) {
@@ -772,9 +775,9 @@ __device__ __forceinline__ void vfo_frontcl_body(const KIdx bid, float* smemf, c
     else { vfo_frontcl_impl<PF, false>(bid, smemf, src, jobs, nw); }
 }
 template <int PF>
-__global__ __launch_bounds__(128, 2) void vfo_frontcl_kernel(IqSrc src, const FrontCMJob* __restrict__ jobs) {
+__global__ __launch_bounds__(128, 2) void vfo_frontcl_kernel(IqSrc src, const FrontCMJob* __restrict__ jobs, int nw) {
     HIP_DYNAMIC_SHARED(float, smemf)
-    vfo_frontcl_body<PF>(kidx(blockIdx), smemf, src, jobs);
+    vfo_frontcl_body<PF>(kidx(blockIdx), smemf, src, jobs, nw);
 }
 
 }  // namespace sdrpp_k

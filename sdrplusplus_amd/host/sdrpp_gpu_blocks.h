@@ -103,7 +103,7 @@ public:
     }
 };
 
-enum class Demod { RAW = SDRPP_DEMOD_RAW, WFM = SDRPP_DEMOD_WFM, NFM = SDRPP_DEMOD_NFM, AM = SDRPP_DEMOD_AM, USB = SDRPP_DEMOD_USB, LSB = SDRPP_DEMOD_LSB, DSB = SDRPP_DEMOD_DSB };
+enum class Demod { RAW = SDRPP_DEMOD_RAW, WFM = SDRPP_DEMOD_WFM, NFM = SDRPP_DEMOD_NFM, AM = SDRPP_DEMOD_AM, USB = SDRPP_DEMOD_USB, LSB = SDRPP_DEMOD_LSB, DSB = SDRPP_DEMOD_DSB, CW = SDRPP_DEMOD_CW };
 
 class IQFrontEnd;
 
@@ -125,6 +125,9 @@ public:
     // demod::Demodulator::setBandwidth of the fused demodulator (FM deviation = bw / 2, NFM / AM audio low-pass, SSB's second
     // translation: fm.h:47-58, am.h:62-72, ssb.h:44-62); RxVFO::setBandwidth stays the channel filter only, as in the reference
     void setDemodBandwidth(double bandwidth);
+    // dsp::demod::CW::setTone (dsp/demod/cw.h:31-36) of a fused CW demodulator: the translation's increment follows the tone, its phase stays continuous
+    // (sdrpp_vfo_set_ssb_phase_delta) — no restart.  Before a CW demodulator is attached it only sets the tone that demodulator will start with.
+    void setCWTone(double tone);
     // The radio module's AF chain behind the demodulator (radio_module.h:98-110, 540-547): RationalResampler<stereo_t> to
     // `audioSamplerate`, optional highPass(300, 100) FIR, optional Deemphasis(tau) (tau <= 0: off).  With the chain attached `audio`
     // carries its output (what afChain.out hands to the sink stream); afRate = the demodulator's getAFSampleRate() (= IF rate for
@@ -174,6 +177,7 @@ public:
 
     double inSamplerate = 0, outSamplerate = 0, bandwidth = 0, offset = 0;
     double demodBandwidth = 0;  // 0: follows `bandwidth`
+    double cwTone = 800.0;      // demodulators/cw.h:107
     Demod demod = Demod::RAW;
     bool lowPass = true, carrierAgc = false;
     double agcAttack = 50.0, agcDecay = 5.0;
@@ -1430,6 +1434,9 @@ private:
             const double tr = v.demod == Demod::USB ? dbw / 2.0 : (v.demod == Demod::LSB ? -dbw / 2.0 : 0.0);
             sdrpp_design_phase_delta(tr, v.outSamplerate, &d.ssb_phase_delta_re, &d.ssb_phase_delta_im);
         }
+        else if (v.demod == Demod::CW) {  // dsp/demod/cw.h:20: the tone alone — the demodulator's bandwidth plays no part (demodulators/cw.h:73)
+            sdrpp_design_phase_delta(v.cwTone, v.outSamplerate, &d.ssb_phase_delta_re, &d.ssb_phase_delta_im);
+        }
         // (keep | 4: the IF chain and the blanker's amplitude estimate move to the new handle — the radio module's IF-chain blocks outlive every re-plan)
         int rc = oldId >= 0 ? sdrpp_vfo_replace(ctx, oldId, &d, keep | 4, &v.id) : sdrpp_vfo_add(ctx, &d, &v.id);
         if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_add: ") + sdrpp_last_error(ctx)); }
@@ -1746,10 +1753,20 @@ inline void RxVFO::setDemodBandwidth(double bw) {
         fe->control([f, self, re, im]() { sdrpp_vfo_set_ssb_phase_delta(f->ctx, self->id, re, im); });
         return;
     }
-    if (demod == Demod::DSB) { return; }
+    if (demod == Demod::DSB || demod == Demod::CW) { return; }  // (CW::setBandwidth is empty, demodulators/cw.h:73: the tone stays)
     fe->tempStop();
     fe->rebuild(*this, 1);  // (the RxVFO in front of the demodulator is not involved)
     fe->tempStart();
+}
+inline void RxVFO::setCWTone(double tone) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    cwTone = tone;
+    if (demod != Demod::CW) { return; }
+    float re, im;
+    sdrpp_design_phase_delta(tone, outSamplerate, &re, &im);
+    IQFrontEnd* f = fe;
+    RxVFO* self = this;
+    fe->control([f, self, re, im]() { sdrpp_vfo_set_ssb_phase_delta(f->ctx, self->id, re, im); });
 }
 inline void RxVFO::setOffset(double off) {
     std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);

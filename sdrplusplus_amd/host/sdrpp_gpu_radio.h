@@ -6,11 +6,12 @@
 // signal processing of its own: it finds the sdrpp_gpu::RxVFO whose `out` stream it was handed as `input`, attaches the requested
 // demodulator to it (RxVFO::attachDemod) and returns that VFO's `audio` stream from getOutput().  The interface is taken from
 // whatever header declares it — `Base` is the radio module's demod::Demodulator inside an SDR++ tree — so this file restates
-// nothing but the per-mode constants of demodulators/{wfm,nfm,am,usb,lsb,dsb}.h.
+// nothing but the per-mode constants of demodulators/{wfm,nfm,am,usb,lsb,dsb,cw}.h.
 //
 //   #include "demod.h"                                   // radio module: declares demod::Demodulator
 //   #include <sdrpp_gpu_radio.h>
 //   using GpuWFM = sdrpp_gpu::FusedDemodulator<demod::Demodulator, sdrpp_gpu::Demod::WFM>;
+//   using GpuCW = sdrpp_gpu::FusedDemodulator<demod::Demodulator, sdrpp_gpu::Demod::CW>;   // setTone / setAGCAttack / setAGCDecay: cw.h's menu
 //   ... demod = new GpuWFM(&sigpath::iqFrontEnd);  demod->init(name, &config, vfo->output, bw, audioSR);
 //
 // The radio module's IF chain (radio_module.h:84-96) sits between the VFO and the demodulator; a fused VFO has no place for CPU blocks
@@ -32,7 +33,7 @@ class ConfigManager;  // core/src/config.h (only ever passed through)
 namespace sdrpp_gpu {
 
 // Per-mode constants of the radio module's analog demodulators (decoder_modules/radio/src/demodulators/*.h, "INFO" blocks:
-// wfm.h:267-282, nfm.h:55-70, am.h:75-90, usb.h:69-84, lsb.h:68-83, dsb.h:68-83).  vfoReference: ImGui::WaterfallVFO::REF_LOWER = 0,
+// wfm.h:267-282, nfm.h:55-70, am.h:75-90, usb.h:69-84, lsb.h:68-83, dsb.h:68-83, cw.h:81-96).  vfoReference: ImGui::WaterfallVFO::REF_LOWER = 0,
 // REF_CENTER = 1, REF_UPPER = 2 (gui/widgets/waterfall.h:26-30); deemphasis mode: DEEMP_MODE_50US = 1, DEEMP_MODE_NONE = 3
 // (demod.h:8-14).
 struct DemodInfo {
@@ -50,12 +51,14 @@ inline const DemodInfo& demodInfo(Demod m) {
     static const DemodInfo usb{ "USB", 24000.0, 2800.0, 500.0, 12000.0, 100.0, 0, false, 3, false, true };
     static const DemodInfo lsb{ "LSB", 24000.0, 2800.0, 500.0, 12000.0, 100.0, 2, false, 3, false, true };
     static const DemodInfo dsb{ "DSB", 24000.0, 4600.0, 1000.0, 12000.0, 100.0, 1, false, 3, false, true };
+    static const DemodInfo cw{ "CW", 3000.0, 200.0, 50.0, 500.0, 10.0, 1, false, 3, false, false };
     switch (m) {
     case Demod::WFM: return wfm;
     case Demod::NFM: return nfm;
     case Demod::AM: return am;
     case Demod::USB: return usb;
     case Demod::LSB: return lsb;
+    case Demod::CW: return cw;
     default: return dsb;
     }
 }
@@ -98,8 +101,8 @@ public:
     int getDefaultDeemphasisMode() override { return demodInfo(MODE).defaultDeemphasisMode; }
     bool getFMIFNRAllowed() override { return demodInfo(MODE).fmIfnrAllowed; }
     bool getNBAllowed() override { return demodInfo(MODE).nbAllowed; }
-    bool getHighPassAllowed() override { return true; }
-    bool getSquelchAllowed() override { return true; }
+    bool getHighPassAllowed() override { return MODE != Demod::CW; }  // cw.h:95-96: the one demodulator that allows neither
+    bool getSquelchAllowed() override { return MODE != Demod::CW; }
     dsp::stream<dsp::stereo_t>* getOutput() override { return vfo ? &vfo->audio : nullptr; }
 
     // what the reference's showMenu() toggles (wfm.h:104-111 / nfm.h:37-43 "Low Pass"; am.h:40-63, usb.h:40-57 AGC attack / decay, carrier AGC)
@@ -107,6 +110,12 @@ public:
     void setAGCAttack(double attack) { _agcAttack = attack; apply(); }
     void setAGCDecay(double decay) { _agcDecay = decay; apply(); }
     void setCarrierAgc(bool enabled) { _carrierAgc = enabled; apply(); }
+    // CW only (cw.h:62-70, the menu's clamp to 250 .. 1250 Hz): the beat note — the translation's phase stays continuous, nothing restarts
+    void setTone(int tone) {
+        if (MODE != Demod::CW) { throw std::runtime_error("[sdrpp_gpu::FusedDemodulator] the tone belongs to the CW demodulator"); }
+        _tone = tone < 250 ? 250 : (tone > 1250 ? 1250 : tone);
+        if (vfo) { vfo->setCWTone((double)_tone); }
+    }
     // the radio module's IF chain on the device (radio_module.h:633-713; clamps :908-911: MIN_NB 1, MAX_NB 10, MIN_SQUELCH -100, MAX_SQUELCH 0)
     void setNBEnabled(bool enabled) { _nbEnabled = enabled; applyIF(); }
     void setNBLevel(float level) { _nbLevel = level < 1.0f ? 1.0f : (level > 10.0f ? 10.0f : level); applyIF(); }
@@ -149,6 +158,7 @@ private:
     void apply() {
         if (!vfo) { return; }
         vfo->demodBandwidth = _bandwidth;
+        if (MODE == Demod::CW) { vfo->cwTone = (double)_tone; }
         vfo->attachDemod(MODE, _lowPass, _agcAttack, _agcDecay, _carrierAgc);
     }
 
@@ -166,7 +176,8 @@ private:
     std::string _name;
     double _bandwidth = 0.0;
     bool _lowPass = true, _carrierAgc = false;
-    double _agcAttack = 50.0, _agcDecay = 5.0;  // am.h:98-99, usb.h:92-93
+    double _agcAttack = (MODE == Demod::CW) ? 100.0 : 50.0, _agcDecay = 5.0;  // am.h:98-99, usb.h:92-93; cw.h:105-106
+    int _tone = 800;  // cw.h:107
     bool _nbEnabled = false, _squelchEnabled = false, _fmnrEnabled = false;
     bool _rdsOut = false;
     int _fmnrBins = 32;  // radio_module.h:91

@@ -13,7 +13,7 @@ from . import capi
 
 PLANS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "decim_plans.bin")
 
-# radio-module defaults: (IF sample rate, default bandwidth) — wfm.h:268-270, nfm.h:56-58, am.h:76-78, usb.h:70-72, lsb.h, dsb.h
+# radio-module defaults: (IF sample rate, default bandwidth) — wfm.h:268-270, nfm.h:56-58, am.h:76-78, usb.h:70-72, lsb.h, dsb.h, cw.h:82-84
 RADIO_DEFAULTS = {
     "WFM": (250000.0, 150000.0),
     "NFM": (50000.0, 12500.0),
@@ -21,9 +21,11 @@ RADIO_DEFAULTS = {
     "USB": (24000.0, 2800.0),
     "LSB": (24000.0, 2800.0),
     "DSB": (24000.0, 4600.0),
+    "CW": (3000.0, 200.0),
 }
 DEMOD_CODES = {"RAW": capi.DEMOD_RAW, "WFM": capi.DEMOD_WFM, "NFM": capi.DEMOD_NFM, "AM": capi.DEMOD_AM,
-               "USB": capi.DEMOD_USB, "LSB": capi.DEMOD_LSB, "DSB": capi.DEMOD_DSB}
+               "USB": capi.DEMOD_USB, "LSB": capi.DEMOD_LSB, "DSB": capi.DEMOD_DSB, "CW": capi.DEMOD_CW}
+CW_AGC_DEFAULTS = (100.0, 5.0)  # demodulators/cw.h:105-106 (SSB's and AM's are 50 / 5)
 
 
 class DecimPlans:
@@ -79,9 +81,14 @@ def meter_table(vfos):
     return [(float(offset), float(bandwidth)) for offset, bandwidth in vfos]
 
 
-def vfo_desc(in_sr, out_sr, bandwidth, offset, mode="RAW", low_pass=True, agc_attack=50.0, agc_decay=5.0, carrier_agc=False, nco_mode=0):
+def vfo_desc(in_sr, out_sr, bandwidth, offset, mode="RAW", low_pass=True, agc_attack=None, agc_decay=None, carrier_agc=False, nco_mode=0, tone=800.0):
     """Build a sdrpp_vfo_desc for RxVFO(in_sr -> out_sr, bandwidth, offset) followed by radio demodulator `mode`.
+    agc_attack / agc_decay None: the mode's own defaults (50 / 5; CW 100 / 5).  tone: CW's beat note in Hz (demodulators/cw.h:107).
     Returns (desc, keepalive) — keepalive holds the numpy arrays the descriptor points into (sdrpp_vfo_add copies them)."""
+    if agc_attack is None:
+        agc_attack = CW_AGC_DEFAULTS[0] if mode == "CW" else 50.0
+    if agc_decay is None:
+        agc_decay = CW_AGC_DEFAULTS[1] if mode == "CW" else 5.0
     d = capi.VfoDesc()
     d.nco_mode = int(nco_mode)  # 0: the context's NCO mode, 1: closed form, 2: the reference's float rotator recursion (this VFO only)
     keep = []
@@ -147,6 +154,8 @@ def vfo_desc(in_sr, out_sr, bandwidth, offset, mode="RAW", low_pass=True, agc_at
     elif mode in ("USB", "LSB", "DSB"):
         tr = {"USB": bandwidth / 2.0, "LSB": -bandwidth / 2.0, "DSB": 0.0}[mode]  # ssb.h:106-117
         d.ssb_phase_delta_re, d.ssb_phase_delta_im = capi.design_phase_delta(tr, out_sr)
+    elif mode == "CW":  # dsp/demod/cw.h:20: xlator.init(NULL, tone, samplerate) — the bandwidth plays no part (demodulators/cw.h:73)
+        d.ssb_phase_delta_re, d.ssb_phase_delta_im = capi.design_phase_delta(tone, out_sr)
     return d, keep
 
 
