@@ -66,6 +66,10 @@ int sdrpp_device_info(sdrpp_ctx* ctx, char* buf, int buflen);
 int sdrpp_design_low_pass(double cutoff, double trans_width, double sample_rate, int odd_tap_count, float* taps, int max);
 int sdrpp_design_high_pass(double cutoff, double trans_width, double sample_rate, int odd_tap_count, float* taps, int max);
 /* iq_frontend.cpp:280-291: kind 0 RECTANGULAR, 1 BLACKMAN, 2 NUTTALL; includes the (-1)^i fftshift factor. */
+/* taps::bandPass<complex_t> (dsp/taps/band_pass.h:11-25): `count` complex taps, interleaved (re, im), into taps[0 .. 2 * count) while 2 * count <= max; returns count */
+int sdrpp_design_band_pass_complex(double band_start, double band_stop, double trans_width, double sample_rate, int odd_tap_count, float* taps, int max);
+/* loop::PhaseControlLoop<float>::criticallyDamped (dsp/loop/phase_control_loop.h:31-36) as loop::PLL::init calls it, evaluated in float like the reference */
+void sdrpp_design_pll(double bandwidth, float* alpha, float* beta);
 int sdrpp_design_fft_window(int kind, int nz, float* window);
 /* iq_frontend.h:59-63 */
 void sdrpp_design_reshape_params(double sample_rate, int fft_size, double fft_rate, int* skip, int* nz);
@@ -425,6 +429,41 @@ int sdrpp_vfo_rds_device_buffer(sdrpp_ctx* ctx, int id, const float** out, int* 
 int sdrpp_abi_sizeof_rds_desc(void);
 /* Test and statistics hook: polyphase banks of RDS branches the context holds in device memory (identical descriptions share one). */
 int sdrpp_rds_bank_count(sdrpp_ctx* ctx);
+
+/* ---- Stereo branch of the WFM demodulator (dsp/demod/broadcast_fm.h:147-191 with _stereo on; decoder_modules/radio/src/demodulators/wfm.h `_stereo`) --------
+ * What dsp::demod::BroadcastFM computes per IF sample i with its stereo decoder on:
+ *     m[i]  = Quadrature(x[i])                                  the discriminator the mono path has
+ *     p[i]  = FIR<complex_t, complex_t>(m[i] + 0j)              pilot_taps: taps::bandPass<complex_t>(18750, 19250, 3000, if_rate, true), 317 taps at 250 kS/s
+ *     v[i]  = phasor(phase)                                     loop::PLL (pll.h:64-70): the phase BEFORE the update
+ *     e     = normalizePhase(atan2f(p.im, p.re) - phase);  freq += beta * e, clamped to [min_freq, max_freq];  phase += freq + alpha * e, wrapped to +-pi
+ *     q     = (m[i - delay] + 0j) * conj(v) * conj(v);  lmr = 2 q.re;  l = m[i - delay] + lmr,  r = m[i - delay] - lmr
+ *     out   = (alFir(l), arFir(r))                              the VFO description's audio taps; audio_ntaps == 0: no filter (`_lowPass` off)
+ * in float throughout, the loop in the reference's operations and order.  The result does not depend on how the stream is cut into pushes: the same
+ * samples give the same bits in one push, in pushes of one sample, pipelined or in launch groups.  The (l, r) frames are the VFO's output: the AF chain,
+ * the recorder sink, sdrpp_vfo_read and the pipelined results read them as they read the mono frames.
+ * Only for SDRPP_DEMOD_WFM VFOs (anything else: SDRPP_ERR_UNSUPPORTED).  SDRPP_ERR_INVALID: no taps, an even tap count, a delay below 1 — and a loop
+ * description outside these limits, which bound the phase step so that the loop's wrap into +-pi ends after at most two rounds: alpha, beta, init_freq,
+ * min_freq and max_freq finite; min_freq < max_freq; |min_freq|, |max_freq|, |init_freq| <= pi; |alpha| * pi + max(|min_freq|, |max_freq|) <= 4 pi (the
+ * reference's description: 0.48 + 0.25 pi).  SDRPP_ERR_UNSUPPORTED: more than 576 pilot taps, or a VFO whose audio low-pass has more than 289 (the kernels' tiles).
+ * SWITCHING is BroadcastFM::setStereo, which calls reset(): a call that changes `enabled` — or attaches an enabled branch, replaces the description of an
+ * enabled one, or detaches an enabled one (desc == NULL) — makes the demodulator start over from the next sample: discriminator's previous phase 0, pilot
+ * filter, both delays and both audio filters cleared, the loop at phase 0 and init_freq; the mono path likewise (its discriminator and audio filter
+ * cleared).  RxVFO's own state, the IF chain's and the RDS branch's are not touched.  A call with the same description and the same `enabled` changes
+ * nothing.  sdrpp_vfo_reset clears the branch with the rest of the demodulator.  sdrpp_vfo_replace with keep & 2 and a WFM description moves the branch,
+ * parameters and state, to the new handle (a handle with another stream capacity or audio filter length gets the description attached afresh: with an
+ * enabled branch its demodulator starts from the reset() state).
+ * The arrays are copied during the call. */
+typedef struct sdrpp_stereo_desc {
+    const float* pilot_taps;      /* pilot_ntaps complex taps, interleaved (re, im): sdrpp_design_band_pass_complex(18750, 19250, 3000, if_rate, 1, ...) */
+    int pilot_ntaps;              /* odd                                                                                                              */
+    int delay;                    /* (pilot_ntaps - 1) / 2 + 1 (broadcast_fm.h:47-48)                                                                 */
+    float alpha, beta;            /* sdrpp_design_pll(25000 / if_rate, ...)  (broadcast_fm.h:46)                                                       */
+    float init_freq;              /* (float)hzToRads(19000, if_rate), radians per sample                                                               */
+    float min_freq, max_freq;     /* (float)hzToRads(18750 / 19250, if_rate)                                                                           */
+    int enabled;
+} sdrpp_stereo_desc;
+int sdrpp_vfo_set_stereo(sdrpp_ctx* ctx, int id, const sdrpp_stereo_desc* desc);
+int sdrpp_abi_sizeof_stereo_desc(void);
 
 /* ---- WaterFall display state around the raw-line history (core/src/gui/widgets/waterfall.cpp) ---------------
  * The last `height` raw dB lines stay resident in HBM in the reference's ring order (getFFTBuffer :875-886), so a zoom / pan /

@@ -94,6 +94,22 @@ class RdsDesc(C.Structure):
     ]
 
 
+class StereoDesc(C.Structure):
+    """struct sdrpp_stereo_desc (include/sdrpp_gpu.h): the WFM demodulator's stereo branch — pilot filter, PLL, L-R matrix."""
+
+    _fields_ = [
+        ("pilot_taps", c_float_p),
+        ("pilot_ntaps", C.c_int),
+        ("delay", C.c_int),
+        ("alpha", C.c_float),
+        ("beta", C.c_float),
+        ("init_freq", C.c_float),
+        ("min_freq", C.c_float),
+        ("max_freq", C.c_float),
+        ("enabled", C.c_int),
+    ]
+
+
 class IfDesc(C.Structure):
     """struct sdrpp_if_desc (include/sdrpp_gpu.h): the radio IF chain (noise blanker -> power squelch) in front of the demodulator."""
 
@@ -257,6 +273,13 @@ def load():
     L.sdrpp_rds_bank_count.argtypes = [vp]
     L.sdrpp_pipeline_set_rds_results.argtypes = [vp, C.c_int]
     L.sdrpp_result_rds.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(c_float_p), c_int_p]
+    L.sdrpp_abi_sizeof_stereo_desc.argtypes = []
+    if L.sdrpp_abi_sizeof_stereo_desc() != C.sizeof(StereoDesc):
+        raise ImportError("sdrpp_stereo_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_stereo_desc(), C.sizeof(StereoDesc)))
+    L.sdrpp_vfo_set_stereo.argtypes = [vp, C.c_int, C.POINTER(StereoDesc)]
+    L.sdrpp_design_band_pass_complex.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, c_float_p, C.c_int]
+    L.sdrpp_design_pll.restype = None
+    L.sdrpp_design_pll.argtypes = [C.c_double, c_float_p, c_float_p]
     L.sdrpp_abi_sizeof_meter_desc.argtypes = []
     if L.sdrpp_abi_sizeof_meter_desc() != C.sizeof(MeterDesc):
         raise ImportError("sdrpp_meter_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_meter_desc(), C.sizeof(MeterDesc)))
@@ -361,6 +384,7 @@ EXPORTED_SYMBOLS = [
     "sdrpp_vfo_set_rec", "sdrpp_vfo_rec_read", "sdrpp_abi_sizeof_rec_desc", "sdrpp_result_rec",
     "sdrpp_vfo_set_rds", "sdrpp_vfo_rds_count", "sdrpp_vfo_rds_read", "sdrpp_vfo_rds_device_buffer", "sdrpp_abi_sizeof_rds_desc", "sdrpp_rds_bank_count",
     "sdrpp_pipeline_set_rds_results", "sdrpp_result_rds",
+    "sdrpp_vfo_set_stereo", "sdrpp_abi_sizeof_stereo_desc", "sdrpp_design_band_pass_complex", "sdrpp_design_pll",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
     "sdrpp_vfo_set_if", "sdrpp_vfo_set_fmnr", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
     "sdrpp_fft_configure", "sdrpp_fft_disable", "sdrpp_fft_set_view", "sdrpp_fft_lines", "sdrpp_fft_read", "sdrpp_fft_copy_device", "sdrpp_fft_device_buffers",
@@ -396,6 +420,24 @@ def design_high_pass(cutoff, trans_width, sample_rate, odd=False):
     taps = np.zeros(max(n, 1), dtype=np.float32)
     L.sdrpp_design_high_pass(cutoff, trans_width, sample_rate, int(odd), taps.ctypes.data_as(c_float_p), n)
     return taps[:n]
+
+
+def design_band_pass_complex(band_start, band_stop, trans_width, sample_rate, odd=False):
+    """taps::bandPass<complex_t> (dsp/taps/band_pass.h) -> complex64 taps"""
+    L = load()
+    n = L.sdrpp_design_band_pass_complex(band_start, band_stop, trans_width, sample_rate, int(odd), None, 0)
+    if n <= 0:
+        raise SdrppError(n, "sdrpp_design_band_pass_complex")
+    taps = np.empty(n, dtype=np.complex64)
+    L.sdrpp_design_band_pass_complex(band_start, band_stop, trans_width, sample_rate, int(odd), taps.view(np.float32).ctypes.data_as(c_float_p), 2 * n)
+    return taps
+
+
+def design_pll(bandwidth):
+    """PhaseControlLoop<float>::criticallyDamped as loop::PLL::init calls it -> (alpha, beta), float32 values"""
+    a, b = C.c_float(), C.c_float()
+    load().sdrpp_design_pll(bandwidth, C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def design_fft_window(kind, nz):
@@ -777,6 +819,12 @@ class Context:
         if n.value > 0:
             C.memmove(out.ctypes.data, data, n.value * 8)
         return out
+
+    def vfo_set_stereo(self, vid, desc, keepalive=None):
+        """Attach the WFM demodulator's stereo branch (sdrpp_vfo_set_stereo; radio.stereo_desc), switch it (desc.enabled: BroadcastFM::setStereo, the
+        demodulator starts over) or, with None, detach it.  `keepalive` is only there so that a caller can pass what radio.stereo_desc returns: the library
+        copies the taps during the call."""
+        self._chk(self.L.sdrpp_vfo_set_stereo(self.h, vid, C.byref(desc) if desc is not None else None))
 
     def vfo_set_if(self, vid, if_desc):
         """Attach (or, with None, detach) the radio IF chain: noise blanker -> power squelch in front of the demodulator (sdrpp_vfo_set_if).

@@ -156,6 +156,20 @@ struct Vfo {
         bool ran = false;              // the most recent block was planned with the branch on
         std::vector<int> tk;           // a launch group: cumulative output counts at every push end
     } rds;
+    // Stereo branch of the WFM demodulator (sdrpp_vfo_set_stereo; broadcast_fm.h:147-191): while it is on it REPLACES the audio low-pass job — pilot filter, PLL and
+    // matrix write the VFO's output stream.  Its streams are its own, with histories like every stream: the discriminator values m (the two delay lines and,
+    // through them, the two audio filters' lines), the pilot's angles (no memory) and the loop phases (the audio filters' lines).  The loop's (phase, freq) live
+    // on the device.  Switching it on or off is BroadcastFM::setStereo -> reset(): stereo_reset_demod (vfo_ctl.h)
+    struct Stereo {
+        bool attached = false, on = false;
+        std::vector<float> ptaps;      // K complex pilot taps, interleaved
+        int K = 0, delay = 0;
+        float alpha = 0.0f, beta = 0.0f, init_freq = 0.0f, min_freq = 0.0f, max_freq = 0.0f;
+        float* d_ptaps = nullptr;
+        float2* d_state = nullptr;     // PhaseControlLoop::phase, ::freq (device, persistent)
+        std::vector<Stream> st;        // [0] m, [1] pilot angle, [2] loop phase: real streams at the IF rate
+        bool ran = false;              // the most recent block was planned with the branch on
+    } stereo;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
     ToepTab tp_chan, tp_audio;
     // front end as one filter (what the fused translate + filter kernels evaluate): stages 0 (+ 1) of the plan

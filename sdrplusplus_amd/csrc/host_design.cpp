@@ -63,6 +63,38 @@ int sdrpp_design_high_pass(double cutoff, double trans_width, double sample_rate
     return windowedSinc(count, hzToRads((sample_rate / 2.0) - cutoff, sample_rate), true, taps, max);
 }
 
+// taps/band_pass.h:11-25 with T = complex_t through taps/windowed_sinc.h:9-29: the window function returns phasor(-offsetOmega * (float)n) * nuttall(n, N)
+// (complex_t * double: both parts times (float)nuttall), the tap is {(float)sinc, 0} * that (complex_t * complex_t, every product in place) * corr (complex_t * double)
+int sdrpp_design_band_pass_complex(double band_start, double band_stop, double trans_width, double sample_rate, int odd, float* taps, int max) {
+    if (!(band_stop > band_start)) { return SDRPP_ERR_INVALID; }
+    const float offsetOmega = hzToRads((band_start + band_stop) / 2.0, sample_rate);
+    int count = estimateTapCount(trans_width, sample_rate);
+    if (odd && !(count % 2)) { count++; }
+    const double omega = hzToRads((band_stop - band_start) / 2.0, sample_rate);
+    const double half = (double)count / 2.0;
+    const double corr = 1.0 * omega / kPi;
+    for (int i = 0; i < count && 2 * i + 1 < max; i++) {
+        const double t = (double)i - half + 0.5;
+        const double n = t - half;
+        const float x = -offsetOmega * (float)n;
+        const float w = (float)nuttall(n, (double)count);
+        const float wr = cosf(x) * w, wi = sinf(x) * w;
+        const float cr = (float)sinc(t * omega), ci = 0.0f;
+        const float pr = (cr * wr) - (ci * wi), pi = (ci * wr) + (cr * wi);
+        taps[2 * i] = pr * (float)corr;
+        taps[2 * i + 1] = pi * (float)corr;
+    }
+    return count;
+}
+
+void sdrpp_design_pll(double bandwidth_d, float* alpha, float* beta) {
+    const float bandwidth = bandwidth_d;  // criticallyDamped(T bandwidth, ...) with T = float
+    const float dampningFactor = sqrt(2.0) / 2.0;
+    const float denominator = (1.0 + 2.0 * dampningFactor * bandwidth + bandwidth * bandwidth);
+    *alpha = (4 * dampningFactor * bandwidth) / denominator;
+    *beta = (4 * bandwidth * bandwidth) / denominator;
+}
+
 int sdrpp_design_fft_window(int kind, int nz, float* window) {
     if (kind < 0 || kind > 2 || nz <= 0 || !window) { return SDRPP_ERR_INVALID; }
     for (int i = 0; i < nz; i++) {

@@ -477,6 +477,13 @@ void rds_free_own(Vfo::Rds& r) {
     for (auto& s : r.st) { stream_free(s); }
     r.st.clear();
 }
+// what a stereo branch owns
+void stereo_free(Vfo::Stereo& s) {
+    dev_free(s.d_ptaps);
+    dev_free(s.d_state);
+    for (auto& q : s.st) { stream_free(q); }
+    s = Vfo::Stereo{};
+}
 // Outputs per tile and LDS row pitch of the branch's fused first stage (vfo_rds_front_body) for K taps decimating by D: the window of a tile, de-interleaved
 // by decimation phase, and its phases must fit the wavefront's share of the role's LDS.  The pitch serves the window's STORES (8 bytes per lane, carried out 16
 // lanes at a time over 32 dword banks: 16 consecutive samples must land on 16 different 8-byte banks — consecutive samples lie `pitch` float2 apart, D of them
@@ -515,6 +522,7 @@ void af_detach(Vfo& v) {
 }
 void vfo_free(Vfo& v) {
     rds_free_own(v.rds);
+    stereo_free(v.stereo);
     af_detach(v);
     rate_free(v.rate);
     for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { dev_free(v.d_staps_nat[i]); }
@@ -531,7 +539,25 @@ void vfo_free(Vfo& v) {
     v.st.clear();
 }
 
+// The stereo branch starts over (PLL::reset, Delay::reset, FIR::reset as BroadcastFM::reset calls them): the loop at its initial phase and frequency, its
+// streams' histories zero.
+int stereo_clear(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Stereo& s = v.stereo;
+    if (!s.attached) { return SDRPP_OK; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (auto& q : s.st) {
+        for (int i = 0; i < 2; i++) {
+            if (q.hist[i]) { HIPCHK(c, hipMemset(q.hist[i], 0, (size_t)std::max(q.hist_len, 1) * q.width * sizeof(float))); }
+        }
+        q.n = 0;
+    }
+    const float2 init = make_float2(0.0f, s.init_freq);  // pll.h:58-60 (BroadcastFM: initial phase 0)
+    HIPCHK(c, hipMemcpy(s.d_state, &init, sizeof(init), hipMemcpyHostToDevice));
+    s.ran = false;
+    return SDRPP_OK;
+}
 int vfo_reset_state(sdrpp_ctx* c, Vfo& v) {
+    if (int rc = stereo_clear(c, v)) { return rc; }
     v.phi = 0.0;
     v.phi2 = 0.0;
     v.seen = 0;

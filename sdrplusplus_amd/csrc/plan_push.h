@@ -8,9 +8,9 @@ namespace {
 struct PlanSnapshot {
     struct V { RateChain::Pos pos, af_pos, rds_pos; double phi, phi2; long long seen; int i_if, lvl_if, lvl_out, lvl_af, lvl_ifc; size_t nrecs;
                int af_last, af_state;
-               int rds_lvl; double rds_phi; bool rds_frozen, rds_ran; int rds_line_cur, rds_line_fed; };
+               int rds_lvl; double rds_phi; bool rds_frozen, rds_ran; int rds_line_cur, rds_line_fed; bool stereo_ran; };
     std::vector<V> v;
-    std::vector<int> nc;  // n and cur of every stream of every VFO (its own, then its RDS branch's), in the order of the walk
+    std::vector<int> nc;  // n and cur of every stream of every VFO (its own, then its RDS branch's and its stereo branch's), in the order of the walk
     int64_t fft_pos, fft_next;
     int n_lines, iq_cur, wf_cur, wf_lines;
     bool wf_have;
@@ -28,8 +28,8 @@ void plan_snapshot(sdrpp_ctx* c, PlanSnapshot& S, bool rotate = false) {
         q.phi = v.phi; q.phi2 = v.phi2; q.seen = v.seen; q.i_if = v.i_if; q.lvl_if = v.lvl_if; q.lvl_out = v.lvl_out; q.lvl_af = v.lvl_af; q.lvl_ifc = v.lvl_ifc;
         q.nrecs = v.recs.size();
         q.af_last = v.af.i_last; q.af_state = v.af.state_cur;
-        q.rds_lvl = v.rds.lvl; q.rds_phi = v.rds.phi; q.rds_frozen = v.rds.frozen; q.rds_ran = v.rds.ran; q.rds_line_cur = v.rds.line_cur; q.rds_line_fed = v.rds.line_fed;
-        for (auto* list : { &v.st, &v.rds.st }) {
+        q.rds_lvl = v.rds.lvl; q.rds_phi = v.rds.phi; q.rds_frozen = v.rds.frozen; q.rds_ran = v.rds.ran; q.rds_line_cur = v.rds.line_cur; q.rds_line_fed = v.rds.line_fed; q.stereo_ran = v.stereo.ran;
+        for (auto* list : { &v.st, &v.rds.st, &v.stereo.st }) {
             for (auto& st : *list) {
                 S.nc.push_back(st.n);
                 S.nc.push_back(st.cur);
@@ -53,8 +53,8 @@ void plan_restore(sdrpp_ctx* c, const PlanSnapshot& S) {
         v.rate.pos = q.pos; v.af.rate.pos = q.af_pos; v.rds.rate.pos = q.rds_pos;
         v.phi = q.phi; v.phi2 = q.phi2; v.seen = q.seen; v.i_if = q.i_if; v.lvl_if = q.lvl_if; v.lvl_out = q.lvl_out; v.lvl_af = q.lvl_af; v.lvl_ifc = q.lvl_ifc;
         v.af.i_last = q.af_last; v.af.state_cur = q.af_state;
-        v.rds.lvl = q.rds_lvl; v.rds.phi = q.rds_phi; v.rds.frozen = q.rds_frozen; v.rds.ran = q.rds_ran; v.rds.line_cur = q.rds_line_cur; v.rds.line_fed = q.rds_line_fed;
-        for (auto* list : { &v.st, &v.rds.st }) {
+        v.rds.lvl = q.rds_lvl; v.rds.phi = q.rds_phi; v.rds.frozen = q.rds_frozen; v.rds.ran = q.rds_ran; v.rds.line_cur = q.rds_line_cur; v.rds.line_fed = q.rds_line_fed; v.stereo.ran = q.stereo_ran;
+        for (auto* list : { &v.st, &v.rds.st, &v.stereo.st }) {
             for (auto& st : *list) {
                 st.n = *nc++;
                 st.cur = *nc++;
@@ -121,6 +121,7 @@ int push_common(sdrpp_ctx* c, const float* d_iq, int64_t count, const std::vecto
         for (auto& kv : c->vfos) {
             for (auto& s : kv.second->st) { s.n = 0; }
             for (auto& s : kv.second->rds.st) { s.n = 0; }
+            for (auto& s : kv.second->stereo.st) { s.n = 0; }
         }
         return SDRPP_OK;
     }
@@ -145,6 +146,7 @@ int push_common(sdrpp_ctx* c, const float* d_iq, int64_t count, const std::vecto
             for (auto& kv : c->vfos) {
                 for (auto& s : kv.second->st) { s.n = 0; }
                 for (auto& s : kv.second->rds.st) { s.n = 0; }
+                for (auto& s : kv.second->stereo.st) { s.n = 0; }
             }
             return arena_end(c);
         }

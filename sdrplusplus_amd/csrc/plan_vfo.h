@@ -236,6 +236,12 @@ struct BankPlan {
     Lev<RdsJob> rdsj;
     Lev<RdsRotXJob> rdsx;
     Lev<RdsLineJob> rdsl;
+    // stereo branch of the WFM demodulator (stereo_branch): its three job kinds, filed as jobs of the IF chain's role like the RDS branch's — the loop's
+    // per-VFO records SDRPP_ST_PACK to a job
+    Lev<StereoPilotJob> stp;
+    Lev<StereoLoopVfo> stl;
+    Lev<StereoLoopJob> stlj;  // (filled by upload once stl's records have their addresses)
+    Lev<StereoMatrixJob> stm;
     Lev<CarryJob> carry;  // history carries at the level of the stream's consumer (a pass without pipelining: all at the last level)
     int max_rot = 0;
     // front-end jobs (group_front)
@@ -272,7 +278,7 @@ struct BankPlan {
         for (auto& t : tlists) { f(*t.L); }
         f(f_dec); f(poly);
         for (auto& q : polyb) { f(q); }
-        f(chan); f(seq); f(rdsj); f(rdsx); f(rdsl); f(ifc); f(pre); f(audio); f(audio_fm);  // (rdsj / rdsx in front of ifc: upload files them there)
+        f(chan); f(seq); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stlj); f(stm); f(ifc); f(pre); f(audio); f(audio_fm);  // (rdsj / rdsx in front of ifc: upload files them there)
         f(af_dec); f(af_hpf); f(af_poly); f(af_deemp);
         f(ssbx_l); f(carry);
     }
@@ -415,6 +421,7 @@ struct BankPlan {
         ChainCtx x(v, L0 + 1);
         for (auto& s : v.st) { s.clevel = 0; s.wlevel = 0; }
         for (auto& s : v.rds.st) { s.clevel = 0; s.wlevel = 0; }
+        for (auto& s : v.stereo.st) { s.clevel = 0; s.wlevel = 0; }
         x.at.cur->wlevel = x.at.lvl;
         const bool agc_mode = v.d.demod == SDRPP_DEMOD_AM || (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_CW);
         x.ifc_on = v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base;
@@ -456,7 +463,9 @@ struct BankPlan {
         }
         if_chain(x);
         const ChainCursor feed = x.at;  // the stream the demodulator reads
-        if (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) { demod_fm(x); }
+        v.stereo.ran = v.stereo.on;
+        if (v.stereo.on) { stereo_branch(x); }  // (WFM only: stereo_apply)
+        else if (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) { demod_fm(x); }
         else if (v.d.demod == SDRPP_DEMOD_AM) { demod_am(x); }
         else if (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_CW) { demod_ssb(x); }
         if (v.af.on && v.i_out >= 0) { af_chain(x); }
@@ -619,7 +628,7 @@ struct BankPlan {
     void pipe_decide(ChainCtx& x) {
         Vfo& v = x.v;
         const int last_dec = v.rate.n_stages - 1;
-        x.piped = c->pipe_on && !ticking && !x.ifc_on && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= x.first_sep && v.rate.tp_stage[last_dec].ok &&
+        x.piped = c->pipe_on && !ticking && !x.ifc_on && !v.stereo.on && (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) && last_dec >= x.first_sep && v.rate.tp_stage[last_dec].ok &&
                   v.i_poly >= 0 && v.rate.tp_poly.ok && v.i_chan >= 0 && v.chan_ntaps > 0 && v.tp_chan.ok && v.tp_audio.ok;
         if (!x.piped) { return; }
         x.pj = PipeJob{};
@@ -677,6 +686,34 @@ struct BankPlan {
             pipes.push_back(x.pj);
             pipe_lds = std::max(pipe_lds, x.pj_lds);
         }
+        v.lvl_out = x.at.lvl;
+    }
+    // Stereo branch of the WFM demodulator (broadcast_fm.h:147-191) in place of the audio low-pass job: pilot (discriminator, pilot filter, angle), loop (the
+    // PLL's recursion), matrix (phasor, L-R, the two audio low-passes), a level each, off the stream the demodulator reads.  Pilot and matrix: a job per run of
+    // SDRPP_ST_SEG samples; loop: a record per VFO (upload packs them into jobs).  Nothing here depends on where a block or a push ends: a launch group is one block.
+    void stereo_branch(ChainCtx& x) {
+        Vfo& v = x.v;
+        Vfo::Stereo& s = v.stereo;
+        const Stream& in = *x.at.cur;
+        const int n = in.n, lvl = x.at.lvl;
+        Stream &sm = s.st[0], &sa = s.st[1], &sp = s.st[2], &out = v.st[(size_t)v.i_out];
+        const StreamIn sin = stream_in(in);
+        for (int lo = 0; lo < n; lo += SDRPP_ST_SEG) {
+            stp.add(lvl + 1, StereoPilotJob{ sin, sm.data, sa.data, s.d_ptaps, s.K, lo, std::min(lo + SDRPP_ST_SEG, n), v.d.inv_deviation });
+        }
+        x.at.step(sm, n);
+        sa.n = n;
+        sa.wlevel = lvl + 1;
+        sa.clevel = lvl + 2;
+        if (n > 0) { stl.add(lvl + 2, StereoLoopVfo{ sa.data, sp.data, s.d_state, s.alpha, s.beta, s.min_freq, s.max_freq, n }); }
+        sp.n = n;
+        sp.wlevel = lvl + 2;
+        sp.clevel = lvl + 3;
+        StreamIn min_ = stream_in(sm), pin = stream_in(sp);
+        for (int lo = 0; lo < n; lo += SDRPP_ST_SEG) {
+            stm.add(lvl + 3, StereoMatrixJob{ min_, pin, reinterpret_cast<float2*>(out.data), v.d_audio, v.audio_ntaps, s.delay, lo, std::min(lo + SDRPP_ST_SEG, n) });
+        }
+        x.at.step(out, n, 2);
         v.lvl_out = x.at.lvl;
     }
     // envelope (one level), AGC / DC loop (the next), then the audio filter on the real stream `dem`: the IF stream's consumers have no memory
@@ -842,6 +879,11 @@ struct BankPlan {
                 // an AF chain is up to a dozen levels later, when the stream's ring buffer (kRing = 4) already holds a later block
                 const int cl = !ticking ? carry_last : (s.clevel > 0 ? s.clevel : (s.wlevel > 0 ? s.wlevel + 1 : x.at.lvl + 1));
                 carry.add(cl, CarryJob{ s.data, s.hist[s.cur], s.hist[s.cur ^ 1], s.hist_len, s.n, s.width, s.hist_len });
+            }
+        }
+        if (v.stereo.ran) {  // the stereo branch's own streams
+            for (auto& s : v.stereo.st) {
+                if (s.hist_len > 0 && s.data) { carry.add(!ticking ? carry_last : s.clevel, CarryJob{ s.data, s.hist[s.cur], s.hist[s.cur ^ 1], s.hist_len, s.n, s.width, s.hist_len }); }
             }
         }
         if (v.rds.ran) {  // the RDS branch's own streams (every one of them is written and read whenever the branch runs)
@@ -1181,6 +1223,18 @@ struct BankPlan {
                 }
                 i++;
             }
+            if constexpr (std::is_same_v<decltype(L), Lev<StereoLoopJob>&>) {  // the loops' per-VFO records have their addresses now: SDRPP_ST_PACK of them to a job — the fewer
+                // rows a wavefront stages, the longer its chunks (SDRPP_ST_LOOP_CHUNK elements together); rows lie an odd number of floats apart in its LDS
+                for (int l = 0; l < stl.top; l++) {
+                    for (size_t k = 0; k < stl.at[l].size(); k += SDRPP_ST_PACK) {
+                        const int nv = (int)std::min<size_t>(SDRPP_ST_PACK, stl.at[l].size() - k);
+                        const int chunk = SDRPP_ST_LOOP_CHUNK / nv;
+                        int nmax = 0;
+                        for (int q = 0; q < nv; q++) { nmax = std::max(nmax, stl.at[l][k + (size_t)q].n); }
+                        stlj.add(l, StereoLoopJob{ stl.dev[l] + k, nv, chunk, chunk | 1, nmax });
+                    }
+                }
+            }
             if constexpr (std::is_same_v<decltype(L), Lev<IfcJob>&>) {  // the RDS branches' records have their addresses now: their jobs of the IF chain's role
                 for (int l = 0; l < rdsj.top && !rc; l++) {
                     for (size_t k = 0; k < rdsj.at[l].size(); k++) {
@@ -1207,6 +1261,32 @@ struct BankPlan {
                         ifc.add(l, j);
                     }
                 }
+                // ... and the stereo branches': a job per pilot, loop and matrix record
+                for (int l = 0; l < stp.top && !rc; l++) {
+                    for (size_t k = 0; k < stp.at[l].size(); k++) {
+                        IfcJob j{};
+                        j.in = reinterpret_cast<const float2*>(stp.dev[l] + k);
+                        j.kind = 5;
+                        ifc.add(l, j);
+                    }
+                }
+                for (int l = 0; l < stlj.top && !rc; l++) {
+                    for (size_t k = 0; k < stlj.at[l].size(); k++) {
+                        IfcJob j{};
+                        j.in = reinterpret_cast<const float2*>(stlj.dev[l] + k);
+                        j.kind = 6;
+                        ifc.add(l, j);
+                    }
+                }
+                for (int l = 0; l < stm.top && !rc; l++) {
+                    for (size_t k = 0; k < stm.at[l].size(); k++) {
+                        IfcJob j{};
+                        j.in = reinterpret_cast<const float2*>(stm.dev[l] + k);
+                        j.kind = 7;
+                        ifc.add(l, j);
+                    }
+                }
+                if (stp.top > 0 || stl.top > 0 || stm.top > 0) { ifc_lds = std::max(ifc_lds, (size_t)4 * SDRPP_ST_LDS_WAVE * sizeof(float)); }
             }
             if (!rc && !arena_push_lev(c, L)) { rc = arena_fail(c); }
         });
@@ -1627,6 +1707,11 @@ int do_vfos_plan(sdrpp_ctx* c, const IqSrc& src, int64_t count, const CarryJob& 
     for (size_t i = 0; i < c->vfo_list.size(); i++) {
         for (auto& s : c->vfo_list[i]->st) {
             if (s.hist_len > 0 && s.data) { s.cur ^= 1; }
+        }
+        if (c->vfo_list[i]->stereo.ran) {
+            for (auto& s : c->vfo_list[i]->stereo.st) {
+                if (s.hist_len > 0 && s.data) { s.cur ^= 1; }
+            }
         }
         if (c->vfo_list[i]->rds.ran) {
             for (auto& s : c->vfo_list[i]->rds.st) {

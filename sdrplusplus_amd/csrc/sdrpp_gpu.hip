@@ -921,6 +921,16 @@ int sdrpp_vfo_set_rds(sdrpp_ctx* c, int id, const sdrpp_rds_desc* d, int enabled
     return rds_apply(c, *v, &rd, d->phase_delta_re, d->phase_delta_im, enabled != 0);
 }
 
+// ---- stereo branch of the WFM demodulator: pilot filter -> PLL -> L-R matrix -> L / R low-pass (broadcast_fm.h:147-191) ---------------------------
+int sdrpp_vfo_set_stereo(sdrpp_ctx* c, int id, const sdrpp_stereo_desc* d) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return stereo_apply(c, *v, d);
+}
+int sdrpp_abi_sizeof_stereo_desc(void) { return (int)sizeof(sdrpp_stereo_desc); }
+
 int sdrpp_vfo_rds_count(sdrpp_ctx* c, int id) {
     DeviceScope dev_scope_(c);
     if (!c) { return SDRPP_ERR_INVALID; }

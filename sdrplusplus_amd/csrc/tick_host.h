@@ -637,6 +637,12 @@ int tick_push(sdrpp_ctx* c, const float* d_iq, int64_t count, const CopyJob* lan
                     if (rc) { return rc; }
                 }
             }
+            for (auto& st : kv.second->stereo.st) {
+                if (st.n_extra < kRing - 1 && st.base) {
+                    int rc = stream_ring_ensure(c, st);
+                    if (rc) { return rc; }
+                }
+            }
         }
         if (c->pre.on) {  // the pre-processing chain's stage outputs are per-block buffers too
             for (auto& st : c->pre.st) {

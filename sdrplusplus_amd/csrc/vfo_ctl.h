@@ -37,7 +37,8 @@ Stream& demod_feed(Vfo& v) { return delivered(v, 3) ? *delivered(v, 3) : rx_out(
 // (and the RDS branch's fused first stage recomputes its delay line from it: the stage's K0 - 1 samples and the one in front of them)
 int demod_if_need(const Vfo& v) {
     const int fm = (v.d.demod == SDRPP_DEMOD_WFM || v.d.demod == SDRPP_DEMOD_NFM) ? std::max(v.audio_ntaps, 1) + 1 : 1;
-    return (v.rds.attached && !v.rds.exact) ? std::max(fm, v.rds.rate.ntaps(0)) : fm;
+    const int rds = (v.rds.attached && !v.rds.exact) ? std::max(fm, v.rds.rate.ntaps(0)) : fm;
+    return v.stereo.attached ? std::max(rds, v.stereo.K) : rds;  // (the stereo branch's pilot job recomputes its window of discriminator values from it)
 }
 
 // ---- delay-line hand-overs ----------------------------------------------------------------------------------------------------------
@@ -365,6 +366,7 @@ int fmnr_apply(sdrpp_ctx* c, Vfo& v, bool enabled, int bins) {
 //     states, SSB's second translation                                                                                                     -> keep bit 1
 // (a demodulator SWITCH deletes and creates it, radio_module.h:419-563: bit 1 off).  The AF chain is re-attached by the caller and starts cleared.
 int rds_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n);  // (the RDS branch: below, with the rest of it)
+int stereo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, bool* cleared);  // (the stereo branch: likewise)
 int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
     Stream& of = chan_feed(o);
     Stream& nf = chan_feed(n);
@@ -385,9 +387,13 @@ int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
     }
     if ((keep & 2) && o.d.demod == n.d.demod) {
         // the demodulator's view of the IF stream: the discriminator's previous sample and the audio low-pass's delay line are its newest samples
-        // (behind an IF chain that is what the CHAIN delivered)
-        rc = hist_tail_copy(c, demod_feed(n), demod_feed(o), demod_if_need(n));  // (the new VFO has no chain yet: its RxVFO::out)
-        if (rc) { return rc; }
+        // (behind an IF chain that is what the CHAIN delivered).  The stereo branch moves first: it decides how much of that view the new handle keeps
+        bool st_cleared = false;
+        if (n.d.demod == SDRPP_DEMOD_WFM && (rc = stereo_hand_over(c, o, n, &st_cleared))) { return rc; }
+        if (!st_cleared) {
+            rc = hist_tail_copy(c, demod_feed(n), demod_feed(o), demod_if_need(n));  // (the new VFO has no chain yet: its RxVFO::out)
+            if (rc) { return rc; }
+        }
         if (o.i_dem >= 0 && n.i_dem >= 0) {
             rc = hist_tail_copy(c, n.st[(size_t)n.i_dem], o.st[(size_t)o.i_dem], 1 << 30);
             if (rc) { return rc; }
@@ -711,6 +717,119 @@ int rds_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n) {
         if (n.i_ifc >= 0 && n.st[(size_t)n.i_ifc].base && (rc = stream_grow_hist(c, n.st[(size_t)n.i_ifc], K0))) { return rc; }
     }
     return SDRPP_OK;
+}
+// ---- stereo branch of the WFM demodulator ---------------------------------------------------------------------------------------------
+// BroadcastFM::reset as far as it concerns what the demodulator reads and the RDS branch does not own: the stream the demodulator reads forgets what it
+// has seen (previous phase 0, cleared pilot / audio lines: atan2f(0, 0) = 0 makes a zeroed history exactly that) and the branch starts over (stereo_clear).
+// The RDS branch's first decimator keeps its line (rds_freeze), as xlator / rdsResamp are left alone by reset().
+int stereo_reset_demod(sdrpp_ctx* c, Vfo& v) {
+    if (int rc = rds_freeze(c, v)) { return rc; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    Stream& f = demod_feed(v);
+    for (int i = 0; i < 2; i++) {
+        if (f.hist[i]) { HIPCHK(c, hipMemset(f.hist[i], 0, (size_t)std::max(f.hist_len, 1) * f.width * sizeof(float))); }
+    }
+    return stereo_clear(c, v);
+}
+bool stereo_same_desc(const Vfo::Stereo& s, const sdrpp_stereo_desc* d) {
+    return s.K == d->pilot_ntaps && s.delay == d->delay && s.alpha == d->alpha && s.beta == d->beta && s.init_freq == d->init_freq && s.min_freq == d->min_freq &&
+           s.max_freq == d->max_freq && memcmp(s.ptaps.data(), d->pilot_taps, s.ptaps.size() * sizeof(float)) == 0;
+}
+// every stream the demodulator may read remembers the pilot filter's reach
+int stereo_grow_feeds(sdrpp_ctx* c, Vfo& v, int K) {
+    int rc;
+    if ((rc = stream_grow_hist(c, v.st[(size_t)v.i_chan], K))) { return rc; }
+    if ((rc = stream_grow_hist(c, chan_feed(v), K))) { return rc; }
+    if (v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base && (rc = stream_grow_hist(c, v.st[(size_t)v.i_ifc], K))) { return rc; }
+    return SDRPP_OK;
+}
+// sdrpp_vfo_set_stereo on a VFO the caller has looked up (the stream is idle); d == nullptr: the branch goes
+int stereo_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_stereo_desc* d) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    Vfo::Stereo& s = v.stereo;
+    if (!d) {
+        if (s.attached && s.on) {
+            if (int rc = stereo_reset_demod(c, v)) { return rc; }
+        }
+        stereo_free(s);
+        return SDRPP_OK;
+    }
+    if (v.d.demod != SDRPP_DEMOD_WFM) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the stereo branch needs a WFM VFO"); }
+    if (d->pilot_ntaps <= 0 || !(d->pilot_ntaps & 1) || !d->pilot_taps) { return fail(c, SDRPP_ERR_INVALID, "stereo pilot filter: %d taps (an odd count, with taps)", d->pilot_ntaps); }
+    if (d->pilot_ntaps > SDRPP_ST_PILOT_MAX_TAPS) { return fail(c, SDRPP_ERR_UNSUPPORTED, "stereo pilot filter of %d taps (max %d)", d->pilot_ntaps, SDRPP_ST_PILOT_MAX_TAPS); }
+    if (d->delay <= 0 || d->delay > 65536) { return fail(c, SDRPP_ERR_INVALID, "stereo delay %d", d->delay); }
+    // The loop's wrap subtracts 2 pi until the phase is back inside +-pi: every step may carry it at most kStereoMaxStep beyond, so that it ends after two
+    // rounds for every description that is taken (the reference's own: 0.48 + 0.25 pi)
+    const float kPi = 3.14159265f, kStereoMaxStep = 4.0f * kPi;
+    const bool finite = std::isfinite(d->alpha) && std::isfinite(d->beta) && std::isfinite(d->init_freq) && std::isfinite(d->min_freq) && std::isfinite(d->max_freq);
+    if (!finite || !(d->max_freq > d->min_freq) || fabsf(d->min_freq) > kPi || fabsf(d->max_freq) > kPi || fabsf(d->init_freq) > kPi ||
+        !(fabsf(d->alpha) * kPi + std::max(fabsf(d->min_freq), fabsf(d->max_freq)) <= kStereoMaxStep)) {
+        return fail(c, SDRPP_ERR_INVALID, "stereo loop: frequency limits %g .. %g (an interval within +-pi), initial frequency %g, alpha %g (|alpha| pi + the largest limit <= 4 pi), beta %g: all finite",
+                    d->min_freq, d->max_freq, d->init_freq, d->alpha, d->beta);
+    }
+    if (v.audio_ntaps > SDRPP_ST_AUDIO_MAX_TAPS) { return fail(c, SDRPP_ERR_UNSUPPORTED, "stereo branch behind an audio low-pass of %d taps (max %d)", v.audio_ntaps, SDRPP_ST_AUDIO_MAX_TAPS); }
+    const bool enabled = d->enabled != 0;
+    if (s.attached && stereo_same_desc(s, d)) {  // the same branch: only the switch, which is BroadcastFM::setStereo
+        if (s.on == enabled) { return SDRPP_OK; }
+        s.on = enabled;
+        s.ran = false;
+        return stereo_reset_demod(c, v);
+    }
+    const bool was_on = s.attached && s.on;
+    stereo_free(s);
+    // every early return below gives back what was built so far — and, where an enabled branch has gone with it, makes the demodulator start over as
+    // every other way of switching it off does
+    struct Undo {
+        sdrpp_ctx* c; Vfo& v; bool was_on; bool armed = true;
+        ~Undo() {
+            if (!armed) { return; }
+            stereo_free(v.stereo);
+            if (was_on) { (void)stereo_reset_demod(c, v); }
+        }
+    } undo{ c, v, was_on };
+    int rc;
+    s.K = d->pilot_ntaps;
+    s.delay = d->delay;
+    s.alpha = d->alpha;
+    s.beta = d->beta;
+    s.init_freq = d->init_freq;
+    s.min_freq = d->min_freq;
+    s.max_freq = d->max_freq;
+    s.ptaps.assign(d->pilot_taps, d->pilot_taps + 2 * (size_t)d->pilot_ntaps);
+    if ((rc = upload(c, &s.d_ptaps, s.ptaps.data(), s.ptaps.size()))) { return rc; }
+    if ((rc = dev_alloc(c, &s.d_state, 1))) { return rc; }
+    const size_t cap = v.st[(size_t)v.i_chan].cap;
+    const int hist[3] = { s.delay + v.audio_ntaps - 1, 0, std::max(v.audio_ntaps - 1, 0) };
+    s.st.resize(3);
+    for (int i = 0; i < 3; i++) {
+        if (stream_alloc(c, s.st[(size_t)i], 1, hist[i], cap)) { return SDRPP_ERR_NOMEM; }
+    }
+    if ((rc = stereo_grow_feeds(c, v, s.K))) { return rc; }
+    s.attached = true;
+    s.on = enabled;
+    undo.armed = false;
+    if (enabled || was_on) { return stereo_reset_demod(c, v); }  // (a switch: the demodulator starts over)
+    return stereo_clear(c, v);
+}
+// sdrpp_vfo_replace with keep & 2 between two WFM VFOs: the branch belongs to the demodulator object and moves with it, parameters and state.  Its streams are
+// sized for the IF stream's capacity and the audio filter's length: a new handle that differs in either gets the description attached afresh, and an enabled
+// branch then starts, with the whole demodulator, from the reset() state (*cleared: the caller leaves the new handle's view of the IF stream zero too — a live
+// pilot window in front of zeroed delay and audio lines would be neither the moved state nor a reset one).
+int stereo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, bool* cleared) {
+    Vfo::Stereo& s = o.stereo;
+    *cleared = false;
+    if (!s.attached) { return SDRPP_OK; }
+    if (o.st[(size_t)o.i_chan].cap != n.st[(size_t)n.i_chan].cap || o.audio_ntaps != n.audio_ntaps) {
+        const std::vector<float> taps = s.ptaps;
+        const sdrpp_stereo_desc d{ taps.data(), s.K, s.delay, s.alpha, s.beta, s.init_freq, s.min_freq, s.max_freq, s.on ? 1 : 0 };
+        *cleared = s.on;
+        return stereo_apply(c, n, &d);
+    }
+    n.stereo = std::move(o.stereo);
+    o.stereo = Vfo::Stereo{};
+    n.stereo.ran = false;
+    for (auto& q : n.stereo.st) { q.n = 0; }
+    return stereo_grow_feeds(c, n, n.stereo.K);
 }
 // ---- read-out -----------------------------------------------------------------------------------------------------------------------
 // A pipelined back-end launch whose wavefronts gave up waiting for each other (never seen; a hang would be worse) counted that in THIS context's

@@ -44,6 +44,7 @@ struct IfcJob {
     int nb;
     // kind 1: one segment of FMIF (vfo_fmif_kernels.h) — `in` / `n` are its input stream's data of this push, `out` the chain's output
     // kind 2 / 3 / 4: a job of the WFM demodulator's RDS branch (vfo_rds_kernels.h) — `in` is the address of its RdsJob / RdsRotXJob / RdsLineJob, nothing else is read
+    // kind 5 / 6 / 7: a job of its stereo branch (vfo_stereo_kernels.h) — `in` is the address of its StereoPilotJob / StereoLoopJob / StereoMatrixJob, nothing else is read
     int kind;
     int fm_bins, fm_lo;     // bin count; first sample of the segment
     const float* fm_hist;   // the input stream's history (StreamIn)

@@ -1,10 +1,12 @@
-// The radio's IF chain: noise blanker and power squelch; FMIF (vfo_fmif_kernels.h) and the RDS branch's jobs (vfo_rds_kernels.h) run under the same job record.
+// The radio's IF chain: noise blanker and power squelch; FMIF (vfo_fmif_kernels.h), the RDS branch's jobs (vfo_rds_kernels.h) and the stereo branch's
+// (vfo_stereo_kernels.h) run under the same job record.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <sdrpp_gfx950.h>
 #include "vfo_fmif_kernels.h"
 #include "vfo_rds_kernels.h"
+#include "vfo_stereo_kernels.h"
 
 namespace sdrpp_k {
 
@@ -24,6 +26,12 @@ __device__ __forceinline__ void vfo_ifchain_body(int id, const IfcJob* __restric
     const IfcJob job = jobs[id];
     if (job.kind == 1) {
         vfo_fmif_body(job, smem);
+        return;
+    }
+    if (job.kind >= 5) {  // the WFM demodulator's stereo branch (vfo_stereo_kernels.h): `in` names the job's own record(s)
+        if (job.kind == 5) { vfo_stereo_pilot_call(reinterpret_cast<const StereoPilotJob*>(job.in), smem); }
+        else if (job.kind == 6) { vfo_stereo_loop_call(reinterpret_cast<const StereoLoopJob*>(job.in), smem); }
+        else { vfo_stereo_matrix_call(reinterpret_cast<const StereoMatrixJob*>(job.in), smem); }
         return;
     }
     if (job.kind >= 2) {  // the WFM demodulator's RDS branch (vfo_rds_kernels.h): `in` names the job's own record

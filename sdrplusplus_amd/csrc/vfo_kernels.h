@@ -20,6 +20,7 @@
 #include "vfo_fir_kernels.h"
 #include "vfo_demod_kernels.h"
 #include "vfo_rds_kernels.h"
+#include "vfo_stereo_kernels.h"
 #include "vfo_ifchain_kernels.h"
 #include "vfo_carry_kernels.h"
 #include "vfo_af_kernels.h"

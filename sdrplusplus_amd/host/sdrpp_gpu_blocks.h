@@ -147,6 +147,10 @@ public:
     void attachRDS();
     void detachRDS();
     void setRDSOut(bool enabled);
+    // The WFM demodulator's stereo decoder (dsp/demod/broadcast_fm.h:147-191, `_stereo`; sdrpp_vfo_set_stereo) on the device: pilot filter, PLL, L-R matrix and the
+    // L / R low-passes; `audio` then carries (l, r) frames, and the AF chain and the recorder behind it see them.  A switch is BroadcastFM::setStereo: the
+    // demodulator starts over (discriminator, pilot filter, loop, delays and audio filters cleared).  Re-plans that keep the demodulator keep the decoder's state.
+    void setStereo(bool enabled);
     dsp::stereo_t getRecorderLevel();  // PeakLevelMeter::getLevel / resetLevel: the running maximum over the blocks since the last reset
     void resetRecorderLevel();
     // The waterfall's signal read-out for this VFO (calculateVFOSignalInfo, waterfall.cpp:558-598: what the reference shows for the selected VFO on every
@@ -190,6 +194,7 @@ public:
     double afAudioRate = 48000.0, afDeempTau = 50e-6;
     bool recOn = false, recMono = false, recIgnoreSilence = false;
     bool rdsAttached = false, rdsOn = false;
+    bool stereoAttached = false, stereoOn = false;
     double recVolume = 1.0;
     int recType = SDRPP_REC_INT16;
 
@@ -1445,6 +1450,7 @@ private:
         if (v.afOn && v.demod != Demod::RAW) { applyAF(v); }
         if (v.recOn && v.demod != Demod::RAW) { applyRec(v); }  // (sdrpp_vfo_replace does not carry the sink: the recorder binds to the stream, and the stream lives on)
         if (v.rdsAttached && v.demod == Demod::WFM) { applyRDS(v); }  // (a handle that kept its demodulator has the branch already, state and all: the same description only sets the switch)
+        if (v.stereoAttached && v.demod == Demod::WFM) { applyStereo(v); }  // (likewise: the same description and switch change nothing)
         sendMeters();  // (a new handle, perhaps a new bandwidth or input rate)
     }
 
@@ -1494,6 +1500,29 @@ private:
         r.resamp_taps = rtaps.data();
         int rc = sdrpp_vfo_set_rds(ctx, v.id, &r, v.rdsOn ? 1 : 0);
         if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_rds: ") + sdrpp_last_error(ctx)); }
+    }
+
+    // broadcast_fm.h:43-48: pilotFirTaps = bandPass<complex_t>(18750, 19250, 3000, samplerate, true); pilotPLL.init(NULL, 25000 / samplerate, 0, 19 kHz, 18.75 kHz,
+    // 19.25 kHz in radians per sample); both delays (taps - 1) / 2 + 1
+    void applyStereo(RxVFO& v) {
+        const double sr = v.outSamplerate;
+        const int nt = sdrpp_design_band_pass_complex(18750.0, 19250.0, 3000.0, sr, 1, nullptr, 0);
+        if (nt <= 0) { throw std::runtime_error("[sdrpp_gpu::IQFrontEnd] stereo pilot filter design failed"); }
+        std::vector<float> taps((size_t)nt * 2);
+        sdrpp_design_band_pass_complex(18750.0, 19250.0, 3000.0, sr, 1, taps.data(), 2 * nt);
+        const double twoPi = 2.0 * 3.14159265358979323846;  // math/hz_to_rads.h:6-8
+        sdrpp_stereo_desc s;
+        memset(&s, 0, sizeof(s));
+        s.pilot_taps = taps.data();
+        s.pilot_ntaps = nt;
+        s.delay = (nt - 1) / 2 + 1;
+        sdrpp_design_pll(25000.0 / sr, &s.alpha, &s.beta);
+        s.init_freq = (float)(twoPi * (19000.0 / sr));
+        s.min_freq = (float)(twoPi * (18750.0 / sr));
+        s.max_freq = (float)(twoPi * (19250.0 / sr));
+        s.enabled = v.stereoOn ? 1 : 0;
+        int rc = sdrpp_vfo_set_stereo(ctx, v.id, &s);
+        if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_stereo: ") + sdrpp_last_error(ctx)); }
     }
 
     // radio_module.h:90-91: nb.init(NULL, 500.0 / ifRate, 10.0); powerSquelch.init(NULL, MIN_SQUELCH)
@@ -1886,6 +1915,16 @@ inline void RxVFO::setRDSOut(bool enabled) {
     fe->tempStop();  // broadcast_fm.h:121-128
     rdsOn = enabled;
     if (id >= 0 && demod == Demod::WFM) { fe->applyRDS(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::setStereo(bool enabled) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (enabled && demod != Demod::WFM) { throw std::runtime_error("[sdrpp_gpu::RxVFO] the stereo decoder belongs to the WFM demodulator"); }
+    if (!stereoAttached && !enabled) { return; }
+    fe->tempStop();  // broadcast_fm.h:103-110
+    stereoAttached = true;
+    stereoOn = enabled;
+    if (id >= 0 && demod == Demod::WFM) { fe->applyStereo(*this); }
     fe->tempStart();
 }
 inline dsp::stereo_t RxVFO::getRecorderLevel() {

@@ -132,6 +132,13 @@ public:
         _rdsOut = enabled;
         if (vfo) { vfo->setRDSOut(enabled); }
     }
+    // WFM only (wfm.h `_stereo`, demod.setStereo(_stereo)): the demodulator's stereo decoder on the device; getOutput() then carries (l, r) frames.  As in the
+    // reference every switch makes the demodulator start over (BroadcastFM::setStereo calls reset()).
+    void setStereo(bool enabled) {
+        if (MODE != Demod::WFM) { throw std::runtime_error("[sdrpp_gpu::FusedDemodulator] the stereo decoder belongs to the WFM demodulator"); }
+        _stereo = enabled;
+        if (vfo) { vfo->setStereo(enabled); }
+    }
     dsp::stream<dsp::complex_t>* getRDSOutput() { return (MODE == Demod::WFM && vfo) ? &vfo->rdsOut : nullptr; }
     RxVFO* channel() { return vfo; }
 
@@ -148,12 +155,14 @@ private:
             vfo->setSquelch(false, _squelchLevel);
             vfo->setFMIFNR(false, vfo->fmnrBins);
             if (vfo->rdsAttached) { vfo->detachRDS(); }
+            if (vfo->stereoOn) { vfo->setStereo(false); }
             vfo->attachDemod(Demod::RAW);
         }
         vfo = v;
         apply();
         applyIF();
         if (MODE == Demod::WFM && _rdsOut) { vfo->setRDSOut(true); }
+        if (MODE == Demod::WFM && _stereo) { vfo->setStereo(true); }
     }
     void apply() {
         if (!vfo) { return; }
@@ -180,6 +189,7 @@ private:
     int _tone = 800;  // cw.h:107
     bool _nbEnabled = false, _squelchEnabled = false, _fmnrEnabled = false;
     bool _rdsOut = false;
+    bool _stereo = false;
     int _fmnrBins = 32;  // radio_module.h:91
     float _nbLevel = 10.0f, _squelchLevel = -100.0f;  // radio_module.h:906, :446
 };

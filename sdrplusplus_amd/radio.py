@@ -227,6 +227,23 @@ def rds_desc(if_rate=250e3, out_rate=5000.0, offset=-57000.0):
     return r, keep
 
 
+def stereo_desc(if_rate=250e3, enabled=True):
+    """sdrpp_stereo_desc for the WFM demodulator's stereo branch as BroadcastFM::init sets it up (broadcast_fm.h:43-48): the complex pilot band-pass
+    bandPass<complex_t>(18750, 19250, 3000, if_rate, odd), PLL(25000 / if_rate, phase 0, 19 kHz, limits 18.75 / 19.25 kHz), delay (taps - 1) / 2 + 1.
+    Returns (desc, keepalive)."""
+    s = capi.StereoDesc()
+    taps = np.ascontiguousarray(capi.design_band_pass_complex(18750.0, 19250.0, 3000.0, if_rate, True))
+    s.pilot_taps = _fp(taps.view(np.float32))
+    s.pilot_ntaps = len(taps)
+    s.delay = (len(taps) - 1) // 2 + 1
+    s.alpha, s.beta = capi.design_pll(25000.0 / if_rate)
+    s.init_freq = np.float32(hz_to_rads(19000.0, if_rate))
+    s.min_freq = np.float32(hz_to_rads(18750.0, if_rate))
+    s.max_freq = np.float32(hz_to_rads(19250.0, if_rate))
+    s.enabled = int(bool(enabled))
+    return s, [taps]
+
+
 def if_desc(if_rate, nb=False, nb_level=10.0, squelch=None):
     """sdrpp_if_desc for the radio module's IF chain (radio_module.h:84-96): NoiseBlanker(rate = 500 / if_rate, level; :90, :526) ->
     PowerSquelch(level in dB; None = off).  FMIF, the chain's last block, is switched by Context.vfo_set_fmnr (IFNR_BINS); the CTCSS squelch is not on the device."""
