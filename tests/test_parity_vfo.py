@@ -408,6 +408,47 @@ def test_reference_rotator_mode_retune_and_reset(backend):
     ctx.close()
 
 
+def _look_ahead_is_exercised(name, sr, specs, x, pushes, blocks):
+    """What test_agc_look_ahead_follows_reference_blocks is named for, stated on the CPU: the oracle's IF, block by block, through the float32 restatement of the
+    demodulator tails (test_demod_tails.tail, pinned to the oracle bit for bit there).  Every VFO's AGC must look ahead in at least three different blocks, and
+    a look-ahead cut at the PUSH ends instead of the block ends must move that VFO's audio by more than the test's own 1e-5 bar."""
+    from sdrplusplus_amd import radio
+    from test_demod_tails import desc_params, geom, tail
+    from test_kernel_forms import _parts
+
+    o = S.oracle()
+    push_ends = set(np.cumsum(pushes).tolist())
+    for k, (mode, off) in enumerate(specs):
+        if_rate, bw = radio.RADIO_DEFAULTS[mode]
+        ch = S.OracleChain(sr, if_rate, bw, off, None)
+        xl = o.orc_xlator_create(bw / 2.0, if_rate) if mode == "USB" else None  # the second translation (ssb.h:78), call by call as the demodulator makes them
+        parts, pos = [], 0
+        for n in blocks:
+            y = ch.vfo_process(x[pos:pos + n])
+            pos += n
+            if xl is not None and len(y):
+                y2 = np.empty_like(y)
+                o.orc_xlator_process(xl, len(y), S._fp(y.view(np.float32)), S._fp(y2.view(np.float32)))
+                y = y2
+            parts.append(y)
+        ch.close()
+        if xl is not None:
+            o.orc_xlator_destroy(xl)
+        ends = np.cumsum([len(q) for q in parts]).tolist()
+        at_push = [e for e, cin in zip(ends, np.cumsum(blocks).tolist()) if cin in push_ends]
+        d, keep = radio.vfo_desc(sr, if_rate, bw, off, mode, carrier_agc=(k == 2))
+        tmode = "DSB" if mode == "USB" else ("AMC" if k == 2 else "AMA")
+        ataps = None if mode == "USB" else _parts(d)["ataps"]
+        y = np.concatenate(parts)
+        audio, info = tail(tmode, y, desc_params(d), ends, np.float32, ataps)
+        in_blocks = {geom(q, ends)["block"] for q in info["clips"]}
+        assert len(in_blocks) >= 3, (name, mode, off, "the AGC looks ahead in fewer than three blocks", info["clips"])
+        if len(at_push) < len(ends):
+            cut, _ = tail(tmode, y, desc_params(d), at_push, np.float32, ataps)
+            moved = rms(cut - audio) / max(1.0, rms(audio))
+            assert moved > 1e-5, (name, mode, off, "a look-ahead to the end of the push would pass this test", moved)
+
+
 def test_agc_look_ahead_follows_reference_blocks(backend):
     """loop::AGC rescans to the end of the CURRENT BLOCK when its output would clip (agc.h:91-104).  Bursts 30 dB above the settled
     level make it do so in AM (audio AGC, carrier AGC) and SSB; with sdrpp_set_reference_block the device cuts its look-ahead at the
@@ -438,6 +479,7 @@ def test_agc_look_ahead_follows_reference_blocks(backend):
         blocks = []
         for p in pushes:
             blocks += [B] * (p // B) + ([p % B] if p % B else [])
+        _look_ahead_is_exercised(name, sr, specs, x, pushes, blocks)
         res = _compare_streams(ctx, vids, chains, specs, x, pushes, blocks)
         for key, (e_if, e_a) in res.items():
             assert e_a < 1e-5, (name, key, e_a)  # offsets are multiples of sr/8 or FM/AM-insensitive: no rotator drift in the way
