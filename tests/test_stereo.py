@@ -240,9 +240,9 @@ def test_cuts_give_identical_bits(backend, sizes):
 
 
 # ---- 6. bank shapes ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nst", [1, 3, PACK + 1])
+@pytest.mark.parametrize("nst", [1, 2, 3, PACK, PACK + 1])
 def test_bank_shapes_bit_for_bit_per_vfo(backend, nst):
-    """1, 3 and one more stereo VFO than a loop job packs, mixed with a mono WFM and an NFM VFO: every stereo VFO gives the bits of a bank of one, the mono and
+    """1, 2, 3, as many stereo VFOs as a loop job packs and one more, mixed with a mono WFM and an NFM VFO: every stereo VFO gives the bits of a bank of one, the mono and
     NFM VFOs those of the same bank with no stereo VFO.  (The stereo VFOs get the input with different block phases: VFO k runs with its low-pass on for even k.)"""
     x = case_x("cuts")[:4000]
     sched = schedule(len(x), [1250, 333])
