@@ -338,7 +338,12 @@ struct IdxCols {
 // exchange, twiddles, store — in lock-step on all CUs: 0.31-0.40 of the HBM rate with ~1 050 vector instructions per work-item being only
 // a quarter of the time).  With step a multiple of the tiles per frame a workgroup stays on its columns: window values are loaded once.
 // scratch layout: A[frame][k1][n2] (n2 contiguous); tw_n2k1 has the same [k1][n2] layout and holds tw(n2*k1, N).
-template <int LG1, int C>
+// EARLY: the window values AND the 16 inter-pass twiddles of the workgroup's columns — both depend on (work-item, columns) only — are asked
+// for together with the first tile's samples and stay in registers for the whole walk: one wait for global memory per tile, and the store
+// loop consumes registers.  Without it the twiddle loads sit in the store loop behind the last LDS barrier, every store a whole L2 round
+// trip behind a load issued a few instructions earlier with nothing left to hide it.  32 registers: the tick roles take it, the
+// stand-alone kernels (128-register builds that spill already) do not.  The arithmetic and its order are the same in both forms.
+template <int LG1, int C, bool EARLY>
 __device__ __forceinline__ void fft_pass1_body(const KIdx bid, float2* tw, float2* data, const IqSrc& src, const FrameGeom& g, const float* __restrict__ window,
                                                const float2* __restrict__ tw1_g, const float2* __restrict__ tw_n2k1, float2* __restrict__ scratch, int lg2, int ntiles, int step) {
     constexpr int L1 = 1 << LG1;
@@ -377,20 +382,36 @@ __device__ __forceinline__ void fft_pass1_body(const KIdx bid, float2* tw, float
         }
     };
     float wv[16];
+    float2 wk[EARLY ? 16 : 1];
     int wv_n2 = -1;
+    auto columns = [&](int t, int n2) {  // what belongs to a tile's columns, whatever the frame
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const int n1 = (int)(__brev((unsigned)R0::pos(t, 0, j)) >> (32 - LG1));
+            const int i = (n1 << lg2) + n2;
+            wv[j] = global_load_f32(window, i < g.nz ? i : 0);
+        }
+        if constexpr (EARLY) {
+#pragma unroll
+            for (int i = 0; i < RL::NG; i++) {
+#pragma unroll
+                for (int j = 0; j < RL::GS; j++) { wk[i * RL::GS + j] = global_load_f32x2_boff(tw_n2k1, (unsigned)((RL::pos(t, i, j) << lg2) + n2) * 8u); }
+            }
+        }
+        wv_n2 = n2;
+    };
+    bool marks = true;  // (ticktrace build: the marks of a workgroup are those of its first tile)
     auto transform = [&](float2 (&r)[16], int tile) {
         const int t = opaque(t_), c = opaque(c_);  // (per-tile copies the optimiser cannot see through: it would otherwise hoist every LDS / global
                                                    // address of the transform out of the tile loop and keep ~60 more registers alive across it)
         const int frame = tile / tiles, n2 = (tile % tiles) * C + c;
-        if (n2 != wv_n2) {  // (uniform: all work-items of a workgroup change columns together)
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                const int n1 = (int)(__brev((unsigned)R0::pos(t, 0, j)) >> (32 - LG1));
-                const int i = (n1 << lg2) + n2;
-                wv[j] = global_load_f32(window, i < g.nz ? i : 0);
-            }
-            wv_n2 = n2;
+        if (n2 != wv_n2) { columns(t, n2); }  // (uniform: all work-items of a workgroup change columns together; a grid of fft_walk_grid never does)
+#ifdef SDRPP_TICK_TRACE
+        if (marks) {
+            wave_stores_done();
+            TICK_MARK(0);
         }
+#endif
         if (dense) {  // (uniform) every input of the transform is a windowed sample
 #pragma unroll
             for (int j = 0; j < 16; j++) { r[j] = make_float2(r[j].x * wv[j], r[j].y * wv[j]); }
@@ -406,6 +427,7 @@ __device__ __forceinline__ void fft_pass1_body(const KIdx bid, float2* tw, float
         R0::compute(r, t, tw);
         IdxCols idx{ C, c };
         fft_rounds_after_first<LG1, 4, IdxCols>(r, t, tw, data, idx);
+        if (marks) { TICK_MARK(1); }
         float2* dst = scratch + ((size_t)frame << (LG1 + lg2));  // (uniform; a frame's scratch is at most 8 MiB: 32-bit byte offsets)
 #pragma unroll
         for (int i = 0; i < RL::NG; i++) {
@@ -414,16 +436,33 @@ __device__ __forceinline__ void fft_pass1_body(const KIdx bid, float2* tw, float
                 const int k1 = RL::pos(t, i, j);
                 const unsigned o = (unsigned)((k1 << lg2) + n2) * 8u;
                 const float2 a = r[i * RL::GS + j];
-                const float2 w = global_load_f32x2_boff(tw_n2k1, o);
+                float2 w;
+                if constexpr (EARLY) { w = wk[i * RL::GS + j]; }
+                else { w = global_load_f32x2_boff(tw_n2k1, o); }
                 const float pp = a.y * w.y;
                 const float qq = a.y * w.x;
                 global_store_f32x2_boff(dst, o, make_float2(fmaf(a.x, w.x, -pp), fmaf(a.x, w.y, qq)));
+                if (marks && i == 0 && j == 0) { TICK_MARK(2); }
             }
         }
+        marks = false;
     };
-    float2 r[16], rn[16];
+    float2 r[16];
     int tile = bid.x;
     if (tile >= ntiles) { return; }  // (no barrier has been passed yet)
+    if constexpr (EARLY) {
+        // The 32 registers of the twiddles are those of the next tile's samples: a walk of this form asks for them right behind the current tile's
+        // stores instead of in front of its transform.  What a later tile saves is the workgroup's prologue and the loads of its columns.
+        for (bool first = true; tile < ntiles; tile += step, first = false) {
+            fetch(r, tile);
+            if (first) {  // (uniform)
+                columns(opaque(t_), (tile % tiles) * C + opaque(c_));
+                __syncthreads();  // twiddle table visible
+            }
+            transform(r, tile);
+        }
+        return;
+    }
     fetch(r, tile);
     __syncthreads();  // twiddle table visible
 #ifdef SDRPP_FFT_NO_PREFETCH  // (diagnostic build: the tile walk without the loads in flight)
@@ -434,6 +473,7 @@ __device__ __forceinline__ void fft_pass1_body(const KIdx bid, float2* tw, float
         fetch(r, tile);
     }
 #else
+    float2 rn[16];
     while (true) {
         const int next = tile + step;
         const bool more = next < ntiles;
@@ -452,7 +492,7 @@ __global__ __launch_bounds__(((1 << LG1) / 16) * C, (((1 << LG1) / 16) * C) <= 2
                                                                          float2* __restrict__ scratch, int lg2, int ntiles) {
     __shared__ float2 tw[(1 << LG1) / 2];
     __shared__ float2 data[(1 << LG1) * C];
-    fft_pass1_body<LG1, C>(kidx(blockIdx), tw, data, src, g, window, tw1_g, tw_n2k1, scratch, lg2, ntiles, (int)gridDim.x);
+    fft_pass1_body<LG1, C, false>(kidx(blockIdx), tw, data, src, g, window, tw1_g, tw_n2k1, scratch, lg2, ntiles, (int)gridDim.x);
 }
 
 // ---- N > 4096, pass 2: row FFTs + dB, output bin k = k1 + N1*k2 ------------------------------------------------------------------
@@ -463,9 +503,15 @@ struct IdxRowPad {
 
 // block = (N2/16) * R work-items, t fastest (coalesced row reads); a workgroup walks the tiles bid.x, bid.x + step, ... of the
 // ntiles = nframes * (N1 / R) row tiles and keeps the next tile's rows in flight while it transforms the current one (see fft_pass1_body).
-template <int LG2, int R>
+// PAIR (a frame has an even number of row tiles under every split of fft_split): the walk is over PAIRS of adjacent row tiles of one frame,
+// 2 * bid.x and 2 * bid.x + 1, then `step` pairs on; the dB values of the first tile of a pair wait in 16 registers and leave together with
+// the second's.  Values, group maxima and their places are those of single tiles.  The tick roles take it; the stand-alone kernels, 128-register
+// builds, have no room for the 16 registers and walk single tiles.
+template <int LG2, int R, bool PAIR>
 __device__ __forceinline__ void fft_pass2_body(const KIdx bid, float2* tw, float2* data, const float2* __restrict__ scratch, const float2* __restrict__ tw2_g,
                                                float* __restrict__ out_db, int lg1, int ntiles, float* __restrict__ grp_max, int step) {
+    constexpr bool pair = PAIR;
+    static_assert(((1 << LG2) / 16) * R == 256 && (1 << LG2) * R == 4096 && R % 4 == 0, "256 work-items, 4096 values per tile, whole quads per row tile");
     constexpr int L2 = 1 << LG2;
     constexpr int TPF = L2 / 16;
     constexpr int PITCH = L2 + L2 / 16;
@@ -488,13 +534,22 @@ __device__ __forceinline__ void fft_pass2_body(const KIdx bid, float2* tw, float
         }
     };
     const float inv = 1.0f / (float)((size_t)1 << (LG2 + lg1));
+    float4 held[4];
+    bool marks = true;  // (ticktrace build: the marks of a workgroup are those of its first tile and of its first store)
     auto transform = [&](float2 (&r)[16], int tile) {
         const int t = opaque(t_), row = opaque(row_), tid = opaque((int)threadIdx.x);  // (see fft_pass1_body)
         const int frame = tile / tiles, r0 = (tile % tiles) * R;
+#ifdef SDRPP_TICK_TRACE
+        if (marks && tile == (pair ? 2 : 1) * bid.x) {
+            wave_stores_done();
+            TICK_MARK(0);
+        }
+#endif
         R0::compute(r, t, tw);
         // (fft_rounds_after_first opens with a barrier: the previous tile's dB values have been read out of `data` before it is rewritten)
         IdxRowPad idx{ row * PITCH };
         fft_rounds_after_first<LG2, 4, IdxRowPad>(r, t, tw, data, idx);
+        if (marks && tile == (pair ? 2 : 1) * bid.x) { TICK_MARK(1); }
         // dB values are transposed through LDS so that consecutive lanes write consecutive k1 (k = k1 + N1*k2).
         __syncthreads();
         float* tile_db = reinterpret_cast<float*>(data);  // [k2][R + 1]
@@ -518,20 +573,38 @@ __device__ __forceinline__ void fft_pass2_body(const KIdx bid, float2* tw, float
             }
         }
         __syncthreads();
-        float* dst = out_db + ((size_t)frame << (LG2 + lg1)) + r0;  // (uniform; a line is at most 4 MiB: 32-bit byte offsets)
-        {   // element e = tid + it * (TPF * R), it = 0 .. 15 -> k2 = e / R = tid / R + it * TPF, rr = e % R = tid % R: every step adds constants
-            const int k2_0 = tid / R, rr = tid % R;
+        float* dst = out_db + ((size_t)frame << (LG2 + lg1)) + r0;  // (uniform)
+        {   // the tile as quads of four consecutive k1: quad e = tid + it * 256, it = 0 .. 3 -> k2 = e / QPT = tid / QPT + it * (256 / QPT), q = e % QPT = tid % QPT
+            constexpr int QPT = R / 4;
+            const int k2_0 = tid / QPT, q4 = (tid % QPT) * 4;
+            float4 v[4];
 #pragma unroll
-            for (int it = 0; it < 16; it++) {
-                const int k2 = k2_0 + it * TPF;
-                global_store_f32_boff(dst, (unsigned)((k2 << lg1) + rr) * 4u, tile_db[k2 * (R + 1) + rr]);
+            for (int it = 0; it < 4; it++) {
+                const float* s = &tile_db[(k2_0 + it * (256 / QPT)) * (R + 1) + q4];
+                v[it] = make_float4(s[0], s[1], s[2], s[3]);
+            }
+            if (pair && !(tile & 1)) {  // (uniform) first tile of a pair: its values wait in registers for the second's
+#pragma unroll
+                for (int it = 0; it < 4; it++) { held[it] = v[it]; }
+            }
+            else {
+                // 16-byte stores (r0, the quads and the lines are multiples of four floats); behind the second tile of a pair every k2 gets its 2R
+                // consecutive floats from this one workgroup, back to back — for R = 16 a whole 128-byte line, where single tiles leave each
+                // line half to one workgroup and half to another, at different times and through whichever L2 each of them runs behind
+#pragma unroll
+                for (int it = 0; it < 4; it++) {
+                    const long long o = (long long)(((k2_0 + it * (256 / QPT)) << lg1) + q4);
+                    if (pair) { global_store_f32x4_unaligned(dst - R, o, held[it]); }
+                    global_store_f32x4_unaligned(dst, o, v[it]);
+                    if (marks && it == 0) { TICK_MARK(2); }
+                }
+                marks = false;
             }
         }
         // doZoom's maximum over the R consecutive bins k1 = r0 .. r0 + R - 1 of every k2, while the tile is in LDS: the zoom kernel then
         // reads one value per aligned group of R bins instead of R (waterfall.cpp:65-90 takes a maximum, which does not care how it is split)
         if (grp_max) {
             float* gdst = grp_max + (((size_t)frame << (LG2 + lg1)) + r0) / R;
-            static_assert(TPF * R == 256 && L2 * R == 4096, "256 work-items, 4096 values per tile");
 #pragma unroll
             for (int k2 = tid; k2 < L2; k2 += 256) {
                 float m = __uint_as_float(0xff800000u);
@@ -545,20 +618,22 @@ __device__ __forceinline__ void fft_pass2_body(const KIdx bid, float2* tw, float
         }
     };
     float2 r[16], rn[16];
-    int tile = bid.x;
+    int tile = pair ? 2 * bid.x : bid.x;
     if (tile >= ntiles) { return; }  // (no barrier has been passed yet)
     fetch(r, tile);
     __syncthreads();  // twiddle table visible
+    // (pairs: ntiles is even, so the second tile of a pair is always there)
+    auto after = [&](int cur) { return pair ? ((cur & 1) ? cur - 1 + 2 * step : cur + 1) : cur + step; };
 #ifdef SDRPP_FFT_NO_PREFETCH  // (diagnostic build: the tile walk without the loads in flight)
     while (true) {
         transform(r, tile);
-        tile += step;
+        tile = after(tile);
         if (tile >= ntiles) { break; }
         fetch(r, tile);
     }
 #else
     while (true) {
-        const int next = tile + step;
+        const int next = after(tile);
         const bool more = next < ntiles;
         if (more) { fetch(rn, next); }  // in flight during the transform below
         transform(r, tile);
@@ -574,7 +649,7 @@ __global__ __launch_bounds__(((1 << LG2) / 16) * R, 4) void fft_pass2_kernel(con
                                                                          float* __restrict__ out_db, int lg1, int ntiles, float* __restrict__ grp_max) {
     __shared__ float2 tw[(1 << LG2) / 2];
     __shared__ float2 data[R * ((1 << LG2) + (1 << LG2) / 16)];
-    fft_pass2_body<LG2, R>(kidx(blockIdx), tw, data, scratch, tw2_g, out_db, lg1, ntiles, grp_max, (int)gridDim.x);
+    fft_pass2_body<LG2, R, false>(kidx(blockIdx), tw, data, scratch, tw2_g, out_db, lg1, ntiles, grp_max, (int)gridDim.x);
 }
 
 // ---- N > 65536, pass 2: ONE 4096-point row per workgroup ------------------------------------------------------------------------------

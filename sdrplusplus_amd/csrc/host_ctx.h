@@ -385,6 +385,10 @@ struct sdrpp_ctx {
     int fft_p1_grid = getenv("SDRPP_GPU_FFT_P1_GRID") ? atoi(getenv("SDRPP_GPU_FFT_P1_GRID")) : 1024;
     int fft_p2_grid = getenv("SDRPP_GPU_FFT_P2_GRID") ? atoi(getenv("SDRPP_GPU_FFT_P2_GRID")) : 0;
     int fft_tick_grid = getenv("SDRPP_GPU_FFT_TICK_GRID") ? atoi(getenv("SDRPP_GPU_FFT_TICK_GRID")) : 0;  // ... of a pass-1 / pass-2 role inside a tick (a shared GPU: 18.4 / 16.2 / 18.8 / 18.5 GS/s at 0 / 64 / 128 / 256; cfg 2: 61.7 / - / 57.0)
+    // tiles a workgroup of those roles takes where no grid is forced (plan_fft.h: fft_tick_walk_grid): pass 1 the tiles of its columns from two consecutive
+    // frames, pass 2 one pair of adjacent row tiles.  10^6-sample blocks, tick per block at 1 / 2 / 4 tiles for pass 1 (pass 2: 1 / 1 / 2 pairs): cfg 2
+    // 13.25 / 12.0 / 17.3 us, cfg 3 45.28 / 45.43 / 48.3 us (parent 14.51 and 45.72: profiles/fft_roles_rate.md)
+    int fft_tick_tiles = 2;
     int tick_zoom_groups = getenv("SDRPP_GPU_TICK_ZOOM_GROUPS") ? atoi(getenv("SDRPP_GPU_TICK_ZOOM_GROUPS")) : 8;
     int tick_fcm_waves = getenv("SDRPP_GPU_TICK_FCM_WAVES") ? atoi(getenv("SDRPP_GPU_TICK_FCM_WAVES")) : 768;
     // wavefronts the tiles of ONE matrix front-end job (vfo_frontcm / vfo_frontcl) are dealt out over, in a pass and in a tick alike; 0: the rules of

@@ -12,6 +12,14 @@ inline int fft_walk_grid(int ntiles, int per_frame, int cap) {
     if (cap <= 0 || ntiles <= cap) { return ntiles; }
     return std::max(per_frame, (cap / per_frame) * per_frame);
 }
+// ... of a pass-1 / pass-2 role inside a tick: SDRPP_GPU_FFT_TICK_GRID as the cap it is, else `walk` units per workgroup.  A unit of pass 1 is a
+// tile (a workgroup takes the tiles of its columns from consecutive frames), a unit of pass 2 a PAIR of adjacent row tiles of one frame
+// (fft_pass2_body<.., true>: every k2 then gets the 2R consecutive dB values of both tiles from one workgroup)
+inline int fft_tick_walk_grid(const sdrpp_ctx* c, int units, int per_frame, int walk) {
+    if (c->fft_tick_grid > 0) { return fft_walk_grid(units, per_frame, c->fft_tick_grid); }
+    const int frames = units / per_frame, k = std::max(1, walk);
+    return per_frame * ((frames + k - 1) / k);
+}
 template <int LG, int FPW>
 void launch_single(sdrpp_ctx* c, const IqSrc& src, const FrameGeom& g, float* out) {
     const int blocks = (g.nframes + FPW - 1) / FPW;
@@ -71,7 +79,7 @@ int plan_fft_roles(sdrpp_ctx* c, const IqSrc& src, const FrameGeom& g, float* ou
     r.e.role = p1_role[lg1 - 5];
     {
         const int per_frame = (1 << lg2) / p1_c[lg1 - 5], ntiles = g.nframes * per_frame;
-        r.e.gx = fft_walk_grid(ntiles, per_frame, c->fft_tick_grid);
+        r.e.gx = fft_tick_walk_grid(c, ntiles, per_frame, c->fft_tick_tiles);
         r.e.p.p1 = TickP1{ src, g, c->d_window, c->d_tw1, c->d_twn, c->d_scratch, lg2, ntiles };
     }
     r.lds = tick_lds_fft_p1(lg1, p1_c[lg1 - 5]);
@@ -105,7 +113,8 @@ int plan_fft_roles(sdrpp_ctx* c, const IqSrc& src, const FrameGeom& g, float* ou
     q.e.role = p2_role[lg2 - 7];
     {
         const int per_frame = (1 << lg1) / pass2_rows(lg2), ntiles = g.nframes * per_frame;
-        q.e.gx = fft_walk_grid(ntiles, per_frame, c->fft_tick_grid);
+        static_assert(pass2_rows(7) * 2 <= (1 << 6), "every split of fft_split leaves a frame an even number of row tiles");  // (lg1 >= 6 for m = 13, and R shrinks as lg2 grows)
+        q.e.gx = fft_tick_walk_grid(c, ntiles / 2, per_frame / 2, c->fft_tick_tiles / 2);
         q.e.p.p2 = TickP2{ c->d_scratch, c->d_tw2, out, grp, lg1, ntiles };
     }
     q.lds = tick_lds_fft_p2(lg2, pass2_rows(lg2));

@@ -222,13 +222,14 @@ __device__ __forceinline__ void tick_fft_p1(const KIdx bid, const KIdx gdim, flo
     const IqSrc src = q.src;
     const FrameGeom g = q.g;
     float2* tw = reinterpret_cast<float2*>(smem);
-    fft_pass1_body<LG1, C>(bid, tw, tw + (1 << LG1) / 2, src, g, q.window, q.tw1, q.twn, q.scratch, q.lg2, q.ntiles, gdim.x);
+    // (the form with the columns' window values and inter-pass twiddles in registers: in a tick a workgroup's life is what the FFT roles cost)
+    fft_pass1_body<LG1, C, true>(bid, tw, tw + (1 << LG1) / 2, src, g, q.window, q.tw1, q.twn, q.scratch, q.lg2, q.ntiles, gdim.x);
 }
 template <int LG2, int R>
 __device__ __forceinline__ void tick_fft_p2(const KIdx bid, const KIdx gdim, float* smem, const TickP2& q) {
     static_assert(((1 << LG2) / 16) * R == 256, "tick roles run in 256-thread workgroups");
     float2* tw = reinterpret_cast<float2*>(smem);
-    fft_pass2_body<LG2, R>(bid, tw, tw + (1 << LG2) / 2, q.scratch, q.tw2, q.out, q.lg1, q.ntiles, q.grp, gdim.x);
+    fft_pass2_body<LG2, R, true>(bid, tw, tw + (1 << LG2) / 2, q.scratch, q.tw2, q.out, q.lg1, q.ntiles, q.grp, gdim.x);  // (pairs of row tiles: the planner counts its grid in pairs)
 }
 // (a zoom workgroup of the stand-alone kernel covers 256 / TP pixels of one line — a few microseconds of latency and next to no work, yet a
 // resident workgroup slot for that long: in a tick, where slots are what the roles compete for, one workgroup walks `groups` such pixel groups)
