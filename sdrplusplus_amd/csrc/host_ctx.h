@@ -201,6 +201,20 @@ struct Vfo {
         int base = -1;  // first AF stream in st (they are appended behind the VFO's own streams)
     } af;
 };
+// Every stream of a VFO: its own, then its RDS branch's, then its stereo branch's (the order plan_snapshot records them in).  ran_only: a branch's streams
+// only if the most recent plan ran the branch.
+template <class F>
+void for_each_stream(Vfo& v, F&& f, bool ran_only = false) {
+    for (auto& s : v.st) { f(s); }
+    if (!ran_only || v.rds.ran) {
+        for (auto& s : v.rds.st) { f(s); }
+    }
+    if (!ran_only || v.stereo.ran) {
+        for (auto& s : v.stereo.st) { f(s); }
+    }
+}
+template <class F>
+void for_each_stream_that_ran(Vfo& v, F&& f) { for_each_stream(v, f, true); }
 
 struct TimingPair { hipEvent_t a, b; int family; };
 

@@ -497,7 +497,7 @@ bool rds_tile_geometry(int K, int D, int* tile, int* pitch) {
             const int g = 16 / D;
             while (P % (2 * g) != g) { P++; }
         }
-        if (2 * D * P + (t - 1) * D + K + 1 <= SDRPP_RDS_LDS_WAVE) {  // the window, then one phase per sample and one in front
+        if (2 * D * P + (t - 1) * D + K + 1 <= SDRPP_WAVE_LDS_FLOATS) {  // the window, then one phase per sample and one in front
             *tile = t;
             *pitch = P;
             return true;
@@ -696,7 +696,7 @@ void launch_role(sdrpp_ctx* c, const sdrpp_ctx::RoleLaunch& r) {
     case TR_FIRB_Q: hipLaunchKernelGGL((vfo_firb_kernel<1, true, true>), grid, dim3((unsigned)e.aux), r.lds, st, (const FirBJob*)e.jobs); break;
     case TR_PRE: hipLaunchKernelGGL(vfo_demod_pre_kernel, grid, b256, 0, st, (const PreJob*)e.jobs); break;
     case TR_SEQ: hipLaunchKernelGGL(vfo_sequential_kernel, grid, dim3(64), 0, st, (const SeqJob*)e.jobs, e.aux); break;
-    case TR_IFC: hipLaunchKernelGGL(vfo_ifchain_kernel, grid, b256, r.lds, st, (const IfcJob*)e.jobs, e.aux); break;
+    case TR_IFC: hipLaunchKernelGGL(vfo_ifchain_kernel, grid, b256, r.lds, st, (const WaveJob*)e.jobs, e.aux); break;
     case TR_PIPE: hipLaunchKernelGGL(vfo_pipe_kernel<1>, grid, b256, r.lds, st, (const PipeJob*)e.jobs); break;
     case TR_POLYC: hipLaunchKernelGGL(vfo_polyc_kernel, grid, b256, r.lds, st, (const PolyJob*)e.jobs, e.aux); break;
     case TR_DEEMP_P0: hipLaunchKernelGGL((vfo_deemph_kernel<0, 0>), grid, b256, 0, st, (const DeempJob*)e.jobs); break;

@@ -29,13 +29,11 @@ void plan_snapshot(sdrpp_ctx* c, PlanSnapshot& S, bool rotate = false) {
         q.nrecs = v.recs.size();
         q.af_last = v.af.i_last; q.af_state = v.af.state_cur;
         q.rds_lvl = v.rds.lvl; q.rds_phi = v.rds.phi; q.rds_frozen = v.rds.frozen; q.rds_ran = v.rds.ran; q.rds_line_cur = v.rds.line_cur; q.rds_line_fed = v.rds.line_fed; q.stereo_ran = v.stereo.ran;
-        for (auto* list : { &v.st, &v.rds.st, &v.stereo.st }) {
-            for (auto& st : *list) {
-                S.nc.push_back(st.n);
-                S.nc.push_back(st.cur);
-                if (rotate) { stream_rotate(st); }
-            }
-        }
+        for_each_stream(v, [&](Stream& st) {
+            S.nc.push_back(st.n);
+            S.nc.push_back(st.cur);
+            if (rotate) { stream_rotate(st); }
+        });
     }
     S.fft_pos = c->fft_pos; S.fft_next = c->fft_next; S.n_lines = c->n_lines; S.iq_cur = c->iq_cur;
     S.wf_cur = c->wf.cur; S.wf_lines = c->wf.lines; S.wf_have = c->wf.have_latest;
@@ -54,12 +52,10 @@ void plan_restore(sdrpp_ctx* c, const PlanSnapshot& S) {
         v.phi = q.phi; v.phi2 = q.phi2; v.seen = q.seen; v.i_if = q.i_if; v.lvl_if = q.lvl_if; v.lvl_out = q.lvl_out; v.lvl_af = q.lvl_af; v.lvl_ifc = q.lvl_ifc;
         v.af.i_last = q.af_last; v.af.state_cur = q.af_state;
         v.rds.lvl = q.rds_lvl; v.rds.phi = q.rds_phi; v.rds.frozen = q.rds_frozen; v.rds.ran = q.rds_ran; v.rds.line_cur = q.rds_line_cur; v.rds.line_fed = q.rds_line_fed; v.stereo.ran = q.stereo_ran;
-        for (auto* list : { &v.st, &v.rds.st, &v.stereo.st }) {
-            for (auto& st : *list) {
-                st.n = *nc++;
-                st.cur = *nc++;
-            }
-        }
+        for_each_stream(v, [&](Stream& st) {
+            st.n = *nc++;
+            st.cur = *nc++;
+        });
     }
     c->fft_pos = S.fft_pos; c->fft_next = S.fft_next; c->n_lines = S.n_lines; c->iq_cur = S.iq_cur;
     c->wf.cur = S.wf_cur; c->wf.lines = S.wf_lines; c->wf.have_latest = S.wf_have;
@@ -119,9 +115,7 @@ int push_common(sdrpp_ctx* c, const float* d_iq, int64_t count, const std::vecto
     if (count == 0) {  // an empty block produces nothing (and changes no state)
         c->n_lines = 0;
         for (auto& kv : c->vfos) {
-            for (auto& s : kv.second->st) { s.n = 0; }
-            for (auto& s : kv.second->rds.st) { s.n = 0; }
-            for (auto& s : kv.second->stereo.st) { s.n = 0; }
+            for_each_stream(*kv.second, [](Stream& s) { s.n = 0; });
         }
         return SDRPP_OK;
     }
@@ -144,9 +138,7 @@ int push_common(sdrpp_ctx* c, const float* d_iq, int64_t count, const std::vecto
         if (count == 0) {  // the decimator swallowed the whole block (offset carried): nothing reaches the FFT / VFOs
             c->n_lines = 0;
             for (auto& kv : c->vfos) {
-                for (auto& s : kv.second->st) { s.n = 0; }
-                for (auto& s : kv.second->rds.st) { s.n = 0; }
-                for (auto& s : kv.second->stereo.st) { s.n = 0; }
+                for_each_stream(*kv.second, [](Stream& s) { s.n = 0; });
             }
             return arena_end(c);
         }

@@ -213,8 +213,13 @@ struct BankPlan {
     Lev<PolyBJob> polyb[4];  // [0]: LMAX 4, [1]: LMAX 8 (de-interleaved tile); [2], [3]: same with odd decimation (linear tile)
     Lev<FirBJob> chan;
     Lev<SeqJob> seq;
-    Lev<IfcJob> ifc;        // radio IF chain (noise blanker / squelch jobs, FMIF segment jobs): between the channel filter's level and the demodulator's, for the VFOs that carry one
-    size_t ifc_lds = 0;     // ... and the LDS its launches need (FMIF segments only)
+    // The wavefront-job role (TR_IFC, vfo_ifchain_kernels.h).  The chain walk fills one record list per kind; upload files every record under the role once it
+    // has its address in the arena (file_wave): `wave` is the table the role reads, a level's jobs of every kind in one launch.
+    Lev<WaveJob> wave;
+    size_t wave_lds = 0;    // ... and the LDS its launches need (none unless a kind that uses it is filed: wave_kind_uses_lds)
+    // radio IF chain (if_chain), between the channel filter's level and the demodulator's, for the VFOs that carry one: a blanker / squelch record and / or an FMIF record per VFO
+    Lev<NbSqJob> nbsq;
+    Lev<FmifJob> fmif;
     Lev<PreJob> pre;
     Lev<FirBJob> audio;     // AM: real stream -> low-pass -> stereo
     Lev<FirBJob> audio_fm;  // WFM/NFM: IF -> discriminator -> low-pass -> stereo, one kernel
@@ -231,13 +236,12 @@ struct BankPlan {
     Lev<PolyJob> af_poly;
     Lev<DeempJob> af_deemp;
     Lev<SsbRotXJob> ssbx_l;
-    // RDS branch of the WFM demodulator (rds_branch): the fused first stage's jobs / the reference rotator's, filed as jobs of the IF chain's role once their
-    // own records have their place in the arena (upload); the later stages go into the AF chain's lists — complex_t and stereo_t are the same arithmetic there
+    // RDS branch of the WFM demodulator (rds_branch): the fused first stage's records / the reference rotator's / the line splice's; the later stages go into
+    // the AF chain's lists — complex_t and stereo_t are the same arithmetic there
     Lev<RdsJob> rdsj;
     Lev<RdsRotXJob> rdsx;
     Lev<RdsLineJob> rdsl;
-    // stereo branch of the WFM demodulator (stereo_branch): its three job kinds, filed as jobs of the IF chain's role like the RDS branch's — the loop's
-    // per-VFO records SDRPP_ST_PACK to a job
+    // stereo branch of the WFM demodulator (stereo_branch): its three kinds — the loop's per-VFO records SDRPP_ST_PACK to a job
     Lev<StereoPilotJob> stp;
     Lev<StereoLoopVfo> stl;
     Lev<StereoLoopJob> stlj;  // (filled by upload once stl's records have their addresses)
@@ -272,15 +276,18 @@ struct BankPlan {
     ToepPlan tplan[kToepLists][kLevels];
 
     // THE enumeration of the Lev<> job lists, in the order their tables lie in the arena (the matrix-core lists of tlists[] first), for begin(),
-    // upload() and emit_levels().  A new list is one more f(...) here (a matrix-core list: one more row of tlists[]).
+    // upload() and emit_levels().  A new list is one more f(...) here (a matrix-core list: one more row of tlists[]; a record list of the wavefront-job
+    // role: one more file_wave line in upload as well).  The last two are not filled by the chain walk: upload derives them from lists in front of them
+    // once those have their addresses in the arena (stlj from stl, wave from every record list of the role), and pushes them itself.
     template <class F>
     void for_each_list(F&& f) {
         for (auto& t : tlists) { f(*t.L); }
         f(f_dec); f(poly);
         for (auto& q : polyb) { f(q); }
-        f(chan); f(seq); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stlj); f(stm); f(ifc); f(pre); f(audio); f(audio_fm);  // (rdsj / rdsx in front of ifc: upload files them there)
+        f(chan); f(seq); f(nbsq); f(fmif); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stm); f(pre); f(audio); f(audio_fm);
         f(af_dec); f(af_hpf); f(af_poly); f(af_deemp);
         f(ssbx_l); f(carry);
+        f(stlj); f(wave);
     }
 
     explicit BankPlan(sdrpp_ctx* c_) : c(c_), fb(c_->vfo_bounds) {
@@ -304,7 +311,7 @@ struct BankPlan {
         s1.clear(); rot.clear(); rotx.clear(); retune.clear(); pipes.clear();
         for_each_list([](auto& L) { lev_reset(L); });
         pipe_lds = 0;
-        ifc_lds = 0;
+        wave_lds = 0;
         d_pipes = nullptr;
         pipe_seg = 0;
         pipe_lvl = 0;
@@ -419,9 +426,7 @@ struct BankPlan {
 
     int chain(Vfo& v) {
         ChainCtx x(v, L0 + 1);
-        for (auto& s : v.st) { s.clevel = 0; s.wlevel = 0; }
-        for (auto& s : v.rds.st) { s.clevel = 0; s.wlevel = 0; }
-        for (auto& s : v.stereo.st) { s.clevel = 0; s.wlevel = 0; }
+        for_each_stream(v, [](Stream& s) { s.clevel = 0; s.wlevel = 0; });
         x.at.cur->wlevel = x.at.lvl;
         const bool agc_mode = v.d.demod == SDRPP_DEMOD_AM || (v.d.demod >= SDRPP_DEMOD_USB && v.d.demod <= SDRPP_DEMOD_CW);
         x.ifc_on = v.ifc.active() && v.i_ifc >= 0 && v.st[(size_t)v.i_ifc].base;
@@ -652,28 +657,15 @@ struct BankPlan {
             const Stream& in = *x.at.cur;
             Stream& to = fm ? v.st[(size_t)v.i_fmi] : fs;  // in front of FMIF: the stream whose history is FMIF's delay line
             const bool per_block = v.ifc.sq_on && blocks;
-            ifc.add(x.at.lvl + 1, IfcJob{ (const float2*)in.data, (float2*)to.data, v.ifc.d_amp, in.n, v.ifc.nb_on, v.ifc.nb_rate, 1.0f - v.ifc.nb_rate, v.ifc.nb_level, v.ifc.sq_on, v.ifc.sq_level,
-                                          per_block ? x.d_bnd : nullptr, per_block ? x.nbnd : 0 });
+            nbsq.add(x.at.lvl + 1, NbSqJob{ (const float2*)in.data, (float2*)to.data, v.ifc.d_amp, in.n, v.ifc.nb_on, v.ifc.nb_rate, 1.0f - v.ifc.nb_rate, v.ifc.nb_level, v.ifc.sq_on, v.ifc.sq_level,
+                                            per_block ? x.d_bnd : nullptr, per_block ? x.nbnd : 0 });
             x.at.step(to, in.n);
         }
         if (fm) {
-            // FMIF: one level behind the blanker / squelch job (a closed block is zeroed only at that job's end), a job per segment of
-            // kFmifSeg samples — parallel over samples, the stream's history in front of the first
+            // FMIF: one level behind the blanker / squelch job (a closed block is zeroed only at that job's end); file_wave cuts the record into a job
+            // per segment of kFmifSeg samples — parallel over samples, the stream's history in front of the first
             const Stream& in = *x.at.cur;
-            IfcJob j{};
-            j.in = (const float2*)in.data;
-            j.out = (float2*)fs.data;
-            j.n = in.n;
-            j.kind = 1;
-            j.fm_bins = v.ifc.fm_bins;
-            j.fm_hist = in.hist[in.cur];
-            j.fm_hist_len = in.hist_len;
-            j.fm_tab = c->fmif_tabs[v.ifc.fm_bins];
-            for (int lo = 0; lo < in.n; lo += kFmifSeg) {
-                j.fm_lo = lo;
-                ifc.add(x.at.lvl + 1, j);
-            }
-            ifc_lds = (size_t)4 * SDRPP_FMIF_LDS_WAVE * sizeof(float);
+            fmif.add(x.at.lvl + 1, FmifJob{ (const float2*)in.data, (float2*)fs.data, in.n, v.ifc.fm_bins, in.hist[in.cur], in.hist_len, c->fmif_tabs[v.ifc.fm_bins] });
             x.at.step(fs, in.n);
         }
         v.lvl_ifc = x.at.lvl;
@@ -869,6 +861,7 @@ struct BankPlan {
     // history carries for every stream that has a consumer with memory
     void history_carries(ChainCtx& x) {
         Vfo& v = x.v;
+        auto carry_at = [this](int cl, const Stream& s) { carry.add(cl, CarryJob{ s.data, s.hist[s.cur], s.hist[s.cur ^ 1], s.hist_len, s.n, s.width, s.hist_len }); };
         const Stream* phantom = (v.fused_front && v.rate.n_stages >= 2 && !v.nco_exact) ? &v.st[(size_t)v.i_first] : nullptr;  // stage-1 output of a fused front end: never written, never read
         for (auto& s : v.st) {
             const bool idle_fmi = v.i_fmi >= 0 && &s == &v.st[(size_t)v.i_fmi] && !(x.ifc_on && v.ifc.fm_on && v.ifc.nbsq());  // (no chain writes it: nothing to carry)
@@ -878,20 +871,17 @@ struct BankPlan {
                 // later: sdrpp_vfo_set_af, a taps change): one level behind the role that WRITES it — not behind the whole chain, which with
                 // an AF chain is up to a dozen levels later, when the stream's ring buffer (kRing = 4) already holds a later block
                 const int cl = !ticking ? carry_last : (s.clevel > 0 ? s.clevel : (s.wlevel > 0 ? s.wlevel + 1 : x.at.lvl + 1));
-                carry.add(cl, CarryJob{ s.data, s.hist[s.cur], s.hist[s.cur ^ 1], s.hist_len, s.n, s.width, s.hist_len });
+                carry_at(cl, s);
             }
         }
         if (v.stereo.ran) {  // the stereo branch's own streams
             for (auto& s : v.stereo.st) {
-                if (s.hist_len > 0 && s.data) { carry.add(!ticking ? carry_last : s.clevel, CarryJob{ s.data, s.hist[s.cur], s.hist[s.cur ^ 1], s.hist_len, s.n, s.width, s.hist_len }); }
+                if (s.hist_len > 0 && s.data) { carry_at(!ticking ? carry_last : s.clevel, s); }
             }
         }
         if (v.rds.ran) {  // the RDS branch's own streams (every one of them is written and read whenever the branch runs)
             for (auto& s : v.rds.st) {
-                if (s.hist_len > 0 && s.data) {
-                    const int cl = !ticking ? carry_last : (s.clevel > 0 ? s.clevel : s.wlevel + 1);
-                    carry.add(cl, CarryJob{ s.data, s.hist[s.cur], s.hist[s.cur ^ 1], s.hist_len, s.n, s.width, s.hist_len });
-                }
+                if (s.hist_len > 0 && s.data) { carry_at(!ticking ? carry_last : (s.clevel > 0 ? s.clevel : s.wlevel + 1), s); }
             }
         }
     }
@@ -1212,6 +1202,7 @@ struct BankPlan {
             d_pipes = arena_push(c, pipes);
             if (!d_pipes) { return arena_fail(c); }
         }
+        // 1. every list the chain walk filled goes into the arena
         int rc = SDRPP_OK, i = 0;
         for_each_list([&](auto& L) {
             if constexpr (std::is_same_v<decltype(L), Lev<ToepJob>&>) {  // the registry's first kToepLists, in tlists[]' order: list i
@@ -1223,77 +1214,49 @@ struct BankPlan {
                 }
                 i++;
             }
-            if constexpr (std::is_same_v<decltype(L), Lev<StereoLoopJob>&>) {  // the loops' per-VFO records have their addresses now: SDRPP_ST_PACK of them to a job — the fewer
-                // rows a wavefront stages, the longer its chunks (SDRPP_ST_LOOP_CHUNK elements together); rows lie an odd number of floats apart in its LDS
-                for (int l = 0; l < stl.top; l++) {
-                    for (size_t k = 0; k < stl.at[l].size(); k += SDRPP_ST_PACK) {
-                        const int nv = (int)std::min<size_t>(SDRPP_ST_PACK, stl.at[l].size() - k);
-                        const int chunk = SDRPP_ST_LOOP_CHUNK / nv;
-                        int nmax = 0;
-                        for (int q = 0; q < nv; q++) { nmax = std::max(nmax, stl.at[l][k + (size_t)q].n); }
-                        stlj.add(l, StereoLoopJob{ stl.dev[l] + k, nv, chunk, chunk | 1, nmax });
-                    }
-                }
-            }
-            if constexpr (std::is_same_v<decltype(L), Lev<IfcJob>&>) {  // the RDS branches' records have their addresses now: their jobs of the IF chain's role
-                for (int l = 0; l < rdsj.top && !rc; l++) {
-                    for (size_t k = 0; k < rdsj.at[l].size(); k++) {
-                        IfcJob j{};
-                        j.in = reinterpret_cast<const float2*>(rdsj.dev[l] + k);
-                        j.kind = 2;
-                        ifc.add(l, j);
-                        ifc_lds = std::max(ifc_lds, (size_t)4 * SDRPP_RDS_LDS_WAVE * sizeof(float));
-                    }
-                }
-                for (int l = 0; l < rdsl.top && !rc; l++) {
-                    for (size_t k = 0; k < rdsl.at[l].size(); k++) {
-                        IfcJob j{};
-                        j.in = reinterpret_cast<const float2*>(rdsl.dev[l] + k);
-                        j.kind = 4;
-                        ifc.add(l, j);
-                    }
-                }
-                for (int l = 0; l < rdsx.top && !rc; l++) {
-                    for (size_t k = 0; k < rdsx.at[l].size(); k++) {
-                        IfcJob j{};
-                        j.in = reinterpret_cast<const float2*>(rdsx.dev[l] + k);
-                        j.kind = 3;
-                        ifc.add(l, j);
-                    }
-                }
-                // ... and the stereo branches': a job per pilot, loop and matrix record
-                for (int l = 0; l < stp.top && !rc; l++) {
-                    for (size_t k = 0; k < stp.at[l].size(); k++) {
-                        IfcJob j{};
-                        j.in = reinterpret_cast<const float2*>(stp.dev[l] + k);
-                        j.kind = 5;
-                        ifc.add(l, j);
-                    }
-                }
-                for (int l = 0; l < stlj.top && !rc; l++) {
-                    for (size_t k = 0; k < stlj.at[l].size(); k++) {
-                        IfcJob j{};
-                        j.in = reinterpret_cast<const float2*>(stlj.dev[l] + k);
-                        j.kind = 6;
-                        ifc.add(l, j);
-                    }
-                }
-                for (int l = 0; l < stm.top && !rc; l++) {
-                    for (size_t k = 0; k < stm.at[l].size(); k++) {
-                        IfcJob j{};
-                        j.in = reinterpret_cast<const float2*>(stm.dev[l] + k);
-                        j.kind = 7;
-                        ifc.add(l, j);
-                    }
-                }
-                if (stp.top > 0 || stl.top > 0 || stm.top > 0) { ifc_lds = std::max(ifc_lds, (size_t)4 * SDRPP_ST_LDS_WAVE * sizeof(float)); }
-            }
             if (!rc && !arena_push_lev(c, L)) { rc = arena_fail(c); }
         });
         if (rc) { return rc; }
         if (i != kToepLists) { return fail(c, SDRPP_ERR_INVALID, "for_each_list: %d matrix-core lists, tlists[] has %d rows", i, kToepLists); }
+        // ... and the stereo loops' per-VFO records SDRPP_ST_PACK to a job — the fewer rows a wavefront stages, the longer its chunks (SDRPP_ST_LOOP_CHUNK
+        // elements together); rows lie an odd number of floats apart in its LDS
+        for (int l = 0; l < stl.top; l++) {
+            for (size_t k = 0; k < stl.at[l].size(); k += SDRPP_ST_PACK) {
+                const int nv = (int)std::min<size_t>(SDRPP_ST_PACK, stl.at[l].size() - k);
+                const int chunk = SDRPP_ST_LOOP_CHUNK / nv;
+                int nmax = 0;
+                for (int q = 0; q < nv; q++) { nmax = std::max(nmax, stl.at[l][k + (size_t)q].n); }
+                stlj.add(l, StereoLoopJob{ stl.dev[l] + k, nv, chunk, chunk | 1, nmax });
+            }
+        }
+        if (!arena_push_lev(c, stlj)) { return arena_fail(c); }
+        // 2. every record under the role, kind by kind: the order of a level's jobs, four neighbours to a workgroup
+        file_wave(nbsq, WK_NBSQ);
+        file_wave(fmif, WK_FMIF);
+        file_wave(rdsj, WK_RDS_FRONT);
+        file_wave(rdsl, WK_RDS_LINE);
+        file_wave(rdsx, WK_RDS_ROTX);
+        file_wave(stp, WK_ST_PILOT);
+        file_wave(stlj, WK_ST_LOOP);
+        file_wave(stm, WK_ST_MATRIX);
+        // 3. the role's table
+        if (!arena_push_lev(c, wave)) { return arena_fail(c); }
         HostScope hs("arena_commit (H2D)");
         return arena_commit(c);
+    }
+
+    // The records of one kind, in the arena already, as jobs of the wavefront-job role: a job per record — FMIF's records a job per segment of kFmifSeg
+    // samples, its first sample in WaveJob::arg.
+    template <class T>
+    void file_wave(const Lev<T>& recs, WaveKind kind) {
+        for (int l = 0; l < recs.top; l++) {
+            for (size_t k = 0; k < recs.at[l].size(); k++) {
+                int n = 1, step = 1;
+                if constexpr (std::is_same_v<T, FmifJob>) { n = recs.at[l][k].n; step = kFmifSeg; }
+                for (int lo = 0; lo < n; lo += step) { wave.add(l, WaveJob{ recs.dev[l] + k, kind, lo }); }
+                if (wave_kind_uses_lds(kind)) { wave_lds = (size_t)4 * SDRPP_WAVE_LDS_FLOATS * sizeof(float); }
+            }
+        }
     }
 
     // ---- level 1: the front end ----
@@ -1592,10 +1555,10 @@ struct BankPlan {
                     if (rc) { return rc; }
                 }
             }
-            if (l < ifc.top && !ifc.at[l].empty()) {
+            if (l < wave.top && !wave.at[l].empty()) {
                 FamilyTimer t(c, F_DEMOD);
-                const int nj = (int)ifc.at[l].size();
-                emit(c, l, F_DEMOD, TR_IFC, (nj + 3) / 4, 1, ifc_lds, ifc.dev[l], nullptr, nj);
+                const int nj = (int)wave.at[l].size();
+                emit(c, l, F_DEMOD, TR_IFC, (nj + 3) / 4, 1, wave_lds, wave.dev[l], nullptr, nj);
             }
             if ((l < pre.top && !pre.at[l].empty()) || (l < seq.top && !seq.at[l].empty()) || (l < ssbx_l.top && !ssbx_l.at[l].empty())) {
                 FamilyTimer t(c, F_DEMOD);
@@ -1704,20 +1667,10 @@ int do_vfos_plan(sdrpp_ctx* c, const IqSrc& src, int64_t count, const CarryJob& 
     }
     if (rc) { return rc; }
     // flip the ping-pong side of every carried stream
-    for (size_t i = 0; i < c->vfo_list.size(); i++) {
-        for (auto& s : c->vfo_list[i]->st) {
+    for (Vfo* v : c->vfo_list) {
+        for_each_stream_that_ran(*v, [](Stream& s) {
             if (s.hist_len > 0 && s.data) { s.cur ^= 1; }
-        }
-        if (c->vfo_list[i]->stereo.ran) {
-            for (auto& s : c->vfo_list[i]->stereo.st) {
-                if (s.hist_len > 0 && s.data) { s.cur ^= 1; }
-            }
-        }
-        if (c->vfo_list[i]->rds.ran) {
-            for (auto& s : c->vfo_list[i]->rds.st) {
-                if (s.hist_len > 0 && s.data) { s.cur ^= 1; }
-            }
-        }
+        });
     }
     return SDRPP_OK;
 }

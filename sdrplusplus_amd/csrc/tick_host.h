@@ -625,24 +625,11 @@ int tick_push(sdrpp_ctx* c, const float* d_iq, int64_t count, const CopyJob* lan
     bool as_tick = tick_eligible(c);
     if (as_tick) {  // rings of the per-block buffers, result slots (allocated on first use / after a change of the configuration)
         for (auto& kv : c->vfos) {
-            for (auto& st : kv.second->st) {
-                if (st.n_extra < kRing - 1 && st.base) {
-                    int rc = stream_ring_ensure(c, st);
-                    if (rc) { return rc; }
-                }
-            }
-            for (auto& st : kv.second->rds.st) {
-                if (st.n_extra < kRing - 1 && st.base) {
-                    int rc = stream_ring_ensure(c, st);
-                    if (rc) { return rc; }
-                }
-            }
-            for (auto& st : kv.second->stereo.st) {
-                if (st.n_extra < kRing - 1 && st.base) {
-                    int rc = stream_ring_ensure(c, st);
-                    if (rc) { return rc; }
-                }
-            }
+            int rc = SDRPP_OK;
+            for_each_stream(*kv.second, [&](Stream& st) {
+                if (!rc && st.n_extra < kRing - 1 && st.base) { rc = stream_ring_ensure(c, st); }
+            });
+            if (rc) { return rc; }
         }
         if (c->pre.on) {  // the pre-processing chain's stage outputs are per-block buffers too
             for (auto& st : c->pre.st) {

@@ -141,7 +141,7 @@ enum TickRole : int {
     TR_S1D_1,      // Stage1Job[gy], p.src: vfo_stage1_direct_body<1> (first stage alone, decimation >= 32: straight from memory)
     TR_F2_1,       // Front2Job[gy], p.src: vfo_front2_body<1, 0, 0> (first two stages fused, VALU form)
     TR_POLY,       // PolyJob[gy]: vfo_poly_body (a resampler neither the matrix nor the cycle-major form takes: one output per work-item)
-    TR_IFC,        // IfcJob[aux], one wavefront per job (gx = ceil(aux / 4)): vfo_ifchain_body — the radio's IF chain between a VFO's IF stream and its demodulator: a noise blanker / power squelch job per VFO, an FMIF job per segment (IfcJob::kind)
+    TR_IFC,        // WaveJob[aux], the wavefront-job role: one wavefront per job, four to a workgroup (gx = ceil(aux / 4)): vfo_wave_body — every piece of a block's work that is one wavefront wide, each entry naming its kind (WaveKind) and its own record: the radio's IF chain (blanker / squelch, FMIF segments), the RDS and stereo branches' jobs
     TR_COUNT
 };
 struct TickP1 { IqSrc src; FrameGeom g; const float* window; const float2* tw1; const float2* twn; float2* scratch; int lg2, ntiles; };
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256, SET == 1 ? 2 : 3) void tick_kernel(TickL0 l0, 
             } break;
             case TR_IFC: {
                 const int j = bid.x * 4 + ((int)threadIdx.x >> 6);
-                if (j < e_aux) { vfo_ifchain_body(j, reinterpret_cast<const IfcJob*>(e_jobs), smem); }
+                if (j < e_aux) { vfo_wave_body(j, reinterpret_cast<const WaveJob*>(e_jobs), smem); }
             } break;
             case TR_ROT: { const IqSrc src = e.p.src; vfo_rotate_body(bid, gdim, src, reinterpret_cast<const RotJob*>(e_jobs)); } break;
             case TR_FCM_132_4: { const IqSrc src = e.p.src; vfo_frontcm_body<10, 132, 4>(bid, smem, src, reinterpret_cast<const FrontCMJob*>(e_jobs)); } break;

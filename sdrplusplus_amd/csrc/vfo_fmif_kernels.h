@@ -1,4 +1,4 @@
-// FM IF noise reduction on the matrix cores, and the job record it shares with the rest of the radio's IF chain (vfo_ifchain_kernels.h).
+// FM IF noise reduction on the matrix cores: a kind of the wavefront-job role (vfo_ifchain_kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,44 +23,35 @@ namespace sdrpp_k {
 // j + 32: the argmax runs within the lane first (ascending k, strict >), then across the two halves through LDS (equal magnitudes: the lower
 // k), so exact ties resolve as in the reference; a zero row never beats a non-zero maximum, and an all-zero window gives bin 0 and 0.
 // Every output is the n-ascending fmaf chain of its own column — the same value wherever the segment or the block was cut.
-// One WAVEFRONT per segment of SDRPP_FMIF_SEG samples (a job record each, under the IF chain's role).
+// One WAVEFRONT per segment of SDRPP_FMIF_SEG samples (a wave job each, all of a block reading the VFO's one record).
 // =====================================================================================================================
 #define SDRPP_FMIF_TILE 32
 #define SDRPP_FMIF_SEG 256
-#define SDRPP_FMIF_LDS_WAVE ((SDRPP_FMIF_SEG + SDRPP_FMIF_TILE) * 2 + 64 * 4)  // floats per wavefront: the window, then the exchange of the argmax
+#ifndef SDRPP_WAVE_LDS_FLOATS
+#error "a part of vfo_ifchain_kernels.h, the role's header: include that one"
+#endif
+#define SDRPP_FMIF_LDS_FLOATS ((SDRPP_FMIF_SEG + SDRPP_FMIF_TILE) * 2 + 64 * 4)  // of the wavefront's share of the role's LDS: the window, then the exchange of the argmax
 
-// The job record of the IF chain's role (vfo_ifchain_kernels.h): the blanker and squelch of one VFO, or one segment of FMIF.
-struct IfcJob {
-    const float2* in;  // the IF stream of this push (RxVFO::out)
-    float2* out;       // the chain's own output
-    float* amp;        // NoiseBlanker::amp, persistent (device)
+// One record per VFO and block (WK_FMIF); a wave job is one segment of it, its first sample in WaveJob::arg.
+struct FmifJob {
+    const float2* in;   // the input stream's data of this push (RxVFO::out, or the blanker / squelch job's output)
+    float2* out;        // the chain's own output
     int n;
-    int nb_on;
-    float nb_rate, nb_inv_rate, nb_level;
-    int sq_on;
-    float sq_level;
-    // reference blocks inside this push at the IF rate (cumulative sample counts; nullptr: the push is one block)
-    const int* bounds;
-    int nb;
-    // kind 1: one segment of FMIF (vfo_fmif_kernels.h) — `in` / `n` are its input stream's data of this push, `out` the chain's output
-    // kind 2 / 3 / 4: a job of the WFM demodulator's RDS branch (vfo_rds_kernels.h) — `in` is the address of its RdsJob / RdsRotXJob / RdsLineJob, nothing else is read
-    // kind 5 / 6 / 7: a job of its stereo branch (vfo_stereo_kernels.h) — `in` is the address of its StereoPilotJob / StereoLoopJob / StereoMatrixJob, nothing else is read
-    int kind;
-    int fm_bins, fm_lo;     // bin count; first sample of the segment
-    const float* fm_hist;   // the input stream's history (StreamIn)
-    int fm_hist_len;
-    const float* fm_tab;    // [2][32][32]: re / im of A[k][n] at [n][k]
+    int bins;
+    const float* hist;  // the input stream's history (StreamIn)
+    int hist_len;
+    const float* tab;   // [2][32][32]: re / im of A[k][n] at [n][k]
 };
 
-__device__ __forceinline__ void vfo_fmif_body(const IfcJob& job, float* smem) {
+__device__ __forceinline__ void vfo_fmif_body(const FmifJob& job, int lo, float* smem) {
     const int lane = threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
     const int j = lane & 31, h = lane >> 5;
-    float2* W = reinterpret_cast<float2*>(smem + wv * SDRPP_FMIF_LDS_WAVE);
-    float4* EX = reinterpret_cast<float4*>(smem + wv * SDRPP_FMIF_LDS_WAVE + (SDRPP_FMIF_SEG + SDRPP_FMIF_TILE) * 2);
-    const int N = job.fm_bins, lo = job.fm_lo;
+    float2* W = reinterpret_cast<float2*>(smem + wv * SDRPP_WAVE_LDS_FLOATS);
+    float4* EX = reinterpret_cast<float4*>(smem + wv * SDRPP_WAVE_LDS_FLOATS + (SDRPP_FMIF_SEG + SDRPP_FMIF_TILE) * 2);
+    const int N = job.bins;
     const int cnt = min(job.n - lo, SDRPP_FMIF_SEG);  // samples of this segment
     const int nst = (N + 1) >> 1;                     // matrix steps that hold a non-zero column
-    const StreamIn in{ reinterpret_cast<const float*>(job.in), job.fm_hist, job.fm_hist_len, job.n };
+    const StreamIn in{ reinterpret_cast<const float*>(job.in), job.hist, job.hist_len, job.n };
     // W[p] = x[lo - (N-1) + p] for p < cnt + N - 1; zero behind it (an odd N pairs its last column with a zero one: what it multiplies must be finite)
     float2 pf[(SDRPP_FMIF_SEG + SDRPP_FMIF_TILE) / 64 + 1];
 #pragma unroll
@@ -71,8 +62,8 @@ __device__ __forceinline__ void vfo_fmif_body(const IfcJob& job, float* smem) {
     float ar[16], ai[16];
 #pragma unroll
     for (int t = 0; t < 16; t++) {
-        ar[t] = global_load_f32(job.fm_tab, (2 * t + h) * 32 + j);
-        ai[t] = global_load_f32(job.fm_tab, 1024 + (2 * t + h) * 32 + j);
+        ar[t] = global_load_f32(job.tab, (2 * t + h) * 32 + j);
+        ai[t] = global_load_f32(job.tab, 1024 + (2 * t + h) * 32 + j);
     }
 #pragma unroll
     for (int q = 0; q < (SDRPP_FMIF_SEG + SDRPP_FMIF_TILE) / 64 + 1; q++) {

@@ -4,7 +4,7 @@
 // turn_phasor) is that at all of its sites.  The others are not: cmul / cmul_re / cabs_ref serve vfo_rotate_body and vfo_demod_pre_body, cmac
 // the resamplers and the VALU FIR forms, and these sites DELIBERATELY keep the inline expression, because calling the helper there changed
 // instruction selection, scheduling or register allocation of the kernel (and of the tick kernel that holds it as a role):
-//   |x| and the AGC's clamped gain in vfo_sequential_body, |x| in vfo_ifchain_body and vfo_fmif_body;
+//   |x| and the AGC's clamped gain in vfo_sequential_body, |x| in vfo_nbsq_body and vfo_fmif_body;
 //   the complex multiply and the real-tap MAC in the stage-1 epilogues, vfo_front2_body and the matrix front ends' epilogues;
 //   the tap-pair FMA quad in stage1_accumulate, stage1_accumulate_static and vfo_stage1_direct_body.
 // Converting one of them is a change of device code: compare the disassembly and re-measure the kernel, it is not a clean-up.

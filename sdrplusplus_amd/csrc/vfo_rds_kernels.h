@@ -4,7 +4,6 @@
 #include <stdint.h>
 #include <sdrpp_gfx950.h>
 #include "vfo_fir_kernels.h"
-#include "vfo_fmif_kernels.h"
 #include "vfo_math.h"
 #include "vfo_rot_kernels.h"
 #include "vfo_stream.h"
@@ -17,7 +16,7 @@ namespace sdrpp_k {
 //     c[i] = (d[i] + 0j) * e^{j 2 pi (phi + (i - anchor) * theta)}               (FrequencyXlator(-57 kHz), closed form: float64 turns, anchored per push)
 //     y[m] = sum_k h[k] * c[off0 + m * D - (K-1) + k]                            (PowerDecimator's first DecimatingFIR, D : 1, K real taps on the complex stream)
 // in ONE pass over the IF stream: neither d nor c ever goes to memory.  One WAVEFRONT per job (a run of outputs of one push, walked a tile of
-// `tile` outputs at a time) under the IF chain's role, four jobs per workgroup, SDRPP_FMIF_LDS_WAVE floats of LDS each (the role's stride):
+// `tile` outputs at a time) under the wavefront-job role, four jobs per workgroup, SDRPP_WAVE_LDS_FLOATS floats of LDS each (the role's stride):
 //   1. the tile's (tile - 1) * D + K IF samples and the one in front of them — the stream's history in front of the block included — are fetched
 //      four loads in flight per lane, their phases taken ONCE per sample into LDS;
 //   2. the phases become their differences in place, and c = d * phasor goes into the window, de-interleaved by decimation phase: sample s at
@@ -30,7 +29,9 @@ namespace sdrpp_k {
 // was set aside (job.dline: the K newest d the branch was fed, newest last; vfo_rds_line_body keeps it up while blocks shorter than the line arrive),
 // and nothing in front of the block is read.  d[0] always belongs to the running discriminator: job.prev0, the stream's true last sample.
 // =====================================================================================================================
-#define SDRPP_RDS_LDS_WAVE SDRPP_FMIF_LDS_WAVE  // floats of LDS per wavefront: the role's stride (jobs of both kinds share a workgroup)
+#ifndef SDRPP_WAVE_LDS_FLOATS
+#error "a part of vfo_ifchain_kernels.h, the role's header: include that one"
+#endif
 struct RdsJob {
     StreamIn in;          // the stream the demodulator reads: this block's samples, and the history the branch's delay line is recomputed from
     const float2* prev0;  // the sample in front of in.data[0] as the discriminator sees it
@@ -49,8 +50,8 @@ struct RdsJob {
 __device__ __forceinline__ void vfo_rds_front_body(const RdsJob& job, float* smem) {
     const int lane = threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
     const int K = job.K, lgD = job.lgD, D = 1 << lgD, P = job.pitch;
-    float2* C = reinterpret_cast<float2*>(smem + wv * SDRPP_RDS_LDS_WAVE);  // the window: D rows of P
-    float* PH = smem + wv * SDRPP_RDS_LDS_WAVE + 2 * D * P;                 // phases, then (in place) their differences
+    float2* C = reinterpret_cast<float2*>(smem + wv * SDRPP_WAVE_LDS_FLOATS);  // the window: D rows of P
+    float* PH = smem + wv * SDRPP_WAVE_LDS_FLOATS + 2 * D * P;                 // phases, then (in place) their differences
     const UniformF32 taps = as_uniform(job.taps);
     const float2 x0 = global_load_f32x2(job.prev0, 0);
     for (int m0 = job.m_lo; m0 < job.m_hi; m0 += job.tile) {
@@ -189,7 +190,7 @@ __device__ __forceinline__ void vfo_rds_rotate_exact_body(const RdsRotXJob& job)
     if (lane == 0) { *job.state = make_float2(pr, pi); }
 }
 __device__ __attribute__((noinline)) void vfo_rds_rotate_exact_call(const RdsRotXJob* j) { vfo_rds_rotate_exact_body(*j); }
-// Both bodies run as jobs of the IF chain's role (IfcJob::kind 2 and 3, vfo_ifchain_kernels.h): in an ordinary pass vfo_ifchain_kernel is their
-// launch, in a tick TR_IFC their role.
+// Front, line and rotator run as kinds of the wavefront-job role (WK_RDS_FRONT, WK_RDS_LINE, WK_RDS_ROTX, vfo_ifchain_kernels.h): in an ordinary pass
+// vfo_ifchain_kernel is their launch, in a tick TR_IFC their role.
 
 }  // namespace sdrpp_k

@@ -4,7 +4,6 @@
 #include <stdint.h>
 #include <sdrpp_gfx950.h>
 #include "vfo_fir_kernels.h"
-#include "vfo_fmif_kernels.h"
 #include "vfo_math.h"
 #include "vfo_stream.h"
 
@@ -16,19 +15,21 @@ namespace sdrpp_k {
 //     p[i]  = sum_k (m[i - (K-1) + k] + 0j) * h[k]               (FIR<complex_t, complex_t>, K complex taps of taps::bandPass<complex_t>)
 //     v[i]  = phasor(phase);  advance(normalizePhase(arg p[i] - phase))      (loop::PLL, pll.h:64-70; phase_control_loop.h:58-85)
 //     q     = (m[i - D] + 0j) * conj(v[i]) * conj(v[i]);  lmr = 2 q.re;  l = m[i - D] + lmr,  r = m[i - D] - lmr;  alFir(l), arFir(r)
-// Three job kinds of the IF chain's role, a level each:
-//   pilot   (kind 5) everything in front of the loop: parallel over samples, a wavefront per run of SDRPP_ST_SEG samples
-//   loop    (kind 6) the recursion alone: a LANE per VFO, up to SDRPP_ST_PACK VFOs per wavefront (StereoLoopJob: a run of StereoLoopVfo records)
-//   matrix  (kind 7) everything behind the loop: parallel over samples, a wavefront per run of SDRPP_ST_SEG samples
+// Three kinds of the wavefront-job role (vfo_ifchain_kernels.h), a level each:
+//   pilot   (WK_ST_PILOT) everything in front of the loop: parallel over samples, a wavefront per run of SDRPP_ST_SEG samples
+//   loop    (WK_ST_LOOP) the recursion alone: a LANE per VFO, up to SDRPP_ST_PACK VFOs per wavefront (StereoLoopJob: a run of StereoLoopVfo records)
+//   matrix  (WK_ST_MATRIX) everything behind the loop: parallel over samples, a wavefront per run of SDRPP_ST_SEG samples
 // Every sum is a k-ascending fmaf chain per output and every job boundary a function of the block alone: results do not depend on the cut.
-// Each wavefront works in its share of the role's LDS (SDRPP_FMIF_LDS_WAVE floats: jobs of every kind share a workgroup).
+// Each wavefront works in its share of the role's LDS (SDRPP_WAVE_LDS_FLOATS floats: jobs of every kind share a workgroup).
 // =====================================================================================================================
-#define SDRPP_ST_LDS_WAVE SDRPP_FMIF_LDS_WAVE
+#ifndef SDRPP_WAVE_LDS_FLOATS
+#error "a part of vfo_ifchain_kernels.h, the role's header: include that one"
+#endif
 #define SDRPP_ST_SEG 1024          // samples per pilot / matrix job
 #define SDRPP_ST_PILOT_TILE 256    // pilot: outputs per tile (four per lane); its window of tile + K values must fit: K <= SDRPP_ST_PILOT_MAX_TAPS
 #define SDRPP_ST_MATRIX_TILE 128   // matrix: frames per tile (two per lane); two windows of tile + K - 1 values: K <= SDRPP_ST_AUDIO_MAX_TAPS
-#define SDRPP_ST_PILOT_MAX_TAPS (SDRPP_ST_LDS_WAVE - SDRPP_ST_PILOT_TILE)
-#define SDRPP_ST_AUDIO_MAX_TAPS (SDRPP_ST_LDS_WAVE / 2 - SDRPP_ST_MATRIX_TILE + 1)
+#define SDRPP_ST_PILOT_MAX_TAPS (SDRPP_WAVE_LDS_FLOATS - SDRPP_ST_PILOT_TILE)
+#define SDRPP_ST_AUDIO_MAX_TAPS (SDRPP_WAVE_LDS_FLOATS / 2 - SDRPP_ST_MATRIX_TILE + 1)
 #define SDRPP_ST_PACK 8            // loop: VFOs per wavefront (the fewer, the longer the chunks a wavefront stages and the more wavefronts share the work)
 #define SDRPP_ST_LOOP_CHUNK 256    // loop: elements of all rows together a wavefront stages per chunk (four per lane: what it holds in registers while the previous chunk is walked)
 #define SDRPP_ST_LOOP_PTRS 64      // loop: floats of the wavefront's LDS in front of the rows: per row its two addresses and its length (StereoLoopRow)
@@ -49,7 +50,7 @@ struct StereoPilotJob {
 __device__ __forceinline__ void vfo_stereo_pilot_body(const StereoPilotJob& job, float* smem) {
     const int lane = threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
     const int K = job.K;
-    float* PH = smem + wv * SDRPP_ST_LDS_WAVE;  // phases, then (in place) the window of m
+    float* PH = smem + wv * SDRPP_WAVE_LDS_FLOATS;  // phases, then (in place) the window of m
     const UniformF32 taps = as_uniform(job.taps);
     for (int t0 = job.lo; t0 < job.hi; t0 += SDRPP_ST_PILOT_TILE) {
         const int cnt = min(SDRPP_ST_PILOT_TILE, job.hi - t0);
@@ -126,11 +127,11 @@ static_assert(SDRPP_ST_PACK >= 1 && SDRPP_ST_PACK <= 64, "a lane per VFO");
 static_assert(SDRPP_ST_PACK * sizeof(StereoLoopRow) <= SDRPP_ST_LOOP_PTRS * sizeof(float), "the rows' descriptions fit in front of the rows");
 static_assert(SDRPP_ST_LOOP_CHUNK % 64 == 0 && SDRPP_ST_LOOP_CHUNK < 65536, "whole elements per lane; a column fits 16 bits");
 // (nv rows of pitch = (CHUNK / nv) | 1 <= CHUNK / nv + 1 floats: at most CHUNK + nv floats)
-static_assert(SDRPP_ST_LOOP_PTRS + SDRPP_ST_LOOP_CHUNK + SDRPP_ST_PACK <= SDRPP_ST_LDS_WAVE, "the rows of a chunk fit the wavefront's share of the role's LDS");
+static_assert(SDRPP_ST_LOOP_PTRS + SDRPP_ST_LOOP_CHUNK + SDRPP_ST_PACK <= SDRPP_WAVE_LDS_FLOATS, "the rows of a chunk fit the wavefront's share of the role's LDS");
 __device__ __forceinline__ void vfo_stereo_loop_body(const StereoLoopVfo* __restrict__ vfos, int nv, int C, int pitch, int nmax, float* smem) {
     const int lane = threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
-    StereoLoopRow* AD = reinterpret_cast<StereoLoopRow*>(smem + wv * SDRPP_ST_LDS_WAVE);  // nv <= SDRPP_ST_PACK rows
-    float* ROW = smem + wv * SDRPP_ST_LDS_WAVE + SDRPP_ST_LOOP_PTRS;
+    StereoLoopRow* AD = reinterpret_cast<StereoLoopRow*>(smem + wv * SDRPP_WAVE_LDS_FLOATS);  // nv <= SDRPP_ST_PACK rows
+    float* ROW = smem + wv * SDRPP_WAVE_LDS_FLOATS + SDRPP_ST_LOOP_PTRS;
     const float FL_PI = 3.1415926535f, TWO_PI = FL_PI - (-FL_PI);  // phase_control_loop.h:28: phaseDelta = maxPhase - minPhase
     const bool mine = lane < nv;
     const StereoLoopVfo me = vfos[mine ? lane : 0];
@@ -212,8 +213,8 @@ struct StereoMatrixJob {
 __device__ __forceinline__ void vfo_stereo_matrix_body(const StereoMatrixJob& job, float* smem) {
     const int lane = threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
     const int K = job.K;
-    constexpr int P = SDRPP_ST_LDS_WAVE / 2;
-    float* LW = smem + wv * SDRPP_ST_LDS_WAVE;
+    constexpr int P = SDRPP_WAVE_LDS_FLOATS / 2;
+    float* LW = smem + wv * SDRPP_WAVE_LDS_FLOATS;
     float* RW = LW + P;
     const UniformF32 taps = as_uniform(job.taps);
     for (int t0 = job.lo; t0 < job.hi; t0 += SDRPP_ST_MATRIX_TILE) {
@@ -270,29 +271,12 @@ __device__ __forceinline__ void vfo_stereo_matrix_body(const StereoMatrixJob& jo
 
 // (calls, not inlined, as the RDS branch's bodies are: the role's own code and the tick kernel's register allocation stay what they are.  What a call is
 // handed arrives in vector registers although every lane holds the same: the job's address is stated to be wave-uniform and its record read with scalar
-// loads, so that the record, and every address and bound computed from it, stays in scalar registers)
-template <class T>
-__device__ __forceinline__ const T* stereo_uniform_ptr(const T* p) {
-    const uint64_t a = (uint64_t)(uintptr_t)p;
-    const uint32_t lo = (uint32_t)wave_uniform((int)(uint32_t)a), hi = (uint32_t)wave_uniform((int)(uint32_t)(a >> 32));
-    return reinterpret_cast<const T*>((uintptr_t)(((uint64_t)hi << 32) | (uint64_t)lo));
-}
-template <class T>
-__device__ __forceinline__ T stereo_uniform_job(const T* p) {
-    static_assert(sizeof(T) % 4 == 0, "job records are whole words");
-    const UniformI32 u = as_uniform_i32(stereo_uniform_ptr(p));
-    int w[sizeof(T) / 4];
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(T) / 4); i++) { w[i] = u[i]; }
-    T job;
-    __builtin_memcpy(&job, w, sizeof(T));
-    return job;
-}
-__device__ __attribute__((noinline)) void vfo_stereo_pilot_call(const StereoPilotJob* j, float* smem) { vfo_stereo_pilot_body(stereo_uniform_job(j), smem); }
+// loads (wave_uniform_job), so that the record, and every address and bound computed from it, stays in scalar registers)
+__device__ __attribute__((noinline)) void vfo_stereo_pilot_call(const StereoPilotJob* j, float* smem) { vfo_stereo_pilot_body(wave_uniform_job(j), smem); }
 __device__ __attribute__((noinline)) void vfo_stereo_loop_call(const StereoLoopJob* j, float* smem) {
-    const StereoLoopJob job = stereo_uniform_job(j);
+    const StereoLoopJob job = wave_uniform_job(j);
     vfo_stereo_loop_body(job.vfos, min(job.nv, SDRPP_ST_PACK), job.chunk, job.pitch, job.nmax, smem);
 }
-__device__ __attribute__((noinline)) void vfo_stereo_matrix_call(const StereoMatrixJob* j, float* smem) { vfo_stereo_matrix_body(stereo_uniform_job(j), smem); }
+__device__ __attribute__((noinline)) void vfo_stereo_matrix_call(const StereoMatrixJob* j, float* smem) { vfo_stereo_matrix_body(wave_uniform_job(j), smem); }
 
 }  // namespace sdrpp_k
