@@ -465,6 +465,77 @@ typedef struct sdrpp_stereo_desc {
 int sdrpp_vfo_set_stereo(sdrpp_ctx* ctx, int id, const sdrpp_stereo_desc* desc);
 int sdrpp_abi_sizeof_stereo_desc(void);
 
+/* ---- Symbol branch of a RAW VFO: FSK discriminator -> shaping FIR -> Mueller-Mueller clock recovery -> soft symbols and bits ----------------------------
+ * What the pager decoder's POCSAGDSP (decoder_modules/pager_decoder/src/pocsag/dsp.h) computes from its VFO's output:
+ *     d[i]  = Quadrature(x[i]) = normalizePhase(phase(x[i]) - phase(x[i-1])) * inv_deviation          (demod/quadrature.h:39-46)
+ *     f[i]  = FIR<float, float>(d)[i] = sum_k d[i - (K-1) + k] * shape_taps[k]                        (filter/fir.h; sums k-ascending, product and sum rounded apart)
+ *     MM<float> (clock_recovery/mm.h:100-156), per symbol while offset < count:
+ *         p     = clamp((int)floorf(phase * interp_phases), 0, interp_phases - 1)
+ *         out   = sum_k f[offset - (T-1) + k] * interp_bank[p][k]         T = interp_ntaps; volk_32f_x2_dot_prod_32f in the generic order: k ascending
+ *         error = clamp(step(lastOut) * out - lastOut * step(out), -1, 1);  lastOut = out               step(x) = x > 0 ? 1 : -1
+ *         freq  = clamp(freq + omega_gain * error, min_omega, max_omega);  phase += freq + mu_gain * error      (PhaseControlLoop<float, false>::advance)
+ *         delta = floorf(phase);  offset += delta;  phase -= delta
+ *     after the loop offset -= count;  soft = out per symbol, bit = soft > 0.0f                         (digital/binary_slicer.h)
+ * in float throughout, every operation of the recursion in the reference's order.  Built as a general block: the parameters come from the description
+ * (sdrpp_design_pager fills the pager's), the input is the real stream f.
+ * WHERE IT ATTACHES: only SDRPP_DEMOD_RAW VFOs — the pager's VFO has no demodulator; anything else: SDRPP_ERR_UNSUPPORTED.  SOURCE: what a demodulator
+ * would read — the IF chain's output where a chain is active, else RxVFO::out.  The discriminator is the device routine the FM path and the RDS branch
+ * call (|error| <= 3e-7 rad against atan2f: soft values are not the reference's bit for bit).  The branch never changes a bit of any other
+ * output of the VFO.
+ * SDRPP_ERR_INVALID: a parameter that is not finite; shape_ntaps outside 1 .. 64, interp_ntaps outside 1 .. 16, interp_phases outside 1 .. 1024, a missing
+ * array; min_omega >= max_omega; and a loop whose step leaves these bounds: every step delta = floorf(phase + freq + mu_gain * error) with phase in [0, 1),
+ * |error| <= 1 lies in [floorf(min_omega - |mu_gain|), max_omega + |mu_gain| + 1), and the branch demands
+ *     min_omega - |mu_gain| >= 1       every symbol advances at least one sample: the walk ends, and a push of n samples yields at most
+ *                                      ceil(n / floorf(min_omega - |mu_gain|)) + 1 symbols (the capacity of the outputs below; never less than the
+ *                                      reference-typical ceil(n / min_omega) + 1)
+ *     max_omega + |mu_gain| <= 4096    offsets stay far inside the range in which `offset += delta` (an int plus a float, mm.h:147) is exact for every
+ *                                      push the context takes (max_push < 2^24 - 4097 samples at the branch's rate, else SDRPP_ERR_UNSUPPORTED)
+ * (the reference's pager at 24 kS/s: mu_gain 1, omega 10 .. 46.9 +- 5 %).  The rule is stricter than "min_omega >= 1": with mu_gain = 1 a step of
+ * floorf(min_omega - 1) = 0 would neither advance nor bound the output, so descriptions with 1 <= min_omega < 1 + |mu_gain| are refused although the
+ * reference would run them.  The loop stages nothing: for a symbol at `offset` a lane reads the T samples ENDING there (mm.h:113 with bufStart = buffer +
+ * T - 1) and the T taps of one interpolator phase straight from device memory, so no bound on the step follows from any chunk or overlap.
+ * STATE, as the reference keeps it: the discriminator's previous phase, the FIR's delay line, MM's offset, pcl.phase, pcl.freq, lastOut and the T - 1
+ * delay samples.  Attaching starts from a fresh POCSAGDSP: previous phase 0, phase 0, freq = omega, offset 0, lastOut 0, cleared lines.  enabled = 0
+ * freezes all of it — nothing is planned, nothing delivered, nothing advances, whatever the VFO's stream does meanwhile; enabled = 1 with the SAME
+ * description continues from there (the outputs equal an uninterrupted run over the pushes the branch was switched on for).  A call with another
+ * description starts cleared.  desc == NULL detaches.  sdrpp_vfo_reset treats the branch as it treats the RDS branch: the discriminator's previous phase
+ * becomes 0 with the IF history it clears, everything else the branch holds stays (the decoder is a block of its own behind the VFO; to start it over,
+ * attach the description anew after a detach).  sdrpp_vfo_replace with keep & 2 and a RAW
+ * description moves the branch, parameters and state, to the new handle (a handle with another stream capacity gets the description attached afresh,
+ * cleared); otherwise the new handle has none.
+ * The interpolator bank exists ONCE per context for identical banks, however many VFOs carry the branch (sdrpp_sym_bank_count).
+ * OUTPUT of a push: the symbols whose start `offset` lies inside that push — the reference's `while (offset < count)` followed by `offset -= count` — so
+ * the concatenated output does not depend on how the stream is cut: one push, pushes of a single sample, pipelined or in launch groups (where every push
+ * keeps its own count and slice) give the same bits and the same soft values bit for bit.  Outside pipelined mode the accessors name the most recent push
+ * (SDRPP_ERR_INVALID for a VFO without a branch, count 0 while it is switched off); each of them waits for the device and copies the counts to the host, because
+ * the count is the loop's own result — a convenience for a few channels: a receiver with many reads them out of the pipelined results, which cost no wait.
+ * Pipelined: sdrpp_pipeline_set_sym_results / sdrpp_result_sym.  The arrays are copied during the call. */
+typedef struct sdrpp_sym_desc {
+    float inv_deviation;              /* (float)(1.0 / hzToRads(deviation, if_rate)); negative for the pager (deviation -4500)  */
+    int shape_ntaps;                  /* FIR<float, float> in front of the loop, 1 .. 64                                         */
+    const float* shape_taps;
+    float omega;                      /* samples per symbol: pcl.freq after init                                                 */
+    float mu_gain, omega_gain;        /* pcl alpha, beta                                                                         */
+    float min_omega, max_omega;       /* (float)(omega * (1 - lim)), (float)(omega * (1 + lim))                                  */
+    int interp_phases, interp_ntaps;  /* 128, 8; the bank holds interp_phases * interp_ntaps floats                              */
+    const float* interp_bank;         /* phase-major, as buildPolyphaseBank lays it out: sdrpp_design_mm_interp                  */
+} sdrpp_sym_desc;
+int sdrpp_vfo_set_symbols(sdrpp_ctx* ctx, int id, const sdrpp_sym_desc* desc, int enabled);
+/* The branch's output of the most recent push: soft symbols and their bits (soft > 0.0f). */
+int sdrpp_vfo_sym_count(sdrpp_ctx* ctx, int id);
+int sdrpp_vfo_sym_read(sdrpp_ctx* ctx, int id, float* soft_host, uint8_t* bits_host, int max);   /* either array may be NULL; returns the symbols copied */
+int sdrpp_vfo_sym_device_buffers(sdrpp_ctx* ctx, int id, const float** soft, const uint8_t** bits, int* n);
+int sdrpp_abi_sizeof_sym_desc(void);
+/* Test and statistics hook: interpolator banks the context holds in device memory (identical banks share one). */
+int sdrpp_sym_bank_count(sdrpp_ctx* ctx);
+/* MM::generateInterpTaps (mm.h:173-178): windowedSinc(phases * ntaps, hzToRads(0.5 / phases, 1.0), nuttall, phases) through buildPolyphaseBank
+ * (polyphase_bank.h:15-48), phase-major into bank[phases * ntaps]; bit for bit the reference's.  Returns phases * ntaps, or SDRPP_ERR_INVALID. */
+int sdrpp_design_mm_interp(int phases, int ntaps, float* bank);
+/* The scalars of POCSAGDSP::init(in, if_rate, baudrate) (pocsag/dsp.h:20-37) into *desc: inv_deviation for Quadrature(-4500, if_rate), omega = if_rate /
+ * baudrate with MM's gains 1e-4 (omega) and 1.0 (mu) and relative limit 0.05, 128 x 8 interpolator, shape_ntaps = 10.  The two arrays stay the caller's:
+ * ten taps of 0.1f and sdrpp_design_mm_interp(128, 8).  SDRPP_ERR_INVALID for rates that are not positive and finite. */
+int sdrpp_design_pager(double if_rate, double baudrate, sdrpp_sym_desc* desc);
+
 /* ---- WaterFall display state around the raw-line history (core/src/gui/widgets/waterfall.cpp) ---------------
  * The last `height` raw dB lines stay resident in HBM in the reference's ring order (getFFTBuffer :875-886), so a zoom / pan /
  * level change re-renders the whole waterfall on the device (updateWaterfallFb :600-631) instead of re-reading host memory, and
@@ -699,6 +770,14 @@ int sdrpp_result_rec(sdrpp_ctx* ctx, uint64_t ticket, int id, const void** data,
 #define SDRPP_RESULT_RDS 32
 int sdrpp_pipeline_set_rds_results(sdrpp_ctx* ctx, int on);
 int sdrpp_result_rds(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** data, int* count);
+/* Result flag 64: the symbol branches' outputs (sdrpp_vfo_set_symbols) travel in every block's result slot — per branch the per-push counts, then room for
+ * the block's capacity of soft values (4 bytes) and bits (1 byte): 5 bytes per possible symbol, about 12 KB/s per 2400-baud channel.  A call of its own,
+ * with the rules of sdrpp_pipeline_set_rds_results; 64 is independent of 1 and 32.
+ * sdrpp_result_sym: *soft / *bits = the *count symbols VFO `id`'s branch started inside push `ticket` (in a launch group the group's symbols lie in one
+ * piece and every push gets its own count and slice).  Validity as for sdrpp_result_rds; SDRPP_ERR_NOT_FOUND likewise.  Any output may be NULL. */
+#define SDRPP_RESULT_SYM 64
+int sdrpp_pipeline_set_sym_results(sdrpp_ctx* ctx, int on);
+int sdrpp_result_sym(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** soft, const uint8_t** bits, int* count);
 /* Signal meters of push `ticket` (sdrpp_wf_set_meters): *data = [*n_lines][*n_meters][2] floats in the block's result slot, for the lines this push's
  * own samples completed — the rows `zoomed` / `raw` give it — oldest first.  No result flag: while a table is set, EVERY pipelined block with the
  * FFT on carries its meters (n_lines * n_meters * 8 bytes), result_flags = 0 included — sdrpp_result_wait / _release then work for such blocks.

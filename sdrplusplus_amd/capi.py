@@ -94,6 +94,24 @@ class RdsDesc(C.Structure):
     ]
 
 
+class SymDesc(C.Structure):
+    """struct sdrpp_sym_desc (include/sdrpp_gpu.h): the symbol branch of a RAW VFO — discriminator, shaping FIR, Mueller-Mueller clock recovery."""
+
+    _fields_ = [
+        ("inv_deviation", C.c_float),
+        ("shape_ntaps", C.c_int),
+        ("shape_taps", c_float_p),
+        ("omega", C.c_float),
+        ("mu_gain", C.c_float),
+        ("omega_gain", C.c_float),
+        ("min_omega", C.c_float),
+        ("max_omega", C.c_float),
+        ("interp_phases", C.c_int),
+        ("interp_ntaps", C.c_int),
+        ("interp_bank", c_float_p),
+    ]
+
+
 class StereoDesc(C.Structure):
     """struct sdrpp_stereo_desc (include/sdrpp_gpu.h): the WFM demodulator's stereo branch — pilot filter, PLL, L-R matrix."""
 
@@ -190,6 +208,7 @@ class Result(C.Structure):
 ABI_VERSION = 2    # SDRPP_ABI_VERSION (include/sdrpp_gpu.h)
 RESULT_SLOTS = 24  # SDRPP_RESULT_SLOTS: launches (one block each, or a group of up to GROUP_MAX: sdrpp_set_pipeline_group) whose pipelined results can exist at a time
 GROUP_MAX = 32     # SDRPP_GROUP_MAX
+RESULT_SYM = 64    # SDRPP_RESULT_SYM: the symbol branches' soft values, bits and per-push counts in every block's result slot (Context.set_pipelined, Context.result_sym)
 RESULT_RDS = 32    # SDRPP_RESULT_RDS: the RDS branches' samples in every block's result slot (Context.set_pipelined, Context.result_rds)
 
 
@@ -273,6 +292,19 @@ def load():
     L.sdrpp_rds_bank_count.argtypes = [vp]
     L.sdrpp_pipeline_set_rds_results.argtypes = [vp, C.c_int]
     L.sdrpp_result_rds.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(c_float_p), c_int_p]
+    L.sdrpp_abi_sizeof_sym_desc.argtypes = []
+    if L.sdrpp_abi_sizeof_sym_desc() != C.sizeof(SymDesc):
+        raise ImportError("sdrpp_sym_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_sym_desc(), C.sizeof(SymDesc)))
+    c_u8_p = C.POINTER(C.c_uint8)
+    L.sdrpp_vfo_set_symbols.argtypes = [vp, C.c_int, C.POINTER(SymDesc), C.c_int]
+    L.sdrpp_vfo_sym_count.argtypes = [vp, C.c_int]
+    L.sdrpp_vfo_sym_read.argtypes = [vp, C.c_int, c_float_p, c_u8_p, C.c_int]
+    L.sdrpp_vfo_sym_device_buffers.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), c_int_p]
+    L.sdrpp_sym_bank_count.argtypes = [vp]
+    L.sdrpp_pipeline_set_sym_results.argtypes = [vp, C.c_int]
+    L.sdrpp_result_sym.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(c_float_p), C.POINTER(c_u8_p), c_int_p]
+    L.sdrpp_design_mm_interp.argtypes = [C.c_int, C.c_int, c_float_p]
+    L.sdrpp_design_pager.argtypes = [C.c_double, C.c_double, C.POINTER(SymDesc)]
     L.sdrpp_abi_sizeof_stereo_desc.argtypes = []
     if L.sdrpp_abi_sizeof_stereo_desc() != C.sizeof(StereoDesc):
         raise ImportError("sdrpp_stereo_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_stereo_desc(), C.sizeof(StereoDesc)))
@@ -385,6 +417,8 @@ EXPORTED_SYMBOLS = [
     "sdrpp_vfo_set_rds", "sdrpp_vfo_rds_count", "sdrpp_vfo_rds_read", "sdrpp_vfo_rds_device_buffer", "sdrpp_abi_sizeof_rds_desc", "sdrpp_rds_bank_count",
     "sdrpp_pipeline_set_rds_results", "sdrpp_result_rds",
     "sdrpp_vfo_set_stereo", "sdrpp_abi_sizeof_stereo_desc", "sdrpp_design_band_pass_complex", "sdrpp_design_pll",
+    "sdrpp_vfo_set_symbols", "sdrpp_vfo_sym_count", "sdrpp_vfo_sym_read", "sdrpp_vfo_sym_device_buffers", "sdrpp_abi_sizeof_sym_desc", "sdrpp_sym_bank_count",
+    "sdrpp_pipeline_set_sym_results", "sdrpp_result_sym", "sdrpp_design_mm_interp", "sdrpp_design_pager",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
     "sdrpp_vfo_set_if", "sdrpp_vfo_set_fmnr", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
     "sdrpp_fft_configure", "sdrpp_fft_disable", "sdrpp_fft_set_view", "sdrpp_fft_lines", "sdrpp_fft_read", "sdrpp_fft_copy_device", "sdrpp_fft_device_buffers",
@@ -438,6 +472,24 @@ def design_pll(bandwidth):
     a, b = C.c_float(), C.c_float()
     load().sdrpp_design_pll(bandwidth, C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+def design_mm_interp(phases=128, ntaps=8):
+    """MM::generateInterpTaps (clock_recovery/mm.h:173-178) -> the interpolator bank, float32 [phases, ntaps], phase-major"""
+    bank = np.empty((int(phases), int(ntaps)), dtype=np.float32)
+    n = load().sdrpp_design_mm_interp(int(phases), int(ntaps), bank.ctypes.data_as(c_float_p))
+    if n != bank.size:
+        raise SdrppError(n, "sdrpp_design_mm_interp")
+    return bank
+
+
+def design_pager(if_rate, baudrate):
+    """The scalars of POCSAGDSP::init(in, if_rate, baudrate) -> a SymDesc whose two arrays are still to be set"""
+    d = SymDesc()
+    rc = load().sdrpp_design_pager(float(if_rate), float(baudrate), C.byref(d))
+    if rc < 0:
+        raise SdrppError(rc, "sdrpp_design_pager")
+    return d
 
 
 def design_fft_window(kind, nz):
@@ -820,6 +872,35 @@ class Context:
             C.memmove(out.ctypes.data, data, n.value * 8)
         return out
 
+    def vfo_set_symbols(self, vid, desc, enabled=True, keepalive=None):
+        """Attach the symbol branch to a RAW VFO (sdrpp_vfo_set_symbols; radio.pager_desc), switch it (the same description: enabled = False freezes its
+        state, True continues) or, with desc None, detach it.  `keepalive` is only there so that a caller can pass what radio.pager_desc returns: the library
+        copies every array during the call, nothing is kept."""
+        self._chk(self.L.sdrpp_vfo_set_symbols(self.h, vid, C.byref(desc) if desc is not None else None, int(bool(enabled))))
+
+    def vfo_sym_count(self, vid):
+        return self._chk(self.L.sdrpp_vfo_sym_count(self.h, vid))
+
+    def vfo_sym_read(self, vid):
+        """The symbol branch's output of the last push -> (soft float32 [n], bits uint8 [n]).  (Two waits for the device, one for the count and one in the read:
+        a convenience path — many channels are read out of the pipelined results, result_sym.)"""
+        n = self.vfo_sym_count(vid)
+        soft, bits = np.empty(max(n, 1), np.float32), np.empty(max(n, 1), np.uint8)
+        got = self._chk(self.L.sdrpp_vfo_sym_read(self.h, vid, soft.ctypes.data_as(c_float_p), bits.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return soft[:got], bits[:got]
+
+    def sym_bank_count(self):
+        """Interpolator banks of symbol branches this context holds in device memory (identical banks share one)."""
+        return self._chk(self.L.sdrpp_sym_bank_count(self.h))
+
+    def result_sym(self, ticket, vid):
+        """sdrpp_result_sym (result flag RESULT_SYM), between result_wait and result_release of that ticket -> this push's (soft, bits), copies."""
+        soft, bits, n = c_float_p(), C.POINTER(C.c_uint8)(), C.c_int(0)
+        self._chk(self.L.sdrpp_result_sym(self.h, int(ticket), vid, C.byref(soft), C.byref(bits), C.byref(n)))
+        if n.value <= 0:
+            return np.zeros(0, np.float32), np.zeros(0, np.uint8)
+        return np.ctypeslib.as_array(soft, shape=(n.value,)).copy(), np.ctypeslib.as_array(bits, shape=(n.value,)).copy()
+
     def vfo_set_stereo(self, vid, desc, keepalive=None):
         """Attach the WFM demodulator's stereo branch (sdrpp_vfo_set_stereo; radio.stereo_desc), switch it (desc.enabled: BroadcastFM::setStereo, the
         demodulator starts over) or, with None, detach it.  `keepalive` is only there so that a caller can pass what radio.stereo_desc returns: the library
@@ -911,10 +992,13 @@ class Context:
     def set_pipelined(self, on, result_flags=0):
         """result_flags: 1 = every VFO's output block (AF output where a chain is attached), 2 = zoomed lines + palette indices, 4 = raw dB lines,
         8 = the pre-processed IQ stream (with a pre-processing chain), 16 = the recorder sinks' converted blocks (result_rec) into page-locked result slots,
-        32 (RESULT_RDS) = the RDS branches' samples (result_rds; the library switches that one by a call of its own, sdrpp_pipeline_set_rds_results)."""
-        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags) & ~RESULT_RDS))
+        32 (RESULT_RDS) = the RDS branches' samples (result_rds; the library switches that one by a call of its own, sdrpp_pipeline_set_rds_results),
+        64 (RESULT_SYM) = the symbol branches' outputs (result_sym; likewise, sdrpp_pipeline_set_sym_results)."""
+        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags) & ~(RESULT_RDS | RESULT_SYM)))
         if on and (int(result_flags) & RESULT_RDS):
             self._chk(self.L.sdrpp_pipeline_set_rds_results(self.h, 1))
+        if on and (int(result_flags) & RESULT_SYM):
+            self._chk(self.L.sdrpp_pipeline_set_sym_results(self.h, 1))
 
     def set_pipeline_group(self, max_blocks, adaptive=False, stable_words=False):
         """sdrpp_set_pipeline_group: up to `max_blocks` pushes per launch (every push keeps its own ticket and results); adaptive: the group follows

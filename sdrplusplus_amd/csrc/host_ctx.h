@@ -170,6 +170,28 @@ struct Vfo {
         std::vector<Stream> st;        // [0] m, [1] pilot angle, [2] loop phase: real streams at the IF rate
         bool ran = false;              // the most recent block was planned with the branch on
     } stereo;
+    // Symbol branch of a RAW VFO (sdrpp_vfo_set_symbols; pocsag/dsp.h, clock_recovery/mm.h): discriminator -> shaping FIR (front) -> MM clock recovery (loop), off
+    // the stream a demodulator would read.  Everything it remembers is its own and lives on the device — switched off it freezes while the VFO's streams move
+    // on: the front's two carried lines in two sides (vfo_sym_kernels.h; `cur`: the side the next block reads) and the loop's four words.  Its per-block
+    // buffers are streams without history, so that pipelined mode gives them its ring like every other per-block buffer.
+    struct Sym {
+        bool attached = false, on = false;
+        float inv_deviation = 0.0f, omega = 0.0f, mu_gain = 0.0f, omega_gain = 0.0f, min_omega = 0.0f, max_omega = 0.0f;
+        int K = 0, phases = 0, T = 0;
+        std::vector<float> taps;
+        unsigned long long bank_key = 0;  // the context's shared interpolator bank this branch holds a reference to (0: none)
+        const float* d_bank = nullptr;    // ... borrowed
+        float* d_taps = nullptr;
+        float* d_lines = nullptr;         // two sides of K + T floats: K - 1 discriminator values and the previous phase, then T - 1 filter outputs (SymFrontJob)
+        int cur = 0;
+        float* d_state = nullptr;         // pcl.phase, pcl.freq, lastOut, offset
+        int min_step = 1;                 // floorf(min_omega - |mu_gain|) >= 1: a block of n samples starts at most ceil(n / min_step) + 1 symbols
+        std::vector<Stream> st;           // [0] the front's [T - 1][n] floats, [1] soft values, [2] bits (bytes), [3] symbols per push (ints)
+        int lvl = 1;                      // level (do_vfos_plan) at which the loop of the most recent block runs
+        bool ran = false;                 // the most recent block was planned with the branch on
+        int n_if = 0, npush = 0, cap = 0; // ... its samples, its pushes, the symbols its outputs have room for
+        int cap_of(int n) const { return (n + min_step - 1) / min_step + 1; }
+    } sym;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
     ToepTab tp_chan, tp_audio;
     // front end as one filter (what the fused translate + filter kernels evaluate): stages 0 (+ 1) of the plan
@@ -201,7 +223,7 @@ struct Vfo {
         int base = -1;  // first AF stream in st (they are appended behind the VFO's own streams)
     } af;
 };
-// Every stream of a VFO: its own, then its RDS branch's, then its stereo branch's (the order plan_snapshot records them in).  ran_only: a branch's streams
+// Every stream of a VFO: its own, then its RDS branch's, its stereo branch's and its symbol branch's (the order plan_snapshot records them in).  ran_only: a branch's streams
 // only if the most recent plan ran the branch.
 template <class F>
 void for_each_stream(Vfo& v, F&& f, bool ran_only = false) {
@@ -211,6 +233,9 @@ void for_each_stream(Vfo& v, F&& f, bool ran_only = false) {
     }
     if (!ran_only || v.stereo.ran) {
         for (auto& s : v.stereo.st) { f(s); }
+    }
+    if (!ran_only || v.sym.ran) {
+        for (auto& s : v.sym.st) { f(s); }
     }
 }
 template <class F>
@@ -364,6 +389,9 @@ struct sdrpp_ctx {
     struct RdsBank { float* d_bank = nullptr; int refs = 0; int interp = 0, tpp = 0; std::vector<float> taps; };
     std::map<unsigned long long, RdsBank> rds_banks;  // polyphase banks of the RDS branches, ONE per distinct description (2.4 MB each), freed with their last user
 
+    struct SymBank { float* d_bank = nullptr; int refs = 0; int phases = 0, T = 0; std::vector<float> taps; };
+    std::map<unsigned long long, SymBank> sym_banks;  // interpolator banks of the symbol branches, ONE per distinct bank, freed with their last user
+
     // ---- pipelined ("tick") execution: one launch per block, the stages of consecutive blocks skewed over consecutive launches
     //      (tick_kernels.h; sdrpp_set_pipelined) ----
     struct RoleLaunch { TickEntry e; size_t lds; int level; int fam; bool to_host; };  // to_host: a copy into a page-locked result slot
@@ -382,13 +410,15 @@ struct sdrpp_ctx {
         int n_iq = 0;                                        // pre-processed IQ samples delivered (result flag 8)
         std::vector<int> rds_ids, rds_counts;                // result flag 32: the VFOs whose RDS branch ran in the block, this push's samples
         std::vector<size_t> rds_off;                         // ... and where they lie in the slot
+        std::vector<int> sym_ids, sym_push;                  // result flag 64: the VFOs whose symbol branch ran in the block, this push's index in its launch group
+        std::vector<size_t> sym_cnt_off, sym_soft_off, sym_bits_off;  // ... where the group's per-push counts, its soft values and its bits lie in the slot
         std::vector<int> rec_ids;                            // result flag 16: the VFOs that had a recorder sink when the block was planned,
         std::vector<size_t> rec_off, rec_info_off;           // ... where this push's converted samples and its sdrpp_rec_info lie in the slot
         int n_meters = -1;                                   // signal meters the block was pushed with (-1: no table then); its n_lines x n_meters x 2 floats
         size_t off_meters = 0;
     };
     bool pipelined = false;
-    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks, bit 5: RDS branches (sdrpp_pipeline_set_rds_results)
+    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks, bit 5: RDS branches (sdrpp_pipeline_set_rds_results), bit 6: symbol branches (sdrpp_pipeline_set_sym_results)
     int num_cus = 256;
     int tick_l0_at = getenv("SDRPP_GPU_TICK_L0_AT") ? atoi(getenv("SDRPP_GPU_TICK_L0_AT")) : 0;  // (read when the context is created)
     // grid rules of the roles inside a tick (the stand-alone kernels size their grids for a GPU of their own; in a tick ~8 roles share it, and

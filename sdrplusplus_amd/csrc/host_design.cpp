@@ -34,9 +34,9 @@ double hzToRads(double f, double sr) { return 2.0 * kPi * (f / sr); }           
 int estimateTapCount(double tw, double sr) { return (int)(3.8 * sr / tw); }      // taps/estimate_tap_count.h:5
 
 // taps/windowed_sinc.h:9-29 specialised to the two windows the hot path uses
-int windowedSinc(int count, double omega, bool alternate, float* taps, int max) {
+int windowedSinc(int count, double omega, bool alternate, float* taps, int max, double norm = 1.0) {
     const double half = (double)count / 2.0;
-    const double corr = omega / kPi;  // norm = 1.0
+    const double corr = norm * omega / kPi;
     for (int i = 0; i < count && i < max; i++) {
         const double t = (double)i - half + 0.5;
         double w = nuttall(t - half, (double)count);
@@ -85,6 +85,35 @@ int sdrpp_design_band_pass_complex(double band_start, double band_stop, double t
         taps[2 * i + 1] = pi * (float)corr;
     }
     return count;
+}
+
+// clock_recovery/mm.h:173-178 (generateInterpTaps) through multirate/polyphase_bank.h:15-48: tap i of the prototype is tap i / phases of phase
+// (phases - 1) - (i % phases)
+int sdrpp_design_mm_interp(int phases, int ntaps, float* bank) {
+    if (phases < 1 || phases > 1024 || ntaps < 1 || ntaps > 16 || !bank) { return SDRPP_ERR_INVALID; }
+    const int count = phases * ntaps;
+    std::vector<float> lp((size_t)count);
+    const double bw = 0.5 / (double)phases;
+    windowedSinc(count, hzToRads(bw, 1.0), false, lp.data(), count, (double)phases);
+    for (int i = 0; i < count; i++) { bank[(size_t)((phases - 1) - (i % phases)) * (size_t)ntaps + (size_t)(i / phases)] = lp[(size_t)i]; }
+    return count;
+}
+
+// pocsag/dsp.h:20-37: demod.init(NULL, -4500.0, samplerate); recov.init(NULL, samplerate / baudrate, 1e-4, 1.0, 0.05) — MM::init hands
+// pcl.init(muGain, omegaGain, 0, 0, 1, omega, omega * (1 - lim), omega * (1 + lim)) doubles that become the loop's floats (mm.h:32)
+int sdrpp_design_pager(double if_rate, double baudrate, sdrpp_sym_desc* d) {
+    if (!d || !(if_rate > 0.0) || !(baudrate > 0.0) || !std::isfinite(if_rate) || !std::isfinite(baudrate)) { return SDRPP_ERR_INVALID; }
+    const double omega = if_rate / baudrate, lim = 0.05;
+    d->inv_deviation = (float)(1.0 / hzToRads(-4500.0, if_rate));  // quadrature.h:18-25
+    d->shape_ntaps = 10;
+    d->omega = (float)omega;
+    d->mu_gain = (float)1.0;
+    d->omega_gain = (float)1e-4;
+    d->min_omega = (float)(omega * (1.0 - lim));
+    d->max_omega = (float)(omega * (1.0 + lim));
+    d->interp_phases = 128;
+    d->interp_ntaps = 8;
+    return SDRPP_OK;
 }
 
 void sdrpp_design_pll(double bandwidth_d, float* alpha, float* beta) {

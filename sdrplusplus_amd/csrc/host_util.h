@@ -484,6 +484,14 @@ void stereo_free(Vfo::Stereo& s) {
     for (auto& q : s.st) { stream_free(q); }
     s = Vfo::Stereo{};
 }
+// what a symbol branch owns by itself (its share of the context's interpolator banks is given back by sym_detach, vfo_ctl.h)
+void sym_free_own(Vfo::Sym& y) {
+    dev_free(y.d_taps);
+    dev_free(y.d_state);
+    dev_free(y.d_lines);
+    for (auto& q : y.st) { stream_free(q); }
+    y.st.clear();
+}
 // Outputs per tile and LDS row pitch of the branch's fused first stage (vfo_rds_front_body) for K taps decimating by D: the window of a tile, de-interleaved
 // by decimation phase, and its phases must fit the wavefront's share of the role's LDS.  The pitch serves the window's STORES (8 bytes per lane, carried out 16
 // lanes at a time over 32 dword banks: 16 consecutive samples must land on 16 different 8-byte banks — consecutive samples lie `pitch` float2 apart, D of them
@@ -523,6 +531,7 @@ void af_detach(Vfo& v) {
 void vfo_free(Vfo& v) {
     rds_free_own(v.rds);
     stereo_free(v.stereo);
+    sym_free_own(v.sym);
     af_detach(v);
     rate_free(v.rate);
     for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { dev_free(v.d_staps_nat[i]); }

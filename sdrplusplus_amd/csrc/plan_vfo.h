@@ -246,6 +246,10 @@ struct BankPlan {
     Lev<StereoLoopVfo> stl;
     Lev<StereoLoopJob> stlj;  // (filled by upload once stl's records have their addresses)
     Lev<StereoMatrixJob> stm;
+    // symbol branch of a RAW VFO (sym_branch): the front's records, the loop's per-VFO records up to SDRPP_SYM_PACK to a job
+    Lev<SymFrontJob> syf;
+    Lev<SymLoopVfo> syl;
+    Lev<SymLoopJob> sylj;  // (filled by upload once syl's records have their addresses)
     Lev<CarryJob> carry;  // history carries at the level of the stream's consumer (a pass without pipelining: all at the last level)
     int max_rot = 0;
     // front-end jobs (group_front)
@@ -277,17 +281,17 @@ struct BankPlan {
 
     // THE enumeration of the Lev<> job lists, in the order their tables lie in the arena (the matrix-core lists of tlists[] first), for begin(),
     // upload() and emit_levels().  A new list is one more f(...) here (a matrix-core list: one more row of tlists[]; a record list of the wavefront-job
-    // role: one more file_wave line in upload as well).  The last two are not filled by the chain walk: upload derives them from lists in front of them
-    // once those have their addresses in the arena (stlj from stl, wave from every record list of the role), and pushes them itself.
+    // role: one more file_wave line in upload as well).  The last three are not filled by the chain walk: upload derives them from lists in front of them
+    // once those have their addresses in the arena (stlj from stl, sylj from syl, wave from every record list of the role), and pushes them itself.
     template <class F>
     void for_each_list(F&& f) {
         for (auto& t : tlists) { f(*t.L); }
         f(f_dec); f(poly);
         for (auto& q : polyb) { f(q); }
-        f(chan); f(seq); f(nbsq); f(fmif); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stm); f(pre); f(audio); f(audio_fm);
+        f(chan); f(seq); f(nbsq); f(fmif); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stm); f(syf); f(syl); f(pre); f(audio); f(audio_fm);
         f(af_dec); f(af_hpf); f(af_poly); f(af_deemp);
         f(ssbx_l); f(carry);
-        f(stlj); f(wave);
+        f(stlj); f(sylj); f(wave);
     }
 
     explicit BankPlan(sdrpp_ctx* c_) : c(c_), fb(c_->vfo_bounds) {
@@ -482,6 +486,14 @@ struct BankPlan {
         }
         else {
             for (auto& s : v.rds.st) { s.n = 0; }
+        }
+        v.sym.ran = v.sym.attached && v.sym.on;
+        if (v.sym.ran) {
+            if (int rc = sym_branch(x, feed)) { return rc; }
+            last_lvl = std::max(last_lvl, v.sym.lvl);
+        }
+        else {
+            for (auto& s : v.sym.st) { s.n = 0; }
         }
         phase_advance(x);
         x.at.lvl = last_lvl;
@@ -848,6 +860,40 @@ struct BankPlan {
         if (r.i_poly >= 0) { poly_step(x, r.st[(size_t)r.i_poly], R, nullptr, 0, 0, t_af_poly, af_poly); }  // (5000 phases: the branch keeps no matrix table)
         r.i_last = (int)(x.at.cur - &r.st[0]);
         r.lvl = x.at.lvl;
+    }
+    // Symbol branch of a RAW VFO (pocsag/dsp.h, clock_recovery/mm.h): front (discriminator, shaping FIR: a job per run of SDRPP_SYM_SEG samples) one level behind
+    // the stream a demodulator would read (`feed`), loop (MM's recursion: a record per VFO, upload packs them into jobs) the level after.  The front reads one
+    // side of the branch's carried lines and its last job writes the other: the sides flip with every block that has samples.  A launch group is one block
+    // to the front; the loop is handed the push ends at the stream's rate and counts the symbols push by push.  A block without samples still files the loop's
+    // record: it writes the zeros of its counts and leaves the state as it is.
+    int sym_branch(ChainCtx& x, const ChainCursor& feed) {
+        Vfo& v = x.v;
+        Vfo::Sym& y = v.sym;
+        const Stream& in = *feed.cur;
+        const int lvl = feed.lvl, n = in.n;
+        Stream &buf = y.st[0], &soft = y.st[1], &bits = y.st[2], &cnt = y.st[3];
+        y.n_if = n;
+        y.npush = x.split ? (int)v.tk_if.size() : 1;
+        y.cap = y.cap_of(n);
+        y.lvl = lvl + 2;
+        for (int lo = 0; lo < n; lo += SDRPP_SYM_SEG) {  // (the branch's delay lines are its own: the feed's history is not read)
+            syf.add(lvl + 1, SymFrontJob{ reinterpret_cast<const float2*>(in.data), y.d_lines, buf.data, y.d_taps, n, y.cur, y.K, y.T, lo, std::min(lo + SDRPP_SYM_SEG, n), y.inv_deviation, 0 });
+        }
+        if (n > 0) { y.cur ^= 1; }
+        const int* d_ends = nullptr;
+        if (x.split) {
+            d_ends = arena_push(c, v.tk_if);
+            if (!d_ends) { return arena_fail(c); }
+        }
+        syl.add(lvl + 2, SymLoopVfo{ buf.data, soft.data, reinterpret_cast<uint8_t*>(bits.data), reinterpret_cast<int*>(cnt.data), y.d_state, y.d_bank, d_ends, y.mu_gain, y.omega_gain, y.min_omega,
+                                     y.max_omega, y.phases, y.T, n, y.npush, y.cap, 0 });
+        buf.n = n;
+        soft.n = y.cap;
+        bits.n = (y.cap + 3) / 4;
+        cnt.n = y.npush;
+        for (auto& s : y.st) { s.wlevel = lvl + 2; }
+        buf.wlevel = lvl + 1;
+        return SDRPP_OK;
     }
     void phase_advance(ChainCtx& x) {
         Vfo& v = x.v;
@@ -1230,6 +1276,14 @@ struct BankPlan {
             }
         }
         if (!arena_push_lev(c, stlj)) { return arena_fail(c); }
+        // ... and the symbol loops' per-VFO records, a lane each: as few jobs as SDRPP_SYM_PACK lanes allow, the records spread evenly over them
+        for (int l = 0; l < syl.top; l++) {
+            const size_t N = syl.at[l].size();
+            if (N == 0) { continue; }
+            const size_t njobs = (N + SDRPP_SYM_PACK - 1) / SDRPP_SYM_PACK, per = (N + njobs - 1) / njobs;
+            for (size_t k = 0; k < N; k += per) { sylj.add(l, SymLoopJob{ syl.dev[l] + k, (int)std::min(per, N - k), 0 }); }
+        }
+        if (!arena_push_lev(c, sylj)) { return arena_fail(c); }
         // 2. every record under the role, kind by kind: the order of a level's jobs, four neighbours to a workgroup
         file_wave(nbsq, WK_NBSQ);
         file_wave(fmif, WK_FMIF);
@@ -1239,6 +1293,8 @@ struct BankPlan {
         file_wave(stp, WK_ST_PILOT);
         file_wave(stlj, WK_ST_LOOP);
         file_wave(stm, WK_ST_MATRIX);
+        file_wave(syf, WK_SYM_FRONT);
+        file_wave(sylj, WK_SYM_LOOP);
         // 3. the role's table
         if (!arena_push_lev(c, wave)) { return arena_fail(c); }
         HostScope hs("arena_commit (H2D)");

@@ -382,6 +382,8 @@ int sdrpp_destroy(sdrpp_ctx* c) {
     for (auto& kv : c->vfos) { vfo_free(*kv.second); }
     for (auto& kv : c->rds_banks) { dev_free(kv.second.d_bank); }
     c->rds_banks.clear();
+    for (auto& kv : c->sym_banks) { dev_free(kv.second.d_bank); }
+    c->sym_banks.clear();
     c->vfos.clear();
     for (auto& e : c->s1_tap_cache) { (void)hipFree(e.second); }
     for (auto& e : c->fmif_tabs) { (void)hipFree(e.second); }
@@ -758,6 +760,7 @@ int sdrpp_vfo_remove(sdrpp_ctx* c, int id) {
     LOOKUP_VFO(v, c, id);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     rds_detach(c, *v);
+    sym_detach(c, *v);
     vfo_free(*v);
     c->vfos.erase(id);
     vfo_list_rebuild(c);
@@ -958,6 +961,48 @@ int sdrpp_vfo_rds_device_buffer(sdrpp_ctx* c, int id, const float** out, int* n_
 int sdrpp_abi_sizeof_rds_desc(void) { return (int)sizeof(sdrpp_rds_desc); }
 int sdrpp_rds_bank_count(sdrpp_ctx* c) { return c ? (int)c->rds_banks.size() : SDRPP_ERR_INVALID; }
 
+// ---- symbol branch of a RAW VFO: discriminator -> shaping FIR -> MM clock recovery -> soft symbols, bits (pocsag/dsp.h, clock_recovery/mm.h) -----------
+int sdrpp_vfo_set_symbols(sdrpp_ctx* c, int id, const sdrpp_sym_desc* d, int enabled) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return sym_apply(c, *v, d, enabled != 0);
+}
+int sdrpp_vfo_sym_count(sdrpp_ctx* c, int id) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return sym_count(c, *v);
+}
+int sdrpp_vfo_sym_read(sdrpp_ctx* c, int id, float* soft, uint8_t* bits, int max) {
+    DeviceScope dev_scope_(c);
+    if (!c || max < 0) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    const int have = sym_count(c, *v);
+    if (have < 0) { return have; }
+    const int n = std::min(have, max);
+    if (n > 0 && soft) { HIPCHK(c, hipMemcpy(soft, v->sym.st[1].data, (size_t)n * sizeof(float), hipMemcpyDeviceToHost)); }
+    if (n > 0 && bits) { HIPCHK(c, hipMemcpy(bits, v->sym.st[2].data, (size_t)n, hipMemcpyDeviceToHost)); }
+    return n;
+}
+int sdrpp_vfo_sym_device_buffers(sdrpp_ctx* c, int id, const float** soft, const uint8_t** bits, int* n) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    const int have = sym_count(c, *v);
+    if (have < 0) { return have; }
+    if (soft) { *soft = v->sym.st[1].data; }
+    if (bits) { *bits = reinterpret_cast<const uint8_t*>(v->sym.st[2].data); }
+    if (n) { *n = have; }
+    return SDRPP_OK;
+}
+int sdrpp_abi_sizeof_sym_desc(void) { return (int)sizeof(sdrpp_sym_desc); }
+int sdrpp_sym_bank_count(sdrpp_ctx* c) { return c ? (int)c->sym_banks.size() : SDRPP_ERR_INVALID; }
+
 int sdrpp_vfo_read_pcm(sdrpp_ctx* c, int id, int which, int pcm_type, float scale, void* dst_host, int max_frames) {
     DeviceScope dev_scope_(c);
     if (!c || !dst_host || max_frames < 0 || (pcm_type != 0 && pcm_type != 1)) { return SDRPP_ERR_INVALID; }
@@ -1125,6 +1170,7 @@ int sdrpp_vfo_reset(sdrpp_ctx* c, int id) {
     FLUSH_PENDING(c);
     LOOKUP_VFO(v, c, id);
     if (int rc = rds_freeze(c, *v)) { return rc; }  // (the RDS branch's delay line is not the demodulator's: it outlives the history cleared below)
+    if (int rc = sym_reset_prev(c, *v)) { return rc; }
     return vfo_reset_state(c, *v);
 }
 
@@ -1696,6 +1742,33 @@ int sdrpp_result_rds(sdrpp_ctx* c, uint64_t ticket, int id, const float** data, 
         return SDRPP_OK;
     }
     return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of an RDS branch of VFO %d", (unsigned long long)ticket, id);
+}
+int sdrpp_pipeline_set_sym_results(sdrpp_ctx* c, int on) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    if (!c->pipelined) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_pipeline_set_sym_results outside pipelined mode"); }
+    FLUSH_PENDING(c);
+    c->res_flags = on ? (c->res_flags | SDRPP_RESULT_SYM) : (c->res_flags & ~SDRPP_RESULT_SYM);
+    return SDRPP_OK;
+}
+// (the counts are the loop's own result: they lie in the slot, complete since sdrpp_result_wait returned for this block)
+int sdrpp_result_sym(sdrpp_ctx* c, uint64_t ticket, int id, const float** soft, const uint8_t** bits, int* count) {
+    if (!c) { return SDRPP_ERR_INVALID; }
+    sdrpp_ctx::Result* R = result_of(c, ticket);
+    if (!R || !R->held) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_result_sym: block %llu is not held (between sdrpp_result_wait and sdrpp_result_release)", (unsigned long long)ticket); }
+    for (size_t i = 0; i < R->sym_ids.size(); i++) {
+        if (R->sym_ids[i] != id) { continue; }
+        int cnt[kGroupMax] = {};
+        const int j = std::min(R->sym_push[i], kGroupMax - 1);
+        memcpy(cnt, R->base + R->sym_cnt_off[i], (size_t)(j + 1) * sizeof(int));
+        size_t lo = 0;
+        for (int q = 0; q < j; q++) { lo += (size_t)std::max(cnt[q], 0); }
+        if (soft) { *soft = reinterpret_cast<const float*>(R->base + R->sym_soft_off[i]) + lo; }
+        if (bits) { *bits = reinterpret_cast<const uint8_t*>(R->base + R->sym_bits_off[i]) + lo; }
+        if (count) { *count = cnt[j]; }
+        return SDRPP_OK;
+    }
+    return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of a symbol branch of VFO %d", (unsigned long long)ticket, id);
 }
 int sdrpp_result_meters(sdrpp_ctx* c, uint64_t ticket, const float** data, int* n_lines, int* n_meters) {
     if (!c) { return SDRPP_ERR_INVALID; }

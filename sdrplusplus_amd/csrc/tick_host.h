@@ -277,6 +277,12 @@ size_t tick_results_need(sdrpp_ctx* c) {
             if (r.attached && !r.st.empty()) { need += ((r.st.back().cap + 16) * 8 + 15) & ~(size_t)15; }
         }
     }
+    if (c->res_flags & 64) {  // symbol branches: per-push counts, then the largest block's capacity of soft values and of bits
+        for (auto& kv : c->vfos) {
+            const Vfo::Sym& y = kv.second->sym;
+            if (y.attached && y.st.size() == 4) { need += (size_t)kGroupMax * 4 + (((y.st[1].cap + 16) * 4 + 15) & ~(size_t)15) + ((y.st[1].cap + 16 + 15) & ~(size_t)15); }
+        }
+    }
     if ((c->res_flags & 8) && c->pre.on) {
         size_t cap = c->pre.out.base ? c->pre.out.cap : 0;
         for (auto& st : c->pre.st) { cap = std::max(cap, st.cap); }
@@ -498,6 +504,28 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
             const size_t bytes = (size_t)s.n * 8;
             if (bytes) { copies.push_back(ResCopy{ s.data, off, bytes, r.lvl + 1 }); }
             off += (bytes + 15) & ~(size_t)15;
+        }
+    }
+    if (c->res_flags & 64) {
+        // every symbol branch that ran in this block: the loop's per-push counts, then what its outputs have room for in this block (how many of them are symbols
+        // is the loop's own result: the counts say, sdrpp_result_sym reads them once the block is complete)
+        for (auto& kv : c->vfos) {
+            const Vfo& v = *kv.second;
+            const Vfo::Sym& y = v.sym;
+            if (!y.attached || !y.ran) { continue; }
+            if (y.npush != k) { return fail(c, SDRPP_ERR_INVALID, "internal: VFO %d's symbol branch planned %d pushes, the block has %d", v.id, y.npush, k); }
+            const size_t cnt_off = off, soft_off = cnt_off + (((size_t)k * 4 + 15) & ~(size_t)15), bits_off = soft_off + (((size_t)y.cap * 4 + 15) & ~(size_t)15);
+            for (int j = 0; j < k; j++) {
+                R[j]->sym_ids.push_back(v.id);
+                R[j]->sym_push.push_back(j);
+                R[j]->sym_cnt_off.push_back(cnt_off);
+                R[j]->sym_soft_off.push_back(soft_off);
+                R[j]->sym_bits_off.push_back(bits_off);
+            }
+            copies.push_back(ResCopy{ y.st[3].data, cnt_off, (size_t)k * 4, y.lvl + 1 });
+            copies.push_back(ResCopy{ y.st[1].data, soft_off, (size_t)y.cap * 4, y.lvl + 1 });
+            copies.push_back(ResCopy{ y.st[2].data, bits_off, ((size_t)y.cap + 3) & ~(size_t)3, y.lvl + 1 });
+            off = bits_off + (((size_t)y.cap + 15) & ~(size_t)15);
         }
     }
     if (off > c->res_cap) { return fail(c, SDRPP_ERR_INVALID, "internal: results of %zu bytes exceed what a launch may deliver (%zu)", off, c->res_cap); }

@@ -367,6 +367,7 @@ int fmnr_apply(sdrpp_ctx* c, Vfo& v, bool enabled, int bins) {
 // (a demodulator SWITCH deletes and creates it, radio_module.h:419-563: bit 1 off).  The AF chain is re-attached by the caller and starts cleared.
 int rds_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n);  // (the RDS branch: below, with the rest of it)
 int stereo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, bool* cleared);  // (the stereo branch: likewise)
+int sym_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n);  // (the symbol branch: likewise)
 int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
     Stream& of = chan_feed(o);
     Stream& nf = chan_feed(n);
@@ -426,6 +427,9 @@ int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
     }
     if ((keep & 2) && o.d.demod == n.d.demod && n.d.demod == SDRPP_DEMOD_WFM) {
         if ((rc = rds_hand_over(c, o, n))) { return rc; }
+    }
+    if ((keep & 2) && o.d.demod == n.d.demod && n.d.demod == SDRPP_DEMOD_RAW) {
+        if ((rc = sym_hand_over(c, o, n))) { return rc; }
     }
     if (keep & 4) {  // ... and FMIF with them: its bin count, whether it is plugged in, and its delay line
         if ((rc = fmif_line_save(c, o))) { return rc; }
@@ -831,6 +835,165 @@ int stereo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, bool* cleared) {
     for (auto& q : n.stereo.st) { q.n = 0; }
     return stereo_grow_feeds(c, n, n.stereo.K);
 }
+// ---- symbol branch of a RAW VFO -------------------------------------------------------------------------------------------------------
+void sym_detach(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Sym& y = v.sym;
+    if (y.bank_key) {
+        auto it = c->sym_banks.find(y.bank_key);
+        if (it != c->sym_banks.end() && --it->second.refs <= 0) {
+            dev_free(it->second.d_bank);
+            c->sym_banks.erase(it);
+        }
+    }
+    sym_free_own(y);
+    y = Vfo::Sym{};
+}
+// The context's shared interpolator bank (keyed by rds_bank_hash over its shape and its floats, one reference per branch): uploaded with its first user
+int sym_bank_acquire(sdrpp_ctx* c, Vfo::Sym& y, const float* bank) {
+    const int n = y.phases * y.T;
+    const unsigned long long key = rds_bank_hash(y.phases, y.T, bank, n);
+    auto it = c->sym_banks.find(key);
+    if (it != c->sym_banks.end() && (it->second.phases != y.phases || it->second.T != y.T || memcmp(it->second.taps.data(), bank, (size_t)n * sizeof(float)) != 0)) {
+        return fail(c, SDRPP_ERR_UNSUPPORTED, "interpolator bank: two different banks under one key");  // (a 64-bit collision: never seen)
+    }
+    if (it == c->sym_banks.end()) {
+        sdrpp_ctx::SymBank B;
+        B.taps.assign(bank, bank + n);
+        if (int rc = upload(c, &B.d_bank, B.taps.data(), B.taps.size())) { return rc; }
+        B.phases = y.phases;
+        B.T = y.T;
+        it = c->sym_banks.emplace(key, std::move(B)).first;
+    }
+    it->second.refs++;
+    y.bank_key = key;
+    y.d_bank = it->second.d_bank;
+    return SDRPP_OK;
+}
+// a fresh POCSAGDSP: previous phase 0, cleared lines, phase 0, freq = omega, lastOut 0, offset 0
+int sym_clear(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Sym& y = v.sym;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemset(y.d_lines, 0, (size_t)2 * (size_t)(y.K + y.T) * sizeof(float)));
+    const int zero = 0;
+    float st[4] = { 0.0f, y.omega, 0.0f, 0.0f };
+    memcpy(&st[3], &zero, sizeof(int));
+    HIPCHK(c, hipMemcpy(y.d_state, st, sizeof(st), hipMemcpyHostToDevice));
+    y.cur = 0;
+    y.ran = false;
+    for (auto& q : y.st) { q.n = 0; }
+    return SDRPP_OK;
+}
+bool sym_same_desc(const Vfo::Sym& y, const sdrpp_sym_desc* d, const sdrpp_ctx* c) {
+    if (y.inv_deviation != d->inv_deviation || y.K != d->shape_ntaps || y.omega != d->omega || y.mu_gain != d->mu_gain || y.omega_gain != d->omega_gain || y.min_omega != d->min_omega ||
+        y.max_omega != d->max_omega || y.phases != d->interp_phases || y.T != d->interp_ntaps || memcmp(y.taps.data(), d->shape_taps, y.taps.size() * sizeof(float)) != 0) {
+        return false;
+    }
+    auto it = c->sym_banks.find(y.bank_key);
+    return it != c->sym_banks.end() && memcmp(it->second.taps.data(), d->interp_bank, it->second.taps.size() * sizeof(float)) == 0;
+}
+// sdrpp_vfo_set_symbols on a VFO the caller has looked up (the stream is idle); d == nullptr: the branch goes
+int sym_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_sym_desc* d, bool enabled) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!d) {
+        sym_detach(c, v);
+        return SDRPP_OK;
+    }
+    if (v.d.demod != SDRPP_DEMOD_RAW) { return fail(c, SDRPP_ERR_UNSUPPORTED, "the symbol branch needs a RAW VFO"); }
+    if (d->shape_ntaps < 1 || d->shape_ntaps > SDRPP_SYM_MAX_SHAPE_TAPS || !d->shape_taps) { return fail(c, SDRPP_ERR_INVALID, "symbol branch: shaping filter of %d taps (1 .. %d, with taps)", d->shape_ntaps, SDRPP_SYM_MAX_SHAPE_TAPS); }
+    if (d->interp_ntaps < 1 || d->interp_ntaps > SDRPP_SYM_MAX_INTERP_TAPS || d->interp_phases < 1 || d->interp_phases > SDRPP_SYM_MAX_PHASES || !d->interp_bank) {
+        return fail(c, SDRPP_ERR_INVALID, "symbol branch: interpolator of %d phases x %d taps (1 .. %d x 1 .. %d, with a bank)", d->interp_phases, d->interp_ntaps, SDRPP_SYM_MAX_PHASES, SDRPP_SYM_MAX_INTERP_TAPS);
+    }
+    const bool finite = std::isfinite(d->inv_deviation) && std::isfinite(d->omega) && std::isfinite(d->mu_gain) && std::isfinite(d->omega_gain) && std::isfinite(d->min_omega) && std::isfinite(d->max_omega);
+    // every step floorf(phase + freq + mu_gain * error), phase in [0, 1), |error| <= 1, advances at least one sample and at most SDRPP_SYM_MAX_STEP + 1
+    if (!finite || !(d->min_omega < d->max_omega) || !(d->min_omega - fabsf(d->mu_gain) >= 1.0f) || !(d->max_omega + fabsf(d->mu_gain) <= (float)SDRPP_SYM_MAX_STEP)) {
+        return fail(c, SDRPP_ERR_INVALID, "symbol loop: omega limits %g .. %g, omega %g, mu gain %g, omega gain %g, 1 / deviation %g: all finite, min < max, min - |mu gain| >= 1, max + |mu gain| <= %d",
+                    d->min_omega, d->max_omega, d->omega, d->mu_gain, d->omega_gain, d->inv_deviation, SDRPP_SYM_MAX_STEP);
+    }
+    const size_t cap = v.st[(size_t)v.i_chan].cap;
+    if (cap + 16 >= ((size_t)1 << 24) - (size_t)(SDRPP_SYM_MAX_STEP + 1)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "symbol branch on a stream of up to %zu samples per push (offsets are exact below 2^24)", cap); }
+    Vfo::Sym& y = v.sym;
+    if (y.attached && sym_same_desc(y, d, c)) {  // the same branch: only the switch — everything it holds stays as it is
+        if (y.on && !enabled) {
+            for (auto& q : y.st) { q.n = 0; }
+        }
+        y.on = enabled;
+        y.ran = y.ran && enabled;
+        return SDRPP_OK;
+    }
+    sym_detach(c, v);
+    // every early return below gives back what was built so far
+    struct Undo {
+        sdrpp_ctx* c; Vfo& v; bool armed = true;
+        ~Undo() { if (armed) { sym_detach(c, v); } }
+    } undo{ c, v };
+    int rc;
+    y.inv_deviation = d->inv_deviation;
+    y.K = d->shape_ntaps;
+    y.omega = d->omega;
+    y.mu_gain = d->mu_gain;
+    y.omega_gain = d->omega_gain;
+    y.min_omega = d->min_omega;
+    y.max_omega = d->max_omega;
+    y.phases = d->interp_phases;
+    y.T = d->interp_ntaps;
+    y.min_step = std::max(1, (int)floorf(d->min_omega - fabsf(d->mu_gain)));
+    y.taps.assign(d->shape_taps, d->shape_taps + d->shape_ntaps);
+    if ((rc = upload(c, &y.d_taps, y.taps.data(), y.taps.size()))) { return rc; }
+    if ((rc = sym_bank_acquire(c, y, d->interp_bank))) { return rc; }
+    if ((rc = dev_alloc(c, &y.d_state, 4))) { return rc; }
+    if ((rc = dev_alloc(c, &y.d_lines, (size_t)2 * (size_t)(y.K + y.T)))) { return rc; }
+    // per-block buffers: the front's [T - 1][n] (stream_alloc leaves 16 samples of room behind `cap`: T - 1 <= 15), the symbols a block of `cap` samples can
+    // start, their bits (bytes, four to a float) and the per-push counts
+    const size_t scap = (size_t)y.cap_of((int)cap);
+    const size_t caps[4] = { cap, scap, (scap + 3) / 4, (size_t)kGroupMax };
+    y.st.resize(4);
+    for (int i = 0; i < 4; i++) {
+        if (stream_alloc(c, y.st[(size_t)i], 1, 0, caps[i])) { return SDRPP_ERR_NOMEM; }
+    }
+    if ((rc = sym_clear(c, v))) { return rc; }
+    y.attached = true;
+    y.on = enabled;
+    undo.armed = false;
+    return SDRPP_OK;
+}
+// sdrpp_vfo_replace with keep & 2 between two RAW VFOs: the branch moves with everything it holds; a new handle with another stream capacity gets the
+// description attached afresh (its buffers are sized for the capacity) and starts cleared
+int sym_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n) {
+    Vfo::Sym& y = o.sym;
+    if (!y.attached) { return SDRPP_OK; }
+    if (o.st[(size_t)o.i_chan].cap != n.st[(size_t)n.i_chan].cap) {
+        const std::vector<float> taps = y.taps, bank = c->sym_banks[y.bank_key].taps;
+        const sdrpp_sym_desc d{ y.inv_deviation, y.K, taps.data(), y.omega, y.mu_gain, y.omega_gain, y.min_omega, y.max_omega, y.phases, y.T, bank.data() };
+        return sym_apply(c, n, &d, y.on);
+    }
+    n.sym = std::move(o.sym);
+    o.sym = Vfo::Sym{};
+    n.sym.ran = false;
+    for (auto& q : n.sym.st) { q.n = 0; }
+    return SDRPP_OK;
+}
+// sdrpp_vfo_reset: the IF history it clears is the discriminator's "previous phase 0" (as for the RDS branch); everything else the branch holds stays
+int sym_reset_prev(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Sym& y = v.sym;
+    if (!y.attached) { return SDRPP_OK; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemset(y.d_lines + (size_t)y.cur * (size_t)(y.K + y.T) + (y.K - 1), 0, sizeof(float)));
+    return SDRPP_OK;
+}
+// The symbols of the most recent block: the loop's own counts, read from the device (the host waits for the stream)
+const char* const kNoSym = "VFO %d has no symbol branch";
+int sym_count(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Sym& y = v.sym;
+    if (!y.attached) { return fail(c, SDRPP_ERR_INVALID, kNoSym, v.id); }
+    if (!y.on || !y.ran || y.npush <= 0) { return 0; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int cnt[kGroupMax] = {};
+    HIPCHK(c, hipMemcpy(cnt, y.st[3].data, (size_t)std::min(y.npush, kGroupMax) * sizeof(int), hipMemcpyDeviceToHost));
+    int total = 0;
+    for (int j = 0; j < std::min(y.npush, kGroupMax); j++) { total += cnt[j]; }
+    return std::min(total, y.cap);
+}
+
 // ---- read-out -----------------------------------------------------------------------------------------------------------------------
 // A pipelined back-end launch whose wavefronts gave up waiting for each other (never seen; a hang would be worse) counted that in THIS context's
 // page-locked word.  Called wherever the host has just synchronised with the stream and is about to hand out results.

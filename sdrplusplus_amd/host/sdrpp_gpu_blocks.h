@@ -112,6 +112,8 @@ class RxVFO {
 public:
     dsp::stream<dsp::complex_t> out;   // RxVFO::out (IF); delivered when no demodulator is attached
     dsp::stream<dsp::stereo_t> audio;  // demodulator output (radio's Demodulator::getOutput()) when attached
+    dsp::stream<uint8_t> symOut;         // attachSymbols: POCSAGDSP::out — one bit per symbol
+    dsp::stream<float> symSoft;          // ... and POCSAGDSP::soft
     dsp::stream<dsp::complex_t> rdsOut;  // attachRDS: BroadcastFM::rdsOut — the 5 kS/s baseband RDSDemod consumes, one swap per block that produced samples
     dsp::stream<uint8_t> recorded;     // attachRecorder: one swap per block the recorder would write, the packed bytes of the file's sample type (silent blocks: no swap)
 
@@ -147,6 +149,13 @@ public:
     void attachRDS();
     void detachRDS();
     void setRDSOut(bool enabled);
+    // The pager decoder's DSP (pocsag/dsp.h: Quadrature(-4500 Hz) -> shaping FIR -> MM clock recovery -> slicer; sdrpp_vfo_set_symbols) on the device, for a channel
+    // WITHOUT a demodulator (Demod::RAW): the symbols that start inside a block are delivered on `symOut` (bits) and `symSoft` (soft values) from the worker that
+    // delivers `out`, one swap each per block that produced any.  attachSymbols starts from a fresh POCSAGDSP; setSymbolsOn(false) freezes loop and delay lines,
+    // true continues from them; re-plans that keep the demodulator keep the branch.  sdrpp_gpu::POCSAGDSP (sdrpp_gpu_pager.h) is the reference-shaped face of it.
+    void attachSymbols(double baudrate);
+    void detachSymbols();
+    void setSymbolsOn(bool enabled);
     // The WFM demodulator's stereo decoder (dsp/demod/broadcast_fm.h:147-191, `_stereo`; sdrpp_vfo_set_stereo) on the device: pilot filter, PLL, L-R matrix and the
     // L / R low-passes; `audio` then carries (l, r) frames, and the AF chain and the recorder behind it see them.  A switch is BroadcastFM::setStereo: the
     // demodulator starts over (discriminator, pilot filter, loop, delays and audio filters cleared).  Re-plans that keep the demodulator keep the decoder's state.
@@ -194,6 +203,8 @@ public:
     double afAudioRate = 48000.0, afDeempTau = 50e-6;
     bool recOn = false, recMono = false, recIgnoreSilence = false;
     bool rdsAttached = false, rdsOn = false;
+    bool symAttached = false, symOn = false;
+    double symBaud = 0.0;
     bool stereoAttached = false, stereoOn = false;
     double recVolume = 1.0;
     int recType = SDRPP_REC_INT16;
@@ -386,6 +397,8 @@ public:
         registerOutput(&v->audio);
         registerOutput(&v->recorded);
         registerOutput(&v->rdsOut);
+        registerOutput(&v->symOut);
+        registerOutput(&v->symSoft);
         tempStart();
         return v;
     }
@@ -402,6 +415,8 @@ public:
         unregisterOutput(&it->second->audio);
         unregisterOutput(&it->second->recorded);
         unregisterOutput(&it->second->rdsOut);
+        unregisterOutput(&it->second->symOut);
+        unregisterOutput(&it->second->symSoft);
         vfoOrder.erase(std::remove(vfoOrder.begin(), vfoOrder.end(), it->second), vfoOrder.end());
         delete it->second;
         vfos.erase(it);
@@ -912,13 +927,16 @@ private:
         for (auto& kv : vfos) { rec = rec || (kv.second->recOn && kv.second->demod != Demod::RAW); }
         bool rds = false;
         for (auto& kv : vfos) { rds = rds || (kv.second->rdsAttached && kv.second->demod == Demod::WFM); }
-        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0) | (rds ? SDRPP_RESULT_RDS : 0);  // (a recorder or an RDS branch adds its flag and drops nobody's: `audio` is delivered as before)
+        bool sym = false;
+        for (auto& kv : vfos) { sym = sym || (kv.second->symAttached && kv.second->demod == Demod::RAW); }
+        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0) | (rds ? SDRPP_RESULT_RDS : 0) | (sym ? SDRPP_RESULT_SYM : 0);  // (a recorder or an RDS branch adds its flag and drops nobody's: `audio` is delivered as before)
     }
     int enterPipelined() {
         if (sdrpp_sync(ctx)) { return -1; }  // (nothing is staged in bypass mode; a deferred pass left over from buffered mode runs here)
         sdrpp_set_deferred(ctx, 0);
         pipeFlags = pipelineFlags();
-        if (sdrpp_set_pipelined(ctx, 1, pipeFlags & ~SDRPP_RESULT_RDS) || ((pipeFlags & SDRPP_RESULT_RDS) && sdrpp_pipeline_set_rds_results(ctx, 1))) {  // (flag 32 has a call of its own)
+        if (sdrpp_set_pipelined(ctx, 1, pipeFlags & ~(SDRPP_RESULT_RDS | SDRPP_RESULT_SYM)) || ((pipeFlags & SDRPP_RESULT_RDS) && sdrpp_pipeline_set_rds_results(ctx, 1)) ||
+            ((pipeFlags & SDRPP_RESULT_SYM) && sdrpp_pipeline_set_sym_results(ctx, 1))) {  // (flags 32 and 64 have calls of their own)
             fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] pipelined mode refused: %s\n", sdrpp_last_error(ctx));
             sdrpp_set_deferred(ctx, 1);
             _pipelining = false;
@@ -1070,6 +1088,24 @@ private:
                 jobs.emplace_back([this, v, data, cnt]() {
                     memcpy(v->rdsOut.writeBuf, data, (size_t)cnt * sizeof(dsp::complex_t));
                     if (!v->rdsOut.swap(cnt)) { deliveryFailed = true; }
+                });
+            }
+        }
+        // the symbol branches: this push's bits and soft values (result flag 64), straight out of the slot; a block that started no symbol is not handed on
+        if (pipeFlags & SDRPP_RESULT_SYM) {
+            for (auto& kv : vfos) {
+                RxVFO* v = kv.second;
+                if (!v->symAttached) { continue; }
+                const float* soft = nullptr;
+                const uint8_t* bits = nullptr;
+                int cnt = 0;
+                int rrc = sdrpp_result_sym(ctx, ticket, v->id, &soft, &bits, &cnt);
+                for (size_t q = v->prevIds.size(); rrc == SDRPP_ERR_NOT_FOUND && q-- > 0;) { rrc = sdrpp_result_sym(ctx, ticket, v->prevIds[q], &soft, &bits, &cnt); }
+                if (rrc || cnt <= 0) { continue; }  // (pushed before the attach, or while the branch was switched off)
+                jobs.emplace_back([this, v, soft, bits, cnt]() {
+                    memcpy(v->symOut.writeBuf, bits, (size_t)cnt);
+                    memcpy(v->symSoft.writeBuf, soft, (size_t)cnt * sizeof(float));
+                    if (!v->symOut.swap(cnt) || !v->symSoft.swap(cnt)) { deliveryFailed = true; }
                 });
             }
         }
@@ -1318,6 +1354,20 @@ private:
                 if (!v->rdsOut.swap(got)) { failed = true; }
             });
         }
+        // the symbol branches: the pass's bits and soft values straight into the streams' buffers
+        for (auto& kv : vfos) {
+            RxVFO* v = kv.second;
+            if (!v->symAttached || !v->symOn || v->demod != Demod::RAW || v->id < 0) { continue; }
+            const int got = sdrpp_vfo_sym_read(ctx, v->id, v->symSoft.writeBuf, v->symOut.writeBuf, STREAM_BUFFER_SIZE);
+            if (got < 0) {
+                fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] reading the symbol branch failed: %s\n", sdrpp_last_error(ctx));
+                return -1;
+            }
+            if (got == 0) { continue; }
+            jobs.emplace_back([v, got, &failed]() {
+                if (!v->symOut.swap(got) || !v->symSoft.swap(got)) { failed = true; }
+            });
+        }
         helpers.run(std::move(jobs));
         if (failed) { return -1; }
         SDRPP_BLOCKS_TICK(6)
@@ -1451,6 +1501,7 @@ private:
         if (v.recOn && v.demod != Demod::RAW) { applyRec(v); }  // (sdrpp_vfo_replace does not carry the sink: the recorder binds to the stream, and the stream lives on)
         if (v.rdsAttached && v.demod == Demod::WFM) { applyRDS(v); }  // (a handle that kept its demodulator has the branch already, state and all: the same description only sets the switch)
         if (v.stereoAttached && v.demod == Demod::WFM) { applyStereo(v); }  // (likewise: the same description and switch change nothing)
+        if (v.symAttached && v.demod == Demod::RAW) { applySymbols(v); }  // (likewise)
         sendMeters();  // (a new handle, perhaps a new bandwidth or input rate)
     }
 
@@ -1474,6 +1525,19 @@ private:
     }
 
     // broadcast_fm.h:52-53: xlator.init(NULL, -57000.0, samplerate); rdsResamp.init(NULL, samplerate, 5000.0)
+    // pocsag/dsp.h:20-37 at the channel's rate: sdrpp_design_pager's scalars, ten shaping taps of 0.1f, MM's 128 x 8 interpolator
+    void applySymbols(RxVFO& v) {
+        sdrpp_sym_desc s;
+        memset(&s, 0, sizeof(s));
+        if (sdrpp_design_pager(v.outSamplerate, v.symBaud, &s)) { throw std::runtime_error("[sdrpp_gpu::IQFrontEnd] design_pager: rates must be positive"); }
+        const std::vector<float> taps((size_t)s.shape_ntaps, 0.1f);
+        std::vector<float> bank((size_t)s.interp_phases * (size_t)s.interp_ntaps);
+        sdrpp_design_mm_interp(s.interp_phases, s.interp_ntaps, bank.data());
+        s.shape_taps = taps.data();
+        s.interp_bank = bank.data();
+        int rc = sdrpp_vfo_set_symbols(ctx, v.id, &s, v.symOn ? 1 : 0);
+        if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_symbols: ") + sdrpp_last_error(ctx)); }
+    }
     void applyRDS(RxVFO& v) {
         sdrpp_rds_desc r;
         memset(&r, 0, sizeof(r));
@@ -1915,6 +1979,33 @@ inline void RxVFO::setRDSOut(bool enabled) {
     fe->tempStop();  // broadcast_fm.h:121-128
     rdsOn = enabled;
     if (id >= 0 && demod == Demod::WFM) { fe->applyRDS(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::attachSymbols(double baudrate) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (demod != Demod::RAW) { throw std::runtime_error("[sdrpp_gpu::RxVFO] the symbol branch belongs to a channel without a demodulator"); }
+    fe->tempStop();
+    if (symAttached && id >= 0) { sdrpp_vfo_set_symbols(fe->ctx, id, nullptr, 0); }  // (attaching again starts cleared)
+    symAttached = true;
+    symOn = true;
+    symBaud = baudrate;
+    if (id >= 0) { fe->applySymbols(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::detachSymbols() {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    fe->tempStop();
+    symAttached = false;
+    symOn = false;
+    if (id >= 0) { sdrpp_vfo_set_symbols(fe->ctx, id, nullptr, 0); }
+    fe->tempStart();
+}
+inline void RxVFO::setSymbolsOn(bool enabled) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (!symAttached) { return; }
+    fe->tempStop();
+    symOn = enabled;
+    if (id >= 0 && demod == Demod::RAW) { fe->applySymbols(*this); }
     fe->tempStart();
 }
 inline void RxVFO::setStereo(bool enabled) {

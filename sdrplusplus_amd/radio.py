@@ -244,6 +244,17 @@ def stereo_desc(if_rate=250e3, enabled=True):
     return s, [taps]
 
 
+def pager_desc(if_rate=24000.0, baud=2400.0):
+    """sdrpp_sym_desc for the pager decoder's POCSAGDSP::init(in, if_rate, baud) (pocsag/dsp.h:20-37): Quadrature(-4500 Hz), ten shaping taps of 0.1f,
+    MM<float>(if_rate / baud, omega gain 1e-4, mu gain 1.0, relative limit 0.05) with its 128 x 8 interpolator.  Returns (desc, keepalive)."""
+    s = capi.design_pager(if_rate, baud)
+    taps = np.full(10, np.float32(0.1), dtype=np.float32)
+    bank = capi.design_mm_interp(s.interp_phases, s.interp_ntaps)
+    s.shape_taps = _fp(taps)
+    s.interp_bank = _fp(bank)
+    return s, [taps, bank]
+
+
 def if_desc(if_rate, nb=False, nb_level=10.0, squelch=None):
     """sdrpp_if_desc for the radio module's IF chain (radio_module.h:84-96): NoiseBlanker(rate = 500 / if_rate, level; :90, :526) ->
     PowerSquelch(level in dB; None = off).  FMIF, the chain's last block, is switched by Context.vfo_set_fmnr (IFNR_BINS); the CTCSS squelch is not on the device."""
