@@ -6,7 +6,10 @@ discriminator), orc_xlator(-57000, 250000) (orc_xlator_set_ideal for the closed-
 comparison) and orc_resampler(plans, 250000, 5000, 2) — always applied to the IF stream the device itself delivered (vfo_read_if, or vfo_ifc_read behind an IF chain).
 
 BOUNDS: 1e-5 of the yardstick's RMS over a run (BASELINE.json), 1e-6 between push cuts in closed form (per-push anchoring), bit for bit wherever two paths of the
-device compute the same thing."""
+device compute the same thing.
+
+PER SAMPLE: tests/test_rds_rows.py — every output against a float64 restatement, at every tile, pitch, window, line and rotator-block edge; every value test
+here runs ONE description (first stage 44 taps decimating by 8: tile 29, pitch 34, a window of 268 samples) and sees a run's RMS only."""
 import ctypes as C
 import os
 
