@@ -7,7 +7,8 @@ by exactly (1, 0)) — every such test first checks that the IF stream the devic
 
 BOUNDS (test 2): symbol counts per push equal; every bit equal where |soft_ref| >= 0.05, at most 1 % of a case's symbols below that; soft values within
 max(1e-5 * RMS, 4 x the spread the reference shows under a one-ulp change of its input: <case>_dev_max per symbol, <case>_dev_rms over the case).  The device's
-discriminator is not the reference's atan2f (|error| <= 3e-7 rad), hence the factor.  Everywhere else two paths of the device compute the same thing: bit for bit."""
+discriminator is not the reference's atan2f (|error| <= 3e-7 rad), hence the factor.  Everywhere else two paths of the device compute the same thing: bit for bit.
+Every other description sym_apply takes, and every tile, job, block, clamp, control and bank edge against a restatement of the reference symbol by symbol: test_pager_rows.py."""
 import ctypes as C
 import os
 
