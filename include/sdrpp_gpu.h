@@ -385,7 +385,9 @@ int sdrpp_abi_sizeof_rec_desc(void);
  *     rdsout = RationalResampler<complex_t>(IF rate -> 5000)(c)     (rational_resampler.h:120-165: at 250 kS/s the stored ratio-32 plan
  *              {8 x 44 taps, 2 x 12, 2 x 69}, then the 5000 / 7813 polyphase stage, 593 750 taps, 119 per phase)
  * Every filter is designed on the host (sdrpp_design_phase_delta, the stored decimation plan, sdrpp_design_resampler); the arrays are copied.
- * What becomes of the baseband — RDSDemod's AGC, Costas loop and clock recovery, the group decoder — stays on the host: 5 kS/s and sequential.
+ * What becomes of the baseband — RDSDemod's AGC, Costas loops and clock recovery — runs on the device as well, as a block of its own behind this one
+ * (sdrpp_vfo_set_rds_demod, source 0); only the group decoder, which reads bits, stays on the host.  Giving the branch another description, or detaching
+ * it, detaches a demodulator behind it.
  * Only for SDRPP_DEMOD_WFM VFOs (anything else: SDRPP_ERR_UNSUPPORTED); bad stage or polyphase descriptions give the errors sdrpp_vfo_set_af gives;
  * the first stage must decimate (n_stages >= 1) and its window must fit the kernel's tile (SDRPP_ERR_UNSUPPORTED otherwise: every plan of the
  * reference up to ratio 32 with at most 128 taps does).
@@ -535,6 +537,70 @@ int sdrpp_design_mm_interp(int phases, int ntaps, float* bank);
  * baudrate with MM's gains 1e-4 (omega) and 1.0 (mu) and relative limit 0.05, 128 x 8 interpolator, shape_ntaps = 10.  The two arrays stay the caller's:
  * ten taps of 0.1f and sdrpp_design_mm_interp(128, 8).  SDRPP_ERR_INVALID for rates that are not positive and finite. */
 int sdrpp_design_pager(double if_rate, double baudrate, sdrpp_sym_desc* desc);
+
+/* ---- RDS demodulator: AGC -> Costas loop -> complex band-pass -> Costas loop -> MM clock recovery -> slicer -> differential decoder ---------------------
+ * What the radio module's RDSDemod (decoder_modules/radio/src/rds_demod.h:64-74) computes from BroadcastFM::rdsOut, per 5 kS/s sample x[i] and per symbol:
+ *     a[i]  = x[i] * gain;  gain += (set_point - |a[i]|) * rate, clamped to max_gain from above only                     (loop/fast_agc.h)
+ *     c[i]  = a[i] * phasor(-phase1);  e = clamp(c.re * c.im, -1, 1)                                                      (loop/costas.h, ORDER 2)
+ *             freq1 = clamp(freq1 + beta * e, min_freq, max_freq);  phase1 += freq1 + alpha * e, wrapped into +-FL_M_PI  (loop/phase_control_loop.h:58-85)
+ *     f[i]  = sum_k c[i - (K-1) + k] * taps[k]          FIR<complex_t, complex_t>: volk_32fc_x2_dot_prod_32fc in the generic order, every product and sum rounded apart
+ *     r[i]  = (f[i] * phasor(-phase2)).re, the second loop advanced likewise
+ *     MM<float> over r exactly as the symbol branch runs it (above); soft = its output, b = soft > 0, bit = (b - last + 2) % 2, last = b
+ * in float throughout, every operation of the three recursions in the reference's order.  A general block: every parameter comes from the description
+ * (sdrpp_design_rds_demod fills the radio's).  The group decoder (rds::Decoder) stays host code and reads the bits.
+ * SOURCE 0: the output of the VFO's RDS branch — needs sdrpp_vfo_set_rds on that (WFM) VFO first, SDRPP_ERR_INVALID otherwise; it runs in the blocks the
+ * branch runs in, and detaching the RDS branch detaches the demodulator.  SOURCE 1: the stream a demodulator would read, on SDRPP_DEMOD_RAW VFOs only
+ * (SDRPP_ERR_UNSUPPORTED otherwise): a BPSK demodulator for any channel.  It never changes a bit of any other output.
+ * SDRPP_ERR_INVALID, each with its reason in sdrpp_last_error: a value that is not finite; n_taps outside 1 .. 256, interp_ntaps outside 1 .. 16,
+ * interp_phases outside 1 .. 1024, a missing array; a source other than 0 or 1; min >= max for a loop's frequency limits or for omega's; MM's step bounds
+ * as the symbol branch has them (min_omega - |mu_gain| >= 1, max_omega + |mu_gain| <= 4096); and a Costas loop with
+ *     max(|min_freq|, |max_freq|) + |alpha| > 2 pi      or      |init_phase| > pi
+ * — the reference wraps the phase with `while (phase > max) phase -= 2 pi`; under this bound (|error| <= 1) one conditional subtraction and one conditional
+ * addition are that loop exactly, and that is what the device runs: no trip count on the device depends on a sample's value.  Samples that are not numbers
+ * give unspecified values; the block ends and stays inside its arrays.
+ * STATE: gain, both loops' phase and frequency, the filter's K - 1 newest inputs, MM's four words and T - 1 samples, the decoder's last bit.  A fresh attach
+ * and a call with another description start as RDSDemod::init leaves them; enabled = 0 freezes everything (nothing planned, nothing delivered) and enabled = 1
+ * with the SAME description continues; desc == NULL detaches.  sdrpp_vfo_rds_demod_reset is RDSDemod::reset(): gain, loops, filter line, MM (offset, phase,
+ * omega, lastOut — its T - 1 delay samples stay, as MM::reset leaves them) and the decoder's last bit.  sdrpp_vfo_reset leaves the demodulator alone, as it
+ * leaves the RDS branch's own streams.  sdrpp_vfo_replace with keep & 2 and the same demodulator kind moves it, parameters and state, to the new handle (a
+ * source-0 demodulator moves with its RDS branch; a handle with another stream capacity gets the description attached afresh, cleared).
+ * Tap table and interpolator bank exist ONCE per context for identical descriptions (sdrpp_rdsd_bank_count).
+ * OUTPUT of a push: the symbols whose start lies inside it, as for the symbol branch: the concatenated output does not depend on how the stream is cut.
+ * The accessors name the most recent push (SDRPP_ERR_INVALID without a demodulator, count 0 while it is switched off) and wait for the device.
+ * Pipelined: sdrpp_pipeline_set_rds_bits_results / sdrpp_result_rds_bits.
+ * The arrays are copied during the call. */
+typedef struct sdrpp_rdsd_loop {
+    float alpha, beta;                /* PhaseControlLoop::criticallyDamped(bandwidth): sdrpp_design_pll                          */
+    float init_phase, init_freq;      /* radians, radians per sample                                                             */
+    float min_freq, max_freq;
+} sdrpp_rdsd_loop;
+typedef struct sdrpp_rdsd_desc {
+    int source;                       /* 0: the VFO's RDS branch, 1: the stream a demodulator would read (RAW VFOs)               */
+    float agc_set_point, agc_max_gain, agc_rate, agc_init_gain;
+    sdrpp_rdsd_loop loop1, loop2;     /* in front of and behind the band-pass                                                     */
+    int n_taps;                       /* complex taps, 1 .. 256                                                                   */
+    const float* taps;                /* interleaved (re, im): sdrpp_design_band_pass_complex(0, 2375, 100, rate, 0, ...)          */
+    float omega;                      /* MM, as in sdrpp_sym_desc                                                                 */
+    float mu_gain, omega_gain;
+    float min_omega, max_omega;
+    int interp_phases, interp_ntaps;
+    const float* interp_bank;
+} sdrpp_rdsd_desc;
+int sdrpp_vfo_set_rds_demod(sdrpp_ctx* ctx, int id, const sdrpp_rdsd_desc* desc, int enabled);
+int sdrpp_vfo_rds_demod_reset(sdrpp_ctx* ctx, int id);
+/* The demodulator's output of the most recent push: soft symbols (MM's output) and decoded bits. */
+int sdrpp_vfo_rds_demod_count(sdrpp_ctx* ctx, int id);
+int sdrpp_vfo_rds_demod_read(sdrpp_ctx* ctx, int id, float* soft_host, uint8_t* bits_host, int max);   /* either array may be NULL; returns the symbols copied */
+int sdrpp_vfo_rds_demod_device_buffers(sdrpp_ctx* ctx, int id, const float** soft, const uint8_t** bits, int* n);
+int sdrpp_abi_sizeof_rdsd_desc(void);
+/* Test and statistics hook: tap table / interpolator bank pairs of RDS demodulators the context holds in device memory (identical descriptions share one). */
+int sdrpp_rdsd_bank_count(sdrpp_ctx* ctx);
+/* Every field of *desc as RDSDemod::init (rds_demod.h:19-41) leaves its members, for a stream of `rate` samples per second (the radio's: 5000), source 0:
+ * FastAGC(1.0, 1e6, 0.1, 1.0); Costas<2>(0.005f); bandPass<complex_t>(0, 2375, 100, rate) through sdrpp_design_band_pass_complex into taps[]; Costas<2>(0.01)
+ * at hzToRads(1187.5, rate) +- 10 %; MM(rate / 1187.5, 1e-6, 0.01, 0.01) with sdrpp_design_mm_interp(128, 8) into bank[].  The two arrays stay the caller's
+ * (max_taps complex taps, max_bank floats) and desc points at them.  Returns the number of complex taps (190 at 5000), or SDRPP_ERR_INVALID: a rate that
+ * is not positive and finite, an array that is missing or too small (1024 floats of bank). */
+int sdrpp_design_rds_demod(double rate, sdrpp_rdsd_desc* desc, float* taps, int max_taps, float* bank, int max_bank);
 
 /* ---- WaterFall display state around the raw-line history (core/src/gui/widgets/waterfall.cpp) ---------------
  * The last `height` raw dB lines stay resident in HBM in the reference's ring order (getFFTBuffer :875-886), so a zoom / pan /
@@ -778,6 +844,15 @@ int sdrpp_result_rds(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** data
 #define SDRPP_RESULT_SYM 64
 int sdrpp_pipeline_set_sym_results(sdrpp_ctx* ctx, int on);
 int sdrpp_result_sym(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** soft, const uint8_t** bits, int* count);
+/* Result flag 128: the RDS demodulators' outputs (sdrpp_vfo_set_rds_demod) travel in every block's result slot, in the symbol branch's layout — per
+ * demodulator the per-push counts, then room for the block's capacity of soft values (4 bytes) and decoded bits (1 byte): 5 bytes per possible symbol, about
+ * 6 KB/s per channel.  A call of its own, with the rules of sdrpp_pipeline_set_rds_results; 128 is independent of 1, 32 and 64: a host that only wants the
+ * bits leaves flag 32 off and stops paying for the 5 kS/s samples.
+ * sdrpp_result_rds_bits: *soft / *bits = the *count symbols VFO `id`'s demodulator started inside push `ticket` (in a launch group the group's symbols lie
+ * in one piece and every push gets its own count and slice).  Validity as for sdrpp_result_rds; SDRPP_ERR_NOT_FOUND likewise.  Any output may be NULL. */
+#define SDRPP_RESULT_RDS_BITS 128
+int sdrpp_pipeline_set_rds_bits_results(sdrpp_ctx* ctx, int on);
+int sdrpp_result_rds_bits(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** soft, const uint8_t** bits, int* count);
 /* Signal meters of push `ticket` (sdrpp_wf_set_meters): *data = [*n_lines][*n_meters][2] floats in the block's result slot, for the lines this push's
  * own samples completed — the rows `zoomed` / `raw` give it — oldest first.  No result flag: while a table is set, EVERY pipelined block with the
  * FFT on carries its meters (n_lines * n_meters * 8 bytes), result_flags = 0 included — sdrpp_result_wait / _release then work for such blocks.

@@ -112,6 +112,43 @@ class SymDesc(C.Structure):
     ]
 
 
+class RdsdLoop(C.Structure):
+    """struct sdrpp_rdsd_loop (include/sdrpp_gpu.h): one Costas loop of the RDS demodulator."""
+
+    _fields_ = [
+        ("alpha", C.c_float),
+        ("beta", C.c_float),
+        ("init_phase", C.c_float),
+        ("init_freq", C.c_float),
+        ("min_freq", C.c_float),
+        ("max_freq", C.c_float),
+    ]
+
+
+class RdsdDesc(C.Structure):
+    """struct sdrpp_rdsd_desc (include/sdrpp_gpu.h): the RDS demodulator — AGC, two Costas loops around a complex band-pass, MM clock recovery, bits."""
+
+    _fields_ = [
+        ("source", C.c_int),
+        ("agc_set_point", C.c_float),
+        ("agc_max_gain", C.c_float),
+        ("agc_rate", C.c_float),
+        ("agc_init_gain", C.c_float),
+        ("loop1", RdsdLoop),
+        ("loop2", RdsdLoop),
+        ("n_taps", C.c_int),
+        ("taps", c_float_p),
+        ("omega", C.c_float),
+        ("mu_gain", C.c_float),
+        ("omega_gain", C.c_float),
+        ("min_omega", C.c_float),
+        ("max_omega", C.c_float),
+        ("interp_phases", C.c_int),
+        ("interp_ntaps", C.c_int),
+        ("interp_bank", c_float_p),
+    ]
+
+
 class StereoDesc(C.Structure):
     """struct sdrpp_stereo_desc (include/sdrpp_gpu.h): the WFM demodulator's stereo branch — pilot filter, PLL, L-R matrix."""
 
@@ -208,6 +245,7 @@ class Result(C.Structure):
 ABI_VERSION = 2    # SDRPP_ABI_VERSION (include/sdrpp_gpu.h)
 RESULT_SLOTS = 24  # SDRPP_RESULT_SLOTS: launches (one block each, or a group of up to GROUP_MAX: sdrpp_set_pipeline_group) whose pipelined results can exist at a time
 GROUP_MAX = 32     # SDRPP_GROUP_MAX
+RESULT_RDS_BITS = 128  # SDRPP_RESULT_RDS_BITS: the RDS demodulators' soft values, bits and per-push counts in every block's result slot (Context.result_rds_bits)
 RESULT_SYM = 64    # SDRPP_RESULT_SYM: the symbol branches' soft values, bits and per-push counts in every block's result slot (Context.set_pipelined, Context.result_sym)
 RESULT_RDS = 32    # SDRPP_RESULT_RDS: the RDS branches' samples in every block's result slot (Context.set_pipelined, Context.result_rds)
 
@@ -305,6 +343,18 @@ def load():
     L.sdrpp_result_sym.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(c_float_p), C.POINTER(c_u8_p), c_int_p]
     L.sdrpp_design_mm_interp.argtypes = [C.c_int, C.c_int, c_float_p]
     L.sdrpp_design_pager.argtypes = [C.c_double, C.c_double, C.POINTER(SymDesc)]
+    L.sdrpp_abi_sizeof_rdsd_desc.argtypes = []
+    if L.sdrpp_abi_sizeof_rdsd_desc() != C.sizeof(RdsdDesc):
+        raise ImportError("sdrpp_rdsd_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_rdsd_desc(), C.sizeof(RdsdDesc)))
+    L.sdrpp_vfo_set_rds_demod.argtypes = [vp, C.c_int, C.POINTER(RdsdDesc), C.c_int]
+    L.sdrpp_vfo_rds_demod_reset.argtypes = [vp, C.c_int]
+    L.sdrpp_vfo_rds_demod_count.argtypes = [vp, C.c_int]
+    L.sdrpp_vfo_rds_demod_read.argtypes = [vp, C.c_int, c_float_p, c_u8_p, C.c_int]
+    L.sdrpp_vfo_rds_demod_device_buffers.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), c_int_p]
+    L.sdrpp_rdsd_bank_count.argtypes = [vp]
+    L.sdrpp_pipeline_set_rds_bits_results.argtypes = [vp, C.c_int]
+    L.sdrpp_result_rds_bits.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(c_float_p), C.POINTER(c_u8_p), c_int_p]
+    L.sdrpp_design_rds_demod.argtypes = [C.c_double, C.POINTER(RdsdDesc), c_float_p, C.c_int, c_float_p, C.c_int]
     L.sdrpp_abi_sizeof_stereo_desc.argtypes = []
     if L.sdrpp_abi_sizeof_stereo_desc() != C.sizeof(StereoDesc):
         raise ImportError("sdrpp_stereo_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_stereo_desc(), C.sizeof(StereoDesc)))
@@ -419,6 +469,8 @@ EXPORTED_SYMBOLS = [
     "sdrpp_vfo_set_stereo", "sdrpp_abi_sizeof_stereo_desc", "sdrpp_design_band_pass_complex", "sdrpp_design_pll",
     "sdrpp_vfo_set_symbols", "sdrpp_vfo_sym_count", "sdrpp_vfo_sym_read", "sdrpp_vfo_sym_device_buffers", "sdrpp_abi_sizeof_sym_desc", "sdrpp_sym_bank_count",
     "sdrpp_pipeline_set_sym_results", "sdrpp_result_sym", "sdrpp_design_mm_interp", "sdrpp_design_pager",
+    "sdrpp_vfo_set_rds_demod", "sdrpp_vfo_rds_demod_reset", "sdrpp_vfo_rds_demod_count", "sdrpp_vfo_rds_demod_read", "sdrpp_vfo_rds_demod_device_buffers",
+    "sdrpp_abi_sizeof_rdsd_desc", "sdrpp_rdsd_bank_count", "sdrpp_design_rds_demod", "sdrpp_pipeline_set_rds_bits_results", "sdrpp_result_rds_bits",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
     "sdrpp_vfo_set_if", "sdrpp_vfo_set_fmnr", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
     "sdrpp_fft_configure", "sdrpp_fft_disable", "sdrpp_fft_set_view", "sdrpp_fft_lines", "sdrpp_fft_read", "sdrpp_fft_copy_device", "sdrpp_fft_device_buffers",
@@ -490,6 +542,20 @@ def design_pager(if_rate, baudrate):
     if rc < 0:
         raise SdrppError(rc, "sdrpp_design_pager")
     return d
+
+
+def design_rds_demod(rate=5000.0):
+    """Every member of RDSDemod after init (radio/src/rds_demod.h:19-41) for a stream of `rate` samples per second -> (RdsdDesc, taps complex64 [K], bank
+    float32 [128, 8]); the description points at the two arrays, which the caller keeps alive until it has been attached."""
+    d = RdsdDesc()
+    taps = np.zeros(256, dtype=np.complex64)
+    bank = np.zeros((128, 8), dtype=np.float32)
+    k = load().sdrpp_design_rds_demod(float(rate), C.byref(d), taps.view(np.float32).ctypes.data_as(c_float_p), 256, bank.ctypes.data_as(c_float_p), bank.size)
+    if k < 0:
+        raise SdrppError(k, "sdrpp_design_rds_demod")
+    taps = taps[:k].copy()
+    d.taps = taps.view(np.float32).ctypes.data_as(c_float_p)
+    return d, taps, bank
 
 
 def design_fft_window(kind, nz):
@@ -901,6 +967,38 @@ class Context:
             return np.zeros(0, np.float32), np.zeros(0, np.uint8)
         return np.ctypeslib.as_array(soft, shape=(n.value,)).copy(), np.ctypeslib.as_array(bits, shape=(n.value,)).copy()
 
+    def vfo_set_rds_demod(self, vid, desc, enabled=True, keepalive=None):
+        """Attach the RDS demodulator (sdrpp_vfo_set_rds_demod; radio.rds_demod_desc) behind the VFO's RDS branch (desc.source 0) or on a RAW VFO (source 1),
+        switch it (the same description: enabled = False freezes its state, True continues) or, with desc None, detach it.  `keepalive` is only there so that a
+        caller can pass what radio.rds_demod_desc returns: the library copies every array during the call."""
+        self._chk(self.L.sdrpp_vfo_set_rds_demod(self.h, vid, C.byref(desc) if desc is not None else None, int(bool(enabled))))
+
+    def vfo_rds_demod_reset(self, vid):
+        """RDSDemod::reset()"""
+        self._chk(self.L.sdrpp_vfo_rds_demod_reset(self.h, vid))
+
+    def vfo_rds_demod_count(self, vid):
+        return self._chk(self.L.sdrpp_vfo_rds_demod_count(self.h, vid))
+
+    def vfo_rds_demod_read(self, vid):
+        """The RDS demodulator's output of the last push -> (soft float32 [n], bits uint8 [n])."""
+        n = self.vfo_rds_demod_count(vid)
+        soft, bits = np.empty(max(n, 1), np.float32), np.empty(max(n, 1), np.uint8)
+        got = self._chk(self.L.sdrpp_vfo_rds_demod_read(self.h, vid, soft.ctypes.data_as(c_float_p), bits.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return soft[:got], bits[:got]
+
+    def result_rds_bits(self, ticket, vid):
+        """sdrpp_result_rds_bits (result flag RESULT_RDS_BITS), between result_wait and result_release of that ticket -> this push's (soft, bits), copies."""
+        soft, bits, n = c_float_p(), C.POINTER(C.c_uint8)(), C.c_int(0)
+        self._chk(self.L.sdrpp_result_rds_bits(self.h, int(ticket), vid, C.byref(soft), C.byref(bits), C.byref(n)))
+        if n.value <= 0:
+            return np.zeros(0, np.float32), np.zeros(0, np.uint8)
+        return np.ctypeslib.as_array(soft, shape=(n.value,)).copy(), np.ctypeslib.as_array(bits, shape=(n.value,)).copy()
+
+    def rdsd_bank_count(self):
+        """Tap table / interpolator bank pairs of RDS demodulators this context holds in device memory (identical descriptions share one)."""
+        return self._chk(self.L.sdrpp_rdsd_bank_count(self.h))
+
     def vfo_set_stereo(self, vid, desc, keepalive=None):
         """Attach the WFM demodulator's stereo branch (sdrpp_vfo_set_stereo; radio.stereo_desc), switch it (desc.enabled: BroadcastFM::setStereo, the
         demodulator starts over) or, with None, detach it.  `keepalive` is only there so that a caller can pass what radio.stereo_desc returns: the library
@@ -993,8 +1091,11 @@ class Context:
         """result_flags: 1 = every VFO's output block (AF output where a chain is attached), 2 = zoomed lines + palette indices, 4 = raw dB lines,
         8 = the pre-processed IQ stream (with a pre-processing chain), 16 = the recorder sinks' converted blocks (result_rec) into page-locked result slots,
         32 (RESULT_RDS) = the RDS branches' samples (result_rds; the library switches that one by a call of its own, sdrpp_pipeline_set_rds_results),
-        64 (RESULT_SYM) = the symbol branches' outputs (result_sym; likewise, sdrpp_pipeline_set_sym_results)."""
-        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags) & ~(RESULT_RDS | RESULT_SYM)))
+        64 (RESULT_SYM) = the symbol branches' outputs (result_sym; likewise, sdrpp_pipeline_set_sym_results),
+        128 (RESULT_RDS_BITS) = the RDS demodulators' soft values and bits (result_rds_bits; likewise, sdrpp_pipeline_set_rds_bits_results)."""
+        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags) & ~(RESULT_RDS | RESULT_SYM | RESULT_RDS_BITS)))
+        if on and (int(result_flags) & RESULT_RDS_BITS):
+            self._chk(self.L.sdrpp_pipeline_set_rds_bits_results(self.h, 1))
         if on and (int(result_flags) & RESULT_RDS):
             self._chk(self.L.sdrpp_pipeline_set_rds_results(self.h, 1))
         if on and (int(result_flags) & RESULT_SYM):

@@ -192,6 +192,28 @@ struct Vfo {
         int n_if = 0, npush = 0, cap = 0; // ... its samples, its pushes, the symbols its outputs have room for
         int cap_of(int n) const { return (n + min_step - 1) / min_step + 1; }
     } sym;
+    // RDS demodulator (sdrpp_vfo_set_rds_demod; decoder_modules/radio/src/rds_demod.h): AGC, two Costas loops around a complex band-pass, MM clock recovery, slicer,
+    // differential decoder — one wavefront job per block (vfo_rdsd_kernels.h), behind the RDS branch's output (source 0, WFM) or behind the stream a demodulator
+    // would read (source 1, RAW).  Everything it remembers is its own, in ONE device array updated in place; switched off it freezes.  Its per-block buffers are
+    // streams without history, as the symbol branch's are.
+    struct Rdsd {
+        bool attached = false, on = false;
+        int source = 0;
+        float agc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };   // set point, max gain, rate, initial gain
+        float loop[2][6] = {};                       // alpha, beta, initial phase, initial frequency, min / max frequency
+        float omega = 0.0f, mu_gain = 0.0f, omega_gain = 0.0f, min_omega = 0.0f, max_omega = 0.0f;
+        int K = 0, phases = 0, T = 0;
+        unsigned long long bank_key = 0;  // the context's shared tap table + interpolator bank this demodulator holds a reference to (0: none)
+        const float* d_taps = nullptr;    // ... borrowed
+        const float* d_bank = nullptr;
+        float* d_state = nullptr;         // SDRPP_RDSD_STATE_HEAD words, K - 1 complex values, T - 1 floats (RdsdJob)
+        int min_step = 1;                 // as Sym::min_step
+        std::vector<Stream> st;           // [0] soft values, [1] bits (bytes), [2] symbols per push (ints)
+        int lvl = 1;                      // level (do_vfos_plan) at which the job of the most recent block runs
+        bool ran = false;                 // the most recent block was planned with the demodulator on
+        int n_in = 0, npush = 0, cap = 0; // ... its samples, its pushes, the symbols its outputs have room for
+        int cap_of(int n) const { return (n + min_step - 1) / min_step + 1; }
+    } rdsd;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
     ToepTab tp_chan, tp_audio;
     // front end as one filter (what the fused translate + filter kernels evaluate): stages 0 (+ 1) of the plan
@@ -223,7 +245,7 @@ struct Vfo {
         int base = -1;  // first AF stream in st (they are appended behind the VFO's own streams)
     } af;
 };
-// Every stream of a VFO: its own, then its RDS branch's, its stereo branch's and its symbol branch's (the order plan_snapshot records them in).  ran_only: a branch's streams
+// Every stream of a VFO: its own, then its RDS branch's, its stereo branch's, its symbol branch's and its RDS demodulator's (the order plan_snapshot records them in).  ran_only: a branch's streams
 // only if the most recent plan ran the branch.
 template <class F>
 void for_each_stream(Vfo& v, F&& f, bool ran_only = false) {
@@ -236,6 +258,9 @@ void for_each_stream(Vfo& v, F&& f, bool ran_only = false) {
     }
     if (!ran_only || v.sym.ran) {
         for (auto& s : v.sym.st) { f(s); }
+    }
+    if (!ran_only || v.rdsd.ran) {
+        for (auto& s : v.rdsd.st) { f(s); }
     }
 }
 template <class F>
@@ -390,6 +415,8 @@ struct sdrpp_ctx {
     std::map<unsigned long long, RdsBank> rds_banks;  // polyphase banks of the RDS branches, ONE per distinct description (2.4 MB each), freed with their last user
 
     struct SymBank { float* d_bank = nullptr; int refs = 0; int phases = 0, T = 0; std::vector<float> taps; };
+    struct RdsdBank { float* d_taps = nullptr; float* d_bank = nullptr; int refs = 0; int K = 0, phases = 0, T = 0; std::vector<float> taps, bank; };
+    std::map<unsigned long long, RdsdBank> rdsd_banks;  // tap table + interpolator bank of the RDS demodulators, ONE pair per distinct description, freed with their last user
     std::map<unsigned long long, SymBank> sym_banks;  // interpolator banks of the symbol branches, ONE per distinct bank, freed with their last user
 
     // ---- pipelined ("tick") execution: one launch per block, the stages of consecutive blocks skewed over consecutive launches
@@ -412,13 +439,15 @@ struct sdrpp_ctx {
         std::vector<size_t> rds_off;                         // ... and where they lie in the slot
         std::vector<int> sym_ids, sym_push;                  // result flag 64: the VFOs whose symbol branch ran in the block, this push's index in its launch group
         std::vector<size_t> sym_cnt_off, sym_soft_off, sym_bits_off;  // ... where the group's per-push counts, its soft values and its bits lie in the slot
+        std::vector<int> rdsd_ids, rdsd_push;                // result flag 128: the VFOs whose RDS demodulator ran in the block, this push's index in its launch group
+        std::vector<size_t> rdsd_cnt_off, rdsd_soft_off, rdsd_bits_off;  // ... where the group's per-push counts, its soft values and its bits lie in the slot (the symbol branch's layout)
         std::vector<int> rec_ids;                            // result flag 16: the VFOs that had a recorder sink when the block was planned,
         std::vector<size_t> rec_off, rec_info_off;           // ... where this push's converted samples and its sdrpp_rec_info lie in the slot
         int n_meters = -1;                                   // signal meters the block was pushed with (-1: no table then); its n_lines x n_meters x 2 floats
         size_t off_meters = 0;
     };
     bool pipelined = false;
-    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks, bit 5: RDS branches (sdrpp_pipeline_set_rds_results), bit 6: symbol branches (sdrpp_pipeline_set_sym_results)
+    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks, bit 5: RDS branches (sdrpp_pipeline_set_rds_results), bit 6: symbol branches (sdrpp_pipeline_set_sym_results), bit 7: RDS demodulators (sdrpp_pipeline_set_rds_bits_results)
     int num_cus = 256;
     int tick_l0_at = getenv("SDRPP_GPU_TICK_L0_AT") ? atoi(getenv("SDRPP_GPU_TICK_L0_AT")) : 0;  // (read when the context is created)
     // grid rules of the roles inside a tick (the stand-alone kernels size their grids for a GPU of their own; in a tick ~8 roles share it, and

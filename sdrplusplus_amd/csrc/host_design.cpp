@@ -116,6 +116,46 @@ int sdrpp_design_pager(double if_rate, double baudrate, sdrpp_sym_desc* d) {
     return SDRPP_OK;
 }
 
+void sdrpp_design_pll(double bandwidth_d, float* alpha, float* beta);
+// radio/src/rds_demod.h:19-41: every member as init leaves it, the doubles of the init calls become the members' floats where the classes store floats
+// (fast_agc.h:13-19, pll.h:15-23 through phase_control_loop.h:16-29, mm.h:24-32)
+int sdrpp_design_rds_demod(double rate, sdrpp_rdsd_desc* d, float* taps, int max_taps, float* bank, int max_bank) {
+    if (!d || !taps || !bank || !(rate > 0.0) || !std::isfinite(rate) || max_bank < 128 * 8) { return SDRPP_ERR_INVALID; }
+    const int K = sdrpp_design_band_pass_complex(0.0, 2375.0, 100.0, rate, 0, taps, 0);
+    if (K < 1 || K > max_taps) { return SDRPP_ERR_INVALID; }
+    sdrpp_design_band_pass_complex(0.0, 2375.0, 100.0, rate, 0, taps, 2 * K);
+    if (sdrpp_design_mm_interp(128, 8, bank) != 128 * 8) { return SDRPP_ERR_INVALID; }
+    const float FL_PI = 3.1415926535f;  // FL_M_PI, math/constants.h:4
+    d->source = 0;
+    d->agc_set_point = (float)1.0;
+    d->agc_max_gain = (float)1e6;
+    d->agc_rate = (float)0.1;
+    d->agc_init_gain = (float)1.0;
+    sdrpp_design_pll((double)0.005f, &d->loop1.alpha, &d->loop1.beta);  // costas.init(NULL, 0.005f)
+    d->loop1.init_phase = 0.0f;
+    d->loop1.init_freq = 0.0f;
+    d->loop1.min_freq = (float)(double)-FL_PI;
+    d->loop1.max_freq = (float)(double)FL_PI;
+    const double baudfreq = hzToRads(2375.0 / 2.0, rate);
+    sdrpp_design_pll(0.01, &d->loop2.alpha, &d->loop2.beta);  // costas2.init(NULL, 0.01, 0.0, baudfreq, baudfreq - baudfreq * 0.1, baudfreq + baudfreq * 0.1)
+    d->loop2.init_phase = (float)0.0;
+    d->loop2.init_freq = (float)baudfreq;
+    d->loop2.min_freq = (float)(baudfreq - (baudfreq * 0.1));
+    d->loop2.max_freq = (float)(baudfreq + (baudfreq * 0.1));
+    d->n_taps = K;
+    d->taps = taps;
+    const double omega = rate / (2375.0 / 2.0), lim = 0.01;  // recov.init(NULL, 5000.0 / (2375.0 / 2.0), 1e-6, 0.01, 0.01)
+    d->omega = (float)omega;
+    d->mu_gain = (float)0.01;
+    d->omega_gain = (float)1e-6;
+    d->min_omega = (float)(omega * (1.0 - lim));
+    d->max_omega = (float)(omega * (1.0 + lim));
+    d->interp_phases = 128;
+    d->interp_ntaps = 8;
+    d->interp_bank = bank;
+    return K;
+}
+
 void sdrpp_design_pll(double bandwidth_d, float* alpha, float* beta) {
     const float bandwidth = bandwidth_d;  // criticallyDamped(T bandwidth, ...) with T = float
     const float dampningFactor = sqrt(2.0) / 2.0;

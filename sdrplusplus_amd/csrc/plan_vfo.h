@@ -250,6 +250,8 @@ struct BankPlan {
     Lev<SymFrontJob> syf;
     Lev<SymLoopVfo> syl;
     Lev<SymLoopJob> sylj;  // (filled by upload once syl's records have their addresses)
+    // RDS demodulator (rdsd_branch): a record, and a job, per VFO
+    Lev<RdsdJob> rdsdj;
     Lev<CarryJob> carry;  // history carries at the level of the stream's consumer (a pass without pipelining: all at the last level)
     int max_rot = 0;
     // front-end jobs (group_front)
@@ -288,7 +290,7 @@ struct BankPlan {
         for (auto& t : tlists) { f(*t.L); }
         f(f_dec); f(poly);
         for (auto& q : polyb) { f(q); }
-        f(chan); f(seq); f(nbsq); f(fmif); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stm); f(syf); f(syl); f(pre); f(audio); f(audio_fm);
+        f(chan); f(seq); f(nbsq); f(fmif); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stm); f(syf); f(syl); f(rdsdj); f(pre); f(audio); f(audio_fm);
         f(af_dec); f(af_hpf); f(af_poly); f(af_deemp);
         f(ssbx_l); f(carry);
         f(stlj); f(sylj); f(wave);
@@ -494,6 +496,14 @@ struct BankPlan {
         }
         else {
             for (auto& s : v.sym.st) { s.n = 0; }
+        }
+        v.rdsd.ran = v.rdsd.attached && v.rdsd.on && (v.rdsd.source == 1 || v.rds.ran);
+        if (v.rdsd.ran) {
+            if (int rc = rdsd_branch(x, feed)) { return rc; }
+            last_lvl = std::max(last_lvl, v.rdsd.lvl);
+        }
+        else {
+            for (auto& s : v.rdsd.st) { s.n = 0; }
         }
         phase_advance(x);
         x.at.lvl = last_lvl;
@@ -893,6 +903,35 @@ struct BankPlan {
         cnt.n = y.npush;
         for (auto& s : y.st) { s.wlevel = lvl + 2; }
         buf.wlevel = lvl + 1;
+        return SDRPP_OK;
+    }
+    // RDS demodulator (radio/src/rds_demod.h): ONE job per VFO and block (vfo_rdsd_kernels.h), one level behind the polyphase stage of the RDS chain (source 0)
+    // or behind the stream a demodulator would read (source 1).  Its state is one device array updated in place.  A launch group is one block to the job; it is
+    // handed the push ends at its input's rate and counts the symbols push by push.  A block without samples still files the job: it writes the zeros of its counts.
+    int rdsd_branch(ChainCtx& x, const ChainCursor& feed) {
+        Vfo& v = x.v;
+        Vfo::Rdsd& y = v.rdsd;
+        const bool from_rds = y.source == 0;
+        const Stream& in = from_rds ? v.rds.st[(size_t)v.rds.i_last] : *feed.cur;
+        const int lvl = from_rds ? v.rds.lvl : feed.lvl, n = in.n;
+        const std::vector<int>& tk = from_rds ? v.rds.tk : v.tk_if;
+        Stream &soft = y.st[0], &bits = y.st[1], &cnt = y.st[2];
+        y.n_in = n;
+        y.npush = x.split ? (int)tk.size() : 1;
+        y.cap = y.cap_of(n);
+        y.lvl = lvl + 1;
+        const int* d_ends = nullptr;
+        if (x.split) {
+            d_ends = arena_push(c, tk);
+            if (!d_ends) { return arena_fail(c); }
+        }
+        rdsdj.add(lvl + 1, RdsdJob{ reinterpret_cast<const float2*>(in.data), soft.data, reinterpret_cast<uint8_t*>(bits.data), reinterpret_cast<int*>(cnt.data), y.d_state, y.d_taps, y.d_bank, d_ends,
+                                    y.agc[0], y.agc[1], y.agc[2], y.loop[0][0], y.loop[0][1], y.loop[0][4], y.loop[0][5], y.loop[1][0], y.loop[1][1], y.loop[1][4], y.loop[1][5],
+                                    y.mu_gain, y.omega_gain, y.min_omega, y.max_omega, y.K, y.T, y.phases, n, y.npush, y.cap, 0 });
+        soft.n = y.cap;
+        bits.n = (y.cap + 3) / 4;
+        cnt.n = y.npush;
+        for (auto& s : y.st) { s.wlevel = lvl + 1; }
         return SDRPP_OK;
     }
     void phase_advance(ChainCtx& x) {
@@ -1295,6 +1334,7 @@ struct BankPlan {
         file_wave(stm, WK_ST_MATRIX);
         file_wave(syf, WK_SYM_FRONT);
         file_wave(sylj, WK_SYM_LOOP);
+        file_wave(rdsdj, WK_RDS_DEMOD);
         // 3. the role's table
         if (!arena_push_lev(c, wave)) { return arena_fail(c); }
         HostScope hs("arena_commit (H2D)");

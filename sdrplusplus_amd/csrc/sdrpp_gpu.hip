@@ -383,6 +383,11 @@ int sdrpp_destroy(sdrpp_ctx* c) {
     for (auto& kv : c->rds_banks) { dev_free(kv.second.d_bank); }
     c->rds_banks.clear();
     for (auto& kv : c->sym_banks) { dev_free(kv.second.d_bank); }
+    for (auto& kv : c->rdsd_banks) {
+        dev_free(kv.second.d_taps);
+        dev_free(kv.second.d_bank);
+    }
+    c->rdsd_banks.clear();
     c->sym_banks.clear();
     c->vfos.clear();
     for (auto& e : c->s1_tap_cache) { (void)hipFree(e.second); }
@@ -761,6 +766,7 @@ int sdrpp_vfo_remove(sdrpp_ctx* c, int id) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     rds_detach(c, *v);
     sym_detach(c, *v);
+    rdsd_detach(c, *v);
     vfo_free(*v);
     c->vfos.erase(id);
     vfo_list_rebuild(c);
@@ -1002,6 +1008,56 @@ int sdrpp_vfo_sym_device_buffers(sdrpp_ctx* c, int id, const float** soft, const
 }
 int sdrpp_abi_sizeof_sym_desc(void) { return (int)sizeof(sdrpp_sym_desc); }
 int sdrpp_sym_bank_count(sdrpp_ctx* c) { return c ? (int)c->sym_banks.size() : SDRPP_ERR_INVALID; }
+
+// ---- RDS demodulator: AGC -> Costas -> band-pass -> Costas -> MM clock recovery -> slicer -> differential decoder (radio/src/rds_demod.h) -----------------
+int sdrpp_vfo_set_rds_demod(sdrpp_ctx* c, int id, const sdrpp_rdsd_desc* d, int enabled) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return rdsd_apply(c, *v, d, enabled != 0);
+}
+int sdrpp_vfo_rds_demod_reset(sdrpp_ctx* c, int id) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    if (!v->rdsd.attached) { return fail(c, SDRPP_ERR_INVALID, kNoRdsd, id); }
+    return rdsd_clear(c, *v, false);
+}
+int sdrpp_vfo_rds_demod_count(sdrpp_ctx* c, int id) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return rdsd_count(c, *v);
+}
+int sdrpp_vfo_rds_demod_read(sdrpp_ctx* c, int id, float* soft, uint8_t* bits, int max) {
+    DeviceScope dev_scope_(c);
+    if (!c || max < 0) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    const int have = rdsd_count(c, *v);
+    if (have < 0) { return have; }
+    const int n = std::min(have, max);
+    if (n > 0 && soft) { HIPCHK(c, hipMemcpy(soft, v->rdsd.st[0].data, (size_t)n * sizeof(float), hipMemcpyDeviceToHost)); }
+    if (n > 0 && bits) { HIPCHK(c, hipMemcpy(bits, v->rdsd.st[1].data, (size_t)n, hipMemcpyDeviceToHost)); }
+    return n;
+}
+int sdrpp_vfo_rds_demod_device_buffers(sdrpp_ctx* c, int id, const float** soft, const uint8_t** bits, int* n) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    const int have = rdsd_count(c, *v);
+    if (have < 0) { return have; }
+    if (soft) { *soft = v->rdsd.st[0].data; }
+    if (bits) { *bits = reinterpret_cast<const uint8_t*>(v->rdsd.st[1].data); }
+    if (n) { *n = have; }
+    return SDRPP_OK;
+}
+int sdrpp_abi_sizeof_rdsd_desc(void) { return (int)sizeof(sdrpp_rdsd_desc); }
+int sdrpp_rdsd_bank_count(sdrpp_ctx* c) { return c ? (int)c->rdsd_banks.size() : SDRPP_ERR_INVALID; }
 
 int sdrpp_vfo_read_pcm(sdrpp_ctx* c, int id, int which, int pcm_type, float scale, void* dst_host, int max_frames) {
     DeviceScope dev_scope_(c);
@@ -1769,6 +1825,33 @@ int sdrpp_result_sym(sdrpp_ctx* c, uint64_t ticket, int id, const float** soft, 
         return SDRPP_OK;
     }
     return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of a symbol branch of VFO %d", (unsigned long long)ticket, id);
+}
+int sdrpp_pipeline_set_rds_bits_results(sdrpp_ctx* c, int on) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    if (!c->pipelined) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_pipeline_set_rds_bits_results outside pipelined mode"); }
+    FLUSH_PENDING(c);
+    c->res_flags = on ? (c->res_flags | SDRPP_RESULT_RDS_BITS) : (c->res_flags & ~SDRPP_RESULT_RDS_BITS);
+    return SDRPP_OK;
+}
+// (the counts are the job's own result: they lie in the slot, complete since sdrpp_result_wait returned for this block)
+int sdrpp_result_rds_bits(sdrpp_ctx* c, uint64_t ticket, int id, const float** soft, const uint8_t** bits, int* count) {
+    if (!c) { return SDRPP_ERR_INVALID; }
+    sdrpp_ctx::Result* R = result_of(c, ticket);
+    if (!R || !R->held) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_result_rds_bits: block %llu is not held (between sdrpp_result_wait and sdrpp_result_release)", (unsigned long long)ticket); }
+    for (size_t i = 0; i < R->rdsd_ids.size(); i++) {
+        if (R->rdsd_ids[i] != id) { continue; }
+        int cnt[kGroupMax] = {};
+        const int j = std::min(R->rdsd_push[i], kGroupMax - 1);
+        memcpy(cnt, R->base + R->rdsd_cnt_off[i], (size_t)(j + 1) * sizeof(int));
+        size_t lo = 0;
+        for (int q = 0; q < j; q++) { lo += (size_t)std::max(cnt[q], 0); }
+        if (soft) { *soft = reinterpret_cast<const float*>(R->base + R->rdsd_soft_off[i]) + lo; }
+        if (bits) { *bits = reinterpret_cast<const uint8_t*>(R->base + R->rdsd_bits_off[i]) + lo; }
+        if (count) { *count = cnt[j]; }
+        return SDRPP_OK;
+    }
+    return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of an RDS demodulator of VFO %d", (unsigned long long)ticket, id);
 }
 int sdrpp_result_meters(sdrpp_ctx* c, uint64_t ticket, const float** data, int* n_lines, int* n_meters) {
     if (!c) { return SDRPP_ERR_INVALID; }

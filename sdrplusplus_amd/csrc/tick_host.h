@@ -283,6 +283,12 @@ size_t tick_results_need(sdrpp_ctx* c) {
             if (y.attached && y.st.size() == 4) { need += (size_t)kGroupMax * 4 + (((y.st[1].cap + 16) * 4 + 15) & ~(size_t)15) + ((y.st[1].cap + 16 + 15) & ~(size_t)15); }
         }
     }
+    if (c->res_flags & 128) {  // RDS demodulators: the symbol branch's layout
+        for (auto& kv : c->vfos) {
+            const Vfo::Rdsd& y = kv.second->rdsd;
+            if (y.attached && y.st.size() == 3) { need += (size_t)kGroupMax * 4 + (((y.st[0].cap + 16) * 4 + 15) & ~(size_t)15) + ((y.st[0].cap + 16 + 15) & ~(size_t)15); }
+        }
+    }
     if ((c->res_flags & 8) && c->pre.on) {
         size_t cap = c->pre.out.base ? c->pre.out.cap : 0;
         for (auto& st : c->pre.st) { cap = std::max(cap, st.cap); }
@@ -525,6 +531,27 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
             copies.push_back(ResCopy{ y.st[3].data, cnt_off, (size_t)k * 4, y.lvl + 1 });
             copies.push_back(ResCopy{ y.st[1].data, soft_off, (size_t)y.cap * 4, y.lvl + 1 });
             copies.push_back(ResCopy{ y.st[2].data, bits_off, ((size_t)y.cap + 3) & ~(size_t)3, y.lvl + 1 });
+            off = bits_off + (((size_t)y.cap + 15) & ~(size_t)15);
+        }
+    }
+    if (c->res_flags & 128) {
+        // every RDS demodulator that ran in this block: the job's per-push counts, then what its outputs have room for in this block (the symbol branch's layout)
+        for (auto& kv : c->vfos) {
+            const Vfo& v = *kv.second;
+            const Vfo::Rdsd& y = v.rdsd;
+            if (!y.attached || !y.ran) { continue; }
+            if (y.npush != k) { return fail(c, SDRPP_ERR_INVALID, "internal: VFO %d's RDS demodulator planned %d pushes, the block has %d", v.id, y.npush, k); }
+            const size_t cnt_off = off, soft_off = cnt_off + (((size_t)k * 4 + 15) & ~(size_t)15), bits_off = soft_off + (((size_t)y.cap * 4 + 15) & ~(size_t)15);
+            for (int j = 0; j < k; j++) {
+                R[j]->rdsd_ids.push_back(v.id);
+                R[j]->rdsd_push.push_back(j);
+                R[j]->rdsd_cnt_off.push_back(cnt_off);
+                R[j]->rdsd_soft_off.push_back(soft_off);
+                R[j]->rdsd_bits_off.push_back(bits_off);
+            }
+            copies.push_back(ResCopy{ y.st[2].data, cnt_off, (size_t)k * 4, y.lvl + 1 });
+            copies.push_back(ResCopy{ y.st[0].data, soft_off, (size_t)y.cap * 4, y.lvl + 1 });
+            copies.push_back(ResCopy{ y.st[1].data, bits_off, ((size_t)y.cap + 3) & ~(size_t)3, y.lvl + 1 });
             off = bits_off + (((size_t)y.cap + 15) & ~(size_t)15);
         }
     }

@@ -368,10 +368,13 @@ int fmnr_apply(sdrpp_ctx* c, Vfo& v, bool enabled, int bins) {
 int rds_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n);  // (the RDS branch: below, with the rest of it)
 int stereo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, bool* cleared);  // (the stereo branch: likewise)
 int sym_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n);  // (the symbol branch: likewise)
+int rdsd_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, size_t old_cap);  // (the RDS demodulator: likewise)
+size_t rdsd_in_cap(const Vfo& v, int source);
 int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
     Stream& of = chan_feed(o);
     Stream& nf = chan_feed(n);
     int rc;
+    const size_t rdsd_cap = (o.rdsd.attached && (o.rdsd.source == 1 || o.rds.attached)) ? rdsd_in_cap(o, o.rdsd.source) : 0;  // (before the RDS branch moves)
     if (keep & 1) {
         if (o.nco_exact == n.nco_exact) {
             n.phi = o.phi;
@@ -430,6 +433,9 @@ int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
     }
     if ((keep & 2) && o.d.demod == n.d.demod && n.d.demod == SDRPP_DEMOD_RAW) {
         if ((rc = sym_hand_over(c, o, n))) { return rc; }
+    }
+    if ((keep & 2) && o.d.demod == n.d.demod) {
+        if ((rc = rdsd_hand_over(c, o, n, rdsd_cap))) { return rc; }
     }
     if (keep & 4) {  // ... and FMIF with them: its bin count, whether it is plugged in, and its delay line
         if ((rc = fmif_line_save(c, o))) { return rc; }
@@ -564,8 +570,10 @@ unsigned long long rds_bank_hash(int interp, int decim, const float* taps, int n
     }
     return h ? h : 1ull;
 }
+void rdsd_detach(sdrpp_ctx* c, Vfo& v);
 void rds_detach(sdrpp_ctx* c, Vfo& v) {
     Vfo::Rds& r = v.rds;
+    if (v.rdsd.attached && v.rdsd.source == 0) { rdsd_detach(c, v); }  // (a demodulator behind the branch goes with it)
     if (r.bank_key) {
         auto it = c->rds_banks.find(r.bank_key);
         if (it != c->rds_banks.end() && --it->second.refs <= 0) {
@@ -989,6 +997,221 @@ int sym_count(sdrpp_ctx* c, Vfo& v) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int cnt[kGroupMax] = {};
     HIPCHK(c, hipMemcpy(cnt, y.st[3].data, (size_t)std::min(y.npush, kGroupMax) * sizeof(int), hipMemcpyDeviceToHost));
+    int total = 0;
+    for (int j = 0; j < std::min(y.npush, kGroupMax); j++) { total += cnt[j]; }
+    return std::min(total, y.cap);
+}
+
+// ---- RDS demodulator behind the RDS branch (source 0) or on a RAW VFO (source 1) ------------------------------------------------------------------
+void rdsd_detach(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Rdsd& y = v.rdsd;
+    if (y.bank_key) {
+        auto it = c->rdsd_banks.find(y.bank_key);
+        if (it != c->rdsd_banks.end() && --it->second.refs <= 0) {
+            dev_free(it->second.d_taps);
+            dev_free(it->second.d_bank);
+            c->rdsd_banks.erase(it);
+        }
+    }
+    rdsd_free_own(y);
+    y = Vfo::Rdsd{};
+}
+// The context's shared tap table and interpolator bank (keyed by rds_bank_hash over both, one reference per demodulator): uploaded with their first user
+int rdsd_bank_acquire(sdrpp_ctx* c, Vfo::Rdsd& y, const float* taps, const float* bank) {
+    std::vector<float> all(taps, taps + 2 * (size_t)y.K);
+    all.insert(all.end(), bank, bank + (size_t)y.phases * (size_t)y.T);
+    const unsigned long long key = rds_bank_hash(y.K, y.phases * 32 + y.T, all.data(), (int)all.size());
+    auto it = c->rdsd_banks.find(key);
+    if (it != c->rdsd_banks.end() && (it->second.K != y.K || it->second.phases != y.phases || it->second.T != y.T || memcmp(it->second.taps.data(), taps, 2 * (size_t)y.K * sizeof(float)) != 0 ||
+                                     memcmp(it->second.bank.data(), bank, (size_t)y.phases * (size_t)y.T * sizeof(float)) != 0)) {
+        return fail(c, SDRPP_ERR_UNSUPPORTED, "rds demodulator tables: two different descriptions under one key");  // (a 64-bit collision: never seen)
+    }
+    if (it == c->rdsd_banks.end()) {
+        sdrpp_ctx::RdsdBank B;
+        B.taps.assign(taps, taps + 2 * (size_t)y.K);
+        B.bank.assign(bank, bank + (size_t)y.phases * (size_t)y.T);
+        if (int rc = upload(c, &B.d_taps, B.taps.data(), B.taps.size())) { return rc; }
+        if (int rc = upload(c, &B.d_bank, B.bank.data(), B.bank.size())) {
+            dev_free(B.d_taps);
+            return rc;
+        }
+        B.K = y.K;
+        B.phases = y.phases;
+        B.T = y.T;
+        it = c->rdsd_banks.emplace(key, std::move(B)).first;
+    }
+    it->second.refs++;
+    y.bank_key = key;
+    y.d_taps = it->second.d_taps;
+    y.d_bank = it->second.d_bank;
+    return SDRPP_OK;
+}
+// RDSDemod::reset() (rds_demod.h:51-62); `fresh`: RDSDemod::init — MM's delay samples cleared as well (a new object's buffer)
+int rdsd_clear(sdrpp_ctx* c, Vfo& v, bool fresh) {
+    Vfo::Rdsd& y = v.rdsd;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int zero = 0;
+    float st[SDRPP_RDSD_STATE_HEAD] = {};
+    st[0] = y.agc[3];
+    st[1] = y.loop[0][2]; st[2] = y.loop[0][3];
+    st[3] = y.loop[1][2]; st[4] = y.loop[1][3];
+    st[5] = 0.0f; st[6] = y.omega; st[7] = 0.0f;
+    memcpy(&st[8], &zero, sizeof(int));
+    memcpy(&st[9], &zero, sizeof(int));
+    HIPCHK(c, hipMemcpy(y.d_state, st, sizeof(st), hipMemcpyHostToDevice));
+    const size_t line = 2 * (size_t)(y.K - 1) + (fresh ? (size_t)(y.T - 1) : 0);
+    if (line > 0) { HIPCHK(c, hipMemset(y.d_state + SDRPP_RDSD_STATE_HEAD, 0, line * sizeof(float))); }
+    y.ran = false;
+    for (auto& q : y.st) { q.n = 0; }
+    return SDRPP_OK;
+}
+bool rdsd_same_desc(const Vfo::Rdsd& y, const sdrpp_rdsd_desc* d, const sdrpp_ctx* c) {
+    const sdrpp_rdsd_loop* lp[2] = { &d->loop1, &d->loop2 };
+    for (int i = 0; i < 2; i++) {
+        const float f[6] = { lp[i]->alpha, lp[i]->beta, lp[i]->init_phase, lp[i]->init_freq, lp[i]->min_freq, lp[i]->max_freq };
+        if (memcmp(f, y.loop[i], sizeof(f)) != 0) { return false; }
+    }
+    const float agc[4] = { d->agc_set_point, d->agc_max_gain, d->agc_rate, d->agc_init_gain };
+    if (y.source != d->source || memcmp(agc, y.agc, sizeof(agc)) != 0 || y.K != d->n_taps || y.omega != d->omega || y.mu_gain != d->mu_gain || y.omega_gain != d->omega_gain ||
+        y.min_omega != d->min_omega || y.max_omega != d->max_omega || y.phases != d->interp_phases || y.T != d->interp_ntaps) {
+        return false;
+    }
+    auto it = c->rdsd_banks.find(y.bank_key);
+    return it != c->rdsd_banks.end() && memcmp(it->second.taps.data(), d->taps, it->second.taps.size() * sizeof(float)) == 0 &&
+           memcmp(it->second.bank.data(), d->interp_bank, it->second.bank.size() * sizeof(float)) == 0;
+}
+// the stream the demodulator reads: the RDS branch's last stage (source 0) or the VFO's channel stream (source 1: what a demodulator would read)
+size_t rdsd_in_cap(const Vfo& v, int source) { return source == 0 ? v.rds.st[(size_t)v.rds.i_last].cap : v.st[(size_t)v.i_chan].cap; }
+// sdrpp_vfo_set_rds_demod on a VFO the caller has looked up (the stream is idle); d == nullptr: the demodulator goes
+int rdsd_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_rdsd_desc* d, bool enabled) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!d) {
+        rdsd_detach(c, v);
+        return SDRPP_OK;
+    }
+    if (d->source != 0 && d->source != 1) { return fail(c, SDRPP_ERR_INVALID, "rds demodulator: source %d (0: the RDS branch, 1: the stream a demodulator would read)", d->source); }
+    if (d->source == 0 && !v.rds.attached) { return fail(c, SDRPP_ERR_INVALID, "rds demodulator, source 0: VFO %d has no RDS branch (sdrpp_vfo_set_rds first)", v.id); }
+    if (d->source == 1 && v.d.demod != SDRPP_DEMOD_RAW) { return fail(c, SDRPP_ERR_UNSUPPORTED, "rds demodulator, source 1: needs a RAW VFO"); }
+    if (d->n_taps < 1 || d->n_taps > SDRPP_RDSD_MAX_TAPS || !d->taps) { return fail(c, SDRPP_ERR_INVALID, "rds demodulator: band-pass of %d complex taps (1 .. %d, with taps)", d->n_taps, SDRPP_RDSD_MAX_TAPS); }
+    if (d->interp_ntaps < 1 || d->interp_ntaps > SDRPP_SYM_MAX_INTERP_TAPS || !d->interp_bank) {
+        return fail(c, SDRPP_ERR_INVALID, "rds demodulator: interpolator of %d taps per phase (1 .. %d, with a bank)", d->interp_ntaps, SDRPP_SYM_MAX_INTERP_TAPS);
+    }
+    if (d->interp_phases < 1 || d->interp_phases > SDRPP_SYM_MAX_PHASES) { return fail(c, SDRPP_ERR_INVALID, "rds demodulator: interpolator of %d phases (1 .. %d)", d->interp_phases, SDRPP_SYM_MAX_PHASES); }
+    if (!std::isfinite(d->agc_set_point) || !std::isfinite(d->agc_max_gain) || !std::isfinite(d->agc_rate) || !std::isfinite(d->agc_init_gain)) {
+        return fail(c, SDRPP_ERR_INVALID, "rds demodulator: AGC set point %g, max gain %g, rate %g, initial gain %g: all finite", d->agc_set_point, d->agc_max_gain, d->agc_rate, d->agc_init_gain);
+    }
+    const sdrpp_rdsd_loop* lp[2] = { &d->loop1, &d->loop2 };
+    for (int i = 0; i < 2; i++) {
+        const sdrpp_rdsd_loop& l = *lp[i];
+        if (!std::isfinite(l.alpha) || !std::isfinite(l.beta) || !std::isfinite(l.init_phase) || !std::isfinite(l.init_freq) || !std::isfinite(l.min_freq) || !std::isfinite(l.max_freq)) {
+            return fail(c, SDRPP_ERR_INVALID, "rds demodulator: loop %d has a value that is not finite", i + 1);
+        }
+        if (!(l.min_freq < l.max_freq)) { return fail(c, SDRPP_ERR_INVALID, "rds demodulator: loop %d frequency limits %g .. %g: min < max", i + 1, l.min_freq, l.max_freq); }
+        // the bounded-loop rule: a step of at most 2 pi from a phase inside +-pi is wrapped by ONE subtraction or addition (vfo_rdsd_kernels.h)
+        if (!((double)std::max(fabsf(l.min_freq), fabsf(l.max_freq)) + (double)fabsf(l.alpha) <= 2.0 * 3.14159265358979323846) || !(fabsf(l.init_phase) <= 3.1415926535f)) {
+            return fail(c, SDRPP_ERR_INVALID, "rds demodulator: loop %d with frequency limits %g .. %g, alpha %g, initial phase %g: max(|min|, |max|) + |alpha| <= 2 pi and |phase| <= pi, else the phase wrap is no single step",
+                        i + 1, l.min_freq, l.max_freq, l.alpha, l.init_phase);
+        }
+    }
+    if (!std::isfinite(d->omega) || !std::isfinite(d->mu_gain) || !std::isfinite(d->omega_gain) || !std::isfinite(d->min_omega) || !std::isfinite(d->max_omega)) {
+        return fail(c, SDRPP_ERR_INVALID, "rds demodulator: clock recovery has a value that is not finite");
+    }
+    if (!(d->min_omega < d->max_omega) || !(d->min_omega - fabsf(d->mu_gain) >= 1.0f) || !(d->max_omega + fabsf(d->mu_gain) <= (float)SDRPP_SYM_MAX_STEP)) {
+        return fail(c, SDRPP_ERR_INVALID, "rds demodulator: omega limits %g .. %g, mu gain %g: min < max, min - |mu gain| >= 1, max + |mu gain| <= %d", d->min_omega, d->max_omega, d->mu_gain, SDRPP_SYM_MAX_STEP);
+    }
+    const size_t cap = rdsd_in_cap(v, d->source);
+    if (cap + 16 >= ((size_t)1 << 24) - (size_t)(SDRPP_SYM_MAX_STEP + 1)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "rds demodulator on a stream of up to %zu samples per push (offsets are exact below 2^24)", cap); }
+    Vfo::Rdsd& y = v.rdsd;
+    if (y.attached && rdsd_same_desc(y, d, c)) {  // the same demodulator: only the switch — everything it holds stays as it is
+        if (y.on && !enabled) {
+            for (auto& q : y.st) { q.n = 0; }
+        }
+        y.on = enabled;
+        y.ran = y.ran && enabled;
+        return SDRPP_OK;
+    }
+    rdsd_detach(c, v);
+    // every early return below gives back what was built so far
+    struct Undo {
+        sdrpp_ctx* c; Vfo& v; bool armed = true;
+        ~Undo() { if (armed) { rdsd_detach(c, v); } }
+    } undo{ c, v };
+    int rc;
+    y.source = d->source;
+    const float agc[4] = { d->agc_set_point, d->agc_max_gain, d->agc_rate, d->agc_init_gain };
+    memcpy(y.agc, agc, sizeof(agc));
+    for (int i = 0; i < 2; i++) {
+        const float f[6] = { lp[i]->alpha, lp[i]->beta, lp[i]->init_phase, lp[i]->init_freq, lp[i]->min_freq, lp[i]->max_freq };
+        memcpy(y.loop[i], f, sizeof(f));
+    }
+    y.K = d->n_taps;
+    y.omega = d->omega;
+    y.mu_gain = d->mu_gain;
+    y.omega_gain = d->omega_gain;
+    y.min_omega = d->min_omega;
+    y.max_omega = d->max_omega;
+    y.phases = d->interp_phases;
+    y.T = d->interp_ntaps;
+    y.min_step = std::max(1, (int)floorf(d->min_omega - fabsf(d->mu_gain)));
+    if ((rc = rdsd_bank_acquire(c, y, d->taps, d->interp_bank))) { return rc; }
+    if ((rc = dev_alloc(c, &y.d_state, (size_t)SDRPP_RDSD_STATE_HEAD + 2 * (size_t)(y.K - 1) + (size_t)(y.T - 1) + 1))) { return rc; }
+    // per-block buffers: the symbols a block of `cap` samples can start, their bits (bytes, four to a float) and the per-push counts
+    const size_t scap = (size_t)y.cap_of((int)cap);
+    const size_t caps[3] = { scap, (scap + 3) / 4, (size_t)kGroupMax };
+    y.st.resize(3);
+    for (int i = 0; i < 3; i++) {
+        if (stream_alloc(c, y.st[(size_t)i], 1, 0, caps[i])) { return SDRPP_ERR_NOMEM; }
+    }
+    if ((rc = rdsd_clear(c, v, true))) { return rc; }
+    y.attached = true;
+    y.on = enabled;
+    undo.armed = false;
+    return SDRPP_OK;
+}
+// the description a demodulator was attached with (the arrays are the context's copies: valid while the demodulator holds its reference)
+sdrpp_rdsd_desc rdsd_desc_of(const sdrpp_ctx* c, const Vfo::Rdsd& y) {
+    const sdrpp_ctx::RdsdBank& B = c->rdsd_banks.at(y.bank_key);
+    sdrpp_rdsd_desc d{};
+    d.source = y.source;
+    d.agc_set_point = y.agc[0]; d.agc_max_gain = y.agc[1]; d.agc_rate = y.agc[2]; d.agc_init_gain = y.agc[3];
+    sdrpp_rdsd_loop* lp[2] = { &d.loop1, &d.loop2 };
+    for (int i = 0; i < 2; i++) { *lp[i] = sdrpp_rdsd_loop{ y.loop[i][0], y.loop[i][1], y.loop[i][2], y.loop[i][3], y.loop[i][4], y.loop[i][5] }; }
+    d.n_taps = y.K;
+    d.taps = B.taps.data();
+    d.omega = y.omega; d.mu_gain = y.mu_gain; d.omega_gain = y.omega_gain; d.min_omega = y.min_omega; d.max_omega = y.max_omega;
+    d.interp_phases = y.phases; d.interp_ntaps = y.T;
+    d.interp_bank = B.bank.data();
+    return d;
+}
+// sdrpp_vfo_replace with keep & 2 between two VFOs of the same demodulator kind, after the RDS / symbol branches have moved: the demodulator moves with
+// everything it holds; a new handle whose input stream has another capacity gets the description attached afresh (its buffers are sized for it), cleared.
+// A source-0 demodulator whose RDS branch did not arrive at the new handle stays behind and goes with the old handle.
+int rdsd_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, size_t old_cap) {
+    Vfo::Rdsd& y = o.rdsd;
+    if (!y.attached) { return SDRPP_OK; }
+    if (y.source == 0 && !n.rds.attached) { return SDRPP_OK; }
+    if (old_cap != rdsd_in_cap(n, y.source)) {
+        const sdrpp_ctx::RdsdBank B = c->rdsd_banks.at(y.bank_key);  // (a copy: attaching may let go of the table's last reference)
+        sdrpp_rdsd_desc d = rdsd_desc_of(c, y);
+        d.taps = B.taps.data();
+        d.interp_bank = B.bank.data();
+        return rdsd_apply(c, n, &d, y.on);
+    }
+    n.rdsd = std::move(o.rdsd);
+    o.rdsd = Vfo::Rdsd{};
+    n.rdsd.ran = false;
+    for (auto& q : n.rdsd.st) { q.n = 0; }
+    return SDRPP_OK;
+}
+// The symbols of the most recent block: the job's own counts, read from the device (the host waits for the stream)
+const char* const kNoRdsd = "VFO %d has no RDS demodulator";
+int rdsd_count(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Rdsd& y = v.rdsd;
+    if (!y.attached) { return fail(c, SDRPP_ERR_INVALID, kNoRdsd, v.id); }
+    if (!y.on || !y.ran || y.npush <= 0) { return 0; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int cnt[kGroupMax] = {};
+    HIPCHK(c, hipMemcpy(cnt, y.st[2].data, (size_t)std::min(y.npush, kGroupMax) * sizeof(int), hipMemcpyDeviceToHost));
     int total = 0;
     for (int j = 0; j < std::min(y.npush, kGroupMax); j++) { total += cnt[j]; }
     return std::min(total, y.cap);

@@ -112,6 +112,8 @@ class RxVFO {
 public:
     dsp::stream<dsp::complex_t> out;   // RxVFO::out (IF); delivered when no demodulator is attached
     dsp::stream<dsp::stereo_t> audio;  // demodulator output (radio's Demodulator::getOutput()) when attached
+    dsp::stream<uint8_t> rdsBits;        // attachRDSDemod: RDSDemod::out — one differentially decoded bit per symbol, one swap per block that started a symbol
+    dsp::stream<float> rdsSoft;          // ... and RDSDemod::soft (MM's output), swapped only while soft output is enabled
     dsp::stream<uint8_t> symOut;         // attachSymbols: POCSAGDSP::out — one bit per symbol
     dsp::stream<float> symSoft;          // ... and POCSAGDSP::soft
     dsp::stream<dsp::complex_t> rdsOut;  // attachRDS: BroadcastFM::rdsOut — the 5 kS/s baseband RDSDemod consumes, one swap per block that produced samples
@@ -149,6 +151,15 @@ public:
     void attachRDS();
     void detachRDS();
     void setRDSOut(bool enabled);
+    // The radio's RDSDemod (decoder_modules/radio/src/rds_demod.h; sdrpp_vfo_set_rds_demod, source 0) on the device behind the RDS branch: the symbols that start
+    // inside a block are delivered on `rdsBits` and — while `soft` is set — on `rdsSoft`, from the worker that delivers `rdsOut`, block by block or out of the
+    // pipelined result slots (flag 128); a block without a symbol is not handed on.  WHILE IT IS ATTACHED `rdsOut` IS NO LONGER WRITTEN: nobody reads it any more, and
+    // a dsp::stream without a reader blocks its writer (pipelined blocks still in flight at the attach are not written to it either).  attachRDSDemod attaches the RDS branch where it is not yet, and starts from a fresh RDSDemod;
+    // resetRDSDemod is RDSDemod::reset().  sdrpp_gpu::RDSDemod (sdrpp_gpu_rds.h) is the reference-shaped face of it.
+    void attachRDSDemod(bool soft);
+    void detachRDSDemod();
+    void setRDSDemodSoft(bool soft);
+    void resetRDSDemod();
     // The pager decoder's DSP (pocsag/dsp.h: Quadrature(-4500 Hz) -> shaping FIR -> MM clock recovery -> slicer; sdrpp_vfo_set_symbols) on the device, for a channel
     // WITHOUT a demodulator (Demod::RAW): the symbols that start inside a block are delivered on `symOut` (bits) and `symSoft` (soft values) from the worker that
     // delivers `out`, one swap each per block that produced any.  attachSymbols starts from a fresh POCSAGDSP; setSymbolsOn(false) freezes loop and delay lines,
@@ -203,6 +214,13 @@ public:
     double afAudioRate = 48000.0, afDeempTau = 50e-6;
     bool recOn = false, recMono = false, recIgnoreSilence = false;
     bool rdsAttached = false, rdsOn = false;
+    bool rdsdAttached = false, rdsdSoft = false;
+    // pipelined blocks are delivered late: whether a block's soft values are handed on is what held when the block was PUSHED — (first ticket, soft) per change
+    std::deque<std::pair<uint64_t, bool>> rdsdSoftFrom;
+    bool rdsdSoftAt(uint64_t ticket) {
+        while (rdsdSoftFrom.size() > 1 && rdsdSoftFrom[1].first <= ticket) { rdsdSoftFrom.pop_front(); }
+        return rdsdSoftFrom.empty() ? rdsdSoft : rdsdSoftFrom.front().second;
+    }
     bool symAttached = false, symOn = false;
     double symBaud = 0.0;
     bool stereoAttached = false, stereoOn = false;
@@ -397,6 +415,8 @@ public:
         registerOutput(&v->audio);
         registerOutput(&v->recorded);
         registerOutput(&v->rdsOut);
+        registerOutput(&v->rdsBits);
+        registerOutput(&v->rdsSoft);
         registerOutput(&v->symOut);
         registerOutput(&v->symSoft);
         tempStart();
@@ -415,6 +435,8 @@ public:
         unregisterOutput(&it->second->audio);
         unregisterOutput(&it->second->recorded);
         unregisterOutput(&it->second->rdsOut);
+        unregisterOutput(&it->second->rdsBits);
+        unregisterOutput(&it->second->rdsSoft);
         unregisterOutput(&it->second->symOut);
         unregisterOutput(&it->second->symSoft);
         vfoOrder.erase(std::remove(vfoOrder.begin(), vfoOrder.end(), it->second), vfoOrder.end());
@@ -452,6 +474,14 @@ public:
 
     // The VFO whose `out` stream this is (NULL if none): how a demod::Demodulator-shaped adaptor (sdrpp_gpu_radio.h), which is handed
     // `&vfo->out` as its input stream exactly like a CPU demodulator, finds the channel it is fused into.
+    // the VFO whose RDS branch's output `stream` is (sdrpp_gpu::RDSDemod binds through it)
+    RxVFO* vfoOfRDSStream(dsp::stream<dsp::complex_t>* stream) {
+        std::lock_guard<std::recursive_mutex> lck(ctrlMtx);
+        for (auto& kv : vfos) {
+            if (&kv.second->rdsOut == stream) { return kv.second; }
+        }
+        return nullptr;
+    }
     RxVFO* vfoOfStream(dsp::stream<dsp::complex_t>* stream) {
         std::lock_guard<std::recursive_mutex> lck(ctrlMtx);
         for (auto& kv : vfos) {
@@ -926,17 +956,20 @@ private:
         bool rec = false;
         for (auto& kv : vfos) { rec = rec || (kv.second->recOn && kv.second->demod != Demod::RAW); }
         bool rds = false;
-        for (auto& kv : vfos) { rds = rds || (kv.second->rdsAttached && kv.second->demod == Demod::WFM); }
+        for (auto& kv : vfos) { rds = rds || (kv.second->rdsAttached && !kv.second->rdsdAttached && kv.second->demod == Demod::WFM); }  // (flag 32 only while some VFO still needs its samples)
+        bool rdsd = false;
+        for (auto& kv : vfos) { rdsd = rdsd || (kv.second->rdsdAttached && kv.second->demod == Demod::WFM); }
         bool sym = false;
         for (auto& kv : vfos) { sym = sym || (kv.second->symAttached && kv.second->demod == Demod::RAW); }
-        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0) | (rds ? SDRPP_RESULT_RDS : 0) | (sym ? SDRPP_RESULT_SYM : 0);  // (a recorder or an RDS branch adds its flag and drops nobody's: `audio` is delivered as before)
+        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0) | (rds ? SDRPP_RESULT_RDS : 0) | (sym ? SDRPP_RESULT_SYM : 0) | (rdsd ? SDRPP_RESULT_RDS_BITS : 0);  // (a recorder or an RDS branch adds its flag and drops nobody's: `audio` is delivered as before)
     }
     int enterPipelined() {
         if (sdrpp_sync(ctx)) { return -1; }  // (nothing is staged in bypass mode; a deferred pass left over from buffered mode runs here)
         sdrpp_set_deferred(ctx, 0);
         pipeFlags = pipelineFlags();
-        if (sdrpp_set_pipelined(ctx, 1, pipeFlags & ~(SDRPP_RESULT_RDS | SDRPP_RESULT_SYM)) || ((pipeFlags & SDRPP_RESULT_RDS) && sdrpp_pipeline_set_rds_results(ctx, 1)) ||
-            ((pipeFlags & SDRPP_RESULT_SYM) && sdrpp_pipeline_set_sym_results(ctx, 1))) {  // (flags 32 and 64 have calls of their own)
+        if (sdrpp_set_pipelined(ctx, 1, pipeFlags & ~(SDRPP_RESULT_RDS | SDRPP_RESULT_SYM | SDRPP_RESULT_RDS_BITS)) || ((pipeFlags & SDRPP_RESULT_RDS) && sdrpp_pipeline_set_rds_results(ctx, 1)) ||
+            ((pipeFlags & SDRPP_RESULT_SYM) && sdrpp_pipeline_set_sym_results(ctx, 1)) ||
+            ((pipeFlags & SDRPP_RESULT_RDS_BITS) && sdrpp_pipeline_set_rds_bits_results(ctx, 1))) {  // (flags 32, 64 and 128 have calls of their own)
             fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] pipelined mode refused: %s\n", sdrpp_last_error(ctx));
             sdrpp_set_deferred(ctx, 1);
             _pipelining = false;
@@ -1079,7 +1112,7 @@ private:
         if (pipeFlags & SDRPP_RESULT_RDS) {
             for (auto& kv : vfos) {
                 RxVFO* v = kv.second;
-                if (!v->rdsAttached) { continue; }
+                if (!v->rdsAttached || v->rdsdAttached) { continue; }  // (behind a bound demodulator nobody reads rdsOut)
                 const float* data = nullptr;
                 int cnt = 0;
                 int rrc = sdrpp_result_rds(ctx, ticket, v->id, &data, &cnt);
@@ -1088,6 +1121,28 @@ private:
                 jobs.emplace_back([this, v, data, cnt]() {
                     memcpy(v->rdsOut.writeBuf, data, (size_t)cnt * sizeof(dsp::complex_t));
                     if (!v->rdsOut.swap(cnt)) { deliveryFailed = true; }
+                });
+            }
+        }
+        // the RDS demodulators: this push's bits and soft values (result flag 128), straight out of the slot; a block that started no symbol is not handed on
+        if (pipeFlags & SDRPP_RESULT_RDS_BITS) {
+            for (auto& kv : vfos) {
+                RxVFO* v = kv.second;
+                if (!v->rdsdAttached) { continue; }
+                const float* soft = nullptr;
+                const uint8_t* bits = nullptr;
+                int cnt = 0;
+                int rrc = sdrpp_result_rds_bits(ctx, ticket, v->id, &soft, &bits, &cnt);
+                for (size_t q = v->prevIds.size(); rrc == SDRPP_ERR_NOT_FOUND && q-- > 0;) { rrc = sdrpp_result_rds_bits(ctx, ticket, v->prevIds[q], &soft, &bits, &cnt); }
+                if (rrc || cnt <= 0) { continue; }  // (pushed before the attach, or while the branch was switched off)
+                const bool withSoft = v->rdsdSoftAt(ticket);
+                jobs.emplace_back([this, v, soft, bits, cnt, withSoft]() {
+                    memcpy(v->rdsBits.writeBuf, bits, (size_t)cnt);
+                    if (!v->rdsBits.swap(cnt)) { deliveryFailed = true; }
+                    if (withSoft) {
+                        memcpy(v->rdsSoft.writeBuf, soft, (size_t)cnt * sizeof(float));
+                        if (!v->rdsSoft.swap(cnt)) { deliveryFailed = true; }
+                    }
                 });
             }
         }
@@ -1344,6 +1399,20 @@ private:
         for (auto& kv : vfos) {
             RxVFO* v = kv.second;
             if (!v->rdsAttached || !v->rdsOn || v->demod != Demod::WFM || v->id < 0) { continue; }
+            if (v->rdsdAttached) {  // the demodulator's bits (and soft values) in place of the samples nobody reads any more
+                const bool withSoft = v->rdsdSoft;
+                const int ns = sdrpp_vfo_rds_demod_read(ctx, v->id, withSoft ? v->rdsSoft.writeBuf : nullptr, v->rdsBits.writeBuf, STREAM_BUFFER_SIZE);
+                if (ns < 0) {
+                    fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] reading the RDS demodulator failed: %s\n", sdrpp_last_error(ctx));
+                    return -1;
+                }
+                if (ns == 0) { continue; }
+                jobs.emplace_back([v, ns, withSoft, &failed]() {
+                    if (!v->rdsBits.swap(ns)) { failed = true; }
+                    if (withSoft && !v->rdsSoft.swap(ns)) { failed = true; }
+                });
+                continue;
+            }
             const int got = sdrpp_vfo_rds_read(ctx, v->id, reinterpret_cast<float*>(v->rdsOut.writeBuf), STREAM_BUFFER_SIZE);
             if (got < 0) {
                 fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] reading the RDS branch failed: %s\n", sdrpp_last_error(ctx));
@@ -1500,6 +1569,7 @@ private:
         if (v.afOn && v.demod != Demod::RAW) { applyAF(v); }
         if (v.recOn && v.demod != Demod::RAW) { applyRec(v); }  // (sdrpp_vfo_replace does not carry the sink: the recorder binds to the stream, and the stream lives on)
         if (v.rdsAttached && v.demod == Demod::WFM) { applyRDS(v); }  // (a handle that kept its demodulator has the branch already, state and all: the same description only sets the switch)
+        if (v.rdsdAttached && v.rdsAttached && v.demod == Demod::WFM) { applyRDSDemod(v); }  // (likewise: moved with the branch, the same description only sets the switch)
         if (v.stereoAttached && v.demod == Demod::WFM) { applyStereo(v); }  // (likewise: the same description and switch change nothing)
         if (v.symAttached && v.demod == Demod::RAW) { applySymbols(v); }  // (likewise)
         sendMeters();  // (a new handle, perhaps a new bandwidth or input rate)
@@ -1537,6 +1607,16 @@ private:
         s.interp_bank = bank.data();
         int rc = sdrpp_vfo_set_symbols(ctx, v.id, &s, v.symOn ? 1 : 0);
         if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_symbols: ") + sdrpp_last_error(ctx)); }
+    }
+    // rds_demod.h:19-41 at the branch's 5 kS/s: every member as RDSDemod::init leaves it (sdrpp_design_rds_demod), behind the VFO's RDS branch
+    void applyRDSDemod(RxVFO& v) {
+        sdrpp_rdsd_desc d;
+        memset(&d, 0, sizeof(d));
+        std::vector<float> taps(2 * 256), bank(128 * 8);
+        if (sdrpp_design_rds_demod(5000.0, &d, taps.data(), 256, bank.data(), (int)bank.size()) < 0) { throw std::runtime_error("[sdrpp_gpu::IQFrontEnd] design_rds_demod failed"); }
+        d.source = 0;
+        int rc = sdrpp_vfo_set_rds_demod(ctx, v.id, &d, 1);
+        if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_rds_demod: ") + sdrpp_last_error(ctx)); }
     }
     void applyRDS(RxVFO& v) {
         sdrpp_rds_desc r;
@@ -1960,6 +2040,7 @@ inline void RxVFO::attachRDS() {
     rdsAttached = true;
     rdsOn = true;
     if (id >= 0) { fe->applyRDS(*this); }
+    if (rdsdAttached && id >= 0) { fe->applyRDSDemod(*this); }  // (the library detached it with the branch: a fresh one behind the fresh branch)
     fe->tempStart();
 }
 inline void RxVFO::detachRDS() {
@@ -1967,6 +2048,7 @@ inline void RxVFO::detachRDS() {
     fe->tempStop();
     rdsAttached = false;
     rdsOn = false;
+    rdsdAttached = false;  // (a demodulator behind the branch goes with it)
     if (id >= 0) { sdrpp_vfo_set_rds(fe->ctx, id, nullptr, 0); }
     fe->tempStart();
 }
@@ -1979,6 +2061,43 @@ inline void RxVFO::setRDSOut(bool enabled) {
     fe->tempStop();  // broadcast_fm.h:121-128
     rdsOn = enabled;
     if (id >= 0 && demod == Demod::WFM) { fe->applyRDS(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::attachRDSDemod(bool soft) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (demod != Demod::WFM) { throw std::runtime_error("[sdrpp_gpu::RxVFO] the RDS demodulator reads the WFM demodulator's RDS branch"); }
+    fe->tempStop();
+    if (!rdsAttached) {
+        rdsAttached = true;
+        rdsOn = true;
+        if (id >= 0) { fe->applyRDS(*this); }
+    }
+    if (rdsdAttached && id >= 0) { sdrpp_vfo_set_rds_demod(fe->ctx, id, nullptr, 0); }  // (attaching again starts cleared)
+    rdsdAttached = true;
+    rdsdSoft = soft;
+    rdsdSoftFrom.emplace_back(rdsdSoftFrom.empty() ? 0 : sdrpp_ticket(fe->ctx) + 1, soft);
+    if (id >= 0) { fe->applyRDSDemod(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::detachRDSDemod() {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    fe->tempStop();
+    rdsdAttached = false;
+    if (id >= 0) { sdrpp_vfo_set_rds_demod(fe->ctx, id, nullptr, 0); }
+    fe->tempStart();
+}
+inline void RxVFO::setRDSDemodSoft(bool soft) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    fe->tempStop();  // rds_demod.h:43-49
+    rdsdSoft = soft;
+    rdsdSoftFrom.emplace_back(rdsdSoftFrom.empty() ? 0 : sdrpp_ticket(fe->ctx) + 1, soft);
+    fe->tempStart();
+}
+inline void RxVFO::resetRDSDemod() {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (!rdsdAttached) { return; }
+    fe->tempStop();  // rds_demod.h:51-62
+    if (id >= 0) { sdrpp_vfo_rds_demod_reset(fe->ctx, id); }
     fe->tempStart();
 }
 inline void RxVFO::attachSymbols(double baudrate) {

@@ -139,6 +139,16 @@ public:
         _stereo = enabled;
         if (vfo) { vfo->setStereo(enabled); }
     }
+    // WFM only: the radio's RDSDemod on the device behind the branch (sdrpp_gpu::RDSDemod in sdrpp_gpu_rds.h is the reference-shaped face: hand it getRDSOutput()).
+    // These are the hooks for a module that wants the bits without the adaptor object: getRDSBits() / getRDSSoft() are RDSDemod::out / ::soft.
+    void setRDSDemod(bool enabled, bool soft = false) {
+        if (MODE != Demod::WFM) { throw std::runtime_error("[sdrpp_gpu::FusedDemodulator] the RDS demodulator belongs to the WFM demodulator"); }
+        if (!vfo) { return; }
+        if (enabled) { vfo->attachRDSDemod(soft); }
+        else { vfo->detachRDSDemod(); }
+    }
+    dsp::stream<uint8_t>* getRDSBits() { return (MODE == Demod::WFM && vfo) ? &vfo->rdsBits : nullptr; }
+    dsp::stream<float>* getRDSSoft() { return (MODE == Demod::WFM && vfo) ? &vfo->rdsSoft : nullptr; }
     dsp::stream<dsp::complex_t>* getRDSOutput() { return (MODE == Demod::WFM && vfo) ? &vfo->rdsOut : nullptr; }
     RxVFO* channel() { return vfo; }
 

@@ -255,6 +255,15 @@ def pager_desc(if_rate=24000.0, baud=2400.0):
     return s, [taps, bank]
 
 
+def rds_demod_desc(rate=5000.0, source=0):
+    """sdrpp_rdsd_desc for the radio module's RDSDemod::init (radio/src/rds_demod.h:19-41) on a stream of `rate` samples per second: FastAGC(1, 1e6, 0.1),
+    Costas<2>(0.005), the 190-tap complex band-pass 0 .. 2375 Hz, Costas<2>(0.01) at 1187.5 Hz +- 10 %, MM<float>(rate / 1187.5, 1e-6, 0.01, 0.01).
+    source 0: behind the VFO's RDS branch; 1: the stream a demodulator would read (RAW VFOs).  Returns (desc, keepalive)."""
+    d, taps, bank = capi.design_rds_demod(rate)
+    d.source = int(source)
+    return d, [taps, bank]
+
+
 def if_desc(if_rate, nb=False, nb_level=10.0, squelch=None):
     """sdrpp_if_desc for the radio module's IF chain (radio_module.h:84-96): NoiseBlanker(rate = 500 / if_rate, level; :90, :526) ->
     PowerSquelch(level in dB; None = off).  FMIF, the chain's last block, is switched by Context.vfo_set_fmnr (IFNR_BINS); the CTCSS squelch is not on the device."""
