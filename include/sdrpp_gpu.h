@@ -602,6 +602,74 @@ int sdrpp_rdsd_bank_count(sdrpp_ctx* ctx);
  * is not positive and finite, an array that is missing or too small (1024 floats of bank). */
 int sdrpp_design_rds_demod(double rate, sdrpp_rdsd_desc* desc, float* taps, int max_taps, float* bank, int max_bank);
 
+/* ---- Meteor QPSK demodulator: root-raised-cosine FIR -> AGC -> QPSK Costas loop -> optional OQPSK delay -> complex MM clock recovery -> int8 pairs ---------
+ * What the meteor_demodulator module's dsp::demod::Meteor (decoder_modules/meteor_demodulator/src/meteor_demod.h:150-167) computes from a 150 kS/s channel,
+ * per sample x[i] and per symbol:
+ *     f[i]  = sum_k x[i - (K-1) + k] * taps[k]          FIR<complex_t, float>: volk_32fc_32f_dot_prod_32fc in the generic order, re and im each accumulated
+ *                                                        sequentially, every product and sum rounded apart
+ *     a[i]  = f[i] * gain;  gain += (set_point - |a[i]|) * rate, clamped to max_gain from above only                       (loop/fast_agc.h)
+ *     c[i]  = a[i] * phasor(-phase);  e = clamp(step(c.re) * c.im - step(c.im) * c.re, -1, 1), or with broken != 0 the four-phase rule of
+ *             meteor_costas.h:35-51 (atan2f, normalizePhase, the lowest |dp| in the reference's order, times the amplitude); the loop advanced as
+ *             sdrpp_rdsd_desc's loops are (loop/phase_control_loop.h:58-85)
+ *     oqpsk != 0:  c[i].im is exchanged with the carried lastI: the imaginary part is delayed by one sample             (meteor_demod.h:155-162)
+ *     MM<complex_t> over c (clock_recovery/mm.h:100-156): the interpolator applied to re and im, the delays _p_2T <- _p_1T <- _p_0T and _c_2T <- _c_1T <- _c_0T
+ *             with _c_0T = step(out) per component, error = ((p0 - p2) * conj(c1) - (c0 - c2) * conj(p1)).re clamped to +-1, pcl.advance, offset += floorf(phase)
+ *     per symbol two outputs: the complex soft symbol, and two int8 values (int8)clamp((int)(v * soft_scale), -127, 127) as the module's sink writes them
+ *             (main.cpp:193-201, soft_scale 84): the conversion truncates towards zero, values beyond +-127 / soft_scale saturate, a NaN gives 0
+ * in float throughout, every operation in the reference's order.  A general block: every parameter comes from the description (sdrpp_design_meteor fills the
+ * module's).  The frame decoder stays host code and reads the int8 pairs: 144 KB/s per channel instead of 1.2 MB/s of IF samples.
+ * Works on SDRPP_DEMOD_RAW VFOs only, on the stream a demodulator would read (SDRPP_ERR_UNSUPPORTED otherwise).  It never changes a bit of any other output.
+ * SDRPP_ERR_INVALID, each with its reason in sdrpp_last_error: a value that is not finite (taps included); n_taps outside 1 .. 256, interp_ntaps outside
+ * 1 .. 16, interp_phases outside 1 .. 1024, a missing array; min >= max for the loop's frequency limits or for omega's; MM's step bounds as the symbol branch
+ * has them (min_omega - |mu_gain| >= 1, max_omega + |mu_gain| <= 4096); and a loop with max(|min_freq|, |max_freq|) + |alpha| > 2 pi or |init_phase| > pi
+ * (the bounded-loop rule of sdrpp_rdsd_desc: no trip count on the device depends on a sample's value).  Samples that are not numbers give unspecified values;
+ * the block ends and stays inside its arrays.
+ * STATE: the filter's K - 1 newest inputs, gain, loop phase and frequency, lastI, MM's phase, frequency, offset, six delay words and T - 1 samples.  A fresh
+ * attach and a call with another description start as Meteor::init leaves them; `broken` and `oqpsk` are modes and no part of the description's identity: the
+ * same description with other modes only sets them.  enabled = 0 freezes everything (nothing planned, nothing delivered) and enabled = 1 with the SAME
+ * description continues; desc == NULL detaches.  sdrpp_vfo_qpsk_set_mode is setBrokenModulation / setOQPSK: the state is kept, the modes hold from the next
+ * push.  sdrpp_vfo_qpsk_reset is Meteor::reset(): the filter line, the gain, the loop, MM's offset / phase / omega and six delay words — lastI and MM's T - 1
+ * delay samples stay, as the reference leaves them.  sdrpp_vfo_reset leaves the demodulator alone.  sdrpp_vfo_replace with keep & 2 between two RAW VFOs
+ * moves it, parameters and state, to the new handle (a handle with another stream capacity gets the description attached afresh, cleared).
+ * Tap table and interpolator bank exist ONCE per context for identical descriptions (sdrpp_qpsk_bank_count).
+ * OUTPUT of a push: the symbols whose start lies inside it: the concatenated output does not depend on how the stream is cut.  The accessors name the most
+ * recent push (SDRPP_ERR_INVALID without a demodulator, count 0 while it is switched off) and wait for the device.  soft_iq: interleaved (re, im), 2 floats per
+ * symbol; packed: 2 int8 per symbol.  Pipelined: sdrpp_pipeline_set_qpsk_results / sdrpp_result_qpsk.
+ * The arrays are copied during the call. */
+typedef struct sdrpp_qpsk_desc {
+    int n_taps;                       /* real taps of the shaping filter, 1 .. 256                                                */
+    const float* taps;                /* sdrpp_design_root_raised_cosine                                                          */
+    float agc_set_point, agc_max_gain, agc_rate, agc_init_gain;
+    sdrpp_rdsd_loop loop;             /* the QPSK Costas loop                                                                     */
+    int broken, oqpsk;                /* MeteorCostas::_broken, Meteor::_oqpsk                                                    */
+    float omega;                      /* MM, as in sdrpp_sym_desc                                                                 */
+    float mu_gain, omega_gain;
+    float min_omega, max_omega;
+    int interp_phases, interp_ntaps;
+    const float* interp_bank;
+    float soft_scale;                 /* int8 = clamp((int)(v * soft_scale), -127, 127): 84 for the module                        */
+} sdrpp_qpsk_desc;
+int sdrpp_vfo_set_qpsk(sdrpp_ctx* ctx, int id, const sdrpp_qpsk_desc* desc, int enabled);
+int sdrpp_vfo_qpsk_set_mode(sdrpp_ctx* ctx, int id, int broken, int oqpsk);
+int sdrpp_vfo_qpsk_reset(sdrpp_ctx* ctx, int id);
+/* The demodulator's output of the most recent push. */
+int sdrpp_vfo_qpsk_count(sdrpp_ctx* ctx, int id);
+int sdrpp_vfo_qpsk_read(sdrpp_ctx* ctx, int id, float* soft_iq, int8_t* packed, int max);   /* either array may be NULL; returns the symbols copied */
+int sdrpp_vfo_qpsk_device_buffers(sdrpp_ctx* ctx, int id, const float** soft_iq, const int8_t** packed, int* n);
+int sdrpp_abi_sizeof_qpsk_desc(void);
+/* Test and statistics hook: tap table / interpolator bank pairs of QPSK demodulators the context holds in device memory (identical descriptions share one). */
+int sdrpp_qpsk_bank_count(sdrpp_ctx* ctx);
+/* taps/root_raised_cosine.h in double, its three branches (t == 0, t == +-Ts / (4 beta), otherwise) included, Ts = samplerate / symbolrate; every tap rounded
+ * to float once.  Returns count, or SDRPP_ERR_INVALID: count < 1 or > max, a missing array, values that are not positive and finite. */
+int sdrpp_design_root_raised_cosine(int count, double beta, double symbolrate, double samplerate, float* taps, int max);
+/* Every field of *desc as Meteor::init (meteor_demod.h:24-43) leaves its members: rootRaisedCosine(rrc_taps, rrc_beta, symbolrate, samplerate) into taps[];
+ * FastAGC(1.0, 10e6, agc_rate) with its initial gain 1.0; MeteorCostas(costas_bw) at phase 0, frequency 0, limits +-FL_M_PI; MM(samplerate / symbolrate,
+ * omega_gain, mu_gain, 0.01 — init does not pass omegaRelLimit on) with sdrpp_design_mm_interp(128, 8) into bank[]; soft_scale 84.  The two arrays stay the
+ * caller's (max_taps taps, max_bank floats) and desc points at them.  Returns the number of taps, or SDRPP_ERR_INVALID: rates or gains that are not finite, an
+ * array that is missing or too small (1024 floats of bank). */
+int sdrpp_design_meteor(double symbolrate, double samplerate, int rrc_taps, double rrc_beta, double agc_rate, double costas_bw, int broken, int oqpsk, double omega_gain,
+                        double mu_gain, sdrpp_qpsk_desc* desc, float* taps, int max_taps, float* bank, int max_bank);
+
 /* ---- WaterFall display state around the raw-line history (core/src/gui/widgets/waterfall.cpp) ---------------
  * The last `height` raw dB lines stay resident in HBM in the reference's ring order (getFFTBuffer :875-886), so a zoom / pan /
  * level change re-renders the whole waterfall on the device (updateWaterfallFb :600-631) instead of re-reading host memory, and
@@ -853,6 +921,15 @@ int sdrpp_result_sym(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** soft
 #define SDRPP_RESULT_RDS_BITS 128
 int sdrpp_pipeline_set_rds_bits_results(sdrpp_ctx* ctx, int on);
 int sdrpp_result_rds_bits(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** soft, const uint8_t** bits, int* count);
+/* Result flag 256: the QPSK demodulators' outputs (sdrpp_vfo_set_qpsk) travel in every block's result slot, in the symbol branch's layout — per demodulator
+ * the per-push counts, then room for the block's capacity of symbols.  By default the int8 pairs only (2 bytes per possible symbol: 144 KB/s per channel at
+ * 72 000 symbols/s); with_soft != 0 adds the float pairs (8 bytes more).  A call of its own, with the rules of sdrpp_pipeline_set_rds_results.
+ * sdrpp_result_qpsk: *soft_iq / *packed = the *count symbols VFO `id`'s demodulator started inside push `ticket` (in a launch group the group's symbols lie
+ * in one piece and every push gets its own count and slice); *soft_iq is NULL where the float pairs were not asked for.  Validity as for sdrpp_result_rds;
+ * SDRPP_ERR_NOT_FOUND likewise.  Any output may be NULL. */
+#define SDRPP_RESULT_QPSK 256
+int sdrpp_pipeline_set_qpsk_results(sdrpp_ctx* ctx, int on, int with_soft);
+int sdrpp_result_qpsk(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** soft_iq, const int8_t** packed, int* count);
 /* Signal meters of push `ticket` (sdrpp_wf_set_meters): *data = [*n_lines][*n_meters][2] floats in the block's result slot, for the lines this push's
  * own samples completed — the rows `zoomed` / `raw` give it — oldest first.  No result flag: while a table is set, EVERY pipelined block with the
  * FFT on carries its meters (n_lines * n_meters * 8 bytes), result_flags = 0 included — sdrpp_result_wait / _release then work for such blocks.

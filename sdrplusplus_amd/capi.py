@@ -149,6 +149,31 @@ class RdsdDesc(C.Structure):
     ]
 
 
+class QpskDesc(C.Structure):
+    """struct sdrpp_qpsk_desc (include/sdrpp_gpu.h): the Meteor QPSK demodulator — RRC FIR, AGC, QPSK Costas loop, OQPSK delay, complex MM, int8 pairs."""
+
+    _fields_ = [
+        ("n_taps", C.c_int),
+        ("taps", c_float_p),
+        ("agc_set_point", C.c_float),
+        ("agc_max_gain", C.c_float),
+        ("agc_rate", C.c_float),
+        ("agc_init_gain", C.c_float),
+        ("loop", RdsdLoop),
+        ("broken", C.c_int),
+        ("oqpsk", C.c_int),
+        ("omega", C.c_float),
+        ("mu_gain", C.c_float),
+        ("omega_gain", C.c_float),
+        ("min_omega", C.c_float),
+        ("max_omega", C.c_float),
+        ("interp_phases", C.c_int),
+        ("interp_ntaps", C.c_int),
+        ("interp_bank", c_float_p),
+        ("soft_scale", C.c_float),
+    ]
+
+
 class StereoDesc(C.Structure):
     """struct sdrpp_stereo_desc (include/sdrpp_gpu.h): the WFM demodulator's stereo branch — pilot filter, PLL, L-R matrix."""
 
@@ -245,6 +270,7 @@ class Result(C.Structure):
 ABI_VERSION = 2    # SDRPP_ABI_VERSION (include/sdrpp_gpu.h)
 RESULT_SLOTS = 24  # SDRPP_RESULT_SLOTS: launches (one block each, or a group of up to GROUP_MAX: sdrpp_set_pipeline_group) whose pipelined results can exist at a time
 GROUP_MAX = 32     # SDRPP_GROUP_MAX
+RESULT_QPSK = 256  # SDRPP_RESULT_QPSK: the QPSK demodulators' int8 pairs (and, asked for, float pairs) and per-push counts in every block's result slot (Context.result_qpsk)
 RESULT_RDS_BITS = 128  # SDRPP_RESULT_RDS_BITS: the RDS demodulators' soft values, bits and per-push counts in every block's result slot (Context.result_rds_bits)
 RESULT_SYM = 64    # SDRPP_RESULT_SYM: the symbol branches' soft values, bits and per-push counts in every block's result slot (Context.set_pipelined, Context.result_sym)
 RESULT_RDS = 32    # SDRPP_RESULT_RDS: the RDS branches' samples in every block's result slot (Context.set_pipelined, Context.result_rds)
@@ -355,6 +381,22 @@ def load():
     L.sdrpp_pipeline_set_rds_bits_results.argtypes = [vp, C.c_int]
     L.sdrpp_result_rds_bits.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(c_float_p), C.POINTER(c_u8_p), c_int_p]
     L.sdrpp_design_rds_demod.argtypes = [C.c_double, C.POINTER(RdsdDesc), c_float_p, C.c_int, c_float_p, C.c_int]
+    c_i8_p = C.POINTER(C.c_int8)
+    L.sdrpp_abi_sizeof_qpsk_desc.argtypes = []
+    if L.sdrpp_abi_sizeof_qpsk_desc() != C.sizeof(QpskDesc):
+        raise ImportError("sdrpp_qpsk_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_qpsk_desc(), C.sizeof(QpskDesc)))
+    L.sdrpp_vfo_set_qpsk.argtypes = [vp, C.c_int, C.POINTER(QpskDesc), C.c_int]
+    L.sdrpp_vfo_qpsk_set_mode.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.sdrpp_vfo_qpsk_reset.argtypes = [vp, C.c_int]
+    L.sdrpp_vfo_qpsk_count.argtypes = [vp, C.c_int]
+    L.sdrpp_vfo_qpsk_read.argtypes = [vp, C.c_int, c_float_p, c_i8_p, C.c_int]
+    L.sdrpp_vfo_qpsk_device_buffers.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), c_int_p]
+    L.sdrpp_qpsk_bank_count.argtypes = [vp]
+    L.sdrpp_pipeline_set_qpsk_results.argtypes = [vp, C.c_int, C.c_int]
+    L.sdrpp_result_qpsk.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(c_float_p), C.POINTER(c_i8_p), c_int_p]
+    L.sdrpp_design_root_raised_cosine.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, c_float_p, C.c_int]
+    L.sdrpp_design_meteor.argtypes = [C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(QpskDesc), c_float_p, C.c_int,
+                                      c_float_p, C.c_int]
     L.sdrpp_abi_sizeof_stereo_desc.argtypes = []
     if L.sdrpp_abi_sizeof_stereo_desc() != C.sizeof(StereoDesc):
         raise ImportError("sdrpp_stereo_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_stereo_desc(), C.sizeof(StereoDesc)))
@@ -471,6 +513,8 @@ EXPORTED_SYMBOLS = [
     "sdrpp_pipeline_set_sym_results", "sdrpp_result_sym", "sdrpp_design_mm_interp", "sdrpp_design_pager",
     "sdrpp_vfo_set_rds_demod", "sdrpp_vfo_rds_demod_reset", "sdrpp_vfo_rds_demod_count", "sdrpp_vfo_rds_demod_read", "sdrpp_vfo_rds_demod_device_buffers",
     "sdrpp_abi_sizeof_rdsd_desc", "sdrpp_rdsd_bank_count", "sdrpp_design_rds_demod", "sdrpp_pipeline_set_rds_bits_results", "sdrpp_result_rds_bits",
+    "sdrpp_vfo_set_qpsk", "sdrpp_vfo_qpsk_set_mode", "sdrpp_vfo_qpsk_reset", "sdrpp_vfo_qpsk_count", "sdrpp_vfo_qpsk_read", "sdrpp_vfo_qpsk_device_buffers",
+    "sdrpp_abi_sizeof_qpsk_desc", "sdrpp_qpsk_bank_count", "sdrpp_design_root_raised_cosine", "sdrpp_design_meteor", "sdrpp_pipeline_set_qpsk_results", "sdrpp_result_qpsk",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
     "sdrpp_vfo_set_if", "sdrpp_vfo_set_fmnr", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
     "sdrpp_fft_configure", "sdrpp_fft_disable", "sdrpp_fft_set_view", "sdrpp_fft_lines", "sdrpp_fft_read", "sdrpp_fft_copy_device", "sdrpp_fft_device_buffers",
@@ -555,6 +599,34 @@ def design_rds_demod(rate=5000.0):
         raise SdrppError(k, "sdrpp_design_rds_demod")
     taps = taps[:k].copy()
     d.taps = taps.view(np.float32).ctypes.data_as(c_float_p)
+    return d, taps, bank
+
+
+def design_root_raised_cosine(count, beta, symbolrate, samplerate):
+    """taps/root_raised_cosine.h -> float32 [count]"""
+    taps = np.zeros(max(int(count), 1), dtype=np.float32)
+    k = load().sdrpp_design_root_raised_cosine(int(count), float(beta), float(symbolrate), float(samplerate), taps.ctypes.data_as(c_float_p), taps.size)
+    if k < 0:
+        raise SdrppError(k, "sdrpp_design_root_raised_cosine")
+    return taps[:k]
+
+
+_F32 = lambda v: float(np.float32(v))  # (the module writes these arguments as float literals: 0.6f, 0.1f, 0.005f)
+
+
+def design_meteor(symbolrate=72000.0, samplerate=150000.0, rrc_taps=33, rrc_beta=_F32(0.6), agc_rate=_F32(0.1), costas_bw=_F32(0.005), broken=False, oqpsk=False, omega_gain=1e-6,
+                  mu_gain=0.01):
+    """Every member of dsp::demod::Meteor after init (meteor_demodulator/src/meteor_demod.h:24-43) -> (QpskDesc, taps float32 [K], bank float32 [128, 8]); the
+    description points at the two arrays, which the caller keeps alive until it has been attached.  The defaults are the module's (main.cpp:66)."""
+    d = QpskDesc()
+    taps = np.zeros(256, dtype=np.float32)
+    bank = np.zeros((128, 8), dtype=np.float32)
+    k = load().sdrpp_design_meteor(float(symbolrate), float(samplerate), int(rrc_taps), float(rrc_beta), float(agc_rate), float(costas_bw), int(bool(broken)), int(bool(oqpsk)),
+                                   float(omega_gain), float(mu_gain), C.byref(d), taps.ctypes.data_as(c_float_p), 256, bank.ctypes.data_as(c_float_p), bank.size)
+    if k < 0:
+        raise SdrppError(k, "sdrpp_design_meteor")
+    taps = taps[:k].copy()
+    d.taps = taps.ctypes.data_as(c_float_p)
     return d, taps, bank
 
 
@@ -999,6 +1071,49 @@ class Context:
         """Tap table / interpolator bank pairs of RDS demodulators this context holds in device memory (identical descriptions share one)."""
         return self._chk(self.L.sdrpp_rdsd_bank_count(self.h))
 
+    def vfo_set_qpsk(self, vid, desc, enabled=True, keepalive=None):
+        """Attach the Meteor QPSK demodulator (sdrpp_vfo_set_qpsk; radio.meteor_desc) to a RAW VFO, switch it (the same description: enabled = False freezes its
+        state, True continues) or, with desc None, detach it.  `keepalive` is only there so that a caller can pass what radio.meteor_desc returns: the library
+        copies every array during the call."""
+        self._chk(self.L.sdrpp_vfo_set_qpsk(self.h, vid, C.byref(desc) if desc is not None else None, int(bool(enabled))))
+
+    def vfo_qpsk_set_mode(self, vid, broken, oqpsk):
+        """setBrokenModulation / setOQPSK: the state is kept, the modes hold from the next push."""
+        self._chk(self.L.sdrpp_vfo_qpsk_set_mode(self.h, vid, int(bool(broken)), int(bool(oqpsk))))
+
+    def vfo_qpsk_reset(self, vid):
+        """Meteor::reset()"""
+        self._chk(self.L.sdrpp_vfo_qpsk_reset(self.h, vid))
+
+    def vfo_qpsk_count(self, vid):
+        return self._chk(self.L.sdrpp_vfo_qpsk_count(self.h, vid))
+
+    def vfo_qpsk_read(self, vid):
+        """The QPSK demodulator's output of the last push -> (soft complex64 [n], packed int8 [n, 2])."""
+        n = self.vfo_qpsk_count(vid)
+        soft, packed = np.empty(max(n, 1), np.complex64), np.empty((max(n, 1), 2), np.int8)
+        got = self._chk(self.L.sdrpp_vfo_qpsk_read(self.h, vid, soft.view(np.float32).ctypes.data_as(c_float_p), packed.ctypes.data_as(C.POINTER(C.c_int8)), n))
+        return soft[:got], packed[:got]
+
+    def set_qpsk_results(self, on, with_soft=False):
+        """sdrpp_pipeline_set_qpsk_results (pipelined mode): result flag RESULT_QPSK, the int8 pairs alone or with the float pairs."""
+        self._chk(self.L.sdrpp_pipeline_set_qpsk_results(self.h, int(bool(on)), int(bool(with_soft))))
+
+    def result_qpsk(self, ticket, vid):
+        """sdrpp_result_qpsk (result flag RESULT_QPSK), between result_wait and result_release of that ticket -> this push's (soft or None, packed), copies."""
+        soft, packed, n = c_float_p(), C.POINTER(C.c_int8)(), C.c_int(0)
+        self._chk(self.L.sdrpp_result_qpsk(self.h, int(ticket), vid, C.byref(soft), C.byref(packed), C.byref(n)))
+        k = max(n.value, 0)
+        s = None
+        if soft:
+            s = np.ctypeslib.as_array(soft, shape=(2 * k,)).copy().view(np.complex64) if k else np.zeros(0, np.complex64)
+        p = np.ctypeslib.as_array(packed, shape=(2 * k,)).copy().reshape(-1, 2) if k else np.zeros((0, 2), np.int8)
+        return s, p
+
+    def qpsk_bank_count(self):
+        """Tap table / interpolator bank pairs of QPSK demodulators this context holds in device memory (identical descriptions share one)."""
+        return self._chk(self.L.sdrpp_qpsk_bank_count(self.h))
+
     def vfo_set_stereo(self, vid, desc, keepalive=None):
         """Attach the WFM demodulator's stereo branch (sdrpp_vfo_set_stereo; radio.stereo_desc), switch it (desc.enabled: BroadcastFM::setStereo, the
         demodulator starts over) or, with None, detach it.  `keepalive` is only there so that a caller can pass what radio.stereo_desc returns: the library
@@ -1092,8 +1207,11 @@ class Context:
         8 = the pre-processed IQ stream (with a pre-processing chain), 16 = the recorder sinks' converted blocks (result_rec) into page-locked result slots,
         32 (RESULT_RDS) = the RDS branches' samples (result_rds; the library switches that one by a call of its own, sdrpp_pipeline_set_rds_results),
         64 (RESULT_SYM) = the symbol branches' outputs (result_sym; likewise, sdrpp_pipeline_set_sym_results),
-        128 (RESULT_RDS_BITS) = the RDS demodulators' soft values and bits (result_rds_bits; likewise, sdrpp_pipeline_set_rds_bits_results)."""
-        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags) & ~(RESULT_RDS | RESULT_SYM | RESULT_RDS_BITS)))
+        128 (RESULT_RDS_BITS) = the RDS demodulators' soft values and bits (result_rds_bits; likewise, sdrpp_pipeline_set_rds_bits_results),
+        256 (RESULT_QPSK) = the QPSK demodulators' int8 pairs (result_qpsk; likewise, sdrpp_pipeline_set_qpsk_results — set_qpsk_results adds the float pairs)."""
+        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags) & ~(RESULT_RDS | RESULT_SYM | RESULT_RDS_BITS | RESULT_QPSK)))
+        if on and (int(result_flags) & RESULT_QPSK):
+            self._chk(self.L.sdrpp_pipeline_set_qpsk_results(self.h, 1, 0))
         if on and (int(result_flags) & RESULT_RDS_BITS):
             self._chk(self.L.sdrpp_pipeline_set_rds_bits_results(self.h, 1))
         if on and (int(result_flags) & RESULT_RDS):

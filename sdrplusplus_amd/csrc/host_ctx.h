@@ -214,6 +214,31 @@ struct Vfo {
         int n_in = 0, npush = 0, cap = 0; // ... its samples, its pushes, the symbols its outputs have room for
         int cap_of(int n) const { return (n + min_step - 1) / min_step + 1; }
     } rdsd;
+    // Meteor QPSK demodulator (sdrpp_vfo_set_qpsk; decoder_modules/meteor_demodulator/src/meteor_demod.h): root-raised-cosine FIR, AGC, QPSK Costas loop, OQPSK
+    // delay, complex MM — the filter as segment jobs over the stream a demodulator would read (RAW), everything sequential as one wavefront job a level behind
+    // (vfo_qpsk_kernels.h).  Everything it remembers is its own: the filter's two-sided line (the host flips `cur` per block that has samples) and ONE device
+    // array updated in place; switched off it freezes.  Its per-block buffers are streams without history.
+    struct Qpsk {
+        bool attached = false, on = false;
+        float agc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };   // set point, max gain, rate, initial gain
+        float loop[6] = {};                          // alpha, beta, initial phase, initial frequency, min / max frequency
+        int broken = 0, oqpsk = 0;                   // MeteorCostas::_broken, Meteor::_oqpsk (sdrpp_vfo_qpsk_set_mode)
+        float omega = 0.0f, mu_gain = 0.0f, omega_gain = 0.0f, min_omega = 0.0f, max_omega = 0.0f;
+        float soft_scale = 0.0f;
+        int K = 0, phases = 0, T = 0;
+        unsigned long long bank_key = 0;  // the context's shared tap table + interpolator bank this demodulator holds a reference to (0: none)
+        const float* d_taps = nullptr;    // ... borrowed
+        const float* d_bank = nullptr;
+        float* d_lines = nullptr;         // the filter's line: two sides of 2 K floats (QpskFrontJob)
+        int cur = 0;                      // ... the side the next block reads
+        float* d_state = nullptr;         // SDRPP_QPSK_STATE_HEAD words, T - 1 complex values (QpskLoopJob)
+        int min_step = 1;                 // as Sym::min_step
+        std::vector<Stream> st;           // [0] the filter's output (complex), [1] soft symbols (complex), [2] int8 pairs, [3] symbols per push (ints)
+        int lvl = 2;                      // level (do_vfos_plan) at which the loop job of the most recent block runs
+        bool ran = false;                 // the most recent block was planned with the demodulator on
+        int n_in = 0, npush = 0, cap = 0; // ... its samples, its pushes, the symbols its outputs have room for
+        int cap_of(int n) const { return (n + min_step - 1) / min_step + 1; }
+    } qpsk;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
     ToepTab tp_chan, tp_audio;
     // front end as one filter (what the fused translate + filter kernels evaluate): stages 0 (+ 1) of the plan
@@ -245,7 +270,7 @@ struct Vfo {
         int base = -1;  // first AF stream in st (they are appended behind the VFO's own streams)
     } af;
 };
-// Every stream of a VFO: its own, then its RDS branch's, its stereo branch's, its symbol branch's and its RDS demodulator's (the order plan_snapshot records them in).  ran_only: a branch's streams
+// Every stream of a VFO: its own, then its RDS branch's, its stereo branch's, its symbol branch's, its RDS demodulator's and its QPSK demodulator's (the order plan_snapshot records them in).  ran_only: a branch's streams
 // only if the most recent plan ran the branch.
 template <class F>
 void for_each_stream(Vfo& v, F&& f, bool ran_only = false) {
@@ -261,6 +286,9 @@ void for_each_stream(Vfo& v, F&& f, bool ran_only = false) {
     }
     if (!ran_only || v.rdsd.ran) {
         for (auto& s : v.rdsd.st) { f(s); }
+    }
+    if (!ran_only || v.qpsk.ran) {
+        for (auto& s : v.qpsk.st) { f(s); }
     }
 }
 template <class F>
@@ -417,6 +445,8 @@ struct sdrpp_ctx {
     struct SymBank { float* d_bank = nullptr; int refs = 0; int phases = 0, T = 0; std::vector<float> taps; };
     struct RdsdBank { float* d_taps = nullptr; float* d_bank = nullptr; int refs = 0; int K = 0, phases = 0, T = 0; std::vector<float> taps, bank; };
     std::map<unsigned long long, RdsdBank> rdsd_banks;  // tap table + interpolator bank of the RDS demodulators, ONE pair per distinct description, freed with their last user
+    struct QpskBank { float* d_taps = nullptr; float* d_bank = nullptr; int refs = 0; int K = 0, phases = 0, T = 0; std::vector<float> taps, bank; };
+    std::map<unsigned long long, QpskBank> qpsk_banks;  // real tap table + interpolator bank of the QPSK demodulators, ONE pair per distinct description, freed with their last user
     std::map<unsigned long long, SymBank> sym_banks;  // interpolator banks of the symbol branches, ONE per distinct bank, freed with their last user
 
     // ---- pipelined ("tick") execution: one launch per block, the stages of consecutive blocks skewed over consecutive launches
@@ -441,13 +471,16 @@ struct sdrpp_ctx {
         std::vector<size_t> sym_cnt_off, sym_soft_off, sym_bits_off;  // ... where the group's per-push counts, its soft values and its bits lie in the slot
         std::vector<int> rdsd_ids, rdsd_push;                // result flag 128: the VFOs whose RDS demodulator ran in the block, this push's index in its launch group
         std::vector<size_t> rdsd_cnt_off, rdsd_soft_off, rdsd_bits_off;  // ... where the group's per-push counts, its soft values and its bits lie in the slot (the symbol branch's layout)
+        std::vector<int> qpsk_ids, qpsk_push;                // result flag 256: the VFOs whose QPSK demodulator ran in the block, this push's index in its launch group
+        std::vector<size_t> qpsk_cnt_off, qpsk_soft_off, qpsk_packed_off;  // ... where the group's per-push counts, its float pairs (SIZE_MAX: not asked for) and its int8 pairs lie in the slot
         std::vector<int> rec_ids;                            // result flag 16: the VFOs that had a recorder sink when the block was planned,
         std::vector<size_t> rec_off, rec_info_off;           // ... where this push's converted samples and its sdrpp_rec_info lie in the slot
         int n_meters = -1;                                   // signal meters the block was pushed with (-1: no table then); its n_lines x n_meters x 2 floats
         size_t off_meters = 0;
     };
     bool pipelined = false;
-    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks, bit 5: RDS branches (sdrpp_pipeline_set_rds_results), bit 6: symbol branches (sdrpp_pipeline_set_sym_results), bit 7: RDS demodulators (sdrpp_pipeline_set_rds_bits_results)
+    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks, bit 5: RDS branches (sdrpp_pipeline_set_rds_results), bit 6: symbol branches (sdrpp_pipeline_set_sym_results), bit 7: RDS demodulators (sdrpp_pipeline_set_rds_bits_results), bit 8: QPSK demodulators (sdrpp_pipeline_set_qpsk_results)
+    bool res_qpsk_soft = false;           // ... with the float pairs beside the int8 pairs
     int num_cus = 256;
     int tick_l0_at = getenv("SDRPP_GPU_TICK_L0_AT") ? atoi(getenv("SDRPP_GPU_TICK_L0_AT")) : 0;  // (read when the context is created)
     // grid rules of the roles inside a tick (the stand-alone kernels size their grids for a GPU of their own; in a tick ~8 roles share it, and

@@ -156,6 +156,61 @@ int sdrpp_design_rds_demod(double rate, sdrpp_rdsd_desc* d, float* taps, int max
     return K;
 }
 
+// taps/root_raised_cosine.h:8-34: Ts = samplerate / symbolrate; the tap in the middle, the two at +-Ts / (4 beta), every other one
+int sdrpp_design_root_raised_cosine(int count, double beta, double symbolrate, double samplerate, float* taps, int max) {
+    if (count < 1 || count > max || !taps || !(beta > 0.0) || !(symbolrate > 0.0) || !(samplerate > 0.0) || !std::isfinite(beta) || !std::isfinite(symbolrate) || !std::isfinite(samplerate)) {
+        return SDRPP_ERR_INVALID;
+    }
+    const double Ts = samplerate / symbolrate;
+    const double half = (double)count / 2.0;
+    const double limit = Ts / (4.0 * beta);
+    const double kSqrt2 = 1.41421356237309504880;  // DB_M_SQRT2, math/constants.h
+    for (int i = 0; i < count; i++) {
+        const double t = (double)i - half + 0.5;
+        double v;
+        if (t == 0.0) { v = (1.0 + beta * (4.0 / kPi - 1.0)) / Ts; }
+        else if (t == limit || t == -limit) { v = ((1.0 + 2.0 / kPi) * std::sin(kPi / (4.0 * beta)) + (1.0 - 2.0 / kPi) * std::cos(kPi / (4.0 * beta))) * beta / (Ts * kSqrt2); }
+        else { v = ((std::sin((1.0 - beta) * kPi * t / Ts) + std::cos((1.0 + beta) * kPi * t / Ts) * 4.0 * beta * t / Ts) / ((1.0 - (4.0 * beta * t / Ts) * (4.0 * beta * t / Ts)) * kPi * t / Ts)) / Ts; }
+        taps[i] = (float)v;
+    }
+    return count;
+}
+
+// meteor_demodulator/src/meteor_demod.h:24-43: every member as init leaves it (fast_agc.h:13-19, meteor_costas.h:13-16 through pll.h:15-23, mm.h:24-32).
+// init takes omegaRelLimit and does not hand it to recov.init: MM's limit is its default, 0.01
+int sdrpp_design_meteor(double symbolrate, double samplerate, int rrc_taps, double rrc_beta, double agc_rate, double costas_bw, int broken, int oqpsk, double omega_gain,
+                        double mu_gain, sdrpp_qpsk_desc* d, float* taps, int max_taps, float* bank, int max_bank) {
+    if (!d || !taps || !bank || max_bank < 128 * 8 || !std::isfinite(agc_rate) || !std::isfinite(costas_bw) || !std::isfinite(omega_gain) || !std::isfinite(mu_gain)) { return SDRPP_ERR_INVALID; }
+    const int K = sdrpp_design_root_raised_cosine(rrc_taps, rrc_beta, symbolrate, samplerate, taps, max_taps);
+    if (K < 1) { return SDRPP_ERR_INVALID; }
+    if (sdrpp_design_mm_interp(128, 8, bank) != 128 * 8) { return SDRPP_ERR_INVALID; }
+    const float FL_PI = 3.1415926535f;  // FL_M_PI, math/constants.h:4
+    d->n_taps = K;
+    d->taps = taps;
+    d->agc_set_point = (float)1.0;  // agc.init(NULL, 1.0, 10e6, agcRate)
+    d->agc_max_gain = (float)10e6;
+    d->agc_rate = (float)agc_rate;
+    d->agc_init_gain = (float)1.0;
+    sdrpp_design_pll(costas_bw, &d->loop.alpha, &d->loop.beta);  // costas.init(NULL, costasBandwidth, brokenModulation)
+    d->loop.init_phase = (float)0.0;
+    d->loop.init_freq = (float)0.0;
+    d->loop.min_freq = (float)(double)-FL_PI;
+    d->loop.max_freq = (float)(double)FL_PI;
+    d->broken = broken != 0;
+    d->oqpsk = oqpsk != 0;
+    const double omega = samplerate / symbolrate, lim = 0.01;  // recov.init(NULL, _samplerate / _symbolrate, omegaGain, muGain, omegaRelLimit = 0.01)
+    d->omega = (float)omega;
+    d->mu_gain = (float)mu_gain;
+    d->omega_gain = (float)omega_gain;
+    d->min_omega = (float)(omega * (1.0 - lim));
+    d->max_omega = (float)(omega * (1.0 + lim));
+    d->interp_phases = 128;
+    d->interp_ntaps = 8;
+    d->interp_bank = bank;
+    d->soft_scale = 84.0f;  // main.cpp:198-199
+    return K;
+}
+
 void sdrpp_design_pll(double bandwidth_d, float* alpha, float* beta) {
     const float bandwidth = bandwidth_d;  // criticallyDamped(T bandwidth, ...) with T = float
     const float dampningFactor = sqrt(2.0) / 2.0;

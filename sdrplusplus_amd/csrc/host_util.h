@@ -498,6 +498,13 @@ void rdsd_free_own(Vfo::Rdsd& y) {
     for (auto& q : y.st) { stream_free(q); }
     y.st.clear();
 }
+// what a QPSK demodulator owns by itself (its share of the context's tables is given back by qpsk_detach, vfo_ctl.h)
+void qpsk_free_own(Vfo::Qpsk& y) {
+    dev_free(y.d_state);
+    dev_free(y.d_lines);
+    for (auto& q : y.st) { stream_free(q); }
+    y.st.clear();
+}
 // Outputs per tile and LDS row pitch of the branch's fused first stage (vfo_rds_front_body) for K taps decimating by D: the window of a tile, de-interleaved
 // by decimation phase, and its phases must fit the wavefront's share of the role's LDS.  The pitch serves the window's STORES (8 bytes per lane, carried out 16
 // lanes at a time over 32 dword banks: 16 consecutive samples must land on 16 different 8-byte banks — consecutive samples lie `pitch` float2 apart, D of them
@@ -539,6 +546,7 @@ void vfo_free(Vfo& v) {
     stereo_free(v.stereo);
     sym_free_own(v.sym);
     rdsd_free_own(v.rdsd);
+    qpsk_free_own(v.qpsk);
     af_detach(v);
     rate_free(v.rate);
     for (int i = 0; i < SDRPP_MAX_DECIM_STAGES; i++) { dev_free(v.d_staps_nat[i]); }

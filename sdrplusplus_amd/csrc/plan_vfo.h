@@ -252,6 +252,9 @@ struct BankPlan {
     Lev<SymLoopJob> sylj;  // (filled by upload once syl's records have their addresses)
     // RDS demodulator (rdsd_branch): a record, and a job, per VFO
     Lev<RdsdJob> rdsdj;
+    // QPSK demodulator (qpsk_branch): a front record (file_wave cuts it into segment jobs) and a loop record per VFO
+    Lev<QpskFrontJob> qpf;
+    Lev<QpskLoopJob> qpl;
     Lev<CarryJob> carry;  // history carries at the level of the stream's consumer (a pass without pipelining: all at the last level)
     int max_rot = 0;
     // front-end jobs (group_front)
@@ -290,7 +293,7 @@ struct BankPlan {
         for (auto& t : tlists) { f(*t.L); }
         f(f_dec); f(poly);
         for (auto& q : polyb) { f(q); }
-        f(chan); f(seq); f(nbsq); f(fmif); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stm); f(syf); f(syl); f(rdsdj); f(pre); f(audio); f(audio_fm);
+        f(chan); f(seq); f(nbsq); f(fmif); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stm); f(syf); f(syl); f(rdsdj); f(qpf); f(qpl); f(pre); f(audio); f(audio_fm);
         f(af_dec); f(af_hpf); f(af_poly); f(af_deemp);
         f(ssbx_l); f(carry);
         f(stlj); f(sylj); f(wave);
@@ -504,6 +507,14 @@ struct BankPlan {
         }
         else {
             for (auto& s : v.rdsd.st) { s.n = 0; }
+        }
+        v.qpsk.ran = v.qpsk.attached && v.qpsk.on;
+        if (v.qpsk.ran) {
+            if (int rc = qpsk_branch(x, feed)) { return rc; }
+            last_lvl = std::max(last_lvl, v.qpsk.lvl);
+        }
+        else {
+            for (auto& s : v.qpsk.st) { s.n = 0; }
         }
         phase_advance(x);
         x.at.lvl = last_lvl;
@@ -934,6 +945,41 @@ struct BankPlan {
         for (auto& s : y.st) { s.wlevel = lvl + 1; }
         return SDRPP_OK;
     }
+    // Meteor QPSK demodulator (meteor_demodulator/src/meteor_demod.h; vfo_qpsk_kernels.h): the shaping filter one level behind the stream a demodulator would
+    // read — ONE record, which file_wave cuts into a job per segment of SDRPP_QPSK_SEG samples, as FMIF's — and everything sequential as ONE job a level behind
+    // that.  The filter's line is two-sided (the block reads side `cur`, its last segment writes the other; flipped here per block that has samples); the loop's
+    // state is one device array updated in place.  A launch group is one block to both; the loop is handed the push ends at the stream's rate and counts the
+    // symbols push by push.  A block without samples files no front job and still files the loop: it writes the zeros of its counts.
+    int qpsk_branch(ChainCtx& x, const ChainCursor& feed) {
+        Vfo& v = x.v;
+        Vfo::Qpsk& y = v.qpsk;
+        const Stream& in = *feed.cur;
+        const int lvl = feed.lvl, n = in.n;
+        Stream &buf = y.st[0], &soft = y.st[1], &packed = y.st[2], &cnt = y.st[3];
+        y.n_in = n;
+        y.npush = x.split ? (int)v.tk_if.size() : 1;
+        y.cap = y.cap_of(n);
+        y.lvl = lvl + 2;
+        if (n > 0) {
+            qpf.add(lvl + 1, QpskFrontJob{ reinterpret_cast<const float2*>(in.data), y.d_lines, reinterpret_cast<float2*>(buf.data), y.d_taps, n, y.cur, y.K, 0 });
+            y.cur ^= 1;
+        }
+        const int* d_ends = nullptr;
+        if (x.split) {
+            d_ends = arena_push(c, v.tk_if);
+            if (!d_ends) { return arena_fail(c); }
+        }
+        qpl.add(lvl + 2, QpskLoopJob{ reinterpret_cast<const float2*>(buf.data), reinterpret_cast<float2*>(soft.data), reinterpret_cast<int8_t*>(packed.data), reinterpret_cast<int*>(cnt.data), y.d_state, y.d_bank,
+                                      d_ends, y.agc[0], y.agc[1], y.agc[2], y.loop[0], y.loop[1], y.loop[4], y.loop[5], y.mu_gain, y.omega_gain, y.min_omega, y.max_omega, y.soft_scale,
+                                      y.broken, y.oqpsk, y.T, y.phases, n, y.npush, y.cap, 0 });
+        buf.n = n;
+        soft.n = y.cap;
+        packed.n = (y.cap + 1) / 2;
+        cnt.n = y.npush;
+        for (auto& s : y.st) { s.wlevel = lvl + 2; }
+        buf.wlevel = lvl + 1;
+        return SDRPP_OK;
+    }
     void phase_advance(ChainCtx& x) {
         Vfo& v = x.v;
         if (x.have_phi_end) { v.phi = x.phi_end; }
@@ -1335,6 +1381,8 @@ struct BankPlan {
         file_wave(syf, WK_SYM_FRONT);
         file_wave(sylj, WK_SYM_LOOP);
         file_wave(rdsdj, WK_RDS_DEMOD);
+        file_wave(qpl, WK_QPSK_LOOP);  // (in front of the filter's jobs: a loop job filed at its filter's level would read the buffer BEFORE it is written wherever wavefronts start in table order — the emulator — and the tests see it)
+        file_wave(qpf, WK_QPSK_FRONT);
         // 3. the role's table
         if (!arena_push_lev(c, wave)) { return arena_fail(c); }
         HostScope hs("arena_commit (H2D)");
@@ -1342,13 +1390,14 @@ struct BankPlan {
     }
 
     // The records of one kind, in the arena already, as jobs of the wavefront-job role: a job per record — FMIF's records a job per segment of kFmifSeg
-    // samples, its first sample in WaveJob::arg.
+    // samples, the QPSK front's a job per segment of SDRPP_QPSK_SEG samples, the segment's first sample in WaveJob::arg.
     template <class T>
     void file_wave(const Lev<T>& recs, WaveKind kind) {
         for (int l = 0; l < recs.top; l++) {
             for (size_t k = 0; k < recs.at[l].size(); k++) {
                 int n = 1, step = 1;
                 if constexpr (std::is_same_v<T, FmifJob>) { n = recs.at[l][k].n; step = kFmifSeg; }
+                if constexpr (std::is_same_v<T, QpskFrontJob>) { n = recs.at[l][k].n; step = SDRPP_QPSK_SEG; }
                 for (int lo = 0; lo < n; lo += step) { wave.add(l, WaveJob{ recs.dev[l] + k, kind, lo }); }
                 if (wave_kind_uses_lds(kind)) { wave_lds = (size_t)4 * SDRPP_WAVE_LDS_FLOATS * sizeof(float); }
             }

@@ -388,6 +388,11 @@ int sdrpp_destroy(sdrpp_ctx* c) {
         dev_free(kv.second.d_bank);
     }
     c->rdsd_banks.clear();
+    for (auto& kv : c->qpsk_banks) {
+        dev_free(kv.second.d_taps);
+        dev_free(kv.second.d_bank);
+    }
+    c->qpsk_banks.clear();
     c->sym_banks.clear();
     c->vfos.clear();
     for (auto& e : c->s1_tap_cache) { (void)hipFree(e.second); }
@@ -767,6 +772,7 @@ int sdrpp_vfo_remove(sdrpp_ctx* c, int id) {
     rds_detach(c, *v);
     sym_detach(c, *v);
     rdsd_detach(c, *v);
+    qpsk_detach(c, *v);
     vfo_free(*v);
     c->vfos.erase(id);
     vfo_list_rebuild(c);
@@ -1058,6 +1064,66 @@ int sdrpp_vfo_rds_demod_device_buffers(sdrpp_ctx* c, int id, const float** soft,
 }
 int sdrpp_abi_sizeof_rdsd_desc(void) { return (int)sizeof(sdrpp_rdsd_desc); }
 int sdrpp_rdsd_bank_count(sdrpp_ctx* c) { return c ? (int)c->rdsd_banks.size() : SDRPP_ERR_INVALID; }
+
+// ---- Meteor QPSK demodulator: RRC FIR -> AGC -> QPSK Costas loop -> OQPSK delay -> complex MM (meteor_demodulator/src/meteor_demod.h) --------------------
+int sdrpp_vfo_set_qpsk(sdrpp_ctx* c, int id, const sdrpp_qpsk_desc* d, int enabled) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return qpsk_apply(c, *v, d, enabled != 0);
+}
+int sdrpp_vfo_qpsk_set_mode(sdrpp_ctx* c, int id, int broken, int oqpsk) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    if (!v->qpsk.attached) { return fail(c, SDRPP_ERR_INVALID, kNoQpsk, id); }
+    v->qpsk.broken = broken != 0;
+    v->qpsk.oqpsk = oqpsk != 0;
+    return SDRPP_OK;
+}
+int sdrpp_vfo_qpsk_reset(sdrpp_ctx* c, int id) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    if (!v->qpsk.attached) { return fail(c, SDRPP_ERR_INVALID, kNoQpsk, id); }
+    return qpsk_clear(c, *v, false);
+}
+int sdrpp_vfo_qpsk_count(sdrpp_ctx* c, int id) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return qpsk_count(c, *v);
+}
+int sdrpp_vfo_qpsk_read(sdrpp_ctx* c, int id, float* soft_iq, int8_t* packed, int max) {
+    DeviceScope dev_scope_(c);
+    if (!c || max < 0) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    const int have = qpsk_count(c, *v);
+    if (have < 0) { return have; }
+    const int n = std::min(have, max);
+    if (n > 0 && soft_iq) { HIPCHK(c, hipMemcpy(soft_iq, v->qpsk.st[1].data, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost)); }
+    if (n > 0 && packed) { HIPCHK(c, hipMemcpy(packed, v->qpsk.st[2].data, (size_t)n * 2, hipMemcpyDeviceToHost)); }
+    return n;
+}
+int sdrpp_vfo_qpsk_device_buffers(sdrpp_ctx* c, int id, const float** soft_iq, const int8_t** packed, int* n) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    const int have = qpsk_count(c, *v);
+    if (have < 0) { return have; }
+    if (soft_iq) { *soft_iq = v->qpsk.st[1].data; }
+    if (packed) { *packed = reinterpret_cast<const int8_t*>(v->qpsk.st[2].data); }
+    if (n) { *n = have; }
+    return SDRPP_OK;
+}
+int sdrpp_abi_sizeof_qpsk_desc(void) { return (int)sizeof(sdrpp_qpsk_desc); }
+int sdrpp_qpsk_bank_count(sdrpp_ctx* c) { return c ? (int)c->qpsk_banks.size() : SDRPP_ERR_INVALID; }
 
 int sdrpp_vfo_read_pcm(sdrpp_ctx* c, int id, int which, int pcm_type, float scale, void* dst_host, int max_frames) {
     DeviceScope dev_scope_(c);
@@ -1668,6 +1734,7 @@ int sdrpp_set_pipelined(sdrpp_ctx* c, int on, int result_flags) {
     c->stage_open = -1;
     c->pipelined = on != 0;
     c->res_flags = on ? result_flags : 0;
+    c->res_qpsk_soft = false;
     return SDRPP_OK;
 }
 int sdrpp_set_pipeline_group(sdrpp_ctx* c, int max_blocks, int adaptive) {
@@ -1852,6 +1919,34 @@ int sdrpp_result_rds_bits(sdrpp_ctx* c, uint64_t ticket, int id, const float** s
         return SDRPP_OK;
     }
     return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of an RDS demodulator of VFO %d", (unsigned long long)ticket, id);
+}
+int sdrpp_pipeline_set_qpsk_results(sdrpp_ctx* c, int on, int with_soft) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    if (!c->pipelined) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_pipeline_set_qpsk_results outside pipelined mode"); }
+    FLUSH_PENDING(c);
+    c->res_flags = on ? (c->res_flags | SDRPP_RESULT_QPSK) : (c->res_flags & ~SDRPP_RESULT_QPSK);
+    c->res_qpsk_soft = on && with_soft;
+    return SDRPP_OK;
+}
+// (the counts are the job's own result: they lie in the slot, complete since sdrpp_result_wait returned for this block)
+int sdrpp_result_qpsk(sdrpp_ctx* c, uint64_t ticket, int id, const float** soft_iq, const int8_t** packed, int* count) {
+    if (!c) { return SDRPP_ERR_INVALID; }
+    sdrpp_ctx::Result* R = result_of(c, ticket);
+    if (!R || !R->held) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_result_qpsk: block %llu is not held (between sdrpp_result_wait and sdrpp_result_release)", (unsigned long long)ticket); }
+    for (size_t i = 0; i < R->qpsk_ids.size(); i++) {
+        if (R->qpsk_ids[i] != id) { continue; }
+        int cnt[kGroupMax] = {};
+        const int j = std::min(R->qpsk_push[i], kGroupMax - 1);
+        memcpy(cnt, R->base + R->qpsk_cnt_off[i], (size_t)(j + 1) * sizeof(int));
+        size_t lo = 0;
+        for (int q = 0; q < j; q++) { lo += (size_t)std::max(cnt[q], 0); }
+        if (soft_iq) { *soft_iq = (R->qpsk_soft_off[i] == SIZE_MAX) ? nullptr : reinterpret_cast<const float*>(R->base + R->qpsk_soft_off[i]) + 2 * lo; }  // (NULL: the float pairs were not asked for)
+        if (packed) { *packed = reinterpret_cast<const int8_t*>(R->base + R->qpsk_packed_off[i]) + 2 * lo; }
+        if (count) { *count = cnt[j]; }
+        return SDRPP_OK;
+    }
+    return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of a QPSK demodulator of VFO %d", (unsigned long long)ticket, id);
 }
 int sdrpp_result_meters(sdrpp_ctx* c, uint64_t ticket, const float** data, int* n_lines, int* n_meters) {
     if (!c) { return SDRPP_ERR_INVALID; }

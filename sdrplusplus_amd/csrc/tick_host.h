@@ -289,6 +289,12 @@ size_t tick_results_need(sdrpp_ctx* c) {
             if (y.attached && y.st.size() == 3) { need += (size_t)kGroupMax * 4 + (((y.st[0].cap + 16) * 4 + 15) & ~(size_t)15) + ((y.st[0].cap + 16 + 15) & ~(size_t)15); }
         }
     }
+    if (c->res_flags & 256) {  // QPSK demodulators: per-push counts, then the block's capacity of int8 pairs (2 bytes) and, where asked for, of float pairs (8 bytes)
+        for (auto& kv : c->vfos) {
+            const Vfo::Qpsk& y = kv.second->qpsk;
+            if (y.attached && y.st.size() == 4) { need += (size_t)kGroupMax * 4 + (c->res_qpsk_soft ? (((y.st[1].cap + 16) * 8 + 15) & ~(size_t)15) : 0) + (((y.st[1].cap + 16) * 2 + 15) & ~(size_t)15); }
+        }
+    }
     if ((c->res_flags & 8) && c->pre.on) {
         size_t cap = c->pre.out.base ? c->pre.out.cap : 0;
         for (auto& st : c->pre.st) { cap = std::max(cap, st.cap); }
@@ -553,6 +559,27 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
             copies.push_back(ResCopy{ y.st[0].data, soft_off, (size_t)y.cap * 4, y.lvl + 1 });
             copies.push_back(ResCopy{ y.st[1].data, bits_off, ((size_t)y.cap + 3) & ~(size_t)3, y.lvl + 1 });
             off = bits_off + (((size_t)y.cap + 15) & ~(size_t)15);
+        }
+    }
+    if (c->res_flags & 256) {
+        // every QPSK demodulator that ran in this block: the job's per-push counts, then [the float pairs] and the int8 pairs its outputs have room for in this block
+        for (auto& kv : c->vfos) {
+            const Vfo& v = *kv.second;
+            const Vfo::Qpsk& y = v.qpsk;
+            if (!y.attached || !y.ran) { continue; }
+            if (y.npush != k) { return fail(c, SDRPP_ERR_INVALID, "internal: VFO %d's QPSK demodulator planned %d pushes, the block has %d", v.id, y.npush, k); }
+            const size_t cnt_off = off, soft_off = cnt_off + (((size_t)k * 4 + 15) & ~(size_t)15), packed_off = soft_off + (c->res_qpsk_soft ? (((size_t)y.cap * 8 + 15) & ~(size_t)15) : 0);
+            for (int j = 0; j < k; j++) {
+                R[j]->qpsk_ids.push_back(v.id);
+                R[j]->qpsk_push.push_back(j);
+                R[j]->qpsk_cnt_off.push_back(cnt_off);
+                R[j]->qpsk_soft_off.push_back(c->res_qpsk_soft ? soft_off : SIZE_MAX);
+                R[j]->qpsk_packed_off.push_back(packed_off);
+            }
+            copies.push_back(ResCopy{ y.st[3].data, cnt_off, (size_t)k * 4, y.lvl + 1 });
+            if (c->res_qpsk_soft) { copies.push_back(ResCopy{ y.st[1].data, soft_off, (size_t)y.cap * 8, y.lvl + 1 }); }
+            copies.push_back(ResCopy{ y.st[2].data, packed_off, ((size_t)y.cap * 2 + 3) & ~(size_t)3, y.lvl + 1 });
+            off = packed_off + (((size_t)y.cap * 2 + 15) & ~(size_t)15);
         }
     }
     if (off > c->res_cap) { return fail(c, SDRPP_ERR_INVALID, "internal: results of %zu bytes exceed what a launch may deliver (%zu)", off, c->res_cap); }

@@ -370,6 +370,7 @@ int stereo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, bool* cleared);  // (the ster
 int sym_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n);  // (the symbol branch: likewise)
 int rdsd_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, size_t old_cap);  // (the RDS demodulator: likewise)
 size_t rdsd_in_cap(const Vfo& v, int source);
+int qpsk_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n);  // (the QPSK demodulator: likewise)
 int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
     Stream& of = chan_feed(o);
     Stream& nf = chan_feed(n);
@@ -436,6 +437,9 @@ int vfo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, int keep) {
     }
     if ((keep & 2) && o.d.demod == n.d.demod) {
         if ((rc = rdsd_hand_over(c, o, n, rdsd_cap))) { return rc; }
+    }
+    if ((keep & 2) && o.d.demod == n.d.demod && n.d.demod == SDRPP_DEMOD_RAW) {
+        if ((rc = qpsk_hand_over(c, o, n))) { return rc; }
     }
     if (keep & 4) {  // ... and FMIF with them: its bin count, whether it is plugged in, and its delay line
         if ((rc = fmif_line_save(c, o))) { return rc; }
@@ -1212,6 +1216,220 @@ int rdsd_count(sdrpp_ctx* c, Vfo& v) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int cnt[kGroupMax] = {};
     HIPCHK(c, hipMemcpy(cnt, y.st[2].data, (size_t)std::min(y.npush, kGroupMax) * sizeof(int), hipMemcpyDeviceToHost));
+    int total = 0;
+    for (int j = 0; j < std::min(y.npush, kGroupMax); j++) { total += cnt[j]; }
+    return std::min(total, y.cap);
+}
+
+// ---- Meteor QPSK demodulator on a RAW VFO -----------------------------------------------------------------------------------------------------
+void qpsk_detach(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Qpsk& y = v.qpsk;
+    if (y.bank_key) {
+        auto it = c->qpsk_banks.find(y.bank_key);
+        if (it != c->qpsk_banks.end() && --it->second.refs <= 0) {
+            dev_free(it->second.d_taps);
+            dev_free(it->second.d_bank);
+            c->qpsk_banks.erase(it);
+        }
+    }
+    qpsk_free_own(y);
+    y = Vfo::Qpsk{};
+}
+// The context's shared real tap table and interpolator bank (keyed by rds_bank_hash over both, one reference per demodulator): uploaded with their first user
+int qpsk_bank_acquire(sdrpp_ctx* c, Vfo::Qpsk& y, const float* taps, const float* bank) {
+    std::vector<float> all(taps, taps + (size_t)y.K);
+    all.insert(all.end(), bank, bank + (size_t)y.phases * (size_t)y.T);
+    const unsigned long long key = rds_bank_hash(y.K, y.phases * 32 + y.T, all.data(), (int)all.size());
+    auto it = c->qpsk_banks.find(key);
+    if (it != c->qpsk_banks.end() && (it->second.K != y.K || it->second.phases != y.phases || it->second.T != y.T || memcmp(it->second.taps.data(), taps, (size_t)y.K * sizeof(float)) != 0 ||
+                                     memcmp(it->second.bank.data(), bank, (size_t)y.phases * (size_t)y.T * sizeof(float)) != 0)) {
+        return fail(c, SDRPP_ERR_UNSUPPORTED, "qpsk demodulator tables: two different descriptions under one key");  // (a 64-bit collision: never seen)
+    }
+    if (it == c->qpsk_banks.end()) {
+        sdrpp_ctx::QpskBank B;
+        B.taps.assign(taps, taps + (size_t)y.K);
+        B.bank.assign(bank, bank + (size_t)y.phases * (size_t)y.T);
+        if (int rc = upload(c, &B.d_taps, B.taps.data(), B.taps.size())) { return rc; }
+        if (int rc = upload(c, &B.d_bank, B.bank.data(), B.bank.size())) {
+            dev_free(B.d_taps);
+            return rc;
+        }
+        B.K = y.K;
+        B.phases = y.phases;
+        B.T = y.T;
+        it = c->qpsk_banks.emplace(key, std::move(B)).first;
+    }
+    it->second.refs++;
+    y.bank_key = key;
+    y.d_taps = it->second.d_taps;
+    y.d_bank = it->second.d_bank;
+    return SDRPP_OK;
+}
+// Meteor::reset() (meteor_demod.h:139-148): the filter line (fir.h:58), the gain, the loop (pll.h:55-62), MM's offset / phase / freq and six delay words
+// (mm.h:87-98).  lastI and MM's T - 1 delay samples stay, as the reference leaves them; `fresh`: Meteor::init — those cleared as well (a new object)
+int qpsk_clear(sdrpp_ctx* c, Vfo& v, bool fresh) {
+    Vfo::Qpsk& y = v.qpsk;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float st[SDRPP_QPSK_STATE_HEAD] = {};
+    if (!fresh) { HIPCHK(c, hipMemcpy(st, y.d_state, sizeof(st), hipMemcpyDeviceToHost)); }
+    const float last_i = fresh ? 0.0f : st[3];
+    memset(st, 0, sizeof(st));
+    st[0] = y.agc[3];
+    st[1] = y.loop[2]; st[2] = y.loop[3];
+    st[3] = last_i;
+    st[4] = 0.0f; st[5] = y.omega;
+    HIPCHK(c, hipMemcpy(y.d_state, st, sizeof(st), hipMemcpyHostToDevice));
+    if (fresh && y.T > 1) { HIPCHK(c, hipMemset(y.d_state + SDRPP_QPSK_STATE_HEAD, 0, 2 * (size_t)(y.T - 1) * sizeof(float))); }
+    HIPCHK(c, hipMemset(y.d_lines, 0, 4 * (size_t)y.K * sizeof(float)));
+    y.ran = false;
+    for (auto& q : y.st) { q.n = 0; }
+    return SDRPP_OK;
+}
+bool qpsk_same_desc(const Vfo::Qpsk& y, const sdrpp_qpsk_desc* d, const sdrpp_ctx* c) {
+    const float f[6] = { d->loop.alpha, d->loop.beta, d->loop.init_phase, d->loop.init_freq, d->loop.min_freq, d->loop.max_freq };
+    const float agc[4] = { d->agc_set_point, d->agc_max_gain, d->agc_rate, d->agc_init_gain };
+    if (memcmp(f, y.loop, sizeof(f)) != 0 || memcmp(agc, y.agc, sizeof(agc)) != 0 || y.K != d->n_taps || y.omega != d->omega || y.mu_gain != d->mu_gain || y.omega_gain != d->omega_gain ||
+        y.min_omega != d->min_omega || y.max_omega != d->max_omega || y.phases != d->interp_phases || y.T != d->interp_ntaps || y.soft_scale != d->soft_scale) {
+        return false;
+    }
+    auto it = c->qpsk_banks.find(y.bank_key);
+    return it != c->qpsk_banks.end() && memcmp(it->second.taps.data(), d->taps, it->second.taps.size() * sizeof(float)) == 0 &&
+           memcmp(it->second.bank.data(), d->interp_bank, it->second.bank.size() * sizeof(float)) == 0;
+}
+// sdrpp_vfo_set_qpsk on a VFO the caller has looked up (the stream is idle); d == nullptr: the demodulator goes.  `broken` and `oqpsk` are modes, not a part of
+// the description's identity: the same description with other modes sets them and keeps the state (sdrpp_vfo_qpsk_set_mode does only that).
+int qpsk_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_qpsk_desc* d, bool enabled) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!d) {
+        qpsk_detach(c, v);
+        return SDRPP_OK;
+    }
+    if (v.d.demod != SDRPP_DEMOD_RAW) { return fail(c, SDRPP_ERR_UNSUPPORTED, "qpsk demodulator: needs a RAW VFO"); }
+    if (d->n_taps < 1 || d->n_taps > SDRPP_QPSK_MAX_TAPS || !d->taps) { return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: shaping filter of %d real taps (1 .. %d, with taps)", d->n_taps, SDRPP_QPSK_MAX_TAPS); }
+    if (d->interp_ntaps < 1 || d->interp_ntaps > SDRPP_SYM_MAX_INTERP_TAPS || !d->interp_bank) {
+        return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: interpolator of %d taps per phase (1 .. %d, with a bank)", d->interp_ntaps, SDRPP_SYM_MAX_INTERP_TAPS);
+    }
+    if (d->interp_phases < 1 || d->interp_phases > SDRPP_SYM_MAX_PHASES) { return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: interpolator of %d phases (1 .. %d)", d->interp_phases, SDRPP_SYM_MAX_PHASES); }
+    if (!std::isfinite(d->agc_set_point) || !std::isfinite(d->agc_max_gain) || !std::isfinite(d->agc_rate) || !std::isfinite(d->agc_init_gain)) {
+        return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: AGC set point %g, max gain %g, rate %g, initial gain %g: all finite", d->agc_set_point, d->agc_max_gain, d->agc_rate, d->agc_init_gain);
+    }
+    const sdrpp_rdsd_loop& l = d->loop;
+    if (!std::isfinite(l.alpha) || !std::isfinite(l.beta) || !std::isfinite(l.init_phase) || !std::isfinite(l.init_freq) || !std::isfinite(l.min_freq) || !std::isfinite(l.max_freq)) {
+        return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: the loop has a value that is not finite");
+    }
+    if (!(l.min_freq < l.max_freq)) { return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: loop frequency limits %g .. %g: min < max", l.min_freq, l.max_freq); }
+    // the bounded-loop rule: a step of at most 2 pi from a phase inside +-pi is wrapped by ONE subtraction or addition (vfo_rdsd_kernels.h)
+    if (!((double)std::max(fabsf(l.min_freq), fabsf(l.max_freq)) + (double)fabsf(l.alpha) <= 2.0 * 3.14159265358979323846) || !(fabsf(l.init_phase) <= 3.1415926535f)) {
+        return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: loop with frequency limits %g .. %g, alpha %g, initial phase %g: max(|min|, |max|) + |alpha| <= 2 pi and |phase| <= pi, else the phase wrap is no single step",
+                    l.min_freq, l.max_freq, l.alpha, l.init_phase);
+    }
+    if (!std::isfinite(d->omega) || !std::isfinite(d->mu_gain) || !std::isfinite(d->omega_gain) || !std::isfinite(d->min_omega) || !std::isfinite(d->max_omega)) {
+        return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: clock recovery has a value that is not finite");
+    }
+    if (!(d->min_omega < d->max_omega) || !(d->min_omega - fabsf(d->mu_gain) >= 1.0f) || !(d->max_omega + fabsf(d->mu_gain) <= (float)SDRPP_SYM_MAX_STEP)) {
+        return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: omega limits %g .. %g, mu gain %g: min < max, min - |mu gain| >= 1, max + |mu gain| <= %d", d->min_omega, d->max_omega, d->mu_gain, SDRPP_SYM_MAX_STEP);
+    }
+    if (!std::isfinite(d->soft_scale)) { return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: soft scale %g: finite", d->soft_scale); }
+    for (int k = 0; k < d->n_taps; k++) {
+        if (!std::isfinite(d->taps[k])) { return fail(c, SDRPP_ERR_INVALID, "qpsk demodulator: tap %d is not finite", k); }
+    }
+    const size_t cap = v.st[(size_t)v.i_chan].cap;  // the stream a demodulator would read
+    if (cap + 16 >= ((size_t)1 << 24) - (size_t)(SDRPP_SYM_MAX_STEP + 1)) { return fail(c, SDRPP_ERR_UNSUPPORTED, "qpsk demodulator on a stream of up to %zu samples per push (offsets are exact below 2^24)", cap); }
+    Vfo::Qpsk& y = v.qpsk;
+    if (y.attached && y.st.size() == 4 && y.st[0].cap == cap && qpsk_same_desc(y, d, c)) {  // the same demodulator: only the switch and the modes — everything it holds stays as it is
+        if (y.on && !enabled) {
+            for (auto& q : y.st) { q.n = 0; }
+        }
+        y.on = enabled;
+        y.ran = y.ran && enabled;
+        y.broken = d->broken != 0;
+        y.oqpsk = d->oqpsk != 0;
+        return SDRPP_OK;
+    }
+    qpsk_detach(c, v);
+    // every early return below gives back what was built so far
+    struct Undo {
+        sdrpp_ctx* c; Vfo& v; bool armed = true;
+        ~Undo() { if (armed) { qpsk_detach(c, v); } }
+    } undo{ c, v };
+    int rc;
+    const float agc[4] = { d->agc_set_point, d->agc_max_gain, d->agc_rate, d->agc_init_gain };
+    memcpy(y.agc, agc, sizeof(agc));
+    const float f[6] = { l.alpha, l.beta, l.init_phase, l.init_freq, l.min_freq, l.max_freq };
+    memcpy(y.loop, f, sizeof(f));
+    y.broken = d->broken != 0;
+    y.oqpsk = d->oqpsk != 0;
+    y.K = d->n_taps;
+    y.omega = d->omega;
+    y.mu_gain = d->mu_gain;
+    y.omega_gain = d->omega_gain;
+    y.min_omega = d->min_omega;
+    y.max_omega = d->max_omega;
+    y.soft_scale = d->soft_scale;
+    y.phases = d->interp_phases;
+    y.T = d->interp_ntaps;
+    y.min_step = std::max(1, (int)floorf(d->min_omega - fabsf(d->mu_gain)));
+    if ((rc = qpsk_bank_acquire(c, y, d->taps, d->interp_bank))) { return rc; }
+    if ((rc = dev_alloc(c, &y.d_state, (size_t)SDRPP_QPSK_STATE_HEAD + 2 * (size_t)(y.T - 1) + 2))) { return rc; }
+    if ((rc = dev_alloc(c, &y.d_lines, 4 * (size_t)y.K))) { return rc; }
+    // per-block buffers: the filter's output, then the symbols a block of `cap` samples can start (float pairs, int8 pairs four to a float) and the per-push counts
+    const size_t scap = (size_t)y.cap_of((int)cap);
+    const int widths[4] = { 2, 2, 1, 1 };
+    const size_t caps[4] = { cap, scap, (scap + 1) / 2, (size_t)kGroupMax };
+    y.st.resize(4);
+    for (int i = 0; i < 4; i++) {
+        if (stream_alloc(c, y.st[(size_t)i], widths[i], 0, caps[i])) { return SDRPP_ERR_NOMEM; }
+    }
+    y.attached = true;  // (qpsk_clear reads nothing of it; set before so that Undo sees a whole object)
+    if ((rc = qpsk_clear(c, v, true))) { return rc; }
+    y.cur = 0;
+    y.on = enabled;
+    undo.armed = false;
+    return SDRPP_OK;
+}
+// the description a demodulator was attached with (the arrays are the context's copies: valid while the demodulator holds its reference)
+sdrpp_qpsk_desc qpsk_desc_of(const sdrpp_ctx* c, const Vfo::Qpsk& y) {
+    const sdrpp_ctx::QpskBank& B = c->qpsk_banks.at(y.bank_key);
+    sdrpp_qpsk_desc d{};
+    d.n_taps = y.K;
+    d.taps = B.taps.data();
+    d.agc_set_point = y.agc[0]; d.agc_max_gain = y.agc[1]; d.agc_rate = y.agc[2]; d.agc_init_gain = y.agc[3];
+    d.loop = sdrpp_rdsd_loop{ y.loop[0], y.loop[1], y.loop[2], y.loop[3], y.loop[4], y.loop[5] };
+    d.broken = y.broken; d.oqpsk = y.oqpsk;
+    d.omega = y.omega; d.mu_gain = y.mu_gain; d.omega_gain = y.omega_gain; d.min_omega = y.min_omega; d.max_omega = y.max_omega;
+    d.interp_phases = y.phases; d.interp_ntaps = y.T;
+    d.interp_bank = B.bank.data();
+    d.soft_scale = y.soft_scale;
+    return d;
+}
+// sdrpp_vfo_replace with keep & 2 between two RAW VFOs: the demodulator moves with everything it holds; a new handle whose stream has another capacity gets
+// the description attached afresh (its buffers are sized for it), cleared.
+int qpsk_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n) {
+    Vfo::Qpsk& y = o.qpsk;
+    if (!y.attached) { return SDRPP_OK; }
+    if (y.st[0].cap != n.st[(size_t)n.i_chan].cap) {
+        const sdrpp_ctx::QpskBank B = c->qpsk_banks.at(y.bank_key);  // (a copy: attaching may let go of the table's last reference)
+        sdrpp_qpsk_desc d = qpsk_desc_of(c, y);
+        d.taps = B.taps.data();
+        d.interp_bank = B.bank.data();
+        return qpsk_apply(c, n, &d, y.on);
+    }
+    qpsk_detach(c, n);
+    n.qpsk = std::move(o.qpsk);
+    o.qpsk = Vfo::Qpsk{};
+    n.qpsk.ran = false;
+    for (auto& q : n.qpsk.st) { q.n = 0; }
+    return SDRPP_OK;
+}
+// The symbols of the most recent block: the job's own counts, read from the device (the host waits for the stream)
+const char* const kNoQpsk = "VFO %d has no QPSK demodulator";
+int qpsk_count(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Qpsk& y = v.qpsk;
+    if (!y.attached) { return fail(c, SDRPP_ERR_INVALID, kNoQpsk, v.id); }
+    if (!y.on || !y.ran || y.npush <= 0) { return 0; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int cnt[kGroupMax] = {};
+    HIPCHK(c, hipMemcpy(cnt, y.st[3].data, (size_t)std::min(y.npush, kGroupMax) * sizeof(int), hipMemcpyDeviceToHost));
     int total = 0;
     for (int j = 0; j < std::min(y.npush, kGroupMax); j++) { total += cnt[j]; }
     return std::min(total, y.cap);

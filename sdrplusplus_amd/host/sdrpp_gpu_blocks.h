@@ -114,6 +114,8 @@ public:
     dsp::stream<dsp::stereo_t> audio;  // demodulator output (radio's Demodulator::getOutput()) when attached
     dsp::stream<uint8_t> rdsBits;        // attachRDSDemod: RDSDemod::out — one differentially decoded bit per symbol, one swap per block that started a symbol
     dsp::stream<float> rdsSoft;          // ... and RDSDemod::soft (MM's output), swapped only while soft output is enabled
+    dsp::stream<dsp::complex_t> qpskOut;  // attachQPSK: dsp::demod::Meteor::out — one complex soft symbol per symbol, one swap per block that started a symbol
+    dsp::stream<int8_t> qpskPacked;       // ... and what the module's sink makes of them: two int8 per symbol (a swap of 2 x the symbols)
     dsp::stream<uint8_t> symOut;         // attachSymbols: POCSAGDSP::out — one bit per symbol
     dsp::stream<float> symSoft;          // ... and POCSAGDSP::soft
     dsp::stream<dsp::complex_t> rdsOut;  // attachRDS: BroadcastFM::rdsOut — the 5 kS/s baseband RDSDemod consumes, one swap per block that produced samples
@@ -165,6 +167,17 @@ public:
     // delivers `out`, one swap each per block that produced any.  attachSymbols starts from a fresh POCSAGDSP; setSymbolsOn(false) freezes loop and delay lines,
     // true continues from them; re-plans that keep the demodulator keep the branch.  sdrpp_gpu::POCSAGDSP (sdrpp_gpu_pager.h) is the reference-shaped face of it.
     void attachSymbols(double baudrate);
+    // The meteor_demodulator module's DSP (dsp::demod::Meteor: RRC FIR -> AGC -> QPSK Costas loop -> OQPSK delay -> complex MM; sdrpp_vfo_set_qpsk) on the device, for a
+    // channel WITHOUT a demodulator (Demod::RAW): the symbols that start inside a block are delivered on `qpskOut` and `qpskPacked` from the worker that delivers
+    // `out`, block by block or out of the pipelined result slots (flag 256); a block without a symbol is not handed on.  WHILE IT IS ATTACHED `out` IS NO LONGER
+    // WRITTEN: nobody reads it any more, and a dsp::stream without a reader blocks its writer (pipelined blocks still in flight at the attach are not written to it
+    // either).  attachQPSK starts from a fresh Meteor; setQPSKMode is setBrokenModulation / setOQPSK (the state is kept); resetQPSK is Meteor::reset().
+    // sdrpp_gpu::Meteor (sdrpp_gpu_meteor.h) is the reference-shaped face of it.
+    struct QPSKParams { double symbolrate, samplerate; int rrcTapCount; double rrcBeta, agcRate, costasBandwidth; bool brokenModulation, oqpsk; double omegaGain, muGain; };
+    void attachQPSK(const QPSKParams& p);
+    void detachQPSK();
+    void setQPSKMode(bool brokenModulation, bool oqpsk);
+    void resetQPSK();
     void detachSymbols();
     void setSymbolsOn(bool enabled);
     // The WFM demodulator's stereo decoder (dsp/demod/broadcast_fm.h:147-191, `_stereo`; sdrpp_vfo_set_stereo) on the device: pilot filter, PLL, L-R matrix and the
@@ -222,6 +235,8 @@ public:
         return rdsdSoftFrom.empty() ? rdsdSoft : rdsdSoftFrom.front().second;
     }
     bool symAttached = false, symOn = false;
+    bool qpskAttached = false;
+    QPSKParams qpskP{};
     double symBaud = 0.0;
     bool stereoAttached = false, stereoOn = false;
     double recVolume = 1.0;
@@ -417,6 +432,8 @@ public:
         registerOutput(&v->rdsOut);
         registerOutput(&v->rdsBits);
         registerOutput(&v->rdsSoft);
+        registerOutput(&v->qpskOut);
+        registerOutput(&v->qpskPacked);
         registerOutput(&v->symOut);
         registerOutput(&v->symSoft);
         tempStart();
@@ -437,6 +454,8 @@ public:
         unregisterOutput(&it->second->rdsOut);
         unregisterOutput(&it->second->rdsBits);
         unregisterOutput(&it->second->rdsSoft);
+        unregisterOutput(&it->second->qpskOut);
+        unregisterOutput(&it->second->qpskPacked);
         unregisterOutput(&it->second->symOut);
         unregisterOutput(&it->second->symSoft);
         vfoOrder.erase(std::remove(vfoOrder.begin(), vfoOrder.end(), it->second), vfoOrder.end());
@@ -961,15 +980,18 @@ private:
         for (auto& kv : vfos) { rdsd = rdsd || (kv.second->rdsdAttached && kv.second->demod == Demod::WFM); }
         bool sym = false;
         for (auto& kv : vfos) { sym = sym || (kv.second->symAttached && kv.second->demod == Demod::RAW); }
-        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0) | (rds ? SDRPP_RESULT_RDS : 0) | (sym ? SDRPP_RESULT_SYM : 0) | (rdsd ? SDRPP_RESULT_RDS_BITS : 0);  // (a recorder or an RDS branch adds its flag and drops nobody's: `audio` is delivered as before)
+        bool qpsk = false;
+        for (auto& kv : vfos) { qpsk = qpsk || (kv.second->qpskAttached && kv.second->demod == Demod::RAW); }
+        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0) | (rds ? SDRPP_RESULT_RDS : 0) | (sym ? SDRPP_RESULT_SYM : 0) | (rdsd ? SDRPP_RESULT_RDS_BITS : 0) | (qpsk ? SDRPP_RESULT_QPSK : 0);  // (a recorder or an RDS branch adds its flag and drops nobody's: `audio` is delivered as before)
     }
     int enterPipelined() {
         if (sdrpp_sync(ctx)) { return -1; }  // (nothing is staged in bypass mode; a deferred pass left over from buffered mode runs here)
         sdrpp_set_deferred(ctx, 0);
         pipeFlags = pipelineFlags();
-        if (sdrpp_set_pipelined(ctx, 1, pipeFlags & ~(SDRPP_RESULT_RDS | SDRPP_RESULT_SYM | SDRPP_RESULT_RDS_BITS)) || ((pipeFlags & SDRPP_RESULT_RDS) && sdrpp_pipeline_set_rds_results(ctx, 1)) ||
+        if (sdrpp_set_pipelined(ctx, 1, pipeFlags & ~(SDRPP_RESULT_RDS | SDRPP_RESULT_SYM | SDRPP_RESULT_RDS_BITS | SDRPP_RESULT_QPSK)) || ((pipeFlags & SDRPP_RESULT_RDS) && sdrpp_pipeline_set_rds_results(ctx, 1)) ||
             ((pipeFlags & SDRPP_RESULT_SYM) && sdrpp_pipeline_set_sym_results(ctx, 1)) ||
-            ((pipeFlags & SDRPP_RESULT_RDS_BITS) && sdrpp_pipeline_set_rds_bits_results(ctx, 1))) {  // (flags 32, 64 and 128 have calls of their own)
+            ((pipeFlags & SDRPP_RESULT_RDS_BITS) && sdrpp_pipeline_set_rds_bits_results(ctx, 1)) ||
+            ((pipeFlags & SDRPP_RESULT_QPSK) && sdrpp_pipeline_set_qpsk_results(ctx, 1, 1))) {  // (flags 32, 64, 128 and 256 have calls of their own; qpskOut wants the float pairs)
             fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] pipelined mode refused: %s\n", sdrpp_last_error(ctx));
             sdrpp_set_deferred(ctx, 1);
             _pipelining = false;
@@ -1075,6 +1097,7 @@ private:
                     const int k = order[q].second, n = r.counts[k];
                     const float* src = r.samples + 2 * (size_t)r.offsets[k];
                     if (v->demod == Demod::RAW) {
+                        if (v->qpskAttached) { continue; }  // (behind a bound QPSK demodulator nobody reads `out`)
                         memcpy(v->out.writeBuf, src, (size_t)n * sizeof(dsp::complex_t));
                         if (!v->out.swap(n)) { failed = true; }
                     }
@@ -1143,6 +1166,24 @@ private:
                         memcpy(v->rdsSoft.writeBuf, soft, (size_t)cnt * sizeof(float));
                         if (!v->rdsSoft.swap(cnt)) { deliveryFailed = true; }
                     }
+                });
+            }
+        }
+        // the QPSK demodulators: this push's soft symbols and int8 pairs (result flag 256), straight out of the slot; a block that started no symbol is not handed on
+        if (pipeFlags & SDRPP_RESULT_QPSK) {
+            for (auto& kv : vfos) {
+                RxVFO* v = kv.second;
+                if (!v->qpskAttached) { continue; }
+                const float* soft = nullptr;
+                const int8_t* packed = nullptr;
+                int cnt = 0;
+                int rrc = sdrpp_result_qpsk(ctx, ticket, v->id, &soft, &packed, &cnt);
+                for (size_t q = v->prevIds.size(); rrc == SDRPP_ERR_NOT_FOUND && q-- > 0;) { rrc = sdrpp_result_qpsk(ctx, ticket, v->prevIds[q], &soft, &packed, &cnt); }
+                if (rrc || cnt <= 0 || !soft) { continue; }  // (pushed before the attach)
+                jobs.emplace_back([this, v, soft, packed, cnt]() {
+                    memcpy(v->qpskOut.writeBuf, soft, (size_t)cnt * sizeof(dsp::complex_t));
+                    memcpy(v->qpskPacked.writeBuf, packed, (size_t)cnt * 2);
+                    if (!v->qpskOut.swap(cnt) || !v->qpskPacked.swap(2 * cnt)) { deliveryFailed = true; }
                 });
             }
         }
@@ -1363,6 +1404,7 @@ private:
                         const float* src = gatherPin + 2 * (size_t)offs[(size_t)order[q].second];
                         if (n <= 0) { continue; }
                         if (v->demod == Demod::RAW) {
+                            if (v->qpskAttached) { continue; }  // (behind a bound QPSK demodulator nobody reads `out`)
                             memcpy(v->out.writeBuf, src, (size_t)n * sizeof(dsp::complex_t));
                             if (!v->out.swap(n)) { failed = true; }
                         }
@@ -1421,6 +1463,20 @@ private:
             if (got == 0) { continue; }
             jobs.emplace_back([v, got, &failed]() {
                 if (!v->rdsOut.swap(got)) { failed = true; }
+            });
+        }
+        // the QPSK demodulators: the pass's soft symbols and int8 pairs straight into the streams' buffers
+        for (auto& kv : vfos) {
+            RxVFO* v = kv.second;
+            if (!v->qpskAttached || v->demod != Demod::RAW || v->id < 0) { continue; }
+            const int got = sdrpp_vfo_qpsk_read(ctx, v->id, reinterpret_cast<float*>(v->qpskOut.writeBuf), v->qpskPacked.writeBuf, STREAM_BUFFER_SIZE / 2);
+            if (got < 0) {
+                fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] reading the QPSK demodulator failed: %s\n", sdrpp_last_error(ctx));
+                return -1;
+            }
+            if (got == 0) { continue; }
+            jobs.emplace_back([v, got, &failed]() {
+                if (!v->qpskOut.swap(got) || !v->qpskPacked.swap(2 * got)) { failed = true; }
             });
         }
         // the symbol branches: the pass's bits and soft values straight into the streams' buffers
@@ -1572,6 +1628,7 @@ private:
         if (v.rdsdAttached && v.rdsAttached && v.demod == Demod::WFM) { applyRDSDemod(v); }  // (likewise: moved with the branch, the same description only sets the switch)
         if (v.stereoAttached && v.demod == Demod::WFM) { applyStereo(v); }  // (likewise: the same description and switch change nothing)
         if (v.symAttached && v.demod == Demod::RAW) { applySymbols(v); }  // (likewise)
+        if (v.qpskAttached && v.demod == Demod::RAW) { applyQPSK(v); }  // (likewise: the same description only sets the switch and the modes)
         sendMeters();  // (a new handle, perhaps a new bandwidth or input rate)
     }
 
@@ -1596,6 +1653,19 @@ private:
 
     // broadcast_fm.h:52-53: xlator.init(NULL, -57000.0, samplerate); rdsResamp.init(NULL, samplerate, 5000.0)
     // pocsag/dsp.h:20-37 at the channel's rate: sdrpp_design_pager's scalars, ten shaping taps of 0.1f, MM's 128 x 8 interpolator
+    // meteor_demod.h:24-43: every member as Meteor::init leaves it (sdrpp_design_meteor)
+    void applyQPSK(RxVFO& v) {
+        sdrpp_qpsk_desc d;
+        memset(&d, 0, sizeof(d));
+        std::vector<float> taps(256), bank(128 * 8);
+        const RxVFO::QPSKParams& p = v.qpskP;
+        if (sdrpp_design_meteor(p.symbolrate, p.samplerate, p.rrcTapCount, p.rrcBeta, p.agcRate, p.costasBandwidth, p.brokenModulation ? 1 : 0, p.oqpsk ? 1 : 0, p.omegaGain, p.muGain, &d,
+                                taps.data(), (int)taps.size(), bank.data(), (int)bank.size()) < 0) {
+            throw std::runtime_error("[sdrpp_gpu::IQFrontEnd] design_meteor: rates must be positive and finite, 1 .. 256 taps");
+        }
+        int rc = sdrpp_vfo_set_qpsk(ctx, v.id, &d, 1);
+        if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_qpsk: ") + sdrpp_last_error(ctx)); }
+    }
     void applySymbols(RxVFO& v) {
         sdrpp_sym_desc s;
         memset(&s, 0, sizeof(s));
@@ -2098,6 +2168,39 @@ inline void RxVFO::resetRDSDemod() {
     if (!rdsdAttached) { return; }
     fe->tempStop();  // rds_demod.h:51-62
     if (id >= 0) { sdrpp_vfo_rds_demod_reset(fe->ctx, id); }
+    fe->tempStart();
+}
+inline void RxVFO::attachQPSK(const QPSKParams& p) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (demod != Demod::RAW) { throw std::runtime_error("[sdrpp_gpu::RxVFO] the QPSK demodulator belongs to a channel without a demodulator"); }
+    fe->tempStop();
+    if (qpskAttached && id >= 0) { sdrpp_vfo_set_qpsk(fe->ctx, id, nullptr, 0); }  // (attaching again starts cleared)
+    qpskAttached = true;
+    qpskP = p;
+    if (id >= 0) { fe->applyQPSK(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::detachQPSK() {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    fe->tempStop();
+    qpskAttached = false;
+    if (id >= 0) { sdrpp_vfo_set_qpsk(fe->ctx, id, nullptr, 0); }
+    fe->tempStart();
+}
+inline void RxVFO::setQPSKMode(bool brokenModulation, bool oqpsk) {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    qpskP.brokenModulation = brokenModulation;
+    qpskP.oqpsk = oqpsk;
+    if (!qpskAttached) { return; }
+    fe->tempStop();  // meteor_demod.h:127-137
+    if (id >= 0) { sdrpp_vfo_qpsk_set_mode(fe->ctx, id, brokenModulation ? 1 : 0, oqpsk ? 1 : 0); }
+    fe->tempStart();
+}
+inline void RxVFO::resetQPSK() {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (!qpskAttached) { return; }
+    fe->tempStop();  // meteor_demod.h:139-148
+    if (id >= 0) { sdrpp_vfo_qpsk_reset(fe->ctx, id); }
     fe->tempStart();
 }
 inline void RxVFO::attachSymbols(double baudrate) {

@@ -264,6 +264,15 @@ def rds_demod_desc(rate=5000.0, source=0):
     return d, [taps, bank]
 
 
+def meteor_desc(symbolrate=72000.0, samplerate=150000.0, rrc_taps=33, rrc_beta=capi._F32(0.6), agc_rate=capi._F32(0.1), costas_bw=capi._F32(0.005), broken=False, oqpsk=False,
+                omega_gain=1e-6, mu_gain=0.01):
+    """sdrpp_qpsk_desc for the meteor_demodulator module's dsp::demod::Meteor::init (meteor_demod.h:24-43): rootRaisedCosine(rrc_taps, rrc_beta), FastAGC(1, 10e6,
+    agc_rate), MeteorCostas(costas_bw), MM<complex_t>(samplerate / symbolrate, omega_gain, mu_gain, 0.01), int8 = value * 84.  The defaults are the module's
+    (main.cpp:66).  For a RAW VFO whose output rate is `samplerate`.  Returns (desc, keepalive)."""
+    d, taps, bank = capi.design_meteor(symbolrate, samplerate, rrc_taps, rrc_beta, agc_rate, costas_bw, broken, oqpsk, omega_gain, mu_gain)
+    return d, [taps, bank]
+
+
 def if_desc(if_rate, nb=False, nb_level=10.0, squelch=None):
     """sdrpp_if_desc for the radio module's IF chain (radio_module.h:84-96): NoiseBlanker(rate = 500 / if_rate, level; :90, :526) ->
     PowerSquelch(level in dB; None = off).  FMIF, the chain's last block, is switched by Context.vfo_set_fmnr (IFNR_BINS); the CTCSS squelch is not on the device."""
