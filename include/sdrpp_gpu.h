@@ -538,6 +538,58 @@ int sdrpp_design_mm_interp(int phases, int ntaps, float* bank);
  * ten taps of 0.1f and sdrpp_design_mm_interp(128, 8).  SDRPP_ERR_INVALID for rates that are not positive and finite. */
 int sdrpp_design_pager(double if_rate, double baudrate, sdrpp_sym_desc* desc);
 
+/* ---- Framer behind a symbol branch: 4FSK slicer -> sync search at every bit offset -> descrambled, de-interleaved frames ---------------------------------
+ * What the M17 decoder's M17Slice4FSK and M17FrameDemux (decoder_modules/m17_decoder/src/m17dsp.h:96-276) compute from the clock recovery's soft symbols,
+ * as a general block: the thresholds, the sync words, the frame length and the two tables come from the description (sdrpp_design_m17 fills M17's).
+ *     slicer, per soft symbol `val`, two bits in this order:   val < 0.0f,   fabsf(val) > high_cut          (both strict: a NaN gives 0, 0)
+ *     demux over delay[0 .. 16 + count): the 16 newest bits of the previous push, then this push's bits; for i from 0 while i < count:
+ *         searching: delay[i .. i + 16) equals sync word t (at EVERY bit offset, odd ones included; the lowest t wins): frame type t begins, the step counter
+ *                    becomes 0, the walk goes on AT THE SAME i; no match: i++
+ *         in a frame: steps 0 .. 15 only advance (the sync word's own bits pass); step 16 + k, k in 0 .. frame_bits - 1, writes delay[i] ^ scramble[k] to
+ *                    position interleave[k] of the frame and advances.  Nothing is searched inside a frame.  With step 16 + frame_bits - 1 the frame is
+ *                    complete, leaves in THIS push, and the search resumes at the next i — a sync word directly behind a frame is found at once.
+ * WHERE IT ATTACHES: only to a VFO that carries a symbol branch (sdrpp_vfo_set_symbols), else SDRPP_ERR_INVALID; it reads the branch's soft values of the same
+ * push, in every push the branch runs in.  Detaching the branch, removing the VFO, or attaching ANOTHER branch description (which replaces the branch) detaches the framer.  It never changes a bit of any other output.
+ * SDRPP_ERR_INVALID, each with its reason in sdrpp_last_error: high_cut not finite; n_sync outside 1 .. 4; frame_bits no multiple of 8 or outside 8 .. 1024;
+ * a missing table; a scramble entry that is not 0 or 1; an interleave table that is not a permutation of 0 .. frame_bits - 1.
+ * STATE, as the reference keeps it: the 16 delay bits, whether a frame is being built, its type, its step counter and the part-built frame.  Attaching starts
+ * cleared: delay 0 (the reference's array is not initialised there), searching.  While the branch or the framer is switched off the state freezes; enabled = 1
+ * with the SAME description continues from there.  Another description, a fresh attach or sdrpp_vfo_framer_reset start cleared.  desc == NULL detaches.
+ * sdrpp_vfo_reset leaves the framer alone, as it leaves the loop.  sdrpp_vfo_replace with keep & 2 moves the framer with the branch, by the branch's rule (a
+ * handle with another stream capacity gets both descriptions attached afresh, cleared).
+ * The two tables exist ONCE per context for identical tables, however many VFOs carry a framer (sdrpp_frame_table_count).
+ * OUTPUT of a push: the frames whose LAST bit was consumed in that push, so the concatenated output does not depend on how the stream is cut.  A frame RECORD
+ * is  [type][0][frame_bits / 8 bytes: the frame, position 0 in the MSB of the first byte]  with the stride rounded up to a multiple of 4 (M17: 48 bytes; the
+ * padding is 0); a push has room for (16 + 2 * symbol capacity) / (16 + frame_bits) + 1 records, which the walk cannot exceed.  Outside pipelined mode the
+ * accessors name the most recent push (count 0 while the branch or the framer is switched off) and wait for the device, like the branch's.
+ * Pipelined: sdrpp_pipeline_set_frame_results / sdrpp_result_frames.  The arrays are copied during the call. */
+typedef struct sdrpp_frame_desc {
+    float high_cut;             /* second slicer threshold; M17: (1 + 1/3) / 2 in float        */
+    int n_sync;                 /* 1 .. 4 sync words of 16 bits, MSB first; index = frame type */
+    uint16_t sync[4];
+    int frame_bits;             /* bits behind the sync word: a multiple of 8, 8 .. 1024; M17: 368 */
+    const uint8_t* scramble;    /* [frame_bits] 0 / 1                                          */
+    const uint16_t* interleave; /* [frame_bits] destination of bit k: a permutation, else SDRPP_ERR_INVALID */
+} sdrpp_frame_desc;
+int sdrpp_vfo_set_framer(sdrpp_ctx* ctx, int id, const sdrpp_frame_desc* desc, int enabled);
+int sdrpp_vfo_framer_reset(sdrpp_ctx* ctx, int id);
+/* The framer's output of the most recent push: the number of frames, their records (sdrpp_frame_record_stride bytes apart). */
+int sdrpp_vfo_frame_count(sdrpp_ctx* ctx, int id);
+int sdrpp_vfo_frame_read(sdrpp_ctx* ctx, int id, uint8_t* records, int max_frames);   /* returns the frames copied */
+int sdrpp_vfo_frame_device_buffer(sdrpp_ctx* ctx, int id, const uint8_t** records, int* n);
+int sdrpp_abi_sizeof_frame_desc(void);
+/* Bytes from one record to the next for frames of `frame_bits` bits: 2 + frame_bits / 8 rounded up to a multiple of 4; SDRPP_ERR_INVALID for a length the framer refuses. */
+int sdrpp_frame_record_stride(int frame_bits);
+/* Test and statistics hook: table pairs (scramble, interleave) the context holds in device memory (identical pairs share one). */
+int sdrpp_frame_table_count(sdrpp_ctx* ctx);
+/* M17Decoder::init (m17dsp.h) for a VFO at if_rate: GFSK::init(.., 4800, if_rate, 2400, 31, 0.5, 1e-6, 0.01, 0.01) into *sym — inv_deviation for
+ * Quadrature(2400, if_rate), omega = if_rate / 4800 with MM's gains 1e-6 (omega) and 0.01 (mu) and relative limit 0.01, 128 x 8 interpolator (the bank stays
+ * the caller's: sdrpp_design_mm_interp), shape_ntaps = 31 with sdrpp_design_root_raised_cosine(31, 0.5, 4800, if_rate) into rrc_taps[] — and M17's framing into
+ * *frame, scramble[368] and interleave[368], stated from the M17 specification: high_cut (1 + 1/3) / 2, sync words 0x55F7 (link setup), 0xFF5D (stream), 0x75FF
+ * (packet), 368 bits, the 46-byte decorrelator sequence MSB first, interleave[k] = (45 k + 92 k^2) mod 368.  The pointers of the two descriptions are set to
+ * the caller's arrays (interp_bank is left alone).  SDRPP_ERR_INVALID for a rate that is not positive and finite, a missing argument or max_taps < 31. */
+int sdrpp_design_m17(double if_rate, sdrpp_sym_desc* sym, float* rrc_taps, int max_taps, sdrpp_frame_desc* frame, uint8_t* scramble, uint16_t* interleave);
+
 /* ---- RDS demodulator: AGC -> Costas loop -> complex band-pass -> Costas loop -> MM clock recovery -> slicer -> differential decoder ---------------------
  * What the radio module's RDSDemod (decoder_modules/radio/src/rds_demod.h:64-74) computes from BroadcastFM::rdsOut, per 5 kS/s sample x[i] and per symbol:
  *     a[i]  = x[i] * gain;  gain += (set_point - |a[i]|) * rate, clamped to max_gain from above only                     (loop/fast_agc.h)
@@ -930,6 +982,14 @@ int sdrpp_result_rds_bits(sdrpp_ctx* ctx, uint64_t ticket, int id, const float**
 #define SDRPP_RESULT_QPSK 256
 int sdrpp_pipeline_set_qpsk_results(sdrpp_ctx* ctx, int on, int with_soft);
 int sdrpp_result_qpsk(sdrpp_ctx* ctx, uint64_t ticket, int id, const float** soft_iq, const int8_t** packed, int* count);
+/* Result flag 512: the framers' outputs (sdrpp_vfo_set_framer) travel in every block's result slot — per framer the per-push frame counts, then room for the
+ * block's capacity of records: about 1.2 KB/s per M17 channel.  A call of its own, with the rules of sdrpp_pipeline_set_sym_results; 512 is independent of
+ * every other flag: 64 is not needed for it.
+ * sdrpp_result_frames: *records = the *count frames VFO `id`'s framer completed inside push `ticket` (in a launch group the group's records lie in one piece
+ * and every push gets its own count and slice).  Validity as for sdrpp_result_rds; SDRPP_ERR_NOT_FOUND likewise.  Any output may be NULL. */
+#define SDRPP_RESULT_FRAMES 512
+int sdrpp_pipeline_set_frame_results(sdrpp_ctx* ctx, int on);
+int sdrpp_result_frames(sdrpp_ctx* ctx, uint64_t ticket, int id, const uint8_t** records, int* count);
 /* Signal meters of push `ticket` (sdrpp_wf_set_meters): *data = [*n_lines][*n_meters][2] floats in the block's result slot, for the lines this push's
  * own samples completed — the rows `zoomed` / `raw` give it — oldest first.  No result flag: while a table is set, EVERY pipelined block with the
  * FFT on carries its meters (n_lines * n_meters * 8 bytes), result_flags = 0 included — sdrpp_result_wait / _release then work for such blocks.

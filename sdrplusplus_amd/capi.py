@@ -149,6 +149,19 @@ class RdsdDesc(C.Structure):
     ]
 
 
+class FrameDesc(C.Structure):
+    """struct sdrpp_frame_desc (include/sdrpp_gpu.h): the framer behind a symbol branch — 4FSK slicer, sync search, descrambled and de-interleaved frames."""
+
+    _fields_ = [
+        ("high_cut", C.c_float),
+        ("n_sync", C.c_int),
+        ("sync", C.c_uint16 * 4),
+        ("frame_bits", C.c_int),
+        ("scramble", C.POINTER(C.c_uint8)),
+        ("interleave", C.POINTER(C.c_uint16)),
+    ]
+
+
 class QpskDesc(C.Structure):
     """struct sdrpp_qpsk_desc (include/sdrpp_gpu.h): the Meteor QPSK demodulator — RRC FIR, AGC, QPSK Costas loop, OQPSK delay, complex MM, int8 pairs."""
 
@@ -270,6 +283,7 @@ class Result(C.Structure):
 ABI_VERSION = 2    # SDRPP_ABI_VERSION (include/sdrpp_gpu.h)
 RESULT_SLOTS = 24  # SDRPP_RESULT_SLOTS: launches (one block each, or a group of up to GROUP_MAX: sdrpp_set_pipeline_group) whose pipelined results can exist at a time
 GROUP_MAX = 32     # SDRPP_GROUP_MAX
+RESULT_FRAMES = 512  # SDRPP_RESULT_FRAMES: the framers' records and per-push frame counts in every block's result slot (Context.result_frames)
 RESULT_QPSK = 256  # SDRPP_RESULT_QPSK: the QPSK demodulators' int8 pairs (and, asked for, float pairs) and per-push counts in every block's result slot (Context.result_qpsk)
 RESULT_RDS_BITS = 128  # SDRPP_RESULT_RDS_BITS: the RDS demodulators' soft values, bits and per-push counts in every block's result slot (Context.result_rds_bits)
 RESULT_SYM = 64    # SDRPP_RESULT_SYM: the symbol branches' soft values, bits and per-push counts in every block's result slot (Context.set_pipelined, Context.result_sym)
@@ -397,6 +411,20 @@ def load():
     L.sdrpp_design_root_raised_cosine.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, c_float_p, C.c_int]
     L.sdrpp_design_meteor.argtypes = [C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(QpskDesc), c_float_p, C.c_int,
                                       c_float_p, C.c_int]
+    L.sdrpp_abi_sizeof_frame_desc.argtypes = []
+    if L.sdrpp_abi_sizeof_frame_desc() != C.sizeof(FrameDesc):
+        raise ImportError("sdrpp_frame_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_frame_desc(), C.sizeof(FrameDesc)))
+    c_u16_p = C.POINTER(C.c_uint16)
+    L.sdrpp_vfo_set_framer.argtypes = [vp, C.c_int, C.POINTER(FrameDesc), C.c_int]
+    L.sdrpp_vfo_framer_reset.argtypes = [vp, C.c_int]
+    L.sdrpp_vfo_frame_count.argtypes = [vp, C.c_int]
+    L.sdrpp_vfo_frame_read.argtypes = [vp, C.c_int, c_u8_p, C.c_int]
+    L.sdrpp_vfo_frame_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), c_int_p]
+    L.sdrpp_frame_record_stride.argtypes = [C.c_int]
+    L.sdrpp_frame_table_count.argtypes = [vp]
+    L.sdrpp_pipeline_set_frame_results.argtypes = [vp, C.c_int]
+    L.sdrpp_result_frames.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(c_u8_p), c_int_p]
+    L.sdrpp_design_m17.argtypes = [C.c_double, C.POINTER(SymDesc), c_float_p, C.c_int, C.POINTER(FrameDesc), c_u8_p, c_u16_p]
     L.sdrpp_abi_sizeof_stereo_desc.argtypes = []
     if L.sdrpp_abi_sizeof_stereo_desc() != C.sizeof(StereoDesc):
         raise ImportError("sdrpp_stereo_desc layout mismatch: library %d bytes, binding %d" % (L.sdrpp_abi_sizeof_stereo_desc(), C.sizeof(StereoDesc)))
@@ -514,6 +542,8 @@ EXPORTED_SYMBOLS = [
     "sdrpp_vfo_set_rds_demod", "sdrpp_vfo_rds_demod_reset", "sdrpp_vfo_rds_demod_count", "sdrpp_vfo_rds_demod_read", "sdrpp_vfo_rds_demod_device_buffers",
     "sdrpp_abi_sizeof_rdsd_desc", "sdrpp_rdsd_bank_count", "sdrpp_design_rds_demod", "sdrpp_pipeline_set_rds_bits_results", "sdrpp_result_rds_bits",
     "sdrpp_vfo_set_qpsk", "sdrpp_vfo_qpsk_set_mode", "sdrpp_vfo_qpsk_reset", "sdrpp_vfo_qpsk_count", "sdrpp_vfo_qpsk_read", "sdrpp_vfo_qpsk_device_buffers",
+    "sdrpp_vfo_set_framer", "sdrpp_vfo_framer_reset", "sdrpp_vfo_frame_count", "sdrpp_vfo_frame_read", "sdrpp_vfo_frame_device_buffer", "sdrpp_abi_sizeof_frame_desc",
+    "sdrpp_frame_record_stride", "sdrpp_frame_table_count", "sdrpp_pipeline_set_frame_results", "sdrpp_result_frames", "sdrpp_design_m17",
     "sdrpp_abi_sizeof_qpsk_desc", "sdrpp_qpsk_bank_count", "sdrpp_design_root_raised_cosine", "sdrpp_design_meteor", "sdrpp_pipeline_set_qpsk_results", "sdrpp_result_qpsk",
     "sdrpp_vfo_set_af", "sdrpp_vfo_af_count", "sdrpp_vfo_af_read", "sdrpp_vfo_af_device_buffer", "sdrpp_abi_sizeof_af_desc",
     "sdrpp_vfo_set_if", "sdrpp_vfo_set_fmnr", "sdrpp_vfo_ifc_count", "sdrpp_vfo_ifc_read", "sdrpp_vfo_ifc_device_buffer", "sdrpp_abi_sizeof_if_desc",
@@ -612,6 +642,25 @@ def design_root_raised_cosine(count, beta, symbolrate, samplerate):
 
 
 _F32 = lambda v: float(np.float32(v))  # (the module writes these arguments as float literals: 0.6f, 0.1f, 0.005f)
+
+
+def design_m17(if_rate):
+    """sdrpp_design_m17 -> (SymDesc, FrameDesc, rrc_taps float32 [31], scramble uint8 [368], interleave uint16 [368]); the descriptions point into the arrays
+    (the interpolator bank is still to be set)"""
+    sym, frame = SymDesc(), FrameDesc()
+    taps, scr, il = np.empty(31, np.float32), np.empty(368, np.uint8), np.empty(368, np.uint16)
+    rc = load().sdrpp_design_m17(float(if_rate), C.byref(sym), taps.ctypes.data_as(c_float_p), 31, C.byref(frame), scr.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                 il.ctypes.data_as(C.POINTER(C.c_uint16)))
+    if rc < 0:
+        raise SdrppError(rc, "sdrpp_design_m17")
+    return sym, frame, taps, scr, il
+
+
+def frame_record_stride(frame_bits):
+    n = load().sdrpp_frame_record_stride(int(frame_bits))
+    if n < 0:
+        raise SdrppError(n, "sdrpp_frame_record_stride")
+    return n
 
 
 def design_meteor(symbolrate=72000.0, samplerate=150000.0, rrc_taps=33, rrc_beta=_F32(0.6), agc_rate=_F32(0.1), costas_bw=_F32(0.005), broken=False, oqpsk=False, omega_gain=1e-6,
@@ -1071,6 +1120,40 @@ class Context:
         """Tap table / interpolator bank pairs of RDS demodulators this context holds in device memory (identical descriptions share one)."""
         return self._chk(self.L.sdrpp_rdsd_bank_count(self.h))
 
+    def vfo_set_framer(self, vid, desc, enabled=True, keepalive=None):
+        """Attach the framer behind a VFO's symbol branch (sdrpp_vfo_set_framer; radio.m17_desc), switch it (the same description: enabled = False freezes its
+        state, True continues) or, with desc None, detach it.  `keepalive` is only there so that a caller can pass what radio.m17_desc returns: the library copies
+        every array during the call, nothing is kept."""
+        self._chk(self.L.sdrpp_vfo_set_framer(self.h, vid, C.byref(desc) if desc is not None else None, int(bool(enabled))))
+
+    def vfo_framer_reset(self, vid):
+        self._chk(self.L.sdrpp_vfo_framer_reset(self.h, vid))
+
+    def vfo_frame_count(self, vid):
+        return self._chk(self.L.sdrpp_vfo_frame_count(self.h, vid))
+
+    def vfo_frame_read(self, vid, frame_bits=368):
+        """The framer's output of the last push -> records uint8 [n, stride]: [type][0][frame_bits / 8 bytes, position 0 in the MSB of the first][padding].  (Two
+        waits for the device: a convenience path — many channels are read out of the pipelined results, result_frames.)"""
+        stride = frame_record_stride(frame_bits)
+        n = self.vfo_frame_count(vid)
+        recs = np.zeros((max(n, 1), stride), np.uint8)
+        got = self._chk(self.L.sdrpp_vfo_frame_read(self.h, vid, recs.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return recs[:got]
+
+    def frame_table_count(self):
+        """Framer tables this context holds in device memory (identical scramble / interleave pairs share one)."""
+        return self._chk(self.L.sdrpp_frame_table_count(self.h))
+
+    def result_frames(self, ticket, vid, frame_bits=368):
+        """sdrpp_result_frames (result flag RESULT_FRAMES), between result_wait and result_release of that ticket -> this push's records uint8 [n, stride], a copy."""
+        stride = frame_record_stride(frame_bits)
+        recs, n = C.POINTER(C.c_uint8)(), C.c_int(0)
+        self._chk(self.L.sdrpp_result_frames(self.h, int(ticket), vid, C.byref(recs), C.byref(n)))
+        if n.value <= 0:
+            return np.zeros((0, stride), np.uint8)
+        return np.ctypeslib.as_array(recs, shape=(n.value * stride,)).copy().reshape(n.value, stride)
+
     def vfo_set_qpsk(self, vid, desc, enabled=True, keepalive=None):
         """Attach the Meteor QPSK demodulator (sdrpp_vfo_set_qpsk; radio.meteor_desc) to a RAW VFO, switch it (the same description: enabled = False freezes its
         state, True continues) or, with desc None, detach it.  `keepalive` is only there so that a caller can pass what radio.meteor_desc returns: the library
@@ -1208,8 +1291,11 @@ class Context:
         32 (RESULT_RDS) = the RDS branches' samples (result_rds; the library switches that one by a call of its own, sdrpp_pipeline_set_rds_results),
         64 (RESULT_SYM) = the symbol branches' outputs (result_sym; likewise, sdrpp_pipeline_set_sym_results),
         128 (RESULT_RDS_BITS) = the RDS demodulators' soft values and bits (result_rds_bits; likewise, sdrpp_pipeline_set_rds_bits_results),
-        256 (RESULT_QPSK) = the QPSK demodulators' int8 pairs (result_qpsk; likewise, sdrpp_pipeline_set_qpsk_results — set_qpsk_results adds the float pairs)."""
-        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags) & ~(RESULT_RDS | RESULT_SYM | RESULT_RDS_BITS | RESULT_QPSK)))
+        256 (RESULT_QPSK) = the QPSK demodulators' int8 pairs (result_qpsk; likewise, sdrpp_pipeline_set_qpsk_results — set_qpsk_results adds the float pairs),
+        512 (RESULT_FRAMES) = the framers' records (result_frames; likewise, sdrpp_pipeline_set_frame_results)."""
+        self._chk(self.L.sdrpp_set_pipelined(self.h, int(bool(on)), int(result_flags) & ~(RESULT_RDS | RESULT_SYM | RESULT_RDS_BITS | RESULT_QPSK | RESULT_FRAMES)))
+        if on and (int(result_flags) & RESULT_FRAMES):
+            self._chk(self.L.sdrpp_pipeline_set_frame_results(self.h, 1))
         if on and (int(result_flags) & RESULT_QPSK):
             self._chk(self.L.sdrpp_pipeline_set_qpsk_results(self.h, 1, 0))
         if on and (int(result_flags) & RESULT_RDS_BITS):

@@ -239,6 +239,24 @@ struct Vfo {
         int n_in = 0, npush = 0, cap = 0; // ... its samples, its pushes, the symbols its outputs have room for
         int cap_of(int n) const { return (n + min_step - 1) / min_step + 1; }
     } qpsk;
+    // Framer behind the symbol branch (sdrpp_vfo_set_framer; m17_decoder/src/m17dsp.h: M17Slice4FSK, M17FrameDemux): one wavefront job per block a level behind
+    // the branch's loop (vfo_frame_kernels.h), reading the loop's soft values and per-push counts of the same block.  Everything it remembers is ONE device array
+    // updated in place; switched off — or with the branch switched off — it freezes.  Its per-block buffers are streams without history, as the branch's are.
+    struct Frame {
+        bool attached = false, on = false;
+        float high_cut = 0.0f;
+        int n_sync = 0;
+        uint16_t sync[4] = { 0, 0, 0, 0 };
+        int frame_bits = 0, stride = 0;
+        unsigned long long tab_key = 0;    // the context's shared table (interleave and scramble in one word per bit) this framer holds a reference to (0: none)
+        const uint32_t* d_table = nullptr; // ... borrowed
+        uint32_t* d_state = nullptr;       // SDRPP_FRAME_STATE_HEAD words, then the part-built frame, a byte per position (FrameJob)
+        std::vector<Stream> st;            // [0] records (bytes), [1] frames per push (ints)
+        int lvl = 3;                       // level (do_vfos_plan) at which the job of the most recent block runs
+        bool ran = false;                  // the most recent block was planned with the framer (and its branch) on
+        int npush = 0, cap = 0;            // ... its pushes, the records its output has room for
+        int cap_of(int sym_cap) const { return (16 + 2 * sym_cap) / (16 + frame_bits) + 1; }
+    } frame;
     std::vector<int> tk_if, tk_af;  // a launch group of several pushes: cumulative sample counts of the IF / demodulator stream and of the AF chain's output at every push end
     ToepTab tp_chan, tp_audio;
     // front end as one filter (what the fused translate + filter kernels evaluate): stages 0 (+ 1) of the plan
@@ -270,7 +288,7 @@ struct Vfo {
         int base = -1;  // first AF stream in st (they are appended behind the VFO's own streams)
     } af;
 };
-// Every stream of a VFO: its own, then its RDS branch's, its stereo branch's, its symbol branch's, its RDS demodulator's and its QPSK demodulator's (the order plan_snapshot records them in).  ran_only: a branch's streams
+// Every stream of a VFO: its own, then its RDS branch's, its stereo branch's, its symbol branch's, its RDS demodulator's, its QPSK demodulator's and its framer's (the order plan_snapshot records them in).  ran_only: a branch's streams
 // only if the most recent plan ran the branch.
 template <class F>
 void for_each_stream(Vfo& v, F&& f, bool ran_only = false) {
@@ -289,6 +307,9 @@ void for_each_stream(Vfo& v, F&& f, bool ran_only = false) {
     }
     if (!ran_only || v.qpsk.ran) {
         for (auto& s : v.qpsk.st) { f(s); }
+    }
+    if (!ran_only || v.frame.ran) {
+        for (auto& s : v.frame.st) { f(s); }
     }
 }
 template <class F>
@@ -447,6 +468,8 @@ struct sdrpp_ctx {
     std::map<unsigned long long, RdsdBank> rdsd_banks;  // tap table + interpolator bank of the RDS demodulators, ONE pair per distinct description, freed with their last user
     struct QpskBank { float* d_taps = nullptr; float* d_bank = nullptr; int refs = 0; int K = 0, phases = 0, T = 0; std::vector<float> taps, bank; };
     std::map<unsigned long long, QpskBank> qpsk_banks;  // real tap table + interpolator bank of the QPSK demodulators, ONE pair per distinct description, freed with their last user
+    struct FrameTab { uint32_t* d_table = nullptr; int refs = 0; std::vector<uint32_t> words; };
+    std::map<unsigned long long, FrameTab> frame_tabs;  // the framers' tables (interleave[k] | scramble[k] << 16), ONE per distinct pair, freed with their last user
     std::map<unsigned long long, SymBank> sym_banks;  // interpolator banks of the symbol branches, ONE per distinct bank, freed with their last user
 
     // ---- pipelined ("tick") execution: one launch per block, the stages of consecutive blocks skewed over consecutive launches
@@ -468,6 +491,8 @@ struct sdrpp_ctx {
         std::vector<int> rds_ids, rds_counts;                // result flag 32: the VFOs whose RDS branch ran in the block, this push's samples
         std::vector<size_t> rds_off;                         // ... and where they lie in the slot
         std::vector<int> sym_ids, sym_push;                  // result flag 64: the VFOs whose symbol branch ran in the block, this push's index in its launch group
+        std::vector<int> frame_ids, frame_push, frame_stride;  // result flag 512: the VFOs whose framer ran in the block, this push's index in its launch group, the record stride
+        std::vector<size_t> frame_cnt_off, frame_rec_off;      // ... where the group's per-push frame counts and its records lie in the slot
         std::vector<size_t> sym_cnt_off, sym_soft_off, sym_bits_off;  // ... where the group's per-push counts, its soft values and its bits lie in the slot
         std::vector<int> rdsd_ids, rdsd_push;                // result flag 128: the VFOs whose RDS demodulator ran in the block, this push's index in its launch group
         std::vector<size_t> rdsd_cnt_off, rdsd_soft_off, rdsd_bits_off;  // ... where the group's per-push counts, its soft values and its bits lie in the slot (the symbol branch's layout)
@@ -479,7 +504,7 @@ struct sdrpp_ctx {
         size_t off_meters = 0;
     };
     bool pipelined = false;
-    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks, bit 5: RDS branches (sdrpp_pipeline_set_rds_results), bit 6: symbol branches (sdrpp_pipeline_set_sym_results), bit 7: RDS demodulators (sdrpp_pipeline_set_rds_bits_results), bit 8: QPSK demodulators (sdrpp_pipeline_set_qpsk_results)
+    int res_flags = 0;                    // bit 0: gather every VFO's output, bit 1: zoomed lines + palette indices, bit 2: raw dB lines, bit 3: pre-processed IQ, bit 4: recorder sinks, bit 5: RDS branches (sdrpp_pipeline_set_rds_results), bit 6: symbol branches (sdrpp_pipeline_set_sym_results), bit 7: RDS demodulators (sdrpp_pipeline_set_rds_bits_results), bit 8: QPSK demodulators (sdrpp_pipeline_set_qpsk_results), bit 9: framers (sdrpp_pipeline_set_frame_results)
     bool res_qpsk_soft = false;           // ... with the float pairs beside the int8 pairs
     int num_cus = 256;
     int tick_l0_at = getenv("SDRPP_GPU_TICK_L0_AT") ? atoi(getenv("SDRPP_GPU_TICK_L0_AT")) : 0;  // (read when the context is created)

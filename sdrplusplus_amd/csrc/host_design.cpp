@@ -176,6 +176,44 @@ int sdrpp_design_root_raised_cosine(int count, double beta, double symbolrate, d
     return count;
 }
 
+// m17_decoder/src/m17dsp.h: M17Decoder::init calls demod.init(input, 4800.0f, sampleRate, 2400.0f, 31, 0.5f, 1e-6f, 0.01f, 0.01f) — GFSK::init (demod/gfsk.h:24-35)
+// hands Quadrature(deviation, samplerate), rootRaisedCosine(31, 0.5, 4800, samplerate) and MM(samplerate / 4800, omegaGain, muGain, omegaRelLimit), every float
+// literal widened to a double on the way.  The framing is stated from the M17 specification: sync words, decorrelator sequence, quadratic interleaver.
+int sdrpp_design_m17(double if_rate, sdrpp_sym_desc* sym, float* rrc_taps, int max_taps, sdrpp_frame_desc* frame, uint8_t* scramble, uint16_t* interleave) {
+    if (!sym || !rrc_taps || !frame || !scramble || !interleave || !(if_rate > 0.0) || !std::isfinite(if_rate)) { return SDRPP_ERR_INVALID; }
+    const double baud = (double)4800.0f, dev = (double)2400.0f, beta = (double)0.5f, omega_gain = (double)1e-6f, mu_gain = (double)0.01f, lim = (double)0.01f;
+    const int K = sdrpp_design_root_raised_cosine(31, beta, baud, if_rate, rrc_taps, max_taps);
+    if (K != 31) { return SDRPP_ERR_INVALID; }
+    const double omega = if_rate / baud;
+    sym->inv_deviation = (float)(1.0 / hzToRads(dev, if_rate));  // quadrature.h:18-25
+    sym->shape_ntaps = K;
+    sym->shape_taps = rrc_taps;
+    sym->omega = (float)omega;
+    sym->mu_gain = (float)mu_gain;
+    sym->omega_gain = (float)omega_gain;
+    sym->min_omega = (float)(omega * (1.0 - lim));
+    sym->max_omega = (float)(omega * (1.0 + lim));
+    sym->interp_phases = 128;
+    sym->interp_ntaps = 8;
+    // the decorrelator sequence of the M17 specification, 46 bytes, read MSB first
+    static const uint8_t kSeq[46] = { 0xD6, 0xB5, 0xE2, 0x30, 0x82, 0xFF, 0x84, 0x62, 0xBA, 0x4E, 0x96, 0x90, 0xD8, 0x98, 0xDD, 0x5D, 0x0C, 0xC8, 0x52, 0x43, 0x91, 0x1D, 0xF8,
+                                      0x6E, 0x68, 0x2F, 0x35, 0xDA, 0x14, 0xEA, 0xCD, 0x76, 0x19, 0x8D, 0xD5, 0x80, 0xD1, 0x33, 0x87, 0x13, 0x57, 0x18, 0x2D, 0x29, 0x78, 0xC3 };
+    for (int k = 0; k < 368; k++) {
+        scramble[k] = (uint8_t)((kSeq[k >> 3] >> (7 - (k & 7))) & 1);
+        interleave[k] = (uint16_t)((45ll * k + 92ll * k * k) % 368);  // the specification's quadratic permutation polynomial
+    }
+    frame->high_cut = (1.0f + (1.0f / 3.0f)) / 2.0f;  // half way between the inner and the outer level
+    frame->n_sync = 3;
+    frame->sync[0] = 0x55F7;  // link setup
+    frame->sync[1] = 0xFF5D;  // stream
+    frame->sync[2] = 0x75FF;  // packet
+    frame->sync[3] = 0;
+    frame->frame_bits = 368;
+    frame->scramble = scramble;
+    frame->interleave = interleave;
+    return SDRPP_OK;
+}
+
 // meteor_demodulator/src/meteor_demod.h:24-43: every member as init leaves it (fast_agc.h:13-19, meteor_costas.h:13-16 through pll.h:15-23, mm.h:24-32).
 // init takes omegaRelLimit and does not hand it to recov.init: MM's limit is its default, 0.01
 int sdrpp_design_meteor(double symbolrate, double samplerate, int rrc_taps, double rrc_beta, double agc_rate, double costas_bw, int broken, int oqpsk, double omega_gain,

@@ -484,6 +484,12 @@ void stereo_free(Vfo::Stereo& s) {
     for (auto& q : s.st) { stream_free(q); }
     s = Vfo::Stereo{};
 }
+// what a framer owns by itself (its share of the context's tables is given back by frame_detach, vfo_ctl.h)
+void frame_free_own(Vfo::Frame& f) {
+    dev_free(f.d_state);
+    for (auto& q : f.st) { stream_free(q); }
+    f.st.clear();
+}
 // what a symbol branch owns by itself (its share of the context's interpolator banks is given back by sym_detach, vfo_ctl.h)
 void sym_free_own(Vfo::Sym& y) {
     dev_free(y.d_taps);
@@ -544,6 +550,7 @@ void af_detach(Vfo& v) {
 void vfo_free(Vfo& v) {
     rds_free_own(v.rds);
     stereo_free(v.stereo);
+    frame_free_own(v.frame);
     sym_free_own(v.sym);
     rdsd_free_own(v.rdsd);
     qpsk_free_own(v.qpsk);

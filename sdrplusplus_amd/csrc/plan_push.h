@@ -10,10 +10,11 @@ struct PlanSnapshot {
                int af_last, af_state;
                int rds_lvl; double rds_phi; bool rds_frozen, rds_ran; int rds_line_cur, rds_line_fed; bool stereo_ran;
                bool sym_ran; int sym_cur, sym_lvl, sym_n_if, sym_npush, sym_cap;
+               bool frame_ran; int frame_lvl, frame_npush, frame_cap;
                bool rdsd_ran; int rdsd_lvl, rdsd_n_in, rdsd_npush, rdsd_cap;
                bool qpsk_ran; int qpsk_cur, qpsk_lvl, qpsk_n_in, qpsk_npush, qpsk_cap; };
     std::vector<V> v;
-    std::vector<int> nc;  // n and cur of every stream of every VFO (its own, then its RDS branch's, its stereo branch's, its symbol branch's, its RDS demodulator's and its QPSK demodulator's), in the order of the walk
+    std::vector<int> nc;  // n and cur of every stream of every VFO (its own, then its RDS branch's, its stereo branch's, its symbol branch's, its RDS demodulator's, its QPSK demodulator's and its framer's), in the order of the walk
     int64_t fft_pos, fft_next;
     int n_lines, iq_cur, wf_cur, wf_lines;
     bool wf_have;
@@ -32,6 +33,7 @@ void plan_snapshot(sdrpp_ctx* c, PlanSnapshot& S, bool rotate = false) {
         q.nrecs = v.recs.size();
         q.af_last = v.af.i_last; q.af_state = v.af.state_cur;
         q.rds_lvl = v.rds.lvl; q.rds_phi = v.rds.phi; q.rds_frozen = v.rds.frozen; q.rds_ran = v.rds.ran; q.rds_line_cur = v.rds.line_cur; q.rds_line_fed = v.rds.line_fed; q.stereo_ran = v.stereo.ran;
+        q.frame_ran = v.frame.ran; q.frame_lvl = v.frame.lvl; q.frame_npush = v.frame.npush; q.frame_cap = v.frame.cap;
         q.sym_ran = v.sym.ran; q.sym_cur = v.sym.cur; q.sym_lvl = v.sym.lvl; q.sym_n_if = v.sym.n_if; q.sym_npush = v.sym.npush; q.sym_cap = v.sym.cap;
         q.rdsd_ran = v.rdsd.ran; q.rdsd_lvl = v.rdsd.lvl; q.rdsd_n_in = v.rdsd.n_in; q.rdsd_npush = v.rdsd.npush; q.rdsd_cap = v.rdsd.cap;
         q.qpsk_ran = v.qpsk.ran; q.qpsk_cur = v.qpsk.cur; q.qpsk_lvl = v.qpsk.lvl; q.qpsk_n_in = v.qpsk.n_in; q.qpsk_npush = v.qpsk.npush; q.qpsk_cap = v.qpsk.cap;
@@ -58,6 +60,7 @@ void plan_restore(sdrpp_ctx* c, const PlanSnapshot& S) {
         v.phi = q.phi; v.phi2 = q.phi2; v.seen = q.seen; v.i_if = q.i_if; v.lvl_if = q.lvl_if; v.lvl_out = q.lvl_out; v.lvl_af = q.lvl_af; v.lvl_ifc = q.lvl_ifc;
         v.af.i_last = q.af_last; v.af.state_cur = q.af_state;
         v.rds.lvl = q.rds_lvl; v.rds.phi = q.rds_phi; v.rds.frozen = q.rds_frozen; v.rds.ran = q.rds_ran; v.rds.line_cur = q.rds_line_cur; v.rds.line_fed = q.rds_line_fed; v.stereo.ran = q.stereo_ran;
+        v.frame.ran = q.frame_ran; v.frame.lvl = q.frame_lvl; v.frame.npush = q.frame_npush; v.frame.cap = q.frame_cap;
         v.sym.ran = q.sym_ran; v.sym.cur = q.sym_cur; v.sym.lvl = q.sym_lvl; v.sym.n_if = q.sym_n_if; v.sym.npush = q.sym_npush; v.sym.cap = q.sym_cap;
         v.rdsd.ran = q.rdsd_ran; v.rdsd.lvl = q.rdsd_lvl; v.rdsd.n_in = q.rdsd_n_in; v.rdsd.npush = q.rdsd_npush; v.rdsd.cap = q.rdsd_cap;
         v.qpsk.ran = q.qpsk_ran; v.qpsk.cur = q.qpsk_cur; v.qpsk.lvl = q.qpsk_lvl; v.qpsk.n_in = q.qpsk_n_in; v.qpsk.npush = q.qpsk_npush; v.qpsk.cap = q.qpsk_cap;

@@ -255,6 +255,8 @@ struct BankPlan {
     // QPSK demodulator (qpsk_branch): a front record (file_wave cuts it into segment jobs) and a loop record per VFO
     Lev<QpskFrontJob> qpf;
     Lev<QpskLoopJob> qpl;
+    // framer behind the symbol branch (frame_branch): a record, and a job, per VFO
+    Lev<FrameJob> frj;
     Lev<CarryJob> carry;  // history carries at the level of the stream's consumer (a pass without pipelining: all at the last level)
     int max_rot = 0;
     // front-end jobs (group_front)
@@ -293,7 +295,7 @@ struct BankPlan {
         for (auto& t : tlists) { f(*t.L); }
         f(f_dec); f(poly);
         for (auto& q : polyb) { f(q); }
-        f(chan); f(seq); f(nbsq); f(fmif); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stm); f(syf); f(syl); f(rdsdj); f(qpf); f(qpl); f(pre); f(audio); f(audio_fm);
+        f(chan); f(seq); f(nbsq); f(fmif); f(rdsj); f(rdsx); f(rdsl); f(stp); f(stl); f(stm); f(syf); f(syl); f(rdsdj); f(qpf); f(qpl); f(frj); f(pre); f(audio); f(audio_fm);
         f(af_dec); f(af_hpf); f(af_poly); f(af_deemp);
         f(ssbx_l); f(carry);
         f(stlj); f(sylj); f(wave);
@@ -499,6 +501,14 @@ struct BankPlan {
         }
         else {
             for (auto& s : v.sym.st) { s.n = 0; }
+        }
+        v.frame.ran = v.frame.attached && v.frame.on && v.sym.ran;
+        if (v.frame.ran) {
+            frame_branch(x);
+            last_lvl = std::max(last_lvl, v.frame.lvl);
+        }
+        else {
+            for (auto& s : v.frame.st) { s.n = 0; }
         }
         v.rdsd.ran = v.rdsd.attached && v.rdsd.on && (v.rdsd.source == 1 || v.rds.ran);
         if (v.rdsd.ran) {
@@ -915,6 +925,41 @@ struct BankPlan {
         for (auto& s : y.st) { s.wlevel = lvl + 2; }
         buf.wlevel = lvl + 1;
         return SDRPP_OK;
+    }
+    // Framer behind the symbol branch (m17_decoder/src/m17dsp.h: M17Slice4FSK, M17FrameDemux): ONE job per VFO and block (vfo_frame_kernels.h), one level behind the
+    // branch's loop, whose soft values and per-push symbol counts of this block it reads.  Its state is one device array updated in place.  A launch group is one
+    // block to the job: it counts the frames push by push.  A block without symbols still files the job: it writes the zeros of its counts.
+    void frame_branch(ChainCtx& x) {
+        Vfo& v = x.v;
+        Vfo::Frame& f = v.frame;
+        const Vfo::Sym& y = v.sym;
+        Stream &recs = f.st[0], &cnt = f.st[1];
+        f.npush = y.npush;
+        f.cap = f.cap_of(y.cap);
+        f.lvl = y.lvl + 1;
+        FrameJob j{};
+        j.soft = y.st[1].data;
+        j.sym_counts = reinterpret_cast<const int*>(y.st[3].data);
+        j.state = f.d_state;
+        j.recs = reinterpret_cast<uint8_t*>(recs.data);
+        j.counts = reinterpret_cast<int*>(cnt.data);
+        j.table = f.d_table;
+        j.high_cut = f.high_cut;
+        j.n_sync = f.n_sync;
+        for (int s = 0; s < f.n_sync; s++) {  // (stream order is LSB first in the job's words: the sync word's first bit in bit 0)
+            uint32_t r = 0;
+            for (int b = 0; b < 16; b++) { r |= (uint32_t)((f.sync[s] >> (15 - b)) & 1) << b; }
+            j.sync[s] = r;
+        }
+        j.frame_bits = f.frame_bits;
+        j.stride = f.stride;
+        j.npush = f.npush;
+        j.sym_cap = y.cap;
+        j.rec_cap = f.cap;
+        frj.add(f.lvl, j);
+        recs.n = (f.cap * f.stride + 3) / 4;
+        cnt.n = f.npush;
+        for (auto& s : f.st) { s.wlevel = f.lvl; }
     }
     // RDS demodulator (radio/src/rds_demod.h): ONE job per VFO and block (vfo_rdsd_kernels.h), one level behind the polyphase stage of the RDS chain (source 0)
     // or behind the stream a demodulator would read (source 1).  Its state is one device array updated in place.  A launch group is one block to the job; it is
@@ -1383,6 +1428,7 @@ struct BankPlan {
         file_wave(rdsdj, WK_RDS_DEMOD);
         file_wave(qpl, WK_QPSK_LOOP);  // (in front of the filter's jobs: a loop job filed at its filter's level would read the buffer BEFORE it is written wherever wavefronts start in table order — the emulator — and the tests see it)
         file_wave(qpf, WK_QPSK_FRONT);
+        file_wave(frj, WK_SYM_FRAME);
         // 3. the role's table
         if (!arena_push_lev(c, wave)) { return arena_fail(c); }
         HostScope hs("arena_commit (H2D)");

@@ -383,6 +383,8 @@ int sdrpp_destroy(sdrpp_ctx* c) {
     for (auto& kv : c->rds_banks) { dev_free(kv.second.d_bank); }
     c->rds_banks.clear();
     for (auto& kv : c->sym_banks) { dev_free(kv.second.d_bank); }
+    for (auto& kv : c->frame_tabs) { dev_free(kv.second.d_table); }
+    c->frame_tabs.clear();
     for (auto& kv : c->rdsd_banks) {
         dev_free(kv.second.d_taps);
         dev_free(kv.second.d_bank);
@@ -1014,6 +1016,57 @@ int sdrpp_vfo_sym_device_buffers(sdrpp_ctx* c, int id, const float** soft, const
 }
 int sdrpp_abi_sizeof_sym_desc(void) { return (int)sizeof(sdrpp_sym_desc); }
 int sdrpp_sym_bank_count(sdrpp_ctx* c) { return c ? (int)c->sym_banks.size() : SDRPP_ERR_INVALID; }
+
+// ---- framer behind the symbol branch: 4FSK slicer -> sync search -> descrambled, de-interleaved frames (m17_decoder/src/m17dsp.h) -----------------------
+int sdrpp_vfo_set_framer(sdrpp_ctx* c, int id, const sdrpp_frame_desc* d, int enabled) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return frame_apply(c, *v, d, enabled != 0);
+}
+int sdrpp_vfo_framer_reset(sdrpp_ctx* c, int id) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return frame_reset(c, *v);
+}
+int sdrpp_vfo_frame_count(sdrpp_ctx* c, int id) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    return frame_count(c, *v);
+}
+int sdrpp_vfo_frame_read(sdrpp_ctx* c, int id, uint8_t* records, int max_frames) {
+    DeviceScope dev_scope_(c);
+    if (!c || max_frames < 0) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    const int have = frame_count(c, *v);
+    if (have < 0) { return have; }
+    const int n = std::min(have, max_frames);
+    if (n > 0 && records) { HIPCHK(c, hipMemcpy(records, v->frame.st[0].data, (size_t)n * (size_t)v->frame.stride, hipMemcpyDeviceToHost)); }
+    return n;
+}
+int sdrpp_vfo_frame_device_buffer(sdrpp_ctx* c, int id, const uint8_t** records, int* n) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    FLUSH_PENDING(c);
+    LOOKUP_VFO(v, c, id);
+    const int have = frame_count(c, *v);
+    if (have < 0) { return have; }
+    if (records) { *records = reinterpret_cast<const uint8_t*>(v->frame.st[0].data); }
+    if (n) { *n = have; }
+    return SDRPP_OK;
+}
+int sdrpp_abi_sizeof_frame_desc(void) { return (int)sizeof(sdrpp_frame_desc); }
+int sdrpp_frame_record_stride(int frame_bits) {
+    if (frame_bits < 8 || frame_bits > SDRPP_FRAME_MAX_BITS || frame_bits % 8 != 0) { return SDRPP_ERR_INVALID; }
+    return frame_record_stride(frame_bits);
+}
+int sdrpp_frame_table_count(sdrpp_ctx* c) { return c ? (int)c->frame_tabs.size() : SDRPP_ERR_INVALID; }
 
 // ---- RDS demodulator: AGC -> Costas -> band-pass -> Costas -> MM clock recovery -> slicer -> differential decoder (radio/src/rds_demod.h) -----------------
 int sdrpp_vfo_set_rds_demod(sdrpp_ctx* c, int id, const sdrpp_rdsd_desc* d, int enabled) {
@@ -1947,6 +2000,32 @@ int sdrpp_result_qpsk(sdrpp_ctx* c, uint64_t ticket, int id, const float** soft_
         return SDRPP_OK;
     }
     return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of a QPSK demodulator of VFO %d", (unsigned long long)ticket, id);
+}
+int sdrpp_pipeline_set_frame_results(sdrpp_ctx* c, int on) {
+    DeviceScope dev_scope_(c);
+    if (!c) { return SDRPP_ERR_INVALID; }
+    if (!c->pipelined) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_pipeline_set_frame_results outside pipelined mode"); }
+    FLUSH_PENDING(c);
+    c->res_flags = on ? (c->res_flags | SDRPP_RESULT_FRAMES) : (c->res_flags & ~SDRPP_RESULT_FRAMES);
+    return SDRPP_OK;
+}
+// (the counts are the job's own result: they lie in the slot, complete since sdrpp_result_wait returned for this block)
+int sdrpp_result_frames(sdrpp_ctx* c, uint64_t ticket, int id, const uint8_t** records, int* count) {
+    if (!c) { return SDRPP_ERR_INVALID; }
+    sdrpp_ctx::Result* R = result_of(c, ticket);
+    if (!R || !R->held) { return fail(c, SDRPP_ERR_INVALID, "sdrpp_result_frames: block %llu is not held (between sdrpp_result_wait and sdrpp_result_release)", (unsigned long long)ticket); }
+    for (size_t i = 0; i < R->frame_ids.size(); i++) {
+        if (R->frame_ids[i] != id) { continue; }
+        int cnt[kGroupMax] = {};
+        const int j = std::min(R->frame_push[i], kGroupMax - 1);
+        memcpy(cnt, R->base + R->frame_cnt_off[i], (size_t)(j + 1) * sizeof(int));
+        size_t lo = 0;
+        for (int q = 0; q < j; q++) { lo += (size_t)std::max(cnt[q], 0); }
+        if (records) { *records = reinterpret_cast<const uint8_t*>(R->base + R->frame_rec_off[i]) + lo * (size_t)R->frame_stride[i]; }
+        if (count) { *count = std::max(cnt[j], 0); }
+        return SDRPP_OK;
+    }
+    return fail(c, SDRPP_ERR_NOT_FOUND, "block %llu holds nothing of a framer of VFO %d", (unsigned long long)ticket, id);
 }
 int sdrpp_result_meters(sdrpp_ctx* c, uint64_t ticket, const float** data, int* n_lines, int* n_meters) {
     if (!c) { return SDRPP_ERR_INVALID; }

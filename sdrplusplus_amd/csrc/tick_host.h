@@ -283,6 +283,12 @@ size_t tick_results_need(sdrpp_ctx* c) {
             if (y.attached && y.st.size() == 4) { need += (size_t)kGroupMax * 4 + (((y.st[1].cap + 16) * 4 + 15) & ~(size_t)15) + ((y.st[1].cap + 16 + 15) & ~(size_t)15); }
         }
     }
+    if (c->res_flags & 512) {  // framers: per-push frame counts, then the largest block's capacity of records
+        for (auto& kv : c->vfos) {
+            const Vfo::Frame& f = kv.second->frame;
+            if (f.attached && f.st.size() == 2) { need += (size_t)kGroupMax * 4 + (((f.st[0].cap + 16) * 4 + 15) & ~(size_t)15); }
+        }
+    }
     if (c->res_flags & 128) {  // RDS demodulators: the symbol branch's layout
         for (auto& kv : c->vfos) {
             const Vfo::Rdsd& y = kv.second->rdsd;
@@ -580,6 +586,27 @@ int tick_results_describe(sdrpp_ctx* c, uint64_t first_ticket, int k, std::vecto
             if (c->res_qpsk_soft) { copies.push_back(ResCopy{ y.st[1].data, soft_off, (size_t)y.cap * 8, y.lvl + 1 }); }
             copies.push_back(ResCopy{ y.st[2].data, packed_off, ((size_t)y.cap * 2 + 3) & ~(size_t)3, y.lvl + 1 });
             off = packed_off + (((size_t)y.cap * 2 + 15) & ~(size_t)15);
+        }
+    }
+    if (c->res_flags & 512) {
+        // every framer that ran in this block: the job's per-push frame counts, then what its records have room for in this block
+        for (auto& kv : c->vfos) {
+            const Vfo& v = *kv.second;
+            const Vfo::Frame& f = v.frame;
+            if (!f.attached || !f.ran) { continue; }
+            if (f.npush != k) { return fail(c, SDRPP_ERR_INVALID, "internal: VFO %d's framer planned %d pushes, the block has %d", v.id, f.npush, k); }
+            const size_t bytes = ((size_t)f.cap * (size_t)f.stride + 3) & ~(size_t)3;
+            const size_t cnt_off = off, rec_off = cnt_off + (((size_t)k * 4 + 15) & ~(size_t)15);
+            for (int j = 0; j < k; j++) {
+                R[j]->frame_ids.push_back(v.id);
+                R[j]->frame_push.push_back(j);
+                R[j]->frame_stride.push_back(f.stride);
+                R[j]->frame_cnt_off.push_back(cnt_off);
+                R[j]->frame_rec_off.push_back(rec_off);
+            }
+            copies.push_back(ResCopy{ f.st[1].data, cnt_off, (size_t)k * 4, f.lvl + 1 });
+            copies.push_back(ResCopy{ f.st[0].data, rec_off, bytes, f.lvl + 1 });
+            off = rec_off + ((bytes + 15) & ~(size_t)15);
         }
     }
     if (off > c->res_cap) { return fail(c, SDRPP_ERR_INVALID, "internal: results of %zu bytes exceed what a launch may deliver (%zu)", off, c->res_cap); }

@@ -847,8 +847,161 @@ int stereo_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, bool* cleared) {
     for (auto& q : n.stereo.st) { q.n = 0; }
     return stereo_grow_feeds(c, n, n.stereo.K);
 }
+// ---- framer behind the symbol branch (M17Slice4FSK, M17FrameDemux) --------------------------------------------------------------------------
+void frame_detach(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Frame& f = v.frame;
+    if (f.tab_key) {
+        auto it = c->frame_tabs.find(f.tab_key);
+        if (it != c->frame_tabs.end() && --it->second.refs <= 0) {
+            dev_free(it->second.d_table);
+            c->frame_tabs.erase(it);
+        }
+    }
+    frame_free_own(f);
+    f = Vfo::Frame{};
+}
+int frame_record_stride(int frame_bits) { return (2 + frame_bits / 8 + 3) & ~3; }
+// the kernel's table: interleave[k] in the low half of word k, scramble[k] in bit 16
+std::vector<uint32_t> frame_words(const sdrpp_frame_desc* d) {
+    std::vector<uint32_t> w((size_t)d->frame_bits);
+    for (int k = 0; k < d->frame_bits; k++) { w[(size_t)k] = (uint32_t)d->interleave[k] | ((uint32_t)(d->scramble[k] & 1) << 16); }
+    return w;
+}
+// The context's shared table (keyed by a hash over its words, one reference per framer): uploaded with its first user
+int frame_tab_acquire(sdrpp_ctx* c, Vfo::Frame& f, const std::vector<uint32_t>& words) {
+    unsigned long long h = 1469598103934665603ull;
+    for (uint32_t u : words) { h = (h ^ u) * 1099511628211ull; }
+    const unsigned long long key = h ? h : 1ull;
+    auto it = c->frame_tabs.find(key);
+    if (it != c->frame_tabs.end() && it->second.words != words) { return fail(c, SDRPP_ERR_UNSUPPORTED, "framer tables: two different pairs under one key"); }  // (a 64-bit collision: never seen)
+    if (it == c->frame_tabs.end()) {
+        sdrpp_ctx::FrameTab T;
+        T.words = words;
+        if (int rc = upload(c, &T.d_table, T.words.data(), T.words.size())) { return rc; }
+        it = c->frame_tabs.emplace(key, std::move(T)).first;
+    }
+    it->second.refs++;
+    f.tab_key = key;
+    f.d_table = it->second.d_table;
+    return SDRPP_OK;
+}
+// a fresh M17FrameDemux: delay 0, searching
+int frame_clear(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Frame& f = v.frame;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemset(f.d_state, 0, (size_t)(SDRPP_FRAME_STATE_HEAD + SDRPP_FRAME_MAX_BITS / 4) * sizeof(uint32_t)));
+    f.ran = false;
+    for (auto& q : f.st) { q.n = 0; }
+    return SDRPP_OK;
+}
+bool frame_same_desc(const Vfo::Frame& f, const sdrpp_frame_desc* d, const sdrpp_ctx* c) {
+    if (f.high_cut != d->high_cut || f.n_sync != d->n_sync || f.frame_bits != d->frame_bits || memcmp(f.sync, d->sync, (size_t)d->n_sync * sizeof(uint16_t)) != 0) { return false; }
+    auto it = c->frame_tabs.find(f.tab_key);
+    return it != c->frame_tabs.end() && it->second.words == frame_words(d);
+}
+// sdrpp_vfo_set_framer on a VFO the caller has looked up (the stream is idle); d == nullptr: the framer goes
+int frame_apply(sdrpp_ctx* c, Vfo& v, const sdrpp_frame_desc* d, bool enabled) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!d) {
+        frame_detach(c, v);
+        return SDRPP_OK;
+    }
+    if (!v.sym.attached || v.sym.st.size() != 4) { return fail(c, SDRPP_ERR_INVALID, "framer: VFO %d carries no symbol branch", v.id); }
+    if (!std::isfinite(d->high_cut)) { return fail(c, SDRPP_ERR_INVALID, "framer: second threshold %g: finite", d->high_cut); }
+    if (d->n_sync < 1 || d->n_sync > SDRPP_FRAME_MAX_SYNC) { return fail(c, SDRPP_ERR_INVALID, "framer: %d sync words (1 .. %d)", d->n_sync, SDRPP_FRAME_MAX_SYNC); }
+    if (d->frame_bits < 8 || d->frame_bits > SDRPP_FRAME_MAX_BITS || d->frame_bits % 8 != 0) { return fail(c, SDRPP_ERR_INVALID, "framer: frames of %d bits (a multiple of 8, 8 .. %d)", d->frame_bits, SDRPP_FRAME_MAX_BITS); }
+    if (!d->scramble || !d->interleave) { return fail(c, SDRPP_ERR_INVALID, "framer: a table is missing"); }
+    {
+        std::vector<char> seen((size_t)d->frame_bits, 0);
+        for (int k = 0; k < d->frame_bits; k++) {
+            if (d->scramble[k] > 1) { return fail(c, SDRPP_ERR_INVALID, "framer: scramble[%d] = %d (0 or 1)", k, (int)d->scramble[k]); }
+            if ((int)d->interleave[k] >= d->frame_bits || seen[(size_t)d->interleave[k]]) { return fail(c, SDRPP_ERR_INVALID, "framer: interleave[%d] = %d: the table is no permutation of 0 .. %d", k, (int)d->interleave[k], d->frame_bits - 1); }
+            seen[(size_t)d->interleave[k]] = 1;
+        }
+    }
+    Vfo::Frame& f = v.frame;
+    if (f.attached && frame_same_desc(f, d, c)) {  // the same framer: only the switch — everything it holds stays as it is
+        if (f.on && !enabled) {
+            for (auto& q : f.st) { q.n = 0; }
+        }
+        f.on = enabled;
+        f.ran = f.ran && enabled;
+        return SDRPP_OK;
+    }
+    frame_detach(c, v);
+    // every early return below gives back what was built so far
+    struct Undo {
+        sdrpp_ctx* c; Vfo& v; bool armed = true;
+        ~Undo() { if (armed) { frame_detach(c, v); } }
+    } undo{ c, v };
+    int rc;
+    f.high_cut = d->high_cut;
+    f.n_sync = d->n_sync;
+    for (int s = 0; s < d->n_sync; s++) { f.sync[s] = d->sync[s]; }
+    f.frame_bits = d->frame_bits;
+    f.stride = frame_record_stride(d->frame_bits);
+    if ((rc = frame_tab_acquire(c, f, frame_words(d)))) { return rc; }
+    if ((rc = dev_alloc(c, &f.d_state, (size_t)(SDRPP_FRAME_STATE_HEAD + SDRPP_FRAME_MAX_BITS / 4)))) { return rc; }
+    // per-block buffers: the records a block of the branch's symbol capacity can complete (bytes, four to a float) and the per-push counts
+    const size_t rcap = (size_t)f.cap_of((int)v.sym.st[1].cap);
+    const size_t caps[2] = { (rcap * (size_t)f.stride + 3) / 4, (size_t)kGroupMax };
+    f.st.resize(2);
+    for (int i = 0; i < 2; i++) {
+        if (stream_alloc(c, f.st[(size_t)i], 1, 0, caps[i])) { return SDRPP_ERR_NOMEM; }
+    }
+    if ((rc = frame_clear(c, v))) { return rc; }
+    f.attached = true;
+    f.on = enabled;
+    undo.armed = false;
+    return SDRPP_OK;
+}
+// sdrpp_vfo_replace with keep & 2, behind sym_hand_over: where the branch moved as it is the framer moves with everything it holds; where the branch was attached
+// afresh (another stream capacity) so is the framer, cleared
+int frame_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n, bool moved) {
+    Vfo::Frame& f = o.frame;
+    if (!f.attached) { return SDRPP_OK; }
+    if (!moved) {
+        const std::vector<uint32_t> words = c->frame_tabs[f.tab_key].words;
+        std::vector<uint8_t> scr(words.size());
+        std::vector<uint16_t> il(words.size());
+        for (size_t k = 0; k < words.size(); k++) {
+            scr[k] = (uint8_t)((words[k] >> 16) & 1u);
+            il[k] = (uint16_t)(words[k] & 0xFFFFu);
+        }
+        sdrpp_frame_desc d{};
+        d.high_cut = f.high_cut;
+        d.n_sync = f.n_sync;
+        for (int s = 0; s < f.n_sync; s++) { d.sync[s] = f.sync[s]; }
+        d.frame_bits = f.frame_bits;
+        d.scramble = scr.data();
+        d.interleave = il.data();
+        return frame_apply(c, n, &d, f.on);
+    }
+    n.frame = std::move(o.frame);
+    o.frame = Vfo::Frame{};
+    n.frame.ran = false;
+    for (auto& q : n.frame.st) { q.n = 0; }
+    return SDRPP_OK;
+}
+int frame_reset(sdrpp_ctx* c, Vfo& v) {
+    if (!v.frame.attached) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no framer", v.id); }
+    return frame_clear(c, v);
+}
+// The frames of the most recent block: the job's own counts, read from the device (the host waits for the stream)
+int frame_count(sdrpp_ctx* c, Vfo& v) {
+    Vfo::Frame& f = v.frame;
+    if (!f.attached) { return fail(c, SDRPP_ERR_INVALID, "VFO %d has no framer", v.id); }
+    if (!f.on || !f.ran || f.npush <= 0) { return 0; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int cnt[kGroupMax] = {};
+    HIPCHK(c, hipMemcpy(cnt, f.st[1].data, (size_t)std::min(f.npush, kGroupMax) * sizeof(int), hipMemcpyDeviceToHost));
+    int total = 0;
+    for (int j = 0; j < std::min(f.npush, kGroupMax); j++) { total += std::max(cnt[j], 0); }
+    return std::min(total, f.cap);
+}
 // ---- symbol branch of a RAW VFO -------------------------------------------------------------------------------------------------------
 void sym_detach(sdrpp_ctx* c, Vfo& v) {
+    frame_detach(c, v);  // (the framer reads the branch's outputs: it goes with it)
     Vfo::Sym& y = v.sym;
     if (y.bank_key) {
         auto it = c->sym_banks.find(y.bank_key);
@@ -976,13 +1129,14 @@ int sym_hand_over(sdrpp_ctx* c, Vfo& o, Vfo& n) {
     if (o.st[(size_t)o.i_chan].cap != n.st[(size_t)n.i_chan].cap) {
         const std::vector<float> taps = y.taps, bank = c->sym_banks[y.bank_key].taps;
         const sdrpp_sym_desc d{ y.inv_deviation, y.K, taps.data(), y.omega, y.mu_gain, y.omega_gain, y.min_omega, y.max_omega, y.phases, y.T, bank.data() };
-        return sym_apply(c, n, &d, y.on);
+        if (int rc = sym_apply(c, n, &d, y.on)) { return rc; }
+        return frame_hand_over(c, o, n, false);
     }
     n.sym = std::move(o.sym);
     o.sym = Vfo::Sym{};
     n.sym.ran = false;
     for (auto& q : n.sym.st) { q.n = 0; }
-    return SDRPP_OK;
+    return frame_hand_over(c, o, n, true);
 }
 // sdrpp_vfo_reset: the IF history it clears is the discriminator's "previous phase 0" (as for the RDS branch); everything else the branch holds stays
 int sym_reset_prev(sdrpp_ctx* c, Vfo& v) {

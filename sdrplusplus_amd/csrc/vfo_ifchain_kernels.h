@@ -1,7 +1,7 @@
 // The tick's wavefront-job role (TR_IFC, `ifc`) and its stand-alone launch: one wavefront per job, four jobs per workgroup.  It began as the radio's IF
 // chain (noise blanker / power squelch, below) and carries every piece of work that is one wavefront wide: FMIF (vfo_fmif_kernels.h), the RDS branch's jobs
-// (vfo_rds_kernels.h), the stereo branch's (vfo_stereo_kernels.h), the symbol branch's (vfo_sym_kernels.h), the RDS demodulator (vfo_rdsd_kernels.h) and the Meteor QPSK
-// demodulator (vfo_qpsk_kernels.h).  Those six headers are parts of this one.
+// (vfo_rds_kernels.h), the stereo branch's (vfo_stereo_kernels.h), the symbol branch's (vfo_sym_kernels.h), the RDS demodulator (vfo_rdsd_kernels.h), the Meteor QPSK
+// demodulator (vfo_qpsk_kernels.h) and the framer behind a symbol branch (vfo_frame_kernels.h).  Those seven headers are parts of this one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,9 +11,9 @@ namespace sdrpp_k {
 
 // What runs in a wavefront.  A new kind is a record struct, a `*_call` that reads it, an entry here, a case in vfo_wave_body and a file_wave line in the
 // planner (BankPlan::upload).  The values never leave the library.
-enum WaveKind : int { WK_NBSQ, WK_FMIF, WK_RDS_FRONT, WK_RDS_ROTX, WK_RDS_LINE, WK_ST_PILOT, WK_ST_LOOP, WK_ST_MATRIX, WK_SYM_FRONT, WK_SYM_LOOP, WK_RDS_DEMOD, WK_QPSK_FRONT, WK_QPSK_LOOP, WK_COUNT };
+enum WaveKind : int { WK_NBSQ, WK_FMIF, WK_RDS_FRONT, WK_RDS_ROTX, WK_RDS_LINE, WK_ST_PILOT, WK_ST_LOOP, WK_ST_MATRIX, WK_SYM_FRONT, WK_SYM_LOOP, WK_RDS_DEMOD, WK_QPSK_FRONT, WK_QPSK_LOOP, WK_SYM_FRAME, WK_COUNT };
 // The table the role reads: entry j is wavefront j's work.  `rec` is the kind's own record (NbSqJob, FmifJob, RdsJob, RdsRotXJob, RdsLineJob, StereoPilotJob,
-// StereoLoopJob, StereoMatrixJob, SymFrontJob, SymLoopJob, RdsdJob, QpskFrontJob, QpskLoopJob); `arg` is the part of the record this wavefront takes where a record is cut into several jobs
+// StereoLoopJob, StereoMatrixJob, SymFrontJob, SymLoopJob, RdsdJob, QpskFrontJob, QpskLoopJob, FrameJob); `arg` is the part of the record this wavefront takes where a record is cut into several jobs
 // (FMIF and the QPSK front: the segment's first sample).
 struct WaveJob {
     const void* rec;
@@ -22,7 +22,7 @@ struct WaveJob {
 };
 static_assert(sizeof(WaveJob) == 16, "the role's table: 16 bytes per wavefront");
 // the kinds that work in the wavefront's share of the role's LDS
-constexpr bool wave_kind_uses_lds(int kind) { return kind == WK_FMIF || kind == WK_RDS_FRONT || kind == WK_ST_PILOT || kind == WK_ST_LOOP || kind == WK_ST_MATRIX || kind == WK_SYM_FRONT || kind == WK_RDS_DEMOD || kind == WK_QPSK_FRONT || kind == WK_QPSK_LOOP; }  // (WK_SYM_LOOP reads its rows and its bank from global memory: vfo_sym_kernels.h)
+constexpr bool wave_kind_uses_lds(int kind) { return kind == WK_FMIF || kind == WK_RDS_FRONT || kind == WK_ST_PILOT || kind == WK_ST_LOOP || kind == WK_ST_MATRIX || kind == WK_SYM_FRONT || kind == WK_RDS_DEMOD || kind == WK_QPSK_FRONT || kind == WK_QPSK_LOOP || kind == WK_SYM_FRAME; }  // (WK_SYM_LOOP reads its rows and its bank from global memory: vfo_sym_kernels.h)
 
 // A record read by the whole wavefront: what a call is handed, and what a lane computes from its own index, lies in vector registers although every lane holds
 // the same.  The address is stated to be wave-uniform and the record read with scalar loads, so that it, and every address and bound computed from it, stays in
@@ -56,6 +56,7 @@ __device__ __forceinline__ T wave_uniform_job(const T* p) {
 #include "vfo_sym_kernels.h"
 #include "vfo_rdsd_kernels.h"
 #include "vfo_qpsk_kernels.h"
+#include "vfo_frame_kernels.h"
 
 namespace sdrpp_k {
 
@@ -68,6 +69,7 @@ static_assert(!wave_kind_uses_lds(WK_SYM_LOOP), "symbol loop: no LDS");
 static_assert(SDRPP_RDSD_LDS_FLOATS <= SDRPP_WAVE_LDS_FLOATS && wave_kind_uses_lds(WK_RDS_DEMOD), "RDS demodulator: the filter's window of a chunk and MM's work buffer");
 static_assert(SDRPP_QPSK_FRONT_LDS_FLOATS <= SDRPP_WAVE_LDS_FLOATS && wave_kind_uses_lds(WK_QPSK_FRONT), "QPSK front: the window of a tile");
 static_assert(SDRPP_QPSK_LOOP_LDS_FLOATS <= SDRPP_WAVE_LDS_FLOATS && wave_kind_uses_lds(WK_QPSK_LOOP), "QPSK loop: MM's work buffer of a chunk");
+static_assert(SDRPP_FRAME_LDS_FLOATS <= SDRPP_WAVE_LDS_FLOATS && wave_kind_uses_lds(WK_SYM_FRAME), "framer: a chunk's bit words, its match mask, the push ends and the frame under construction");
 // (the RDS front's window depends on its filter: the host admits only a tile whose window and phases fit the stride, rds_tile_geometry)
 
 // =====================================================================================================================
@@ -182,6 +184,7 @@ __device__ __forceinline__ void vfo_wave_body(int id, const WaveJob* __restrict_
     case WK_RDS_DEMOD: vfo_rdsd_call(static_cast<const RdsdJob*>(job.rec), smem); break;
     case WK_QPSK_FRONT: vfo_qpsk_front_call(static_cast<const QpskFrontJob*>(job.rec), job.arg, smem); break;
     case WK_QPSK_LOOP: vfo_qpsk_loop_call(static_cast<const QpskLoopJob*>(job.rec), smem); break;
+    case WK_SYM_FRAME: vfo_sym_frame_call(static_cast<const FrameJob*>(job.rec), smem); break;
     default: break;
     }
 }

@@ -19,7 +19,7 @@
 #include "vfo_resample_kernels.h"
 #include "vfo_fir_kernels.h"
 #include "vfo_demod_kernels.h"
-#include "vfo_ifchain_kernels.h"  // (with the kinds of its role: vfo_fmif_kernels.h, vfo_rds_kernels.h, vfo_stereo_kernels.h, vfo_sym_kernels.h)
+#include "vfo_ifchain_kernels.h"  // (with the kinds of its role: vfo_fmif_kernels.h, vfo_rds_kernels.h, vfo_stereo_kernels.h, vfo_sym_kernels.h, vfo_frame_kernels.h)
 #include "vfo_carry_kernels.h"
 #include "vfo_af_kernels.h"
 #include "vfo_rec_kernels.h"

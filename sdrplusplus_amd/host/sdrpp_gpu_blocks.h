@@ -118,6 +118,10 @@ public:
     dsp::stream<int8_t> qpskPacked;       // ... and what the module's sink makes of them: two int8 per symbol (a swap of 2 x the symbols)
     dsp::stream<uint8_t> symOut;         // attachSymbols: POCSAGDSP::out — one bit per symbol
     dsp::stream<float> symSoft;          // ... and POCSAGDSP::soft
+    dsp::stream<uint8_t> m17LinkSetup;   // attachM17: M17FrameDemux::linkSetupOut — one bit per byte, a swap of 368 per link setup frame
+    dsp::stream<uint8_t> m17Lich;        // ... lichOut: a swap of 96 per stream or packet frame
+    dsp::stream<uint8_t> m17Stream;      // ... streamOut: a swap of 368 per stream frame (272 entries and 96 zeros)
+    dsp::stream<uint8_t> m17Packet;      // ... packetOut: likewise per packet frame
     dsp::stream<dsp::complex_t> rdsOut;  // attachRDS: BroadcastFM::rdsOut — the 5 kS/s baseband RDSDemod consumes, one swap per block that produced samples
     dsp::stream<uint8_t> recorded;     // attachRecorder: one swap per block the recorder would write, the packed bytes of the file's sample type (silent blocks: no swap)
 
@@ -167,6 +171,11 @@ public:
     // delivers `out`, one swap each per block that produced any.  attachSymbols starts from a fresh POCSAGDSP; setSymbolsOn(false) freezes loop and delay lines,
     // true continues from them; re-plans that keep the demodulator keep the branch.  sdrpp_gpu::POCSAGDSP (sdrpp_gpu_pager.h) is the reference-shaped face of it.
     void attachSymbols(double baudrate);
+    // The M17 decoder's front (m17_decoder/src/m17dsp.h: dsp::demod::GFSK, M17Slice4FSK, M17FrameDemux; sdrpp_design_m17, sdrpp_vfo_set_symbols + sdrpp_vfo_set_framer)
+    // on the device, for a channel WITHOUT a demodulator: the frames a block completes are delivered on the demux's four streams as the reference swaps them out,
+    // the soft symbols on `symSoft` (the module's diagOut).  attachM17 starts from a fresh chain.
+    void attachM17();
+    void detachM17();
     // The meteor_demodulator module's DSP (dsp::demod::Meteor: RRC FIR -> AGC -> QPSK Costas loop -> OQPSK delay -> complex MM; sdrpp_vfo_set_qpsk) on the device, for a
     // channel WITHOUT a demodulator (Demod::RAW): the symbols that start inside a block are delivered on `qpskOut` and `qpskPacked` from the worker that delivers
     // `out`, block by block or out of the pipelined result slots (flag 256); a block without a symbol is not handed on.  WHILE IT IS ATTACHED `out` IS NO LONGER
@@ -235,6 +244,8 @@ public:
         return rdsdSoftFrom.empty() ? rdsdSoft : rdsdSoftFrom.front().second;
     }
     bool symAttached = false, symOn = false;
+    bool m17Attached = false;            // the symbol branch carries M17's description and the framer behind it
+    std::vector<uint8_t> m17Recs;        // the most recent pass's frame records (ordinary passes)
     bool qpskAttached = false;
     QPSKParams qpskP{};
     double symBaud = 0.0;
@@ -436,6 +447,10 @@ public:
         registerOutput(&v->qpskPacked);
         registerOutput(&v->symOut);
         registerOutput(&v->symSoft);
+        registerOutput(&v->m17LinkSetup);
+        registerOutput(&v->m17Lich);
+        registerOutput(&v->m17Stream);
+        registerOutput(&v->m17Packet);
         tempStart();
         return v;
     }
@@ -458,6 +473,10 @@ public:
         unregisterOutput(&it->second->qpskPacked);
         unregisterOutput(&it->second->symOut);
         unregisterOutput(&it->second->symSoft);
+        unregisterOutput(&it->second->m17LinkSetup);
+        unregisterOutput(&it->second->m17Lich);
+        unregisterOutput(&it->second->m17Stream);
+        unregisterOutput(&it->second->m17Packet);
         vfoOrder.erase(std::remove(vfoOrder.begin(), vfoOrder.end(), it->second), vfoOrder.end());
         delete it->second;
         vfos.erase(it);
@@ -982,14 +1001,17 @@ private:
         for (auto& kv : vfos) { sym = sym || (kv.second->symAttached && kv.second->demod == Demod::RAW); }
         bool qpsk = false;
         for (auto& kv : vfos) { qpsk = qpsk || (kv.second->qpskAttached && kv.second->demod == Demod::RAW); }
-        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0) | (rds ? SDRPP_RESULT_RDS : 0) | (sym ? SDRPP_RESULT_SYM : 0) | (rdsd ? SDRPP_RESULT_RDS_BITS : 0) | (qpsk ? SDRPP_RESULT_QPSK : 0);  // (a recorder or an RDS branch adds its flag and drops nobody's: `audio` is delivered as before)
+        bool frames = false;
+        for (auto& kv : vfos) { frames = frames || (kv.second->symAttached && kv.second->m17Attached && kv.second->demod == Demod::RAW); }
+        return 1 | 4 | ((pre && !iqStreams.empty()) ? 8 : 0) | (rec ? 16 : 0) | (rds ? SDRPP_RESULT_RDS : 0) | (sym ? SDRPP_RESULT_SYM : 0) | (rdsd ? SDRPP_RESULT_RDS_BITS : 0) | (qpsk ? SDRPP_RESULT_QPSK : 0) | (frames ? SDRPP_RESULT_FRAMES : 0);  // (a recorder or an RDS branch adds its flag and drops nobody's: `audio` is delivered as before)
     }
     int enterPipelined() {
         if (sdrpp_sync(ctx)) { return -1; }  // (nothing is staged in bypass mode; a deferred pass left over from buffered mode runs here)
         sdrpp_set_deferred(ctx, 0);
         pipeFlags = pipelineFlags();
-        if (sdrpp_set_pipelined(ctx, 1, pipeFlags & ~(SDRPP_RESULT_RDS | SDRPP_RESULT_SYM | SDRPP_RESULT_RDS_BITS | SDRPP_RESULT_QPSK)) || ((pipeFlags & SDRPP_RESULT_RDS) && sdrpp_pipeline_set_rds_results(ctx, 1)) ||
+        if (sdrpp_set_pipelined(ctx, 1, pipeFlags & ~(SDRPP_RESULT_RDS | SDRPP_RESULT_SYM | SDRPP_RESULT_RDS_BITS | SDRPP_RESULT_QPSK | SDRPP_RESULT_FRAMES)) || ((pipeFlags & SDRPP_RESULT_RDS) && sdrpp_pipeline_set_rds_results(ctx, 1)) ||
             ((pipeFlags & SDRPP_RESULT_SYM) && sdrpp_pipeline_set_sym_results(ctx, 1)) ||
+            ((pipeFlags & SDRPP_RESULT_FRAMES) && sdrpp_pipeline_set_frame_results(ctx, 1)) ||
             ((pipeFlags & SDRPP_RESULT_RDS_BITS) && sdrpp_pipeline_set_rds_bits_results(ctx, 1)) ||
             ((pipeFlags & SDRPP_RESULT_QPSK) && sdrpp_pipeline_set_qpsk_results(ctx, 1, 1))) {  // (flags 32, 64, 128 and 256 have calls of their own; qpskOut wants the float pairs)
             fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] pipelined mode refused: %s\n", sdrpp_last_error(ctx));
@@ -1199,9 +1221,28 @@ private:
                 for (size_t q = v->prevIds.size(); rrc == SDRPP_ERR_NOT_FOUND && q-- > 0;) { rrc = sdrpp_result_sym(ctx, ticket, v->prevIds[q], &soft, &bits, &cnt); }
                 if (rrc || cnt <= 0) { continue; }  // (pushed before the attach, or while the branch was switched off)
                 jobs.emplace_back([this, v, soft, bits, cnt]() {
-                    memcpy(v->symOut.writeBuf, bits, (size_t)cnt);
                     memcpy(v->symSoft.writeBuf, soft, (size_t)cnt * sizeof(float));
+                    if (v->m17Attached) {  // (the M17 module has no stream of binary slices: its bits are the framer's)
+                        if (!v->symSoft.swap(cnt)) { deliveryFailed = true; }
+                        return;
+                    }
+                    memcpy(v->symOut.writeBuf, bits, (size_t)cnt);
                     if (!v->symOut.swap(cnt) || !v->symSoft.swap(cnt)) { deliveryFailed = true; }
+                });
+            }
+        }
+        // the M17 framers: this push's frame records (result flag 512), unpacked onto the demux's four streams
+        if (pipeFlags & SDRPP_RESULT_FRAMES) {
+            for (auto& kv : vfos) {
+                RxVFO* v = kv.second;
+                if (!v->symAttached || !v->m17Attached) { continue; }
+                const uint8_t* recs = nullptr;
+                int cnt = 0;
+                int rrc = sdrpp_result_frames(ctx, ticket, v->id, &recs, &cnt);
+                for (size_t q = v->prevIds.size(); rrc == SDRPP_ERR_NOT_FOUND && q-- > 0;) { rrc = sdrpp_result_frames(ctx, ticket, v->prevIds[q], &recs, &cnt); }
+                if (rrc || cnt <= 0) { continue; }
+                jobs.emplace_back([this, v, recs, cnt]() {
+                    if (!deliverM17(v, recs, cnt)) { deliveryFailed = true; }
                 });
             }
         }
@@ -1490,7 +1531,23 @@ private:
             }
             if (got == 0) { continue; }
             jobs.emplace_back([v, got, &failed]() {
-                if (!v->symOut.swap(got) || !v->symSoft.swap(got)) { failed = true; }
+                if ((!v->m17Attached && !v->symOut.swap(got)) || !v->symSoft.swap(got)) { failed = true; }
+            });
+        }
+        // the M17 framers: the pass's frame records, unpacked onto the demux's four streams
+        for (auto& kv : vfos) {
+            RxVFO* v = kv.second;
+            if (!v->symAttached || !v->m17Attached || !v->symOn || v->demod != Demod::RAW || v->id < 0) { continue; }
+            const int have = sdrpp_vfo_frame_count(ctx, v->id);
+            if (have > 0) { v->m17Recs.resize((size_t)have * 48); }
+            const int got = have > 0 ? sdrpp_vfo_frame_read(ctx, v->id, v->m17Recs.data(), have) : have;
+            if (got < 0) {
+                fprintf(stderr, "[sdrpp_gpu::IQFrontEnd] reading the framer failed: %s\n", sdrpp_last_error(ctx));
+                return -1;
+            }
+            if (got == 0) { continue; }
+            jobs.emplace_back([v, got, &failed]() {
+                if (!deliverM17(v, v->m17Recs.data(), got)) { failed = true; }
             });
         }
         helpers.run(std::move(jobs));
@@ -1666,7 +1723,47 @@ private:
         int rc = sdrpp_vfo_set_qpsk(ctx, v.id, &d, 1);
         if (rc) { throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_qpsk: ") + sdrpp_last_error(ctx)); }
     }
+    // 48-byte frame records ([type][0][46 bytes, position 0 in the MSB of the first]) as M17FrameDemux::run swaps frames out (m17dsp.h:208-221), one bit per byte:
+    // type 0, 368 entries on linkSetupOut; types 1 / 2, positions 0 .. 95 on lichOut (a swap of 96), then positions 96 .. 367 on streamOut / packetOut in a swap of
+    // 368 whose last 96 entries are ZERO here (the reference leaves there whatever the buffer held; nobody reads them)
+    static bool deliverM17(RxVFO* v, const uint8_t* recs, int n) {
+        uint8_t pos[368];
+        for (int r = 0; r < n; r++) {
+            const uint8_t* rec = recs + (size_t)r * 48;
+            for (int p = 0; p < 368; p++) { pos[p] = (uint8_t)((rec[2 + (p >> 3)] >> (7 - (p & 7))) & 1); }
+            if (rec[0] == 0) {
+                memcpy(v->m17LinkSetup.writeBuf, pos, 368);
+                if (!v->m17LinkSetup.swap(368)) { return false; }
+                continue;
+            }
+            dsp::stream<uint8_t>& pay = rec[0] == 1 ? v->m17Stream : v->m17Packet;
+            memcpy(v->m17Lich.writeBuf, pos, 96);
+            if (!v->m17Lich.swap(96)) { return false; }
+            memcpy(pay.writeBuf, pos + 96, 272);
+            memset(pay.writeBuf + 272, 0, 96);
+            if (!pay.swap(368)) { return false; }
+        }
+        return true;
+    }
+    // m17dsp.h: M17Decoder::init's GFSK parameters at the channel's rate and M17's framing (sdrpp_design_m17): the branch, then the framer behind it
+    void applyM17(RxVFO& v) {
+        sdrpp_sym_desc s;
+        sdrpp_frame_desc f;
+        memset(&s, 0, sizeof(s));
+        memset(&f, 0, sizeof(f));
+        float taps[31];
+        uint8_t scr[368];
+        uint16_t il[368];
+        if (sdrpp_design_m17(v.outSamplerate, &s, taps, 31, &f, scr, il)) { throw std::runtime_error("[sdrpp_gpu::IQFrontEnd] design_m17: the rate must be positive and finite"); }
+        std::vector<float> bank((size_t)s.interp_phases * (size_t)s.interp_ntaps);
+        sdrpp_design_mm_interp(s.interp_phases, s.interp_ntaps, bank.data());
+        s.interp_bank = bank.data();
+        if (sdrpp_vfo_set_symbols(ctx, v.id, &s, v.symOn ? 1 : 0) || sdrpp_vfo_set_framer(ctx, v.id, &f, 1)) {
+            throw std::runtime_error(std::string("[sdrpp_gpu::IQFrontEnd] vfo_set_symbols / vfo_set_framer: ") + sdrpp_last_error(ctx));
+        }
+    }
     void applySymbols(RxVFO& v) {
+        if (v.m17Attached) { return applyM17(v); }
         sdrpp_sym_desc s;
         memset(&s, 0, sizeof(s));
         if (sdrpp_design_pager(v.outSamplerate, v.symBaud, &s)) { throw std::runtime_error("[sdrpp_gpu::IQFrontEnd] design_pager: rates must be positive"); }
@@ -2210,15 +2307,32 @@ inline void RxVFO::attachSymbols(double baudrate) {
     if (symAttached && id >= 0) { sdrpp_vfo_set_symbols(fe->ctx, id, nullptr, 0); }  // (attaching again starts cleared)
     symAttached = true;
     symOn = true;
+    m17Attached = false;
     symBaud = baudrate;
     if (id >= 0) { fe->applySymbols(*this); }
     fe->tempStart();
+}
+inline void RxVFO::attachM17() {
+    std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
+    if (demod != Demod::RAW) { throw std::runtime_error("[sdrpp_gpu::RxVFO] the M17 branch belongs to a channel without a demodulator"); }
+    fe->tempStop();
+    if (symAttached && id >= 0) { sdrpp_vfo_set_symbols(fe->ctx, id, nullptr, 0); }  // (attaching again starts cleared; the framer goes with the branch)
+    symAttached = true;
+    symOn = true;
+    m17Attached = true;
+    symBaud = 4800.0;
+    if (id >= 0) { fe->applySymbols(*this); }
+    fe->tempStart();
+}
+inline void RxVFO::detachM17() {
+    detachSymbols();
 }
 inline void RxVFO::detachSymbols() {
     std::lock_guard<std::recursive_mutex> lck(fe->ctrlMtx);
     fe->tempStop();
     symAttached = false;
     symOn = false;
+    m17Attached = false;
     if (id >= 0) { sdrpp_vfo_set_symbols(fe->ctx, id, nullptr, 0); }
     fe->tempStart();
 }

@@ -273,6 +273,16 @@ def meteor_desc(symbolrate=72000.0, samplerate=150000.0, rrc_taps=33, rrc_beta=c
     return d, [taps, bank]
 
 
+def m17_desc(if_rate=14400.0):
+    """The two descriptions of the M17 decoder's front (m17_decoder/src/m17dsp.h) at if_rate: sdrpp_sym_desc for its GFSK demodulator — Quadrature(2400 Hz), 31
+    root-raised-cosine taps (alpha 0.5, 4800 baud), MM<float>(if_rate / 4800, omega gain 1e-6, mu gain 0.01, relative limit 0.01) with its 128 x 8 interpolator —
+    and sdrpp_frame_desc for M17Slice4FSK / M17FrameDemux.  Returns (sym_desc, frame_desc, keepalive)."""
+    sym, frame, taps, scr, il = capi.design_m17(if_rate)
+    bank = capi.design_mm_interp(sym.interp_phases, sym.interp_ntaps)
+    sym.interp_bank = _fp(bank)
+    return sym, frame, [taps, bank, scr, il]
+
+
 def if_desc(if_rate, nb=False, nb_level=10.0, squelch=None):
     """sdrpp_if_desc for the radio module's IF chain (radio_module.h:84-96): NoiseBlanker(rate = 500 / if_rate, level; :90, :526) ->
     PowerSquelch(level in dB; None = off).  FMIF, the chain's last block, is switched by Context.vfo_set_fmnr (IFNR_BINS); the CTCSS squelch is not on the device."""
